@@ -3,7 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W
 
-N > 1 without a launcher re-executes itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
+N > 1 without a launcher starts itself as a child under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
 --master-addr 127.0.0.1` (one rank per GPU, RCCL); under a launcher (RANK / WORLD_SIZE set, the driver's form) it asserts
 that the world size equals N.
 
@@ -30,6 +30,10 @@ to the physical cores) and a plain PyTorch-CPU `(N,7) @ (7,7)` loop (the referen
 timed in a subprocess with its own thread settings.
 
 Prints ONE JSON line on rank 0.
+
+`--dump-outputs DIR` (rank 0) writes what the last timed step returned — the outgoing beam's buffers and its global moments — as
+DIR/<name>.npy after the timed steps, so that two builds can be compared output for output (the inputs are seeded: identical
+from run to run for the same arguments).
 """
 
 from __future__ import annotations
@@ -259,11 +263,25 @@ def cpu_baseline(n_elements: int) -> dict:
                 "sample": f"cpu baseline failed: {type(exc).__name__}: {exc}"}
 
 
+# ---------------------------------------------------------------------------------------------------------------- outputs
+def dump_outputs(path: str, beam, moments) -> None:
+    """The arrays the headline step hands its caller: the outgoing ParticleBeam's buffers (float32 here: 28 MB of particles at 1e6)
+    and the (29,) float64 global moments, one DIR/<name>.npy each."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {name: getattr(beam, name) for name in ("particles", "energy", "particle_charges", "survival_probabilities", "s")}
+    arrays["moments"] = moments
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy"), a.astype(np.float64 if a.dtype == np.float64 else np.float32))
+
+
 # ---------------------------------------------------------------------------------------------------------------- launch
 def self_launch(args) -> None:
-    import torch
-
-    have = torch.cuda.device_count()
+    # the device count comes from a short-lived child, so that this launcher never holds the GPU beside its N ranks
+    have = int(subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"], capture_output=True,
+                              text=True, check=True, timeout=300).stdout.split()[-1])
     if have < args.gpus and not args.one_device_gloo:
         sys.stderr.write(f"bench.py: --gpus {args.gpus} needs {args.gpus} visible GPUs, this node has {have}; "
                          f"run with --gpus {max(have, 1)} or on a larger node\n")
@@ -274,7 +292,7 @@ def self_launch(args) -> None:
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-    os.execvpe(sys.executable, cmd, env)
+    sys.exit(subprocess.run(cmd, env=env).returncode)
 
 
 def rocprof_average_ms() -> float | None:
@@ -953,6 +971,8 @@ def main():
                     help="N = 1: open the one-rank RCCL group BEFORE the headline, so that its step runs the moments "
                          "all-gather + chx_merge_moments too (default: only the scaling legs, after the headline)")
     ap.add_argument("--no-scaling-legs", action="store_true", help="N = 1: skip the one-rank RCCL run of the scaling legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the last step's outputs (rank 0) as DIR/<name>.npy")
     ap.add_argument("--cpu-baseline-worker", type=str, default="", help=argparse.SUPPRESS)
     # smoke test of the multi-rank code path on a ONE-GPU box: every rank on cuda:0, collectives over gloo (RCCL refuses two
     # ranks on one device). Not a measurement.
@@ -1033,6 +1053,8 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     value = world * N_PARTICLES * E * args.steps / dt
     sigma_x = float(state["moments"][8].sqrt())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state["out"], state["moments"])
     # the same step once more over a longer sample (>= 0.25 s of steps): the driver's --steps 20 is 19 ms of GPU work, and the
     # box-to-box scatter of so short a sample should be visible next to it. `steps` / `ms_per_step` above stay exactly as asked.
     long_steps = max(args.steps, int(math.ceil(250.0 / max(ms_per_step, 1e-3))))

@@ -9,12 +9,18 @@
   the 1e6-particle beam.
 
 Every bound below is stated next to the error measured on the MI355X of the test box (this file prints them with -s)."""
+import json
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 1_000_000
 N_CELLS = 25
 SAMPLE = 4096
@@ -105,6 +111,32 @@ def test_headline_step_is_bit_exact_against_the_oracle_at_full_size(ca, oracle, 
     print(f"headline sample vs reference fp32 {e32.max():.2e}, fp64 {e64.max():.2e}")
     assert e32[:5].max() < 2.4e-5 and e64[:5].max() < 2.0e-5
     assert np.array_equal(got[:, 5], x[:, 5]) and np.all(got[:, 6] == 1.0)
+
+
+def test_bench_dump_outputs_are_the_timed_step(ca, tmp_path):
+    """`bench.py --dump-outputs DIR` writes what its last timed step returned: the outgoing beam of the seeded headline input,
+    bit for bit the beam this process gets from the same step, and its global moments; float32 / float64, 64 MB at most."""
+    from cheetah_amd import sharding
+
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--no-configs", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], cwd=ROOT,
+                         env=dict(os.environ, CHX_BENCH_NO_PMC="1"), capture_output=True, text=True, timeout=900)
+    assert res.returncode == 0, res.stderr[-3000:]
+    line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    files = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(files) == {"particles", "energy", "particle_charges", "survival_probabilities", "s", "moments"}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum((tmp_path / f).stat().st_size for f in os.listdir(tmp_path)) <= 64 * 2**20
+    torch.manual_seed(1234)
+    beam = ca.ParticleBeam.from_parameters(num_particles=N, dtype=torch.float32, device="cuda")
+    out = ca.Segment(_fodo(ca)).track_elementwise(beam, fused=False)
+    assert np.array_equal(files["particles"], out.particles.cpu().numpy())
+    assert np.array_equal(files["particle_charges"], out.particle_charges.cpu().numpy())
+    assert float(files["energy"]) == float(out.energy)
+    mom = sharding.global_moments(out).cpu().numpy()
+    assert files["moments"].dtype == np.float64 and np.allclose(files["moments"], mom, rtol=1e-12, atol=0)
+    assert float(np.sqrt(files["moments"][8])) == pytest.approx(line["config"]["sigma_x_out"], rel=1e-12)
 
 
 @pytest.mark.parametrize("precision", ["double", "mixed", "storage"])

@@ -1,7 +1,10 @@
 """world_size-2 gloo test of the multi-GPU collective logic (cheetah_amd/sharding.py) on CPU.
 
 The per-rank partial reductions come from the CPU oracle here (on the GPU box they come from the
-chx_moment_* kernels); what is under test is the sharding arithmetic and the two all-reduces."""
+chx_moment_* kernels); what is under test is the sharding arithmetic and the two all-reduces.
+
+The workers meet at `dist.monitored_barrier()`, gloo's host-side barrier: `dist.barrier()` first asks torch for the machine's
+accelerator, which starts the GPU runtime in every one of these CPU-only processes on a machine that has a GPU."""
 import os
 import socket
 import time
@@ -59,7 +62,7 @@ def _worker(rank, world, port, x, w, q):
     allreduce_grid(grid)
     if rank == 0:
         q.put((out.numpy(), grid.numpy()))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -109,7 +112,7 @@ def _worker_merge(rank, world, port, x, w, q):
     out = gather_merge_moments(torch.from_numpy(np.nan_to_num(local, nan=0.0)))
     if rank == 0:
         q.put(out.numpy())
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -207,7 +210,7 @@ def _worker_chain_rows(rank, world, port, x, w, q):
             local[0, 8 + diag] = ((ws * xs[:, col] ** 2).sum() - W * m * m) / (W - W2 / W)
     rows, n = gather_moments_rows(torch.from_numpy(local))
     q.put((rank, rows.numpy(), n))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -280,7 +283,7 @@ def _worker_beam_properties(rank, world, port, x, w, qc, q):
     assert calls["n"] == 3 and gathers["n"] == 2
     dist.all_gather = real
     q.put((rank, got, local_sigma))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -364,7 +367,7 @@ def _worker_uneven(rank, world, port, x, w, q):
         sharding.allreduce_grid(grid)
         out.append((merged.numpy(), float(grid[0, 0]), (lo, hi)))
     q.put((rank, out))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -472,7 +475,7 @@ def _worker_sharded_gradients(rank, world, port, x, w, qc, q):
         bpm.track(beam_of(x0, w0, q0))
         reading = bpm.reading.clone()
     q.put((rank, float(loss.detach()), float(k.grad), float(a.grad), shares, reading.tolist(), bool(bpm.reading.requires_grad)))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
