@@ -1493,3 +1493,6 @@ from ._ops_sc import _bins3, _si  # noqa: E402,F401
 # ... and the deposits (cloud in cell, histogram, kernel density) and special functions in _ops_deposit.py
 from ._ops_deposit import *  # noqa: E402,F401,F403
 from ._ops_deposit import _cic_args, _cic_deposit_raw, _hist_args, _launch_cic  # noqa: E402,F401
+# ... and the slice statistics (ParticleBeam.slice_statistics) in _ops_slices.py
+from ._ops_slices import *  # noqa: E402,F401,F403
+from ._ops_slices import _slice_moments_bwd_raw, _slice_moments_raw  # noqa: E402,F401

@@ -344,6 +344,24 @@ class ParticleBeam(Beam):
         return ParameterBeam._from_moment_vector(self._moments(), self.particles.dtype, self.energy,
                                                  total_charge=self.total_charge, s=self.s, species=self.species)
 
+    def slice_statistics(self, num_slices: int = 50, tau_range=None, edges=None):
+        """Statistics of the beam's longitudinal slices -> `BeamSlices` (current profile, slice charge, and a ParameterBeam of the
+        slices' moments: slice emittances, Twiss parameters, centroids, energy spread).
+
+        The slices are intervals of tau (`particles[..., 4]`, metres): `edges` (…, S + 1), increasing and broadcastable to the
+        batch shape, used as given; otherwise `num_slices` equal intervals over `tau_range` = (lo, hi) (floats or tensors), or,
+        when both are None, over [min tau, max tau] of the particles with survival probability > 0, per batch row. Membership is
+        torch.histogram's with explicit edges: tau < e_0, tau > e_S and NaN are in no slice, tau == e_S is in the last slice.
+        When all surviving particles share one tau every edge equals it: every surviving particle is in the LAST slice, whose
+        width is 0 and whose current is +inf (for a positive charge).
+
+        One `chx_slice_moments` call (deterministic, no host synchronisation, capturable in a device graph); differentiable
+        with respect to the particles, the survival probabilities and the charges (the edges are constants). Not available
+        inside `sharding.particle_sharded` (NotImplementedError)."""
+        from .slices import slice_statistics
+
+        return slice_statistics(self, num_slices=num_slices, tau_range=tau_range, edges=edges)
+
     def _entry(self, index: int, take_sqrt: bool = False) -> torch.Tensor:
         """One entry of the moment vector (optionally its square root) in the beam's dtype. Under autograd this is ONE node
         (`_MomentEntry`) instead of select -> sqrt -> to, whose three backward nodes cost more host time than the moment

@@ -255,6 +255,25 @@ int chx_moments_bwd(const void* x, const void* w, const double* out, const doubl
  * array), dX and dW may each be NULL. d_out entries 0 (W) and 1 (sum w^2) are honoured here. */
 int chx_moments_bwd_w(const void* x, const void* w, const double* out, const double* d_out, int64_t B, int64_t Bx, int64_t Bw,
                       int64_t N, int dtype, void* dX, void* dW, void* stream);
+/* ---- slice statistics (ParticleBeam.slice_statistics): the particles of row b whose tau (column 4) falls into slice k of
+ * edges[Be][S + 1] (dtype, increasing; torch.histogram's membership: tau < e_0, tau > e_S and NaN are in no slice, tau == e_S is
+ * in the last one) -> out[B][S][29] with chx_moments' statistics of those particles alone (slices without weight: its NaN
+ * pattern) and charge[B][S] = sum q w. w, q (dtype, [Bw][N], [Bq][N]) may be NULL (all ones). 1 <= S <= CHX_SLICES_MAX.
+ * Deterministic: a stable counting sort by slice, fixed pieces of every slice reduced in fp64 about their own mean, the pieces
+ * merged in order; no float atomics. workspace: chx_slice_moments_workspace_bytes(B, N, S) (also for the backward pass).
+ * chx_slice_moments_bwd: given d_out[B][S][29] and d_charge[B][S] (either may be NULL) -> dX[B][N][7], dW[B][N], dQ[B][N]
+ * (dtype; NULL outputs are not computed; rows of broadcast inputs are NOT reduced — the caller sums). A particle in slice k gets
+ * chx_moments_bwd_w's gradient with row k of out / d_out plus the charge terms; particles in no slice and slices whose
+ * cotangent is zero contribute exactly 0. */
+#define CHX_SLICES_MAX 2048
+size_t chx_slice_moments_workspace_bytes(int64_t B, int64_t N, int32_t S);
+int chx_slice_moments(const void* x, const void* w, const void* q, const void* edges, int64_t B, int64_t Bx, int64_t Bw, int64_t Bq,
+                      int64_t Be, int64_t N, int32_t S, int dtype, double* out, double* charge, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int chx_slice_moments_bwd(const void* x, const void* w, const void* q, const void* edges, int64_t B, int64_t Bx, int64_t Bw,
+                          int64_t Bq, int64_t Be, int64_t N, int32_t S, int dtype, const double* out, const double* d_out,
+                          const double* d_charge, void* dX, void* dW, void* dQ, void* workspace, size_t workspace_bytes,
+                          void* stream);
 /* Backward of chx_moments(y), y_n = R x_n, with respect to the MAP R[BR][7][7] (dtype) when the particles x carry no
  * gradient: mu' = A mu + b, cov' = A C A^T (element.py:180-191 + utils/statistics.py:4-62), so
  * dR[B][7][7] (double) = [2 G A C + g_mu mu^T | g_mu; 0] from d_out[B][29] and the INCOMING beam's chx_moments
