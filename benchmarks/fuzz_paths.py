@@ -152,9 +152,11 @@ def one_case(seed):
     if mode < 0.62:
         replayed(rng, seg, els_a, els_b, beam, dt, fails)
         return specs, dt, B, n, fails
+    # (the layouts of assigned tensors come from a generator of their own: the draws above stay what they were for every seed)
+    layouts = np.random.default_rng([seed, 0x1A7])
     for round_ in range(int(rng.integers(1, 4))):
         if round_:
-            mutate(rng, els_a, els_b, fk)
+            mutate(rng, els_a, els_b, fk, layouts)
         check(seg, els_a, els_b, beam, dt, fails, f"track {round_}: ")
         if fails:
             break
@@ -397,9 +399,54 @@ def observables(seg, els_b, beam, dt, fails):
     compare(got.energy, want.energy, 1e-12 if dt == torch.float64 else 2e-7, "track_moments energy", fails)
 
 
-def mutate(rng, els_a, els_b, fk):
+def in_layout(lrng, value):
+    """`value` (a 0-d or (2,) setting) in a drawn layout, as a control loop hands it over: itself, an element or a row of a larger
+    tensor (an offset), a column of a (2, K) matrix (stride K), every second entry of a (4,) tensor (stride 2), a 0-d tensor expanded
+    to (2,) (stride 0). Returns (the tensor to assign, its base). The other entries of the base hold other values."""
+    r = lrng.random()
+    junk = float(lrng.normal()) * 3e-3
+    if value.dim() == 0:
+        if r < 0.4:
+            return value, value
+        base = torch.full((5,), junk, dtype=value.dtype, device=value.device)
+        base[3] = value
+        return base[3], base
+    if value.shape != (2,) or r < 0.2:
+        return value, value
+    if r < 0.4:
+        base = torch.full((4, 2), junk, dtype=value.dtype, device=value.device)
+        base[2] = value
+        return base[2], base
+    if r < 0.6:
+        base = torch.full((2, 3), junk, dtype=value.dtype, device=value.device)
+        base[:, 1] = value
+        return base[:, 1], base
+    if r < 0.8:
+        base = torch.full((4,), junk, dtype=value.dtype, device=value.device)
+        base[::2] = value
+        return base[::2], base
+    base = torch.full((3,), junk, dtype=value.dtype, device=value.device)
+    base[1] = value[0]
+    return base[1].expand(2), base
+
+
+def assign(lrng, ea, eb, name, value):
+    """`value` assigned to setting `name` of `ea` in a drawn layout (sometimes with its base edited in place afterwards), a contiguous
+    copy of the same values to `eb`."""
+    view, base = in_layout(lrng, value)
+    setattr(ea, name, view)
+    if base is not view and lrng.random() < 0.3:
+        with torch.no_grad():
+            base.mul_(float(lrng.uniform(0.5, 1.5)))     # (the walk's copy gets the values the view shows afterwards)
+    setattr(eb, name, view.detach().clone().contiguous())
+
+
+def mutate(rng, els_a, els_b, fk, layouts=None):
     """Between two tracks of the same Segment: settings edited in place, assigned as new tensors, diagnostics switched — the same on
-    both copies (the plans `Segment.track` keeps must follow)."""
+    both copies (the plans `Segment.track` keeps must follow). With `layouts` (a generator of its own, so that `rng` draws what it
+    always drew): the tensors assigned to `ea` come in drawn layouts (`in_layout`), and Quadrupoles and Solenoids get new
+    misalignments."""
+    lrng = layouts
     for ea, eb in zip(els_a, els_b):
         r = rng.random()
         if isinstance(ea, ca.Quadrupole) and r < 0.5:
@@ -408,14 +455,19 @@ def mutate(rng, els_a, els_b, fk):
                 with torch.no_grad():
                     ea.k1.mul_(f)
                     eb.k1.mul_(f)
+            elif lrng is not None:
+                assign(lrng, ea, eb, "k1", ea.k1 * f)
             else:
                 ea.k1 = ea.k1 * f
                 eb.k1 = eb.k1 * f
         elif isinstance(ea, (ca.HorizontalCorrector, ca.VerticalCorrector)) and r < 0.5:
             v = torch.tensor(float(rng.uniform(-2e-4, 2e-4)), **fk)
             if ea.angle.dim() == 0:
-                ea.angle = v
-                eb.angle = v.clone()
+                if lrng is not None:
+                    assign(lrng, ea, eb, "angle", v)
+                else:
+                    ea.angle = v
+                    eb.angle = v.clone()
         elif isinstance(ea, ca.BPM) and r < 0.3:
             ea.is_active = eb.is_active = not ea.is_active
         elif isinstance(ea, ca.Cavity) and r < 0.4:
@@ -424,8 +476,14 @@ def mutate(rng, els_a, els_b, fk):
                 eb.phase.add_(5.0)
         elif isinstance(ea, ca.Drift) and r < 0.1:
             f = float(rng.uniform(0.8, 1.2))
-            ea.length = ea.length * f
-            eb.length = eb.length * f
+            if lrng is not None:
+                assign(lrng, ea, eb, "length", ea.length * f)
+            else:
+                ea.length = ea.length * f
+                eb.length = eb.length * f
+        if lrng is not None and isinstance(ea, (ca.Quadrupole, ca.Solenoid)) and ea.misalignment.shape == (2,) \
+                and lrng.random() < 0.4:
+            assign(lrng, ea, eb, "misalignment", torch.tensor(lrng.normal(size=2) * 1e-4, **fk))
 
 
 def reading_or_refusal(screen):

@@ -232,18 +232,24 @@ class _FastRun:
         self.tensors = tuple([t for ts in self.per_tensors for t in ts])
 
     def verify(self) -> None:
-        """CHX_CHECK_PLANS=1: every stored address against the tensor it was read from."""
-        k = 0
+        """CHX_CHECK_PLANS=1: every stored address against the tensor it was read from. The expected address is derived from
+        the tensor's real stride, and a plan that addresses a setting `_read` would decline (a strided or expanded view) raises,
+        so a plan that took such a tensor by any route is found whatever address it holds."""
         for i, e in enumerate(self.elements):
             r = self.rows[i]
             if r is None or r == "identity":
                 continue
             for j, (t, index) in enumerate(e._builder_scalar_refs()):
-                want = t.data_ptr() if index is None else t.data_ptr() + index * t.element_size()
+                if index is None:
+                    want = t.data_ptr()
+                else:
+                    if t.dim() != 1 or not t.is_contiguous():
+                        raise RuntimeError(f"run plan of element {e.name!r}: setting {j} is entry {index} of a tensor of shape "
+                                           f"{tuple(t.shape)} and stride {t.stride()}, which the plan cannot address")
+                    want = t.data_ptr() + index * t.stride(0) * t.element_size()
                 if self.ptrs[self.slots[i] * _ops.MAX_PARAMS + j] != want:
                     raise RuntimeError(f"run plan of element {e.name!r}: the storage of setting {j} was replaced without an "
                                        "attribute assignment (`.data = ...`, `set_`, `resize_`); assign the tensor instead")
-                k += 1
 
 
 class _LatticePlan:

@@ -408,9 +408,12 @@ class Element(nn.Module):
                     old = buffers[name]
                     buffers[name] = value
                     if type(old) is torch.Tensor and old.dtype == value.dtype and old.shape == value.shape and old.device == value.device \
-                            and not value.requires_grad and not old.requires_grad and self._static_skippable:
+                            and not value.requires_grad and not old.requires_grad and self._static_skippable \
+                            and value.stride() == old.stride() and value.is_contiguous():
                         # only an address changed: the lattice's structure stands (`_hard_epoch` stays), and the plans that
-                        # registered for this element take the new address now instead of re-reading the element at the next track
+                        # registered for this element take the new address now instead of re-reading the element at the next track.
+                        # (A plan addresses entry i of a (2,) setting as data_ptr() + i * element_size(): a strided or expanded
+                        # view — `M[:, j]`, `v[::2]`, `t.expand(2)` — takes the full path below, whose re-read declines it.)
                         before = Element._epoch
                         self._touch(soft=True)
                         hooks = d.get("_hooks")
