@@ -53,6 +53,8 @@ __device__ __forceinline__ void cavity_epilogue(const double* __restrict__ c, co
 // MODE 0: x_out = R[0] x_in                      (single pass)
 // MODE 1: x_out = R[E-1] ... R[0] x_in           (fused run, particle stays in registers)
 // MODE 2: single pass + cavity epilogue
+// MODE 3: MODE 0 in place on a beam that fits the XCDs' L2s (chx_track_elementwise, passes 1..E-1): the loads keep their
+//         lines in L2, so the next pass, whose tile t again lands on workgroup t, reads the tile back from L2
 // Output rows are flat over B*N. Input is flat too (Bx == B) or shared (Bx == 1, handled by
 // indexing with n only). TP = particles per tile, PPT = TP / CHX_BLOCK.
 template <typename T, int PPT, int MODE>
@@ -79,8 +81,9 @@ __global__ __launch_bounds__(CHX_BLOCK) void apply_tile_kernel(
     const bool in_vec = in_vec_ok && (((in_row * N * 7 * (int64_t)sizeof(T)) & 15) == 0);
     const bool out_vec = out_vec_ok && (((b * N * 7 * (int64_t)sizeof(T)) & 15) == 0);
 
-    // streaming pass: bypass L2 allocation unless the input row is shared by several batch rows (re-read by others)
-    const bool nt_in = !(Bx == 1 && B > 1);
+    // streaming pass: bypass L2 allocation unless the input row is shared by several batch rows (re-read by others) or the
+    // pass runs in place on an L2-resident beam (MODE 3)
+    const bool nt_in = MODE != 3 && !(Bx == 1 && B > 1);
     tile_load<T, TP>(gin, lds, np * 7, in_vec, nt_in);
     __syncthreads();
 
@@ -446,6 +449,11 @@ int launch_wave(const void* x_in, const void* R, void* x_out, int64_t B, int64_t
     return CHX_OK;
 }
 
+// Beams up to this size take the wave-staged MODE-0 kernel (launch_tiles).
+constexpr int64_t kSmallBeamBytes = (int64_t)14 * 1024 * 1024 + 700 * 1024;
+// In-place element passes on beams up to this size run as MODE 3 (launch_inplace_pass): 7/8 of the 8 x 4 MiB of L2.
+constexpr int64_t kL2ResidentBytes = (int64_t)28 * 1024 * 1024;
+
 template <typename T, int MODE>
 int launch_tiles(const void* x_in, const void* R, void* x_out, const double* coeffs, int64_t B,
                  int64_t Bx, int64_t BR, int64_t N, int E, hipStream_t s) {
@@ -460,7 +468,7 @@ int launch_tiles(const void* x_in, const void* R, void* x_out, const double* coe
         if (rows_aligned) return launch_wave<T, 1, 64>(x_in, R, x_out, B, Bx, BR, N, s);
         if (PPT > 1) return launch_tiles_ppt<T, 1, MODE>(x_in, R, x_out, coeffs, B, Bx, BR, N, E, s);
     }
-    if (MODE == 0 && B * N * 7 * (int64_t)sizeof(T) <= (int64_t)14 * 1024 * 1024 + 700 * 1024) {
+    if (MODE == 0 && B * N * 7 * (int64_t)sizeof(T) <= kSmallBeamBytes) {
         // a small beam (what a rank of a strong-scaling run holds: 1.25e5 - 5e5 particles): a few hundred workgroup tiles leave
         // most CUs with one dependent load -> barrier -> store chain; four independent waves per workgroup, each staging its own
         // 64 rows, overlap them. Measured, 100 launches back to back (benchmarks/strong_leg_trace.py): 3e5 particles 0.459 ->
@@ -474,6 +482,20 @@ int launch_tiles(const void* x_in, const void* R, void* x_out, const double* coe
     if (MODE == 1 && E >= 4 && N >= 4 * CHX_BLOCK * 64)
         return launch_tiles_ppt<T, 2 * PPT, MODE>(x_in, R, x_out, coeffs, B, Bx, BR, N, E, s);
     return launch_tiles_ppt<T, PPT, MODE>(x_in, R, x_out, coeffs, B, Bx, BR, N, E, s);
+}
+
+// One in-place pass x = R x of chx_track_elementwise (passes 1..E-1). Between 14.7 and 28 MiB the beam stays in the XCDs'
+// L2s from pass to pass: workgroup t always takes tile t, and the dispatcher deals workgroup t to the same XCD in every
+// launch (observed: workgroup 0 on XCC 0, b on XCC b % 8, in every pass; for speed only — every tile is one workgroup's
+// whatever the placement). So the loads allocate in L2 (MODE 3) instead of streaming past it. Measured on MI355X,
+// 1e6 fp32 rows, 100 passes back to back (benchmarks/apply_l2_resident.hip): 9.4 -> 7.7 us per pass, but 11.1 with every
+// tile moved to another XCD each pass. Smaller beams keep the wave-staged kernel, larger ones MODE 0.
+template <typename T>
+int launch_inplace_pass(void* x, const void* R, int64_t B, int64_t BR, int64_t N, hipStream_t s) {
+    const int64_t bytes = B * N * 7 * (int64_t)sizeof(T);
+    if (bytes > kSmallBeamBytes && bytes <= kL2ResidentBytes)
+        return launch_tiles_ppt<T, tile_cfg<T>::PPT, 3>(x, R, x, nullptr, B, B, BR, N, 1, s);
+    return launch_tiles<T, 0>(x, R, x, nullptr, B, B, BR, N, 1, s);
 }
 
 template <typename T>
@@ -559,18 +581,18 @@ extern "C" int chx_track_elementwise(const void* x_in, const void* R, void* x_ou
     const char* Rp = (const char*)R;
     // pass 0 goes x_in -> x_out, every later pass updates x_out IN PLACE: a workgroup reads its whole tile into LDS before
     // it writes the same rows back, and no other workgroup touches them. Measured on MI355X at 1e6 particles: 8.9 us per
-    // pass in place vs 9.3 us ping-ponging between x_out and scratch (half the footprint in L2 / Infinity Cache).
+    // pass in place vs 9.3 us ping-ponging between x_out and scratch (half the footprint in L2 / Infinity Cache); in place
+    // the beam can also stay in the XCDs' L2s from pass to pass (launch_inplace_pass).
     // `scratch` is kept in the signature for ABI stability and is not used.
     (void)scratch;
-    const void* src = x_in;
-    int64_t src_B = Bx;
-    for (int64_t e = 0; e < E; ++e) {
-        st = chx_apply_affine7(src, Rp + (size_t)e * (size_t)BR * 49 * esz, x_out, B, src_B, BR, N, dtype, stream);
-        if (st != CHX_OK) return st;
-        src = x_out;
-        src_B = B;
+    st = chx_apply_affine7(x_in, Rp, x_out, B, Bx, BR, N, dtype, stream);
+    hipStream_t s = (hipStream_t)stream;
+    for (int64_t e = 1; e < E && st == CHX_OK; ++e) {
+        const void* Re = Rp + (size_t)e * (size_t)BR * 49 * esz;
+        st = dtype == CHX_F32 ? launch_inplace_pass<float>(x_out, Re, B, BR, N, s)
+                              : launch_inplace_pass<double>(x_out, Re, B, BR, N, s);
     }
-    return CHX_OK;
+    return st;
 }
 
 extern "C" int chx_cavity_track(const void* x_in, const void* R, const double* coeffs, void* x_out,
