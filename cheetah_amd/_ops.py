@@ -850,9 +850,11 @@ def dkd_track(kind: int, particles, params, param_shape, energy, mass_eV: float,
         e_out = e_out[:1].reshape(energy.shape)
     elif tuple(energy.shape) == tuple(batch_shape):
         e_out = e_out.reshape(batch_shape)
-    else:  # energy broadcast against other vector dims: pick one representative per energy entry
-        idx = torch.arange(energy.numel(), device=x.device).reshape(energy.shape).expand(batch_shape).reshape(-1)
-        e_out = torch.zeros(energy.numel(), dtype=x.dtype, device=x.device).index_copy(0, idx, e_out).reshape(energy.shape)
+    else:  # energy broadcast against other vector dims: the first row of each energy entry represents it (the rows of an
+        # entry are equal). Picked by slicing: an index_copy of all rows would hand each row the entry's gradient
+        lead = (1,) * (len(batch_shape) - energy.dim()) + tuple(energy.shape)
+        pick = tuple(slice(None) if a == b else slice(0, 1) for a, b in zip(lead, batch_shape))
+        e_out = e_out.reshape(batch_shape)[pick].reshape(energy.shape)
     return out.reshape(*batch_shape, N, 7), e_out
 
 
@@ -1430,9 +1432,34 @@ def parameter_track(mu, cov, tm, cavity_coeffs=None, batch_shape=None):
     return mu_out.reshape(*batch_shape, 7), cov_out.reshape(*batch_shape, 7, 7)
 
 
+def _screen_gaussian_autograd(mu, cov, shift, geom, width: int, height: int) -> torch.Tensor:
+    """The image of chx_screen_gaussian as fp64 tensor expressions, used only when the moments or the shift carry gradients:
+    autograd differentiates them. The sample positions carry none, like the reference's `torch.arange` grid (screen.py:284-287).
+    The off-diagonal entry is the mean of cov[0, 2] and cov[2, 0]: the reference's Cholesky factor gives that symmetric
+    gradient."""
+    f64 = torch.float64
+    m, c = mu.to(f64), cov.to(f64)
+    mx, my = m[..., 0], m[..., 2]
+    if shift is not None:
+        mx, my = mx - shift[..., 0].to(f64), my - shift[..., 1].to(f64)
+    cxx, cyy, cxy = c[..., 0, 0], c[..., 2, 2], 0.5 * (c[..., 0, 2] + c[..., 2, 0])
+    mx, my, cxx, cyy, cxy = torch.broadcast_tensors(mx, my, cxx, cyy, cxy)
+    g = geom.detach().to(f64)
+    px = g[0] + torch.arange(width, dtype=f64, device=mu.device) * g[1]
+    py = g[2] + torch.arange(height, dtype=f64, device=mu.device) * g[3]
+    e = lambda t: t[..., None, None]  # noqa: E731
+    dx, dy = px - e(mx), py.unsqueeze(-1) - e(my)          # (…, 1, width), (…, height, 1)
+    det = cxx * cyy - cxy * cxy
+    quad = (e(cyy) * dx * dx - 2.0 * e(cxy) * dx * dy + e(cxx) * dy * dy) / e(det)
+    return ((-0.5 * quad).exp() / e(2.0 * torch.pi * det.sqrt())).to(mu.dtype)
+
+
 def screen_gaussian(mu, cov, shift, geom, width: int, height: int) -> torch.Tensor:
-    """Bivariate-normal screen image (…, height, width) of a ParameterBeam (screen.py:255-291)."""
+    """Bivariate-normal screen image (…, height, width) of a ParameterBeam (screen.py:255-291). Differentiable wrt mu, cov
+    and shift (`_screen_gaussian_autograd`)."""
     require_device(mu, cov, geom)
+    if torch.is_grad_enabled() and (mu.requires_grad or cov.requires_grad or (shift is not None and shift.requires_grad)):
+        return _screen_gaussian_autograd(mu, cov, shift, geom, width, height)
     batch_shape = bshapes(mu.shape[:-1], cov.shape[:-2], shift.shape[:-1] if shift is not None else ())
     B = numel(batch_shape)
     m, Bm = flat_bcast(mu, batch_shape, 1)

@@ -100,7 +100,8 @@ def _launch_cic(a: CicArgs, N: int, ndim: int, device, mode: str = "auto") -> No
 class CicDeposit(torch.autograd.Function):
     """Differentiable deposit (the reference's CIC is differentiable through torch ops,
     utils/cloud_in_cell.py:14); backward = chx_cic_deposit_bwd: gradient wrt the particle coordinates
-    (through the corner weights) and wrt charges / survival probabilities."""
+    (through the corner weights) and wrt charges / survival probabilities; the extent, scale and shift follow from the
+    position gradient."""
 
     @staticmethod
     def forward(ctx, particles, charge, survival, cols, bins, extent, scale, shift, abs_charge, transpose_2d, mode):
@@ -127,7 +128,10 @@ class CicDeposit(torch.autograd.Function):
               "chx_cic_deposit_bwd")
         dweight = dweight.reshape(*batch_shape, N)
         dpos = dpos.reshape(*batch_shape, N, nd)
-        d_particles = d_charge = d_survival = d_extent = d_scale = None
+        d_particles = d_charge = d_survival = d_extent = d_scale = d_shift = None
+        if shift is not None and ctx.needs_input_grad[7]:
+            # v = scale * x - shift (the screen's misalignment, screen.py:196-214): dL/dshift = -sum_n dL/dv
+            d_shift = (-dpos.sum(dim=-2)).sum_to_size(shift.shape).to(shift.dtype)
         if ctx.needs_input_grad[5] or ctx.needs_input_grad[6]:
             # bin-space position pb = (v - l) / (r - l) * bins - 0.5 with v = scale * x - shift, and dpos = dL/dv:
             #   dL/dl = -sum dpos (r - v) / (r - l),  dL/dr = -sum dpos (v - l) / (r - l),  dL/dscale = sum dpos x
@@ -155,7 +159,7 @@ class CicDeposit(torch.autograd.Function):
         if survival is not None and ctx.needs_input_grad[2]:
             c_ = (charge.abs() if abs_charge else charge) if charge is not None else 1.0
             d_survival = (dweight * c_).sum_to_size(survival.shape)
-        return d_particles, d_charge, d_survival, None, None, d_extent, d_scale, None, None, None, None
+        return d_particles, d_charge, d_survival, None, None, d_extent, d_scale, d_shift, None, None, None
 
 
 def cic_deposit(particles, cols, bins, extent, charge=None, survival=None, scale=None, shift=None,
@@ -163,11 +167,11 @@ def cic_deposit(particles, cols, bins, extent, charge=None, survival=None, scale
     """Cloud-in-cell deposition (utils/cloud_in_cell.py:8-451) of columns `cols` of the 7-vectors.
 
     Returns (*batch, *bins); with transpose_2d the 2-D image is written directly as (bins[1], bins[0])
-    (the `.mT` of screen.py:339). Differentiable wrt particles / charge / survival.
+    (the `.mT` of screen.py:339). Differentiable wrt particles / charge / survival / extent / scale / shift.
     """
     if particles.requires_grad or (charge is not None and charge.requires_grad) or (
             survival is not None and survival.requires_grad) or extent.requires_grad or (
-            scale is not None and scale.requires_grad):
+            scale is not None and scale.requires_grad) or (shift is not None and shift.requires_grad):
         return CicDeposit.apply(particles, charge, survival, cols, bins, extent, scale, shift, abs_charge,
                                 transpose_2d, mode)
     return _cic_deposit_raw(particles, cols, bins, extent, charge, survival, scale, shift, abs_charge, transpose_2d,
