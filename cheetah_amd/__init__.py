@@ -29,6 +29,7 @@ from .accelerator import (  # noqa: F401
     Superimposed,
     Undulator,
     VerticalCorrector,
+    Wakefield,
 )
 from .particles import BeamSlices, ParameterBeam, ParticleBeam, Species  # noqa: F401
 from . import converters, graph, latticejson, track_methods, utils  # noqa: F401,E402

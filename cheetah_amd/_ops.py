@@ -1523,3 +1523,6 @@ from ._ops_deposit import _cic_args, _cic_deposit_raw, _hist_args, _launch_cic  
 # ... and the slice statistics (ParticleBeam.slice_statistics) in _ops_slices.py
 from ._ops_slices import *  # noqa: E402,F401,F403
 from ._ops_slices import _slice_moments_bwd_raw, _slice_moments_raw  # noqa: E402,F401
+# ... and the wakefield kick (the Wakefield element) in _ops_wake.py
+from ._ops_wake import *  # noqa: E402,F401,F403
+from ._ops_wake import _wake_kick_bwd_raw, _wake_kick_raw  # noqa: E402,F401

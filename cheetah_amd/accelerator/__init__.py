@@ -11,3 +11,4 @@ from .screen import Screen  # noqa: F401
 from .segment import Segment  # noqa: F401
 from .space_charge_kick import SpaceChargeKick  # noqa: F401
 from .superimposed import Superimposed  # noqa: F401
+from .wakefield import Wakefield  # noqa: F401

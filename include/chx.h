@@ -274,6 +274,33 @@ int chx_slice_moments_bwd(const void* x, const void* w, const void* q, const voi
                           int64_t Bq, int64_t Be, int64_t N, int32_t S, int dtype, const double* out, const double* d_out,
                           const double* d_charge, void* dX, void* dW, void* dQ, void* workspace, size_t workspace_bytes,
                           void* stream);
+/* ---- short-range wakefield (Wakefield element): per batch row b, over the SURVIVING particles (w > 0, finite tau; c = |q| w):
+ * tau_lo, tau_hi, node spacing D = (tau_hi - tau_lo) / (M - 1); node coordinate u = clamp((tau - tau_lo) / D, 0, M - 1) (0 when
+ * D = 0), k = min(floor u, M - 2), f = u - k; node deposits Q_k += (1 - f) c, Q_k+1 += f c (and X, Y with c x, c y when the
+ * transverse table is given); the tables wl[Ll] (V/C), wt[Lt] (V/(C m)) (fp64, entry n at s = n h[0]; Ll or Lt may be 0, not
+ * both) sampled linearly at s = n D, 0 beyond the last entry, the n = 0 sample halved; V_k = -sum_{m<=k} Wl~_{k-m} Q_m,
+ * U_k = sum_{m<=k} Wt~_{k-m} X_m (Y likewise); every particle (dead ones too; NaN tau -> NaN) gets
+ * delta += scale[b] V(u), px += scale[b] Ux(u), py += scale[b] Uy(u) (linear interpolation, fp64, rounded once), scale[B]
+ * fp64 = factor |Z| / p0c. A row without surviving particles is copied bit for bit. out[B][N][7], state[B][CHX_WAKE_STATE_DOUBLES(M)]
+ * (the row header, node kicks and deposits the backward pass reads). x, q, w (dtype, [Bx][N][7], [Bq][N], [Bw][N]).
+ * Deterministic: the deposits are 64-bit fixed-point sums (LDS then global integer atomics), scaled per row and channel from a
+ * bound of the channel's total so that no sum overflows; every other reduction is in a fixed order. 2 <= M <= CHX_WAKE_MAX_BINS.
+ * workspace: chx_wake_workspace_bytes(B, N, M) (also for the backward pass).
+ * chx_wake_kick_bwd: given d_out[B][N][7] (dtype) and the forward's state -> dX[B][N][7], dC[B][N] (dtype; gradient with
+ * respect to c, 0 for particles that do not deposit; may be NULL), d_scale[B], d_wl[Ll], d_wt[Lt] (fp64, summed over the rows;
+ * each may be NULL). The node spacing is a constant (no gradient through tau_lo, tau_hi). Rows of broadcast inputs are NOT
+ * reduced — the caller sums. */
+#define CHX_WAKE_MAX_BINS 4096
+#define CHX_WAKE_STATE_HEADER 8
+#define CHX_WAKE_STATE_DOUBLES(M) (CHX_WAKE_STATE_HEADER + 6 * (int64_t)(M))
+size_t chx_wake_workspace_bytes(int64_t B, int64_t N, int32_t M);
+int chx_wake_kick(const void* x, const void* q, const void* w, const double* scale, const double* wl, int64_t Ll, const double* wt,
+                  int64_t Lt, const double* h, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M, int dtype,
+                  void* out, double* state, void* workspace, size_t workspace_bytes, void* stream);
+int chx_wake_kick_bwd(const void* x, const void* q, const void* w, const double* scale, const double* wl, int64_t Ll,
+                      const double* wt, int64_t Lt, const double* h, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
+                      int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
+                      double* d_wl, double* d_wt, void* workspace, size_t workspace_bytes, void* stream);
 /* Backward of chx_moments(y), y_n = R x_n, with respect to the MAP R[BR][7][7] (dtype) when the particles x carry no
  * gradient: mu' = A mu + b, cov' = A C A^T (element.py:180-191 + utils/statistics.py:4-62), so
  * dR[B][7][7] (double) = [2 G A C + g_mu mu^T | g_mu; 0] from d_out[B][29] and the INCOMING beam's chx_moments
