@@ -1526,3 +1526,6 @@ from ._ops_slices import _slice_moments_bwd_raw, _slice_moments_raw  # noqa: E40
 # ... and the wakefield kick (the Wakefield element) in _ops_wake.py
 from ._ops_wake import *  # noqa: E402,F401,F403
 from ._ops_wake import _wake_kick_bwd_raw, _wake_kick_raw  # noqa: E402,F401
+# ... and the steady-state CSR kick (the CSRKick element) in _ops_csr.py
+from ._ops_csr import *  # noqa: E402,F401,F403
+from ._ops_csr import _csr_kick_bwd_raw, _csr_kick_raw  # noqa: E402,F401

@@ -84,6 +84,35 @@ class Dipole(Element):
     def is_active(self) -> bool:
         return bool((self.angle != 0).any().item())
 
+    def split_for_csr(self, num_kicks: int, num_bins: int = 200) -> list[Element]:
+        """The bend as `num_kicks` x [Dipole of L / n and theta / n, CSRKick(L / n, theta / n, num_bins)]: steady-state CSR kicks
+        spread along the arc. Only the first piece keeps the entrance face (dipole_e1, fringe_integral, the entrance fringe of
+        `fringe_at`) and only the last keeps the exit face; k1, tilt, gap, gap_exit, fringe_type and tracking_method are kept.
+        An RBend becomes Dipole pieces with its effective face angles. A bend of zero angle is returned unchanged, as [self]."""
+        from .csr import CSRKick, check_num_bins, check_num_kicks
+
+        n = check_num_kicks(num_kicks, "Dipole.split_for_csr")
+        num_bins = check_num_bins(num_bins, "Dipole.split_for_csr")
+        if not bool((self.angle != 0).any()):
+            return [self]
+        fk = {"device": self.angle.device, "dtype": self.angle.dtype}
+        length, angle = self.length / n, self.angle / n
+        entrance, exit_ = self.fringe_at in ("both", "entrance"), self.fringe_at in ("both", "exit")
+        parts = []
+        for i in range(n):
+            first, last = i == 0, i == n - 1
+            fringe_in, fringe_out = entrance and first, exit_ and last
+            fringe_at = ("both" if fringe_out else "entrance") if fringe_in else ("exit" if fringe_out else "neither")
+            parts.append(Dipole(
+                length, angle=angle, k1=self.k1, dipole_e1=self._e1 if first else torch.zeros_like(self._e1),
+                dipole_e2=self._e2 if last else torch.zeros_like(self._e2), tilt=self.tilt, gap=self.gap, gap_exit=self.gap_exit,
+                fringe_integral=self.fringe_integral if first else torch.zeros_like(self.fringe_integral),
+                fringe_integral_exit=self.fringe_integral_exit if last else torch.zeros_like(self.fringe_integral_exit),
+                fringe_at=fringe_at, fringe_type=self.fringe_type, tracking_method=self.tracking_method,
+                name=f"{self.name}_csr_{i}", sanitize_name=False, **fk))
+            parts.append(CSRKick(length, angle, num_bins=num_bins, name=f"{self.name}_csr_kick_{i}", sanitize_name=False, **fk))
+        return parts
+
     @property
     def defining_features(self) -> list[str]:
         return super().defining_features + ["length", "angle", "k1", "dipole_e1", "dipole_e2", "tilt", "gap",

@@ -1864,6 +1864,25 @@ class Segment(Element):
         merged_elements.append(current)
         return self.__class__(elements=merged_elements, name=self.name, metadata=deepcopy(self.metadata))
 
+    def with_csr_kicks(self, num_kicks: int, num_bins: int = 200, except_for=None) -> "Segment":
+        """Every bending Dipole (and RBend) split by `Dipole.split_for_csr(num_kicks, num_bins)` into pieces with steady-state CSR
+        kicks between them, nested Segments included; other elements, bends of zero angle and names in `except_for` unchanged."""
+        from .csr import check_num_bins, check_num_kicks
+        from .dipole import Dipole
+
+        check_num_kicks(num_kicks, "Segment.with_csr_kicks")
+        check_num_bins(num_bins, "Segment.with_csr_kicks")
+        except_for = except_for or []
+        elements = []
+        for e in self.elements:
+            if isinstance(e, Segment):
+                elements.append(e.with_csr_kicks(num_kicks, num_bins, except_for))
+            elif isinstance(e, Dipole) and e.name not in except_for:
+                elements += e.split_for_csr(num_kicks, num_bins)
+            else:
+                elements.append(e)
+        return self.__class__(elements=elements, name=self.name, metadata=deepcopy(self.metadata))
+
     def _no_plot(self, *args, **kwargs):
         raise NotImplementedError("Segment.plot_*: plotting is outside this tracking engine (SURVEY.md section 2); "
                                   "`get_beam_attrs_along_segment` gives the numbers the reference's plots draw")

@@ -1,0 +1,412 @@
+// chx_csr.hip — steady-state coherent synchrotron radiation kick (CSRKick element): the 1-D energy change of an ultra-relativistic
+// bunch on a circular arc (Derbenev et al., TESLA-FEL 95-05; Saldin, Schneidmiller, Yurkov, NIM A 398 (1997) 373), with the line
+// density piecewise linear between M nodes in tau and the kernel (z - z')^(-1/3) integrated exactly over every interval. Per batch
+// row, every grid quantity in fp64:
+//   F1. wake_range_kernel     (chx_grid1d_dev.h) partials of the surviving particles' tau range and charge; zeroes the grid
+//   F2. wake_deposit_kernel   (chx_grid1d_dev.h) the row header and the fixed-point node deposit D_k (one channel)
+//   F3. csr_toeplitz_kernel   one workgroup per (row, 64 nodes): b_j = a_(j-1) - a_j formed into LDS, the anti-causal sum
+//                             S_k = sum_j b_j D_(k+j) over the nodes behind, its four waves splitting the sources, merged in order
+//   F4. csr_kick_kernel       one thread per particle: gather of the node kicks times the row's scale (formed by F3 from the
+//                             energy, L and theta pointers), delta updated in fp64, rounded once
+// Backward (same pattern): B1 bounds of the gather's cotangents and the per-row partials of d(scale); B2 their fixed-point deposit;
+// B3 the causal correlation (adjoint of the anti-causal sum); B4 one pass over the particles (adjoint of the deposit and of the
+// node coordinate).
+#include "chx_grid1d_dev.h"
+
+namespace {
+
+constexpr double kCoulomb = 8.9875517923e9;   // k_e = 1 / (4 pi eps0), V m / C
+
+__host__ __device__ inline int64_t csr_state_row(int M) { return CHX_CSR_STATE_DOUBLES(M); }
+
+struct CsrWs {
+    double* part;               // [B][G][kPart] forward partials
+    unsigned long long* grid;   // [B][M] fixed-point deposit
+    double* bpart;              // [B][G][kPart] backward partials
+    double* bhdr;               // [B][kHdr] backward header: valid, S of the cotangent deposit
+    unsigned long long* ggrid;  // [B][M] fixed-point cotangents of the node kicks
+    double* adj;                // [B][M] cotangents of the deposits
+    size_t bytes;
+};
+
+CsrWs csr_ws(void* base, int64_t B, int64_t N, int M) {
+    CsrWs w;
+    char* p = (char*)base;
+    size_t o = 0;
+    auto take = [&](size_t nbytes) { char* r = p ? p + o : nullptr; o += al256(nbytes); return r; };
+    const int G = wake_groups(N);
+    w.part = (double*)take((size_t)(B * G * kPart) * 8);
+    w.grid = (unsigned long long*)take((size_t)(B * M) * 8);
+    w.bpart = (double*)take((size_t)(B * G * kPart) * 8);
+    w.bhdr = (double*)take((size_t)(B * kHdr) * 8);
+    w.ggrid = (unsigned long long*)take((size_t)(B * M) * 8);
+    w.adj = (double*)take((size_t)(B * M) * 8);
+    w.bytes = o;
+    return w;
+}
+
+// The row kicks at all: surviving particles and a node spacing h > 0.
+__device__ __forceinline__ bool csr_live(const double* st) { return st[0] != 0.0 && st[2] > 0.0; }
+
+// The row's scale |Z| L^(1/3) |theta|^(2/3) / p0c in fp64; p0c = beta gamma m c^2 as `Beam.p0c` (wake_scale in _ops_wake.py).
+template <typename T>
+__device__ __forceinline__ double csr_scale(const T* energy, int64_t Be, const T* length, int64_t Bl, const T* angle, int64_t Ba,
+                                            double mass, double absz, int64_t b) {
+    const double e = (double)energy[Be == 1 ? 0 : b], L = (double)length[Bl == 1 ? 0 : b], th = (double)angle[Ba == 1 ? 0 : b];
+    const double gamma = e / mass;
+    const double beta = fabs(gamma) > 0.0 ? sqrt(fmax(1.0 - 1.0 / (gamma * gamma), 0.0)) : 1.0;
+    const double lf = L > 0.0 ? cbrt(L) : (L == 0.0 ? 0.0 : __longlong_as_double(0x7ff8000000000000LL));
+    const double c = cbrt(fabs(th));
+    return absz * lf * (c * c) / (beta * gamma * mass);
+}
+
+// a_j = (j+1)^(2/3) - j^(2/3) without the cancellation.
+__device__ __forceinline__ double csr_a(int j) {
+    const double x = (double)j, y = x + 1.0, cx = cbrt(x), cy = cbrt(y), cxy = cbrt(x * y);
+    return (2.0 * x + 1.0) / (y * cy + cxy * cxy + x * cx);
+}
+
+// LDS table bt[i] = b_(i - 128) for lags 0 <= i - 128 < nlag, zero elsewhere (i < M + 256); scratch at[nlag] for a_j. Every lag
+// j < nlag the workgroup reads must be inside the table; lags beyond M - 1 only meet zero deposits.
+__device__ void csr_b_table(int M, int nlag, double* bt, double* at) {
+    for (int j = threadIdx.x; j < nlag; j += kWB) at[j] = csr_a(j);
+    __syncthreads();
+    for (int i = threadIdx.x; i < M + 256; i += kWB) {
+        const int j = i - 128;
+        bt[i] = (j < 0 || j >= nlag) ? 0.0 : (j == 0 ? -1.0 : at[j - 1] - at[j]);
+    }
+    __syncthreads();
+}
+
+inline size_t toeplitz_lds(int M) { return ((size_t)2 * M + 256 + 4 * 64) * sizeof(double); }
+
+// ---- F3 ----------------------------------------------------------------------------------------------------------------------
+// One workgroup per (row, 64 nodes k0 ... k0 + 63); workgroup 0 stores the row's scale in the last header slot, where F4 and the
+// backward pass read it; wave v takes the source tiles m0 = k0 + 64 (v + 4 i) < M; a tile's 64 deposits
+// are loaded one per lane and broadcast with readlane. Lag m - k of source m0 + j: bt index 128 + m0 + j - k in [65, M + 190].
+template <typename T>
+__global__ __launch_bounds__(kWB) void csr_toeplitz_kernel(int M, const T* __restrict__ energy, int64_t Be,
+                                                           const T* __restrict__ length, int64_t Bl, const T* __restrict__ angle,
+                                                           int64_t Ba, double mass, double absz,
+                                                           const unsigned long long* __restrict__ grid, double* __restrict__ state) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];            // bt[M + 256], at[M], acc[4][64]
+    const int64_t b = blockIdx.y;
+    const int k0 = blockIdx.x * kNodeBlock;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* st = state + b * csr_state_row(M);
+    double* bt = lds;
+    double* acc = lds + 2 * M + 256;
+    const bool live = csr_live(st);
+    if (blockIdx.x == 0 && threadIdx.x == 0) st[kHdr - 1] = csr_scale(energy, Be, length, Bl, angle, Ba, mass, absz, b);
+    if (live) csr_b_table(M, M - k0, bt, lds + M + 256);
+    const unsigned long long* gq = grid + b * M;
+    const double SQ = st[3], h = st[2];
+    const int k = k0 + lane;
+    double v = 0.0;
+    if (live) {
+        for (int m0 = k0 + wave * 64; m0 < M; m0 += kWB) {
+            const int m = m0 + lane;
+            const double d = m < M ? from_fixed(gq[m], SQ) : 0.0;
+            const int base = 128 + m0 - k;
+#pragma unroll 16
+            for (int j = 0; j < 64; ++j) v += bt[base + j] * readlane_d(d, j);
+        }
+    }
+    acc[wave * 64 + lane] = v;
+    __syncthreads();
+    if (wave == 0 && k < M) {
+        const double s = ((acc[lane] + acc[64 + lane]) + acc[128 + lane]) + acc[192 + lane];
+        // 3^(2/3) k_e h^(-4/3): the node energy change per unit |Z| L^(1/3) |theta|^(2/3)
+        st[kHdr + k] = live ? cbrt(9.0) * kCoulomb / (h * cbrt(h)) * s : 0.0;
+    }
+}
+
+// ---- F4 ----------------------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kWB) void csr_kick_kernel(const T* __restrict__ x, int64_t Bx, int64_t N, int M,
+                                                       const double* __restrict__ state, T* __restrict__ out) {
+    const int64_t b = blockIdx.y;
+    const int64_t n = (int64_t)blockIdx.x * kWB + threadIdx.x;
+    if (n >= N) return;
+    const T* xr = x + ((Bx == 1 ? 0 : b) * N + n) * 7;
+    T* o = out + (b * N + n) * 7;
+    T v[7];
+#pragma unroll
+    for (int c = 0; c < 7; ++c) v[c] = xr[c];
+    const double* st = state + b * csr_state_row(M);
+    if (csr_live(st)) {
+        int k;
+        double f;
+        bool in;
+        wake_node((double)v[4], st[1], st[2], M, k, f, in);
+        // no field (a scale of 0: theta = 0 or L = 0; both nodes 0: no charge) leaves delta's bits as they are, NaN tau included
+        const double sc = st[kHdr - 1], n0 = st[kHdr + k], n1 = st[kHdr + k + 1];
+        if (sc != 0.0 && (n0 != 0.0 || n1 != 0.0)) {
+            const double dv = sc * ((1.0 - f) * n0 + f * n1);
+            if (dv != 0.0) v[5] = (T)((double)v[5] + dv);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 7; ++c) o[c] = v[c];
+}
+
+// ---- B1: bound of the gather's cotangents a = scale g_delta; partials of d(scale) = sum g_delta dE(u) -------------------------------
+template <typename T>
+__global__ __launch_bounds__(kWB) void csr_bwd_range_kernel(const T* __restrict__ x, int64_t Bx, int64_t N, int G, int M,
+                                                            const double* __restrict__ state, const T* __restrict__ gout,
+                                                            double* __restrict__ bpart, unsigned long long* __restrict__ ggrid) {
+    __shared__ double red[4 * 4];
+    const int64_t b = blockIdx.y;
+    const int g = blockIdx.x;
+    unsigned long long* gr = ggrid + b * M;
+    for (int64_t i = (int64_t)g * kWB + threadIdx.x; i < M; i += (int64_t)G * kWB) gr[i] = 0ull;
+    const double* st = state + b * csr_state_row(M);
+    const double* node = st + kHdr;
+    const int64_t chunk = (N + G - 1) / G, n0 = g * chunk, n1 = n0 + chunk < N ? n0 + chunk : N;
+    double lo = 0.0, hi = 0.0, s[2] = {0.0, 0.0};
+    if (csr_live(st)) {
+        const double sc = st[kHdr - 1];
+        const T* xb = x + (Bx == 1 ? 0 : b) * N * 7;
+        const T* gb = gout + b * N * 7;
+        for (int64_t n = n0 + threadIdx.x; n < n1; n += kWB) {
+            int k;
+            double f;
+            bool in;
+            wake_node((double)xb[n * 7 + 4], st[1], st[2], M, k, f, in);
+            if (isnan(f)) continue;
+            const double g5 = (double)gb[n * 7 + 5];
+            s[0] += fabs(sc * g5);
+            s[1] += g5 * ((1.0 - f) * node[k] + f * node[k + 1]);
+        }
+    }
+    block_reduce<2>(lo, hi, s, red);
+    if (threadIdx.x == 0) {
+        double* p = bpart + (b * G + g) * kPart;
+        p[0] = s[0]; p[1] = s[1]; p[2] = p[3] = p[4] = p[5] = p[6] = p[7] = 0.0;
+    }
+}
+
+// ---- B2: fixed-point deposit of the gather's cotangents, as F2; workgroup 0 writes d(scale) and the backward header -----------------
+template <typename T>
+__global__ __launch_bounds__(kWB) void csr_bwd_deposit_kernel(const T* __restrict__ x, int64_t Bx, int64_t N, int G, int M,
+                                                              const double* __restrict__ state,
+                                                              const T* __restrict__ gout, const double* __restrict__ bpart,
+                                                              double* __restrict__ bhdr, double* __restrict__ d_scale,
+                                                              unsigned long long* __restrict__ ggrid) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long hist[];
+    __shared__ double red[4 * 4];
+    __shared__ double S;
+    const int64_t b = blockIdx.y;
+    const int g = blockIdx.x;
+    const double* st = state + b * csr_state_row(M);
+    double lo = 0.0, hi = 0.0, s[2] = {0.0, 0.0};
+    for (int gg = threadIdx.x; gg < G; gg += kWB) {
+        const double* p = bpart + (b * G + gg) * kPart;
+        s[0] += p[0]; s[1] += p[1];
+    }
+    block_reduce<2>(lo, hi, s, red);
+    if (threadIdx.x == 0) {
+        S = fixed_scale(s[0]);
+        if (g == 0) {
+            d_scale[b] = s[1];
+            bhdr[b * kHdr] = st[0];
+            bhdr[b * kHdr + 1] = S;
+        }
+    }
+    __syncthreads();
+    if (!csr_live(st)) return;
+    const double S0 = S;
+    for (int i = threadIdx.x; i < M; i += kWB) hist[i] = 0ull;
+    __syncthreads();
+    const T* xb = x + (Bx == 1 ? 0 : b) * N * 7;
+    const T* gb = gout + b * N * 7;
+    const double sc = st[kHdr - 1];
+    const int64_t chunk = (N + G - 1) / G, n0 = g * chunk, n1 = n0 + chunk < N ? n0 + chunk : N;
+    for (int64_t n = n0 + threadIdx.x; n < n1; n += kWB) {
+        int k;
+        double f;
+        bool in;
+        wake_node((double)xb[n * 7 + 4], st[1], st[2], M, k, f, in);
+        if (isnan(f)) continue;
+        const double a = sc * (double)gb[n * 7 + 5];
+        atomicAdd(&hist[k], to_fixed((1.0 - f) * a, S0));
+        atomicAdd(&hist[k + 1], to_fixed(f * a, S0));
+    }
+    __syncthreads();
+    unsigned long long* gr = ggrid + b * M;
+    for (int i = threadIdx.x; i < M; i += kWB) {
+        const unsigned long long v = hist[i];
+        if (v) atomicAdd(&gr[i], v);
+    }
+}
+
+// ---- B3: adjoint of F3, GD_m = 3^(2/3) k_e h^(-4/3) sum_{k <= m} b_(m-k) GV_k ------------------------------------------------------
+// One workgroup per (row, 64 sources m0 ... m0 + 63); wave v takes the target tiles k0 = 64 (v + 4 i) <= m0 + 63. Lag m - k of
+// target k0 + j: bt index 128 + m - k0 - j in [2, M + 190].
+__global__ __launch_bounds__(kWB) void csr_bwd_toeplitz_kernel(int M, const double* __restrict__ state, const double* __restrict__ bhdr,
+                                                               const unsigned long long* __restrict__ ggrid, double* __restrict__ adj) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];            // bt[M + 256], at[M], acc[4][64]
+    const int64_t b = blockIdx.y;
+    const int m0 = blockIdx.x * kNodeBlock;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double* st = state + b * csr_state_row(M);
+    double* bt = lds;
+    double* acc = lds + 2 * M + 256;
+    const int mmax = m0 + kNodeBlock < M ? m0 + kNodeBlock : M;     // sources m < mmax: lags up to mmax - 1
+    const bool live = csr_live(st);
+    if (live) csr_b_table(M, mmax, bt, lds + M + 256);
+    const unsigned long long* gg = ggrid + b * M;
+    const double SV = bhdr[b * kHdr + 1], h = st[2];
+    const int m = m0 + lane;
+    double v = 0.0;
+    if (live) {
+        for (int k0 = wave * 64; k0 < mmax; k0 += kWB) {
+            const int k = k0 + lane;
+            const double a = k < M ? from_fixed(gg[k], SV) : 0.0;
+            const int base = 128 + m - k0;
+#pragma unroll 16
+            for (int j = 0; j < 64; ++j) v += bt[base - j] * readlane_d(a, j);
+        }
+    }
+    acc[wave * 64 + lane] = v;
+    __syncthreads();
+    if (wave == 0 && m < M) {
+        const double s = ((acc[lane] + acc[64 + lane]) + acc[128 + lane]) + acc[192 + lane];
+        adj[b * M + m] = live ? cbrt(9.0) * kCoulomb / (h * cbrt(h)) * s : 0.0;
+    }
+}
+
+// ---- B4: one pass over the particles ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kWB) void csr_bwd_particles_kernel(const T* __restrict__ x, const T* __restrict__ q,
+                                                                const T* __restrict__ w, int64_t Bx, int64_t Bq, int64_t Bw,
+                                                                int64_t N, int M, const double* __restrict__ state,
+                                                                const double* __restrict__ adj, const T* __restrict__ gout,
+                                                                T* __restrict__ dX, T* __restrict__ dC) {
+    const int64_t b = blockIdx.y;
+    const int64_t n = (int64_t)blockIdx.x * kWB + threadIdx.x;
+    if (n >= N) return;
+    const RowPtrs<T> r = row_ptrs(x, q, w, Bx, Bq, Bw, N, b);
+    const T* gr = gout + (b * N + n) * 7;
+    double gv[7];
+#pragma unroll
+    for (int c = 0; c < 7; ++c) gv[c] = (double)gr[c];
+    const double* st = state + b * csr_state_row(M);
+    double dc = 0.0;
+    if (csr_live(st)) {
+        const double tau = (double)r.x[n * 7 + 4];
+        int k;
+        double f;
+        bool in;
+        wake_node(tau, st[1], st[2], M, k, f, in);
+        const double* node = st + kHdr;
+        const double* ad = adj + b * M;
+        const double sc = st[kHdr - 1];
+        double df = sc * gv[5] * (node[k + 1] - node[k]);
+        const double wn = (double)r.w[n];
+        if (wn > 0.0 && isfinite(tau)) {
+            const double c = fabs((double)r.q[n]) * wn;
+            dc = (1.0 - f) * ad[k] + f * ad[k + 1];
+            df += c * (ad[k + 1] - ad[k]);
+        }
+        if (in) gv[4] += df / st[2];
+    }
+    T* o = dX + (b * N + n) * 7;
+#pragma unroll
+    for (int c = 0; c < 7; ++c) o[c] = (T)gv[c];
+    if (dC) dC[b * N + n] = (T)dc;
+}
+
+int check_csr(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M,
+              int dtype, const double* state) {
+    if (!x || !q || !w || !state || B < 1 || B > 65535 || N < 1 || N > 0x7fffffffLL || M < 2 || M > CHX_WAKE_MAX_BINS)
+        return CHX_ERR_INVALID_ARG;
+    if (!chx_bcast_ok(Bx, B) || !chx_bcast_ok(Bq, B) || !chx_bcast_ok(Bw, B)) return CHX_ERR_INVALID_ARG;
+    if (dtype != CHX_F32 && dtype != CHX_F64) return CHX_ERR_DTYPE;
+    if (!chx_aligned16(x)) return CHX_ERR_MISALIGNED;
+    return CHX_OK;
+}
+
+template <typename T>
+int csr_kick_t(const T* x, const T* q, const T* w, const T* energy, const T* length, const T* angle, double mass, double absz,
+               int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Ba, int64_t N, int M, T* out,
+               double* state, const CsrWs& ws, hipStream_t s) {
+    const int G = wake_groups(N);
+    if (!lds_ok(csr_toeplitz_kernel<T>, toeplitz_lds(M))) return CHX_ERR_LAUNCH;
+    hipLaunchKernelGGL(wake_range_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, G, M, 0,
+                       (int64_t)M, ws.part, ws.grid);
+    CHX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(wake_deposit_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), (size_t)M * 8, s, x, q, w, Bx, Bq, Bw, N, G,
+                       M, 0, 1, csr_state_row(M), (int64_t)M, ws.part, state, ws.grid);
+    CHX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(csr_toeplitz_kernel<T>, dim3((unsigned)((M + kNodeBlock - 1) / kNodeBlock), (unsigned)B), dim3(kWB),
+                       toeplitz_lds(M), s, M, energy, Be, length, Bl, angle, Ba, mass, absz, ws.grid, state);
+    CHX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(csr_kick_kernel<T>, dim3((unsigned)((N + kWB - 1) / kWB), (unsigned)B), dim3(kWB), 0, s, x, Bx, N, M, state,
+                       out);
+    CHX_CHECK_LAUNCH();
+    return CHX_OK;
+}
+
+template <typename T>
+int csr_kick_bwd_t(const T* x, const T* q, const T* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int M,
+                   const double* state, const T* gout, T* dX, T* dC, double* d_scale, const CsrWs& ws, hipStream_t s) {
+    const int G = wake_groups(N);
+    if (!lds_ok(csr_bwd_toeplitz_kernel, toeplitz_lds(M))) return CHX_ERR_LAUNCH;
+    hipLaunchKernelGGL(csr_bwd_range_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), 0, s, x, Bx, N, G, M, state, gout,
+                       ws.bpart, ws.ggrid);
+    CHX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(csr_bwd_deposit_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), (size_t)M * 8, s, x, Bx, N, G, M, state,
+                       gout, ws.bpart, ws.bhdr, d_scale, ws.ggrid);
+    CHX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(csr_bwd_toeplitz_kernel, dim3((unsigned)((M + kNodeBlock - 1) / kNodeBlock), (unsigned)B), dim3(kWB),
+                       toeplitz_lds(M), s, M, state, ws.bhdr, ws.ggrid, ws.adj);
+    CHX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(csr_bwd_particles_kernel<T>, dim3((unsigned)((N + kWB - 1) / kWB), (unsigned)B), dim3(kWB), 0, s, x, q, w, Bx,
+                       Bq, Bw, N, M, state, ws.adj, gout, dX, dC);
+    CHX_CHECK_LAUNCH();
+    return CHX_OK;
+}
+
+}  // namespace
+
+extern "C" size_t chx_csr_workspace_bytes(int64_t B, int64_t N, int32_t M) {
+    if (B < 1 || N < 1 || M < 2 || M > CHX_WAKE_MAX_BINS) return 0;
+    return csr_ws(nullptr, B, N, M).bytes;
+}
+
+extern "C" int chx_csr_kick(const void* x, const void* q, const void* w, const void* energy, const void* length, const void* angle,
+                            double mass_eV, double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl,
+                            int64_t Ba, int64_t N, int32_t M, int dtype, void* out, double* state, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    const int st = check_csr(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
+    if (st != CHX_OK) return st;
+    if (!energy || !length || !angle || !(mass_eV > 0.0) || !chx_bcast_ok(Be, B) || !chx_bcast_ok(Bl, B) || !chx_bcast_ok(Ba, B) ||
+        !out)
+        return CHX_ERR_INVALID_ARG;
+    if (!chx_aligned16(out)) return CHX_ERR_MISALIGNED;
+    const CsrWs ws = csr_ws(workspace, B, N, M);
+    if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == CHX_F32)
+        return csr_kick_t<float>((const float*)x, (const float*)q, (const float*)w, (const float*)energy, (const float*)length,
+                                 (const float*)angle, mass_eV, abs_charge, B, Bx, Bq, Bw, Be, Bl, Ba, N, M, (float*)out, state, ws, s);
+    return csr_kick_t<double>((const double*)x, (const double*)q, (const double*)w, (const double*)energy, (const double*)length,
+                              (const double*)angle, mass_eV, abs_charge, B, Bx, Bq, Bw, Be, Bl, Ba, N, M, (double*)out, state, ws, s);
+}
+
+extern "C" int chx_csr_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
+                                int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    const int st = check_csr(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
+    if (st != CHX_OK) return st;
+    if (!d_out || !dX || !d_scale) return CHX_ERR_INVALID_ARG;
+    const CsrWs ws = csr_ws(workspace, B, N, M);
+    if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == CHX_F32)
+        return csr_kick_bwd_t<float>((const float*)x, (const float*)q, (const float*)w, B, Bx, Bq, Bw, N, M, state,
+                                     (const float*)d_out, (float*)dX, (float*)dC, d_scale, ws, s);
+    return csr_kick_bwd_t<double>((const double*)x, (const double*)q, (const double*)w, B, Bx, Bq, Bw, N, M, state,
+                                  (const double*)d_out, (double*)dX, (double*)dC, d_scale, ws, s);
+}

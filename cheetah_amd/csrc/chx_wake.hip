@@ -12,24 +12,11 @@
 // Backward (same pattern): B1 bounds of the cotangents and the per-row partials of d(scale); B2 deposit of the gather's
 // cotangents; B3 the anti-causal correlation (adjoint of the convolution) and B4 the correlation for the sampled wakes' gradient;
 // B5 one pass over the particles (adjoint of the deposit and of the node coordinate); B6 the tables' gradient (adjoint of the
-// sampling), one thread per table entry.
-#include "chx_common.h"
-
-#include <math.h>
+// sampling), one thread per table entry. F1 and F2 live in chx_grid1d_dev.h, shared with the CSR kick (chx_csr.hip).
+#include "chx_grid1d_dev.h"
 
 namespace {
 
-constexpr int kWB = CHX_BLOCK;                // threads per workgroup
-constexpr int kMaxG = 1024;                   // workgroups per row of a particle pass (the merge: thread t takes t, t + 256, ...)
-constexpr int kPart = 8;                      // doubles per workgroup partial
-constexpr int kHdr = CHX_WAKE_STATE_HEADER;   // state row header: valid, tau_lo, D, S[3] (fixed-point scales), tau_hi, (unused)
-constexpr int kNodeBlock = 64;                // nodes per workgroup of the convolution kernels (one per lane)
-
-inline int wake_groups(int64_t N) {
-    const int64_t g = (N + 2047) / 2048;
-    return (int)(g < 1 ? 1 : g > kMaxG ? kMaxG : g);
-}
-inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 __host__ __device__ inline int64_t state_row(int M) { return CHX_WAKE_STATE_DOUBLES(M); }
 
 struct WakeWs {
@@ -60,23 +47,6 @@ WakeWs wake_ws(void* base, int64_t B, int64_t N, int M) {
     return w;
 }
 
-// Node coordinate of a particle: u = clamp((tau - lo) / D, 0, M - 1) (0 when D = 0), k = min(floor(u), M - 2), f = u - k;
-// `in` = the clamp passed u through (du/dtau = 1/D). NaN tau: f = NaN at node 0.
-__device__ __forceinline__ void wake_node(double tau, double lo, double D, int M, int& k, double& f, bool& in) {
-    in = false;
-    if (isnan(tau)) { k = 0; f = tau; return; }
-    double u = 0.0;
-    if (D > 0.0) {
-        const double ur = (tau - lo) / D;
-        in = ur >= 0.0 && ur <= (double)(M - 1);
-        u = in ? ur : (ur < 0.0 ? 0.0 : (double)(M - 1));
-    }
-    int kk = (int)floor(u);
-    if (kk > M - 2) kk = M - 2;
-    k = kk;
-    f = u - (double)kk;
-}
-
 // Position of node n in the table: p = n D / h; false beyond the last entry (the wake is 0 there), else entry j and fraction t
 // of the linear interpolation (1 - t) T[j] + t T[j + 1] (a table of one entry: j = 0, t = 0).
 __device__ __forceinline__ bool wake_table_pos(int n, double D, double h, int64_t L, int64_t& j, double& t) {
@@ -98,187 +68,11 @@ __device__ __forceinline__ double wake_sample(const double* __restrict__ T, int6
     return n == 0 ? 0.5 * v : v;     // the self term (beam loading): half the wake at s = 0
 }
 
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v = fmin(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) v = fmax(v, __shfl_xor(v, d, 64));
-    return v;
-}
-
-// Workgroup reduction in a fixed pattern: lo = min, hi = max, s[K] = sums; valid in thread 0.
-template <int K>
-__device__ __forceinline__ void block_reduce(double& lo, double& hi, double (&s)[K], double* red /* [4][K + 2] */) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    lo = wave_min(lo);
-    hi = wave_max(hi);
-#pragma unroll
-    for (int c = 0; c < K; ++c) s[c] = chx_wave_sum(s[c]);
-    if (lane == 0) {
-        red[wave * (K + 2)] = lo;
-        red[wave * (K + 2) + 1] = hi;
-#pragma unroll
-        for (int c = 0; c < K; ++c) red[wave * (K + 2) + 2 + c] = s[c];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int v = 1; v < kWB / 64; ++v) {
-            lo = fmin(lo, red[v * (K + 2)]);
-            hi = fmax(hi, red[v * (K + 2) + 1]);
-#pragma unroll
-            for (int c = 0; c < K; ++c) s[c] += red[v * (K + 2) + 2 + c];
-        }
-    }
-    __syncthreads();
-}
-
-// Fixed-point scale of a channel whose contributions sum (in magnitude) to at most `bound`: 2^(62 - e) with bound < 2^e, so
-// every partial sum stays below 2^62 (+ N/2 of rounding) < 2^63. 1 for an empty channel; 0 for a non-finite bound (the
-// channel's nodes then read back as NaN).
-__device__ __forceinline__ double fixed_scale(double bound) {
-    if (!isfinite(bound)) return 0.0;
-    if (bound <= 0.0) return 1.0;
-    int e;
-    frexp(bound, &e);
-    int x = 62 - e;
-    if (x > 1000) x = 1000;
-    return ldexp(1.0, x);
-}
-__device__ __forceinline__ unsigned long long to_fixed(double v, double S) { return (unsigned long long)__double2ll_rn(v * S); }
-__device__ __forceinline__ double from_fixed(unsigned long long v, double S) {
-    return S == 0.0 ? __longlong_as_double(0x7ff8000000000000LL) : (double)(long long)v / S;
-}
-
-// The row header from the G partials of F1 (every workgroup of F2 computes the same one: a fixed order). hdr in LDS.
-__device__ void wake_row_header(const double* __restrict__ part, int G, int M, double* hdr, double* red) {
-    const int t = threadIdx.x;
-    double lo = INFINITY, hi = -INFINITY, s[3] = {0.0, 0.0, 0.0};
-    for (int g = t; g < G; g += kWB) {
-        const double* p = part + (int64_t)g * kPart;
-        lo = fmin(lo, p[0]); hi = fmax(hi, p[1]); s[0] += p[2]; s[1] += p[3]; s[2] += p[4];
-    }
-    block_reduce<3>(lo, hi, s, red);
-    if (t == 0) {
-        const bool valid = hi >= lo;
-        hdr[0] = valid ? 1.0 : 0.0;
-        hdr[1] = valid ? lo : 0.0;
-        hdr[2] = valid ? (hi - lo) / (double)(M - 1) : 0.0;
-        for (int c = 0; c < 3; ++c) hdr[3 + c] = fixed_scale(s[c]);
-        hdr[6] = valid ? hi : 0.0;
-        hdr[7] = 0.0;
-    }
-    __syncthreads();
-}
-
-template <typename T> struct RowPtrs {
-    const T* x; const T* q; const T* w;
-};
-template <typename T>
-__device__ __forceinline__ RowPtrs<T> row_ptrs(const T* x, const T* q, const T* w, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
-                                               int64_t b) {
-    RowPtrs<T> r;
-    r.x = x + (Bx == 1 ? 0 : b) * N * 7;
-    r.q = q + (Bq == 1 ? 0 : b) * N;
-    r.w = w + (Bw == 1 ? 0 : b) * N;
-    return r;
-}
-
-// ---- F1 ----------------------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(kWB) void wake_range_kernel(const T* __restrict__ x, const T* __restrict__ q, const T* __restrict__ w,
-                                                        int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int G, int M, int has_t,
-                                                        double* __restrict__ part, unsigned long long* __restrict__ grid) {
-    __shared__ double red[4 * 5];
-    const int64_t b = blockIdx.y;
-    const int g = blockIdx.x;
-    unsigned long long* gr = grid + b * 3 * M;
-    for (int64_t i = (int64_t)g * kWB + threadIdx.x; i < 3 * (int64_t)M; i += (int64_t)G * kWB) gr[i] = 0ull;
-    const RowPtrs<T> r = row_ptrs(x, q, w, Bx, Bq, Bw, N, b);
-    const int64_t chunk = (N + G - 1) / G, n0 = g * chunk, n1 = n0 + chunk < N ? n0 + chunk : N;
-    double lo = INFINITY, hi = -INFINITY, s[3] = {0.0, 0.0, 0.0};
-    for (int64_t n = n0 + threadIdx.x; n < n1; n += kWB) {
-        const double wn = (double)r.w[n], tau = (double)r.x[n * 7 + 4];
-        if (wn > 0.0 && isfinite(tau)) {
-            const double c = fabs((double)r.q[n]) * wn;
-            lo = fmin(lo, tau);
-            hi = fmax(hi, tau);
-            s[0] += c;
-            if (has_t) {
-                s[1] += c * fabs((double)r.x[n * 7]);
-                s[2] += c * fabs((double)r.x[n * 7 + 2]);
-            }
-        }
-    }
-    block_reduce<3>(lo, hi, s, red);
-    if (threadIdx.x == 0) {
-        double* p = part + (b * G + g) * kPart;
-        p[0] = lo; p[1] = hi; p[2] = s[0]; p[3] = s[1]; p[4] = s[2]; p[5] = p[6] = p[7] = 0.0;
-    }
-}
-
-// ---- F2 ----------------------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(kWB) void wake_deposit_kernel(const T* __restrict__ x, const T* __restrict__ q, const T* __restrict__ w,
-                                                          int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int G, int M, int ch0,
-                                                          int nch, const double* __restrict__ part, double* __restrict__ state,
-                                                          unsigned long long* __restrict__ grid) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long hist[];   // [nch][M]
-    __shared__ double hdr[kHdr];
-    __shared__ double red[4 * 5];
-    const int64_t b = blockIdx.y;
-    const int g = blockIdx.x;
-    wake_row_header(part + b * G * kPart, G, M, hdr, red);
-    if (g == 0 && threadIdx.x < kHdr) state[b * state_row(M) + threadIdx.x] = hdr[threadIdx.x];
-    if (hdr[0] == 0.0) return;                       // no surviving particle: nothing to deposit
-    const double lo = hdr[1], D = hdr[2];
-    const double S0 = hdr[3 + ch0], S1 = nch > 1 ? hdr[3 + ch0 + 1] : 0.0, S2 = nch > 2 ? hdr[3 + ch0 + 2] : 0.0;
-    for (int i = threadIdx.x; i < nch * M; i += kWB) hist[i] = 0ull;
-    __syncthreads();
-    const RowPtrs<T> r = row_ptrs(x, q, w, Bx, Bq, Bw, N, b);
-    const int64_t chunk = (N + G - 1) / G, n0 = g * chunk, n1 = n0 + chunk < N ? n0 + chunk : N;
-    for (int64_t n = n0 + threadIdx.x; n < n1; n += kWB) {
-        const double wn = (double)r.w[n], tau = (double)r.x[n * 7 + 4];
-        if (!(wn > 0.0 && isfinite(tau))) continue;
-        const double c = fabs((double)r.q[n]) * wn;
-        int k;
-        double f;
-        bool in;
-        wake_node(tau, lo, D, M, k, f, in);
-        const double a0 = (1.0 - f) * c, a1 = f * c;
-        if (ch0 == 0) {
-            atomicAdd(&hist[k], to_fixed(a0, S0));
-            atomicAdd(&hist[k + 1], to_fixed(a1, S0));
-        }
-        if (ch0 + nch == 3) {                        // transverse channels X, Y: the last two slots
-            const double xn = (double)r.x[n * 7], yn = (double)r.x[n * 7 + 2];
-            const int sx = nch - 2;
-            const double Sx = sx == 0 ? S0 : S1, Sy = sx == 0 ? S1 : S2;
-            atomicAdd(&hist[sx * M + k], to_fixed(a0 * xn, Sx));
-            atomicAdd(&hist[sx * M + k + 1], to_fixed(a1 * xn, Sx));
-            atomicAdd(&hist[(sx + 1) * M + k], to_fixed(a0 * yn, Sy));
-            atomicAdd(&hist[(sx + 1) * M + k + 1], to_fixed(a1 * yn, Sy));
-        }
-    }
-    __syncthreads();
-    unsigned long long* gr = grid + (b * 3 + ch0) * M;
-    for (int i = threadIdx.x; i < nch * M; i += kWB) {
-        const unsigned long long v = hist[i];
-        if (v) atomicAdd(&gr[i], v);
-    }
-}
 
 // ---- F3 ----------------------------------------------------------------------------------------------------------------------
 // One workgroup per (row, 64 nodes k0 ... k0 + 63): the sampled wakes W~[n], n < k0 + 64, in LDS behind 64 zeros (a source m > k
 // reads a zero); wave v takes the source tiles m0 = 64 (v + 4 i); a tile's 64 deposits are loaded one per lane and broadcast with
 // readlane. The four waves' sums are added in order by wave 0.
-__device__ __forceinline__ double readlane_d(double v, int l) {
-    const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
-    return __hiloint2double(hi, lo);
-}
-
 __global__ __launch_bounds__(kWB) void wake_conv_kernel(const double* __restrict__ wl, int64_t Ll, const double* __restrict__ wt,
                                                        int64_t Lt, const double* __restrict__ hp, int M,
                                                        const unsigned long long* __restrict__ grid, double* __restrict__ state) {
@@ -701,12 +495,6 @@ int check_wake(const void* x, const void* q, const void* w, const double* scale,
     return CHX_OK;
 }
 
-// Dynamic LDS above 64 KiB (M > ~2700 nodes) must be requested per kernel (gfx950: 160 KiB per workgroup).
-template <typename K>
-bool lds_ok(K kern, size_t bytes) {
-    return bytes <= 64 * 1024 ||
-           hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
-}
 
 inline size_t conv_lds(int M) { return ((size_t)2 * (64 + M) + 4 * 3 * 64) * sizeof(double); }
 inline size_t samples_lds(int M) { return ((size_t)3 * (M + 128) + 4 * 2 * 64) * sizeof(double); }
@@ -720,10 +508,10 @@ int wake_kick_t(const T* x, const T* q, const T* w, const double* scale, const d
     const int ch0 = has_l ? 0 : 1, nch = has_t ? 3 - ch0 : 1;
     if (!lds_ok(wake_deposit_kernel<T>, (size_t)nch * M * 8) || !lds_ok(wake_conv_kernel, conv_lds(M))) return CHX_ERR_LAUNCH;
     hipLaunchKernelGGL(wake_range_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, G, M, has_t,
-                       ws.part, ws.grid);
+                       3 * (int64_t)M, ws.part, ws.grid);
     CHX_CHECK_LAUNCH();
     hipLaunchKernelGGL(wake_deposit_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), (size_t)nch * M * 8, s, x, q, w, Bx, Bq, Bw,
-                       N, G, M, ch0, nch, ws.part, state, ws.grid);
+                       N, G, M, ch0, nch, state_row(M), 3 * (int64_t)M, ws.part, state, ws.grid);
     CHX_CHECK_LAUNCH();
     hipLaunchKernelGGL(wake_conv_kernel, dim3((unsigned)((M + kNodeBlock - 1) / kNodeBlock), (unsigned)B), dim3(kWB), conv_lds(M), s,
                        wl, Ll, wt, Lt, h, M, ws.grid, state);

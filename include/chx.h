@@ -301,6 +301,31 @@ int chx_wake_kick_bwd(const void* x, const void* q, const void* w, const double*
                       const double* wt, int64_t Lt, const double* h, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
                       int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
                       double* d_wl, double* d_wt, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- steady-state coherent synchrotron radiation (CSRKick element): per batch row b, the surviving particles' grid and node-based
+ * linear deposit D_k (coulomb) exactly as chx_wake_kick's (same tau_lo, node spacing h, u, k, f, clamping, dead particles, NaN tau);
+ * a_j = (j+1)^(2/3) - j^(2/3) in the cancellation-free form (2j+1) / ((j+1)^(4/3) + (j(j+1))^(2/3) + j^(4/3)), b_0 = -1, b_j = a_(j-1)
+ * - a_j; S_k = sum_{j=0}^{M-1-k} b_j D_(k+j) (anti-causal: the sources are the particles behind, at larger tau); node energy change
+ * dE_k [eV] = |Z| 3^(2/3) k_e L^(1/3) |theta|^(2/3) h^(-4/3) S_k (k_e = 8.9875517923e9 V m / C); every particle (dead ones too; NaN tau
+ * -> NaN) gets delta += ((1 - f) dE_k + f dE_(k+1)) / p0c (fp64, rounded once; where the field is zero — theta = 0, L = 0, both nodes 0
+ * — delta keeps its bits, NaN tau included). energy[Be], length[Bl] (L >= 0; a negative L gives NaN), angle[Ba] (theta) are device
+ * arrays of the beam's dtype (each 1 or B rows); p0c = beta gamma m c^2 of the energy and the scale are formed on the device, in fp64.
+ * A row without surviving particles or with h = 0 is copied bit for bit. out[B][N][7], state[B][CHX_CSR_STATE_DOUBLES(M)] (row header
+ * as chx_wake_kick's with the row's scale |Z| L^(1/3) |theta|^(2/3) / p0c in its last slot, then the node kicks dE_k / (|Z| L^(1/3)
+ * |theta|^(2/3))). x, q, w (dtype, [Bx][N][7], [Bq][N], [Bw][N]). Deterministic (64-bit fixed-point deposit, fixed-order sums). 2 <= M
+ * <= CHX_WAKE_MAX_BINS. workspace: chx_csr_workspace_bytes(B, N, M) (also for the backward pass).
+ * chx_csr_kick_bwd: given d_out[B][N][7] (dtype) and the forward's state -> dX[B][N][7] (delta's cotangent passes through), dC[B][N]
+ * (dtype; gradient with respect to c = |q| w, 0 for particles that do not deposit; may be NULL) and d_scale[B] (fp64, gradient with
+ * respect to the row's scale: the caller chains it to energy, L and theta). The node grid is a constant (no gradient through tau_lo,
+ * h). Rows of broadcast inputs are NOT reduced — the caller sums. */
+#define CHX_CSR_STATE_DOUBLES(M) (CHX_WAKE_STATE_HEADER + (int64_t)(M))
+size_t chx_csr_workspace_bytes(int64_t B, int64_t N, int32_t M);
+int chx_csr_kick(const void* x, const void* q, const void* w, const void* energy, const void* length, const void* angle,
+                 double mass_eV, double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl,
+                 int64_t Ba, int64_t N, int32_t M, int dtype, void* out, double* state, void* workspace, size_t workspace_bytes,
+                 void* stream);
+int chx_csr_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M,
+                     int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale, void* workspace,
+                     size_t workspace_bytes, void* stream);
 /* Backward of chx_moments(y), y_n = R x_n, with respect to the MAP R[BR][7][7] (dtype) when the particles x carry no
  * gradient: mu' = A mu + b, cov' = A C A^T (element.py:180-191 + utils/statistics.py:4-62), so
  * dR[B][7][7] (double) = [2 G A C + g_mu mu^T | g_mu; 0] from d_out[B][29] and the INCOMING beam's chx_moments
