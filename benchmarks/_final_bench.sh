@@ -1,13 +1,13 @@
 #!/bin/bash
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
-mkdir -p gpurun_out/r03_final
+OUT=${1:-$(mktemp -d)}
 S=$(date +%s)
-python bench.py > gpurun_out/r03_final/bench.json 2> gpurun_out/r03_final/bench.err
-echo "bench.py default run: rc $? wall $(( $(date +%s) - S )) s"
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+echo "bench.py --full run: rc $? wall $(( $(date +%s) - S )) s"
 python - <<EOF
 import json
-for l in open("gpurun_out/r03_final/bench.json"):
+for l in open("$OUT/bench.json"):
     if l.startswith("{"):
         d=json.loads(l)
         print(d["value"], d["ms_per_step"], d["roofline"]["frac"], d["roofline"]["frac_vs_copy_ceiling"])

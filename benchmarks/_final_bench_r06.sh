@@ -1,12 +1,12 @@
 #!/bin/bash
-# Round 6: the default bench.py run (what the driver runs), and the driver's own --steps 20 --warmup 5 form
+# Round 6: bench.py --full with its default steps, and what its line holds beyond the headline
 R=${GRAFT_REPO_ROOT:-/root/repo}
 cd $R
 OUT=gpurun_out/r06_final
 mkdir -p $OUT
 S=$(date +%s)
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
-echo "bench.py default run: rc $? wall $(( $(date +%s) - S )) s"
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+echo "bench.py --full run: rc $? wall $(( $(date +%s) - S )) s"
 tail -3 $OUT/bench.err
 python - <<PY
 import json

@@ -8,7 +8,7 @@ OUT=$REPO/gpurun_out/prof_${1:-r01}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o bench -- \
-    python $REPO/bench.py --steps 200 --warmup 10 --no-cpu-baseline > $OUT/bench_under_profiler.json 2> $OUT/trace.log
+    python $REPO/bench.py --steps 200 --warmup 10 --full --no-cpu-baseline > $OUT/bench_under_profiler.json 2> $OUT/trace.log
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o probe -- \
     python $REPO/profiles/traffic_probe.py > $OUT/pmc_fetch.log 2>&1
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -o probe -- \

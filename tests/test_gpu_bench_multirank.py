@@ -1,4 +1,4 @@
-"""bench.py's N > 1 path (one process per GPU, barrier + max-over-ranks timing, the three scaling legs with their exchanges),
+"""bench.py's N > 1 path (one process per GPU, barrier + max-over-ranks timing, with --full the scaling legs and their exchanges),
 executed with TWO ranks on the ONE MI355X of the test box: `--one-device-gloo` puts both ranks on cuda:0 and runs the exchanges
 over gloo (RCCL refuses two ranks on one device; the RCCL calls themselves are covered by tests/test_gpu_rccl_single_rank.py).
 The numbers mean nothing — two processes share the GPU — the contract and the sharded code paths are what is checked."""
@@ -21,7 +21,7 @@ def test_two_rank_bench_line_on_one_device():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--one-device-gloo"]
+           "--one-device-gloo", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
@@ -50,7 +50,7 @@ def test_three_rank_bench_line_on_one_device():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "3", "--steps", "2", "--warmup", "1",
-           "--one-device-gloo"]
+           "--one-device-gloo", "--full"]
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

@@ -139,6 +139,20 @@ def test_bench_dump_outputs_are_the_timed_step(ca, tmp_path):
     assert float(np.sqrt(files["moments"][8])) == pytest.approx(line["config"]["sigma_x_out"], rel=1e-12)
 
 
+def test_plain_bench_line_is_the_headline_alone():
+    """Without --full, bench.py measures the headline and nothing else: its line holds the headline, its checked sigma_x and who
+    ran it, and none of what --full adds (headline_long, modes, roofline, configs, scaling legs, CPU baseline)."""
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"],
+                         cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-3000:]
+    line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
+    assert set(line) == {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                         "vs_baseline", "dtype", "data", "config", "timed_region_s", "collectives_forced_in_headline", "distributed"}
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert line["value"] == pytest.approx(1e6 * 100 / (line["ms_per_step"] * 1e-3), rel=1e-6)
+    assert line["config"]["sigma_x_checked"] is True and line["distributed"]["initialized"] is False
+
+
 @pytest.mark.parametrize("precision", ["double", "mixed", "storage"])
 def test_dkd_fodo100_at_full_size(ca, oracle, golden, precision):
     from cheetah_amd import _ops
