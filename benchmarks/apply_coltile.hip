@@ -1,0 +1,253 @@
+// apply_coltile.hip — what does an in-place element pass cost when it stores only the coordinates its map changed?
+//
+// chx_track_elementwise runs passes 1..E-1 in place. A drift changes x, y and tau of a row, a quadrupole x, px, y, py and tau,
+// but in rows of 28 bytes every 128-byte line holds changed dwords, so every pass writes all 28 bytes per particle. Here the
+// passes between the first and the last in-place pass keep every full 512-row tile transposed ([7][512], the same bytes, the
+// same workgroup, the same XCD) and a wave stores a column only if one of its lanes holds other bits than it loaded
+// (chx_common.h: column tiles — the bodies timed here are the ones chx_apply.hip launches). 100 passes back to back, fp32,
+// HIP events, old and new alternating in one process, 5 runs each, every result compared bit for bit with the production
+// structure (nt loads, nt stores, rows) after the same passes:
+//   ab     at one size: variant (i) of apply_l2_resident.hip (rows, L2-allocating loads, nt stores: production MODE 3) against
+//          the column passes (16 bytes per lane and column, nt / plain stores; 8 bytes per lane, 256 lanes), with the
+//          benchmark's FODO cell (quadrupole, drift, quadrupole, drift), a map that changes columns 0..5 in every row
+//          (nothing to skip) and the identity (nothing to store);
+//   sweep  the FODO cell over the sizes around the production thresholds: the in-place pass production uses at that size
+//          (libchx's chx_apply_affine7 in place, or variant (i) between 14.7 and 28 MiB) against the column passes with
+//          L2-allocating or nt loads and nt or plain stores.
+// Results: profiles/r08_coltile.md.
+//
+// Build (after libchx.so) and run:
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Icheetah_amd/csrc -Iinclude benchmarks/apply_coltile.hip \
+//         -Lcheetah_amd -lchx -L/opt/rocm/lib -lhipfft -Wl,-rpath,$PWD/cheetah_amd -o apply_coltile
+//   ./apply_coltile ab [rows]; ./apply_coltile sweep
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <functional>
+#include <vector>
+
+#include "chx.h"
+#include "chx_common.h"
+
+#define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1); } } while (0)
+
+constexpr int TP = 512;  // rows per tile, as tile_cfg<float>
+
+__device__ __forceinline__ void rows_in_lds(const float* __restrict__ R, float* lds, int np) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int p = threadIdx.x + k * CHX_BLOCK;
+        if (p < np) {
+            float x[7], y[7];
+#pragma unroll
+            for (int j = 0; j < 7; ++j) x[j] = lds[p * 7 + j];
+            chx_map7<float, float>(R, x, y);
+#pragma unroll
+            for (int j = 0; j < 7; ++j) lds[p * 7 + j] = y[j];
+        }
+    }
+}
+
+// rows through LDS: NT_LOAD = the production apply_tile_kernel<float,2,0> structure, else its MODE 3 (variant (i) of r07)
+template <bool NT_LOAD>
+__global__ __launch_bounds__(CHX_BLOCK) void k_rows(const float* x_in, const float* __restrict__ R, float* x_out, long N) {
+    __shared__ __attribute__((aligned(16))) float lds[TP * 7];
+    const long n0 = (long)blockIdx.x * TP;
+    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
+    tile_load<float, TP>(x_in + n0 * 7, lds, np * 7, true, NT_LOAD);
+    __syncthreads();
+    rows_in_lds(R, lds, np);
+    __syncthreads();
+    tile_store<float, TP>(x_out + n0 * 7, lds, np * 7, true, true);
+}
+
+template <bool TO_COLUMNS>
+__global__ __launch_bounds__(CHX_BLOCK) void k_edge(float* x, const float* __restrict__ R, long N) {
+    __shared__ __attribute__((aligned(16))) float lds[TP * 7];
+    const long n0 = (long)blockIdx.x * TP;
+    chx_coltile_edge<float, TP, TO_COLUMNS>(x + n0 * 7, R, lds, (int)((N - n0 < TP) ? (N - n0) : TP), true);
+}
+
+template <bool NT_LOAD, bool NT_STORE>
+__global__ __launch_bounds__(TP / 4) void k_col16(float* x, const float* __restrict__ R, long N) {
+    const long n0 = (long)blockIdx.x * TP;
+    if (N - n0 >= TP) chx_coltile_pass<float, TP, NT_LOAD, NT_STORE>(x + n0 * 7, R);
+    else chx_rowtile_pass<float>(x + n0 * 7, R, (int)(N - n0));
+}
+
+// the other lane shape: 256 lanes, two rows and 8 bytes per lane and column
+__global__ __launch_bounds__(TP / 2) void k_col8(float* x, const float* __restrict__ R, long N) {
+    const long n0 = (long)blockIdx.x * TP;
+    if (N - n0 < TP) {
+        chx_rowtile_pass<float>(x + n0 * 7, R, (int)(N - n0));
+        return;
+    }
+    chx_v2f* gv = reinterpret_cast<chx_v2f*>(x + n0 * 7) + threadIdx.x;
+    chx_v2f a[7], y[7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) a[j] = gv[j * (TP / 2)];
+    chx_map7<float, chx_v2f>(R, a, y);
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        const bool changed = __float_as_uint(a[j].x) != __float_as_uint(y[j].x) || __float_as_uint(a[j].y) != __float_as_uint(y[j].y);
+        if (__any(changed)) __builtin_nontemporal_store(y[j], gv + j * (TP / 2));
+    }
+}
+
+struct Stats { float mean, lo, hi; };
+
+int main(int argc, char** argv) {
+    const char* mode = argc > 1 ? argv[1] : "ab";
+    const int E = 100, reps = 5;
+    hipEvent_t t0, t1;
+    CK(hipEventCreate(&t0)); CK(hipEventCreate(&t1));
+
+    // the benchmark's cell at 100 MeV: Quadrupole(0.2, k1 = 4.2), Drift(0.8), Quadrupole(0.2, k1 = -4.2), Drift(0.8)
+    auto drift = [](double L, float* R) {
+        const double g = 1e8 / 510998.95, ig2 = 1.0 / (g * g), b2 = 1.0 - ig2;
+        for (int i = 0; i < 49; ++i) R[i] = (i / 7 == i % 7) ? 1.f : 0.f;
+        R[0 * 7 + 1] = (float)L; R[2 * 7 + 3] = (float)L; R[4 * 7 + 5] = (float)(-L / b2 * ig2);
+    };
+    auto quad = [&](double L, double k1, float* R) {
+        drift(L, R);
+        const double k = std::sqrt(std::fabs(k1)), c = std::cos(k * L), s = std::sin(k * L) / k, ch = std::cosh(k * L),
+                     sh = std::sinh(k * L) / k;
+        const int f = k1 > 0 ? 0 : 2, d = k1 > 0 ? 2 : 0;  // focusing / defocusing plane
+        R[f * 7 + f] = (float)c; R[f * 7 + f + 1] = (float)s; R[(f + 1) * 7 + f] = (float)(-k * k * s); R[(f + 1) * 7 + f + 1] = (float)c;
+        R[d * 7 + d] = (float)ch; R[d * 7 + d + 1] = (float)sh; R[(d + 1) * 7 + d] = (float)(k * k * sh); R[(d + 1) * 7 + d + 1] = (float)ch;
+    };
+    std::vector<float> fodo(E * 49), dense(E * 49), ident(E * 49);
+    for (int e = 0; e < E; ++e) {
+        if (e % 2) drift(0.8, &fodo[e * 49]);
+        else quad(0.2, e % 4 ? -4.2 : 4.2, &fodo[e * 49]);
+        for (int i = 0; i < 7; ++i)
+            for (int j = 0; j < 7; ++j) {
+                ident[e * 49 + i * 7 + j] = i == j ? 1.f : 0.f;
+                // rows 0..5 dense (every column of a particle changes), row 6 keeps the 1
+                dense[e * 49 + i * 7 + j] = i == j ? 1.f : (i < 6 ? 1e-3f * (float)(((i * 3 + j * 5 + e) % 7) - 3) : 0.f);
+            }
+    }
+    float *dR[3];
+    const std::vector<float>* hR[3] = {&fodo, &dense, &ident};
+    const char* map_name[3] = {"FODO cell", "all of columns 0-5 change", "identity"};
+    for (int m = 0; m < 3; ++m) {
+        CK(hipMalloc(&dR[m], E * 196));
+        CK(hipMemcpy(dR[m], hR[m]->data(), E * 196, hipMemcpyHostToDevice));
+    }
+
+    auto run_size = [&](long N, bool sweep) {
+        const unsigned tiles = (unsigned)((N + TP - 1) / TP);
+        const long bytes = N * 28;
+        std::vector<float> hx(N * 7);
+        for (long i = 0; i < N * 7; ++i) hx[i] = i % 7 == 6 ? 1.f : ((float)((i * 2654435761u) % 1000) * 1e-3f - 0.4995f) * 1e-3f;
+        float *x0, *ref, *buf;
+        CK(hipMalloc(&x0, bytes)); CK(hipMalloc(&ref, bytes)); CK(hipMalloc(&buf, bytes));
+        CK(hipMemcpy(x0, hx.data(), bytes, hipMemcpyHostToDevice));
+        std::vector<float> ha(N * 7), hb(N * 7);
+
+        using Launch = std::function<void(float*, const float*)>;  // passes 1..E-1 in place on the buffer, maps R[1..E-1]
+        auto rows_chain = [&](bool nt) {
+            return Launch([=](float* x, const float* R) {
+                for (int e = 1; e < E; ++e) {
+                    if (nt) hipLaunchKernelGGL(k_rows<true>, dim3(tiles), dim3(CHX_BLOCK), 0, 0, x, R + e * 49, x, N);
+                    else hipLaunchKernelGGL(k_rows<false>, dim3(tiles), dim3(CHX_BLOCK), 0, 0, x, R + e * 49, x, N);
+                }
+            });
+        };
+        Launch lib_chain = [=](float* x, const float* R) {
+            for (int e = 1; e < E; ++e)
+                if (chx_apply_affine7(x, R + e * 49, x, 1, 1, 1, N, CHX_F32, nullptr) != CHX_OK) { printf("chx_apply_affine7 failed\n"); exit(1); }
+        };
+        // 0: L2 loads, nt stores; 1: L2 loads, plain stores; 2: nt loads, nt stores; 3: 8 bytes per lane; 4: nt loads, plain stores
+        auto col_chain = [&](int kind) {
+            return Launch([=](float* x, const float* R) {
+                hipLaunchKernelGGL(k_edge<true>, dim3(tiles), dim3(CHX_BLOCK), 0, 0, x, R + 49, N);
+                for (int e = 2; e < E - 1; ++e) {
+                    const float* Re = R + e * 49;
+                    if (kind == 0) hipLaunchKernelGGL((k_col16<false, true>), dim3(tiles), dim3(TP / 4), 0, 0, x, Re, N);
+                    else if (kind == 1) hipLaunchKernelGGL((k_col16<false, false>), dim3(tiles), dim3(TP / 4), 0, 0, x, Re, N);
+                    else if (kind == 2) hipLaunchKernelGGL((k_col16<true, true>), dim3(tiles), dim3(TP / 4), 0, 0, x, Re, N);
+                    else if (kind == 3) hipLaunchKernelGGL(k_col8, dim3(tiles), dim3(TP / 2), 0, 0, x, Re, N);
+                    else hipLaunchKernelGGL((k_col16<true, false>), dim3(tiles), dim3(TP / 4), 0, 0, x, Re, N);
+                }
+                hipLaunchKernelGGL(k_edge<false>, dim3(tiles), dim3(CHX_BLOCK), 0, 0, x, R + (E - 1) * 49, N);
+            });
+        };
+        auto full_run = [&](const Launch& l, float* out, const float* R) {
+            hipLaunchKernelGGL(k_rows<true>, dim3(tiles), dim3(CHX_BLOCK), 0, 0, x0, R, out, N);  // pass 0
+            l(out, R);
+        };
+        auto mismatches = [&](const Launch& l, const float* R) {
+            full_run(rows_chain(true), ref, R);
+            full_run(l, buf, R);
+            CK(hipDeviceSynchronize());
+            CK(hipMemcpy(ha.data(), ref, bytes, hipMemcpyDeviceToHost));
+            CK(hipMemcpy(hb.data(), buf, bytes, hipMemcpyDeviceToHost));
+            long bad = 0;
+            for (long i = 0; i < N * 7; ++i) bad += memcmp(&ha[i], &hb[i], 4) != 0;
+            return bad;
+        };
+        // the variants of one table alternate: run r of every variant before run r + 1 of any; us per in-place pass
+        auto time_all = [&](const std::vector<Launch>& ls, const float* R) {
+            std::vector<Stats> st(ls.size(), Stats{0.f, 1e30f, 0.f});
+            for (const Launch& l : ls) full_run(l, buf, R);  // warm-up
+            CK(hipDeviceSynchronize());
+            for (int r = 0; r < reps; ++r)
+                for (size_t v = 0; v < ls.size(); ++v) {
+                    hipLaunchKernelGGL(k_rows<true>, dim3(tiles), dim3(CHX_BLOCK), 0, 0, x0, R, buf, N);
+                    CK(hipEventRecord(t0, 0));
+                    ls[v](buf, R);
+                    CK(hipEventRecord(t1, 0));
+                    CK(hipEventSynchronize(t1));
+                    float ms;
+                    CK(hipEventElapsedTime(&ms, t0, t1));
+                    const float us = ms * 1e3f / (E - 1);
+                    st[v].mean += us / reps;
+                    st[v].lo = us < st[v].lo ? us : st[v].lo;
+                    st[v].hi = us > st[v].hi ? us : st[v].hi;
+                }
+            return st;
+        };
+        auto report = [&](const char* name, const Stats& s, long bad) {
+            printf("  %-58s %7.3f us/pass (min %7.3f max %7.3f)  mismatches=%ld\n", name, s.mean, s.lo, s.hi, bad);
+            fflush(stdout);
+        };
+        if (!sweep) {
+            const char* names[5] = {"(i) rows, L2 loads, nt stores [production MODE 3]", "columns, 16 B/lane, L2 loads, nt stores",
+                                    "columns, 16 B/lane, L2 loads, plain stores", "columns, 16 B/lane, nt loads, nt stores",
+                                    "columns, 8 B/lane (256 lanes), L2 loads, nt stores"};
+            const std::vector<Launch> ls = {rows_chain(false), col_chain(0), col_chain(1), col_chain(2), col_chain(3)};
+            for (int m = 0; m < 3; ++m) {
+                printf("N=%ld rows fp32 (%.1f MiB), %d in-place passes, maps: %s\n", N, bytes / 1048576.0, E - 1, map_name[m]);
+                const std::vector<Stats> st = time_all(ls, dR[m]);
+                for (size_t v = 0; v < ls.size(); ++v) report(names[v], st[v], mismatches(ls[v], dR[m]));
+            }
+        } else {
+            const bool l2_range = bytes > 14L * 1024 * 1024 + 700 * 1024 && bytes <= 28L * 1024 * 1024;
+            const std::vector<Launch> ls = {l2_range ? rows_chain(false) : lib_chain, col_chain(0), col_chain(1), col_chain(2), col_chain(4)};
+            printf("N=%ld rows fp32 (%.1f MiB), FODO cell\n", N, bytes / 1048576.0);
+            const std::vector<Stats> st = time_all(ls, dR[0]);
+            report(l2_range ? "production in-place pass: rows, MODE 3" : "production in-place pass: libchx chx_apply_affine7", st[0],
+                   mismatches(ls[0], dR[0]));
+            report("columns, L2 loads, nt stores", st[1], mismatches(ls[1], dR[0]));
+            report("columns, L2 loads, plain stores", st[2], mismatches(ls[2], dR[0]));
+            report("columns, nt loads, nt stores", st[3], mismatches(ls[3], dR[0]));
+            report("columns, nt loads, plain stores", st[4], mismatches(ls[4], dR[0]));
+        }
+        CK(hipFree(x0)); CK(hipFree(ref)); CK(hipFree(buf));
+    };
+
+    if (!strcmp(mode, "ab")) run_size(argc > 2 ? atol(argv[2]) : 1000000, false);
+    else if (!strcmp(mode, "sweep")) {
+        if (argc > 2) run_size(atol(argv[2]), true);
+        else
+            for (long N : {20000L, 50000L, 100000L, 300000L, 500000L, 800000L, 1000000L, 1048576L, 1300000L, 1600000L, 3000000L, 16000000L}) run_size(N, true);
+    } else {
+        printf("usage: apply_coltile ab [rows] | sweep [rows]\n");
+        return 2;
+    }
+    for (int m = 0; m < 3; ++m) CK(hipFree(dR[m]));
+    return 0;
+}

@@ -311,6 +311,109 @@ __device__ __forceinline__ void wave_tile_store(T* __restrict__ g, const T* __re
     }
 }
 
+// ---- column tiles: the in-place element passes of chx_track_elementwise between its first and its last one ---------------
+// A full tile of TP rows (TP * 7 values, the same bytes in every pass) holds its rows transposed, [7][TP] instead of [TP][7].
+// A lane then owns 16 bytes of consecutive rows in each of the seven columns, needs no LDS and no barrier, and a column that a
+// map leaves as it was (px, py, delta and the 1 behind a drift) is a store the wave does not issue. Shared with
+// benchmarks/apply_coltile.hip, which times exactly these bodies.
+typedef unsigned chx_v4u __attribute__((ext_vector_type(4)));
+template <typename T> struct chx_col16;   // V: 16 bytes of one column, P: two rows of it (one packed FMA per step in float32)
+template <> struct chx_col16<float> { using V = chx_v4f; using P = chx_v2f; };
+template <> struct chx_col16<double> { using V = chx_v2d; using P = chx_v2d; };
+
+// y = R x, the fma chain j = 0..6 of apply7 (chx_apply.hip), for one row (X = T) or two rows side by side (X = chx_col16<T>::P)
+template <typename T, typename X>
+__device__ __forceinline__ void chx_map7(const T* __restrict__ R, const X (&x)[7], X (&y)[7]) {
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        X acc = x[0] * R[i * 7];
+#pragma unroll
+        for (int j = 1; j < 7; ++j) acc = __builtin_elementwise_fma((X)R[i * 7 + j], x[j], acc);
+        y[i] = acc;
+    }
+}
+
+// One column pass over a full column tile at g, TP / (16 / sizeof(T)) lanes per workgroup. Column i goes back only if some lane
+// of the wave holds a result whose bits differ from what it loaded: memory already holds exactly the bits a skipped store would
+// have written, so the tile is bit for bit what storing everything leaves (NaN payloads, infinities and -0.0 included).
+// g is read and written: no __restrict__. NT_LOAD: the beam does not stay in L2 from pass to pass, stream past it.
+template <typename T, int TP, bool NT_LOAD, bool NT_STORE = true>
+__device__ __forceinline__ void chx_coltile_pass(T* g, const T* __restrict__ R) {
+    using V = typename chx_col16<T>::V;
+    using P = typename chx_col16<T>::P;
+    constexpr int LANES = TP / (16 / (int)sizeof(T));
+    V* gv = reinterpret_cast<V*>(g) + threadIdx.x;
+    V x[7], y[7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) x[j] = NT_LOAD ? __builtin_nontemporal_load(gv + j * LANES) : gv[j * LANES];
+    if constexpr (sizeof(T) == 4) {
+        P lo[7], hi[7], ylo[7], yhi[7];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) { lo[j] = x[j].xy; hi[j] = x[j].zw; }
+        chx_map7<T, P>(R, lo, ylo);
+        chx_map7<T, P>(R, hi, yhi);
+#pragma unroll
+        for (int j = 0; j < 7; ++j) { y[j].xy = ylo[j]; y[j].zw = yhi[j]; }
+    } else {
+        chx_map7<T, P>(R, x, y);
+    }
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        const chx_v4u d = __builtin_bit_cast(chx_v4u, y[j]) ^ __builtin_bit_cast(chx_v4u, x[j]);
+        if (__any((d.x | d.y | d.z | d.w) != 0u)) {
+            if (NT_STORE) __builtin_nontemporal_store(y[j], gv + j * LANES);
+            else gv[j * LANES] = y[j];
+        }
+    }
+}
+
+// The rows of a tile that is not full (the last one of a batch row) stay [np][7] in every pass; a lane takes whole rows.
+template <typename T>
+__device__ __forceinline__ void chx_rowtile_pass(T* g, const T* __restrict__ R, int np) {
+    for (int p = threadIdx.x; p < np; p += blockDim.x) {
+        T x[7], y[7];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) x[j] = g[p * 7 + j];
+        chx_map7<T, T>(R, x, y);
+#pragma unroll
+        for (int j = 0; j < 7; ++j) g[p * 7 + j] = y[j];
+    }
+}
+
+// The pass that enters (TO_COLUMNS) or leaves the column layout, CHX_BLOCK lanes: the tile's bytes go through LDS as in every
+// LDS-staged pass, the lane reads its rows in the layout the tile came in and writes them in the one it leaves in. A tile that is
+// not full is [np][7] on both sides.
+template <typename T, int TP, bool TO_COLUMNS>
+__device__ __forceinline__ void chx_coltile_edge(T* g, const T* __restrict__ R, T* lds, int np, bool vec_ok) {
+    constexpr int PPT = TP / CHX_BLOCK;
+    const bool full = np == TP;
+    const bool in_cols = full && !TO_COLUMNS, out_cols = full && TO_COLUMNS;
+    tile_load<T, TP>(g, lds, np * 7, vec_ok, false);
+    __syncthreads();
+    T y[PPT][7];
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        const int p = threadIdx.x + k * CHX_BLOCK;
+        if (p < np) {
+            T x[7];
+#pragma unroll
+            for (int j = 0; j < 7; ++j) x[j] = in_cols ? lds[j * TP + p] : lds[p * 7 + j];
+            chx_map7<T, T>(R, x, y[k]);
+        }
+    }
+    if (full) __syncthreads();   // the layout changes: every lane has read its rows before another lane's results land on them
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        const int p = threadIdx.x + k * CHX_BLOCK;
+        if (p < np) {
+#pragma unroll
+            for (int j = 0; j < 7; ++j) lds[out_cols ? j * TP + p : p * 7 + j] = y[k][j];
+        }
+    }
+    __syncthreads();
+    tile_store<T, TP>(g, lds, np * 7, vec_ok, true);
+}
+
 static inline int chx_grid_for(int64_t work_items, int per_block, int cap) {
     int64_t g = (work_items + per_block - 1) / per_block;
     if (g < 1) g = 1;

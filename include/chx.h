@@ -191,7 +191,11 @@ int chx_apply_affine7_bwd(const void* dY, const void* R, const void* X, void* dX
 /* Element-by-element tracking of a run of E linear elements WITHOUT merging the maps
  * (`for e in elements: beam = e.track(beam)`, segment.py:571-572): E apply passes
  * pass 0 writes x_out, later passes update x_out in place (tile-local read-then-write); `scratch` is ignored (kept for
- * ABI stability, may be NULL). x_out must not alias x_in. */
+ * ABI stability, may be NULL). x_out must not alias x_in, which is only read.
+ * With E >= 3, 16-byte aligned batch rows and 8 MiB of particles or more, the full tiles of x_out (512 float32 / 256 float64
+ * rows) are held transposed, [7][rows], between pass 1 and pass E-1, and a pass in between stores only the coordinates whose
+ * bits its map changed. Pass E-1 writes rows again: x_out holds [B][N][7] rows, bit for bit those of E plain passes, once the
+ * call's last kernel has run (stream order, as for any output); it must not be read on another stream before that. */
 int chx_track_elementwise(const void* x_in, const void* R /*[E][BR][7][7]*/, void* x_out,
                           void* scratch, int64_t E, int64_t B, int64_t Bx, int64_t BR,
                           int64_t N, int dtype, void* stream);
