@@ -16,9 +16,19 @@
 //          L2-allocating or nt loads and nt or plain stores.
 // Results: profiles/r08_coltile.md.
 //
+// r09 (profiles/r09_map_prologue.md): both tables gain two candidates beside the production kernels, which are kernel for kernel
+// what chx_coltile.hip launches (k_edge_prod, k_col16_prod):
+//   r09 pass       production edge passes, column pass with the map requested before the particles, in one piece (r09_map_request)
+//   r09 pass+edge  the same in the edge passes too; kernel arguments fetched at once, no division for one beam
+// Neither was faster than production beyond the spreads and neither is in the library; their bodies live here (r09_*).
+// Built a second time with -mllvm -amdgpu-kernarg-preload-count=8 (the first 8 dwords of the kernel arguments arrive in scalar
+// registers with the wave), every kernel of this file takes its arguments that way: the two builds, alternating, are the measurement
+// behind that option for chx_coltile.hip.
+//
 // Build (after libchx.so) and run:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Icheetah_amd/csrc -Iinclude benchmarks/apply_coltile.hip \
 //         -Lcheetah_amd -lchx -L/opt/rocm/lib -lhipfft -Wl,-rpath,$PWD/cheetah_amd -o apply_coltile
+//   (the second build: the same line with -mllvm -amdgpu-kernarg-preload-count=8 and -o apply_coltile_preload)
 //   ./apply_coltile ab [rows]; ./apply_coltile sweep
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -63,18 +73,193 @@ __global__ __launch_bounds__(CHX_BLOCK) void k_rows(const float* x_in, const flo
     tile_store<float, TP>(x_out + n0 * 7, lds, np * 7, true, true);
 }
 
+// ---- the production kernels (coltile_edge_kernel, coltile_pass_kernel of chx_coltile.hip) ----
 template <bool TO_COLUMNS>
-__global__ __launch_bounds__(CHX_BLOCK) void k_edge(float* x, const float* __restrict__ R, long N) {
+__global__ __launch_bounds__(CHX_BLOCK) void k_edge_prod(float* x, const float* __restrict__ R, int64_t BR, int64_t N) {
     __shared__ __attribute__((aligned(16))) float lds[TP * 7];
-    const long n0 = (long)blockIdx.x * TP;
-    chx_coltile_edge<float, TP, TO_COLUMNS>(x + n0 * 7, R, lds, (int)((N - n0 < TP) ? (N - n0) : TP), true);
+    const int64_t tiles_per_row = (N + TP - 1) / TP;
+    const int64_t b = blockIdx.x / tiles_per_row;
+    const int64_t n0 = (blockIdx.x - b * tiles_per_row) * TP;
+    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
+    chx_coltile_edge<float, TP, TO_COLUMNS>(x + (b * N + n0) * 7, R + ((BR == 1) ? 0 : b) * 49, lds, np, true);
 }
 
 template <bool NT_LOAD, bool NT_STORE>
-__global__ __launch_bounds__(TP / 4) void k_col16(float* x, const float* __restrict__ R, long N) {
-    const long n0 = (long)blockIdx.x * TP;
-    if (N - n0 >= TP) chx_coltile_pass<float, TP, NT_LOAD, NT_STORE>(x + n0 * 7, R);
-    else chx_rowtile_pass<float>(x + n0 * 7, R, (int)(N - n0));
+__global__ __launch_bounds__(TP / 4) void k_col16_prod(float* x, const float* __restrict__ R, int64_t BR, int64_t N) {
+    const int64_t tiles_per_row = (N + TP - 1) / TP;
+    const int64_t b = blockIdx.x / tiles_per_row;
+    const int64_t n0 = (blockIdx.x - b * tiles_per_row) * TP;
+    float* g = x + (b * N + n0) * 7;
+    const float* __restrict__ Rb = R + ((BR == 1) ? 0 : b) * 49;
+    if (N - n0 >= TP) chx_coltile_pass<float, TP, NT_LOAD, NT_STORE>(g, Rb);
+    else chx_rowtile_pass<float>(g, Rb, (int)(N - n0));
+}
+
+// ---- r09, measured and not taken: the map requested before the particles, in one piece (profiles/r09_map_prologue.md) ----
+// ---- a wave-uniform map held in scalar registers ------------------------------------------------------------------------------
+// An element pass is one generation of waves that all start together and all wait for the same 196 bytes: nothing hides the map's
+// fetch, and left to itself the compiler asks for a float32 map in three or four pieces, each waited for where its first entry is
+// used. r09_map_request() asks for all 49 entries at once (three s_load_dwordx16 and one s_load_dword), as early as the caller
+// places it; r09_map_arrive() is the one wait: from there on the entries are register operands of the FMAs. Between the two the
+// caller forms its addresses and issues its tile loads. R must be wave-uniform and not written by the kernel.
+// A float64 map is 98 scalar registers of 102: it stays a pointer, and the compiler fetches it as before.
+typedef float r09_v16f __attribute__((ext_vector_type(16)));
+typedef float r09_v16f_a4 __attribute__((ext_vector_type(16), aligned(4)));
+template <typename T> struct r09_map_regs {
+    const T* __restrict__ p;
+    __device__ __forceinline__ T operator[](int i) const { return p[i]; }
+};
+template <> struct r09_map_regs<float> {
+    r09_v16f a, b, c;
+    float d;
+    __device__ __forceinline__ float operator[](int i) const { return i < 16 ? a[i] : (i < 32 ? b[i - 16] : (i < 48 ? c[i - 32] : d)); }
+};
+template <typename T>
+__device__ __forceinline__ r09_map_regs<T> r09_map_request(const T* __restrict__ R) {
+    if constexpr (sizeof(T) == 4) {
+        r09_map_regs<float> m;
+        m.a = *reinterpret_cast<const r09_v16f_a4*>(R);
+        m.b = *reinterpret_cast<const r09_v16f_a4*>(R + 16);
+        m.c = *reinterpret_cast<const r09_v16f_a4*>(R + 32);
+        m.d = R[48];
+        return m;
+    } else {
+        return r09_map_regs<T>{R};
+    }
+}
+// The kernel arguments a kernel needs behind its first branch, named here so that they are fetched with the first ones (the compiler
+// otherwise sinks their loads to the first use: one more dependent round trip before the tile's address exists).
+template <typename... A>
+__device__ __forceinline__ void r09_args_now(A... a) { (..., [](auto v) { asm volatile("" ::"s"(v)); }(a)); }
+// (the scheduler may not move an instruction across the barrier: the requests stay above what follows, the wait below what precedes)
+__device__ __forceinline__ void r09_map_requested() { __builtin_amdgcn_sched_barrier(0); }
+template <typename T>
+__device__ __forceinline__ void r09_map_arrive(r09_map_regs<T>& m) {
+    if constexpr (sizeof(T) == 4) {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("" : "+s"(m.a), "+s"(m.b), "+s"(m.c), "+s"(m.d));
+    }
+}
+
+// blockIdx.x = b * tiles_per_row + t -> (b, t). One beam (B == 1: every tile index is below tiles_per_row, which the host computed)
+// takes the uniform branch around the division.
+__device__ __forceinline__ void r09_tile_of_block(unsigned tiles_per_row, unsigned& b, unsigned& t) {
+    b = 0;
+    t = blockIdx.x;
+    if (t >= tiles_per_row) {
+        b = t / tiles_per_row;
+        t -= b * tiles_per_row;
+    }
+}
+
+// y = R x, the fma chain j = 0..6 of apply7 (chx_apply.hip), for one row (X = T) or two rows side by side (X = chx_col16<T>::P);
+// R: a pointer to the 49 entries or a r09_map_regs
+template <typename T, typename X, typename M>
+__device__ __forceinline__ void r09_map7(const M& R, const X (&x)[7], X (&y)[7]) {
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        X acc = x[0] * R[i * 7];
+#pragma unroll
+        for (int j = 1; j < 7; ++j) acc = __builtin_elementwise_fma((X)R[i * 7 + j], x[j], acc);
+        y[i] = acc;
+    }
+}
+
+// One column pass over a full column tile at g, TPn / (16 / sizeof(T)) lanes per workgroup. Column i goes back only if some lane
+// of the wave holds a result whose bits differ from what it loaded: memory already holds exactly the bits a skipped store would
+// have written, so the tile is bit for bit what storing everything leaves (NaN payloads, infinities and -0.0 included).
+// g is read and written: no __restrict__. NT_LOAD: the beam does not stay in L2 from pass to pass, stream past it.
+// R was requested by the caller (r09_map_request): the seven loads leave while it is in flight, one wait before the first FMA.
+template <typename T, int TPn, bool NT_LOAD, bool NT_STORE = true>
+__device__ __forceinline__ void r09_coltile_pass(T* g, r09_map_regs<T>& R) {
+    using V = typename chx_col16<T>::V;
+    using P = typename chx_col16<T>::P;
+    constexpr int LANES = TPn / (16 / (int)sizeof(T));
+    V* gv = reinterpret_cast<V*>(g) + threadIdx.x;
+    V x[7], y[7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) x[j] = NT_LOAD ? __builtin_nontemporal_load(gv + j * LANES) : gv[j * LANES];
+    r09_map_arrive<T>(R);
+    if constexpr (sizeof(T) == 4) {
+        P lo[7], hi[7], ylo[7], yhi[7];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) { lo[j] = x[j].xy; hi[j] = x[j].zw; }
+        r09_map7<T, P>(R, lo, ylo);
+        r09_map7<T, P>(R, hi, yhi);
+#pragma unroll
+        for (int j = 0; j < 7; ++j) { y[j].xy = ylo[j]; y[j].zw = yhi[j]; }
+    } else {
+        r09_map7<T, P>(R, x, y);
+    }
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+        const chx_v4u d = __builtin_bit_cast(chx_v4u, y[j]) ^ __builtin_bit_cast(chx_v4u, x[j]);
+        if (__any((d.x | d.y | d.z | d.w) != 0u)) {
+            if (NT_STORE) __builtin_nontemporal_store(y[j], gv + j * LANES);
+            else gv[j * LANES] = y[j];
+        }
+    }
+}
+
+template <typename T, int TPn, bool TO_COLUMNS>
+__device__ __forceinline__ void r09_coltile_edge(T* g, r09_map_regs<T>& R, T* lds, int np, bool vec_ok) {
+    constexpr int PPT = TPn / CHX_BLOCK;
+    const bool full = np == TPn;
+    const bool in_cols = full && !TO_COLUMNS, out_cols = full && TO_COLUMNS;
+    tile_load<T, TPn>(g, lds, np * 7, vec_ok, false);
+    r09_map_arrive<T>(R);        // requested by the caller before the tile: in scalar registers across the barriers
+    __syncthreads();
+    T y[PPT][7];
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        const int p = threadIdx.x + k * CHX_BLOCK;
+        if (p < np) {
+            T x[7];
+#pragma unroll
+            for (int j = 0; j < 7; ++j) x[j] = in_cols ? lds[j * TPn + p] : lds[p * 7 + j];
+            r09_map7<T, T>(R, x, y[k]);
+        }
+    }
+    if (full) __syncthreads();   // the layout changes: every lane has read its rows before another lane's results land on them
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        const int p = threadIdx.x + k * CHX_BLOCK;
+        if (p < np) {
+#pragma unroll
+            for (int j = 0; j < 7; ++j) lds[out_cols ? j * TPn + p : p * 7 + j] = y[k][j];
+        }
+    }
+    __syncthreads();
+    tile_store<T, TPn>(g, lds, np * 7, vec_ok, true);
+}
+
+template <bool TO_COLUMNS>
+__global__ __launch_bounds__(CHX_BLOCK) void k_edge_r09(float* x, const float* __restrict__ R, int64_t BR, int64_t N, unsigned tiles_per_row) {
+    __shared__ __attribute__((aligned(16))) float lds[TP * 7];
+    r09_args_now(x, N);
+    unsigned b, t;
+    r09_tile_of_block(tiles_per_row, b, t);
+    r09_map_regs<float> Rb = r09_map_request<float>(R + ((BR == 1) ? 0 : (int64_t)b) * 49);
+    r09_map_requested();
+    const int64_t n0 = (int64_t)t * TP;
+    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
+    r09_coltile_edge<float, TP, TO_COLUMNS>(x + ((int64_t)b * N + n0) * 7, Rb, lds, np, true);
+}
+
+template <bool NT_LOAD, bool NT_STORE>
+__global__ __launch_bounds__(TP / 4) void k_col16_r09(float* x, const float* __restrict__ R, int64_t BR, int64_t N, unsigned tiles_per_row) {
+    r09_args_now(x, N);
+    unsigned b, t;
+    r09_tile_of_block(tiles_per_row, b, t);
+    const float* __restrict__ Rp = R + ((BR == 1) ? 0 : (int64_t)b) * 49;
+    const int64_t n0 = (int64_t)t * TP;
+    if (N - n0 >= TP) {
+        r09_map_regs<float> Rb = r09_map_request<float>(Rp);
+        r09_map_requested();
+        r09_coltile_pass<float, TP, NT_LOAD, NT_STORE>(x + ((int64_t)b * N + n0) * 7, Rb);
+    } else {
+        chx_rowtile_pass<float>(x + ((int64_t)b * N + n0) * 7, Rp, (int)(N - n0));
+    }
 }
 
 // the other lane shape: 256 lanes, two rows and 8 bytes per lane and column
@@ -161,18 +346,27 @@ int main(int argc, char** argv) {
                 if (chx_apply_affine7(x, R + e * 49, x, 1, 1, 1, N, CHX_F32, nullptr) != CHX_OK) { printf("chx_apply_affine7 failed\n"); exit(1); }
         };
         // 0: L2 loads, nt stores; 1: L2 loads, plain stores; 2: nt loads, nt stores; 3: 8 bytes per lane; 4: nt loads, plain stores
-        auto col_chain = [&](int kind) {
+        // gen 0: the production kernels; 1: production edge passes, r09 column pass; 2: r09 edge passes and column pass
+        const unsigned tpr = tiles;
+        auto col_chain = [&](int kind, int gen = 0) {
             return Launch([=](float* x, const float* R) {
-                hipLaunchKernelGGL(k_edge<true>, dim3(tiles), dim3(CHX_BLOCK), 0, 0, x, R + 49, N);
+                const int64_t Nl = N, one = 1;
+                const dim3 g(tiles), b16(TP / 4);
+                if (gen == 2) hipLaunchKernelGGL(k_edge_r09<true>, g, dim3(CHX_BLOCK), 0, 0, x, R + 49, one, Nl, tpr);
+                else hipLaunchKernelGGL(k_edge_prod<true>, g, dim3(CHX_BLOCK), 0, 0, x, R + 49, one, Nl);
                 for (int e = 2; e < E - 1; ++e) {
                     const float* Re = R + e * 49;
-                    if (kind == 0) hipLaunchKernelGGL((k_col16<false, true>), dim3(tiles), dim3(TP / 4), 0, 0, x, Re, N);
-                    else if (kind == 1) hipLaunchKernelGGL((k_col16<false, false>), dim3(tiles), dim3(TP / 4), 0, 0, x, Re, N);
-                    else if (kind == 2) hipLaunchKernelGGL((k_col16<true, true>), dim3(tiles), dim3(TP / 4), 0, 0, x, Re, N);
-                    else if (kind == 3) hipLaunchKernelGGL(k_col8, dim3(tiles), dim3(TP / 2), 0, 0, x, Re, N);
-                    else hipLaunchKernelGGL((k_col16<true, false>), dim3(tiles), dim3(TP / 4), 0, 0, x, Re, N);
+                    if (kind == 3) hipLaunchKernelGGL(k_col8, g, dim3(TP / 2), 0, 0, x, Re, N);
+                    else if (gen == 0) {
+                        if (kind == 0) hipLaunchKernelGGL((k_col16_prod<false, true>), g, b16, 0, 0, x, Re, one, Nl);
+                        else if (kind == 1) hipLaunchKernelGGL((k_col16_prod<false, false>), g, b16, 0, 0, x, Re, one, Nl);
+                        else if (kind == 2) hipLaunchKernelGGL((k_col16_prod<true, true>), g, b16, 0, 0, x, Re, one, Nl);
+                        else hipLaunchKernelGGL((k_col16_prod<true, false>), g, b16, 0, 0, x, Re, one, Nl);
+                    } else if (kind == 0) hipLaunchKernelGGL((k_col16_r09<false, true>), g, b16, 0, 0, x, Re, one, Nl, tpr);
+                    else hipLaunchKernelGGL((k_col16_r09<true, true>), g, b16, 0, 0, x, Re, one, Nl, tpr);
                 }
-                hipLaunchKernelGGL(k_edge<false>, dim3(tiles), dim3(CHX_BLOCK), 0, 0, x, R + (E - 1) * 49, N);
+                if (gen == 2) hipLaunchKernelGGL(k_edge_r09<false>, g, dim3(CHX_BLOCK), 0, 0, x, R + (E - 1) * 49, one, Nl, tpr);
+                else hipLaunchKernelGGL(k_edge_prod<false>, g, dim3(CHX_BLOCK), 0, 0, x, R + (E - 1) * 49, one, Nl);
             });
         };
         auto full_run = [&](const Launch& l, float* out, const float* R) {
@@ -215,10 +409,13 @@ int main(int argc, char** argv) {
             fflush(stdout);
         };
         if (!sweep) {
-            const char* names[5] = {"(i) rows, L2 loads, nt stores [production MODE 3]", "columns, 16 B/lane, L2 loads, nt stores",
+            const char* names[7] = {"(i) rows, L2 loads, nt stores [production MODE 3]", "columns, 16 B/lane, L2 loads, nt stores",
                                     "columns, 16 B/lane, L2 loads, plain stores", "columns, 16 B/lane, nt loads, nt stores",
-                                    "columns, 8 B/lane (256 lanes), L2 loads, nt stores"};
-            const std::vector<Launch> ls = {rows_chain(false), col_chain(0), col_chain(1), col_chain(2), col_chain(3)};
+                                    "columns, 8 B/lane (256 lanes), L2 loads, nt stores",
+                                    "r09 pass: columns, L2 loads, nt stores, map prologue in the column pass",
+                                    "r09 pass+edge: the same in the edge passes too"};
+            const std::vector<Launch> ls = {rows_chain(false), col_chain(0), col_chain(1), col_chain(2), col_chain(3), col_chain(0, 1),
+                                            col_chain(0, 2)};
             for (int m = 0; m < 3; ++m) {
                 printf("N=%ld rows fp32 (%.1f MiB), %d in-place passes, maps: %s\n", N, bytes / 1048576.0, E - 1, map_name[m]);
                 const std::vector<Stats> st = time_all(ls, dR[m]);
@@ -226,7 +423,8 @@ int main(int argc, char** argv) {
             }
         } else {
             const bool l2_range = bytes > 14L * 1024 * 1024 + 700 * 1024 && bytes <= 28L * 1024 * 1024;
-            const std::vector<Launch> ls = {l2_range ? rows_chain(false) : lib_chain, col_chain(0), col_chain(1), col_chain(2), col_chain(4)};
+            const std::vector<Launch> ls = {l2_range ? rows_chain(false) : lib_chain, col_chain(0), col_chain(1), col_chain(2), col_chain(4),
+                                            col_chain(0, 1), col_chain(0, 2), col_chain(2, 2)};
             printf("N=%ld rows fp32 (%.1f MiB), FODO cell\n", N, bytes / 1048576.0);
             const std::vector<Stats> st = time_all(ls, dR[0]);
             report(l2_range ? "production in-place pass: rows, MODE 3" : "production in-place pass: libchx chx_apply_affine7", st[0],
@@ -235,6 +433,9 @@ int main(int argc, char** argv) {
             report("columns, L2 loads, plain stores", st[2], mismatches(ls[2], dR[0]));
             report("columns, nt loads, nt stores", st[3], mismatches(ls[3], dR[0]));
             report("columns, nt loads, plain stores", st[4], mismatches(ls[4], dR[0]));
+            report("r09 pass: columns, L2 loads, nt stores", st[5], mismatches(ls[5], dR[0]));
+            report("r09 pass+edge: columns, L2 loads, nt stores", st[6], mismatches(ls[6], dR[0]));
+            report("r09 pass+edge: columns, nt loads, nt stores", st[7], mismatches(ls[7], dR[0]));
         }
         CK(hipFree(x0)); CK(hipFree(ref)); CK(hipFree(buf));
     };

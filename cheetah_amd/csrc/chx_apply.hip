@@ -16,11 +16,12 @@
 //    pass, element-wise and fused kernels, so those agree bit for bit);
 //  * between the first and the last in-place pass of chx_track_elementwise the full tiles are held transposed ([7][TP]):
 //    a lane then moves 16 bytes per column without LDS, and a column a map leaves as it was is not stored
-//    (coltile_edge_kernel, coltile_pass_kernel; the layout never leaves the call).
+//    (coltile_edge_kernel, coltile_pass_kernel in chx_coltile.hip; the layout never leaves the call).
 #include <cstdlib>
 #include <type_traits>
 
 #include "chx_common.h"
+#include "chx_apply_tiles.h"
 #include "chx_cic_dev.h"
 
 namespace {
@@ -421,10 +422,6 @@ __global__ __launch_bounds__(CHX_BLOCK) void apply_shared_wave_kernel(
     }
 }
 
-template <typename T> struct tile_cfg;
-template <> struct tile_cfg<float> { static constexpr int PPT = 2; };   // 512 rows, 14 KiB LDS
-template <> struct tile_cfg<double> { static constexpr int PPT = 1; };  // 256 rows, 14 KiB LDS
-
 template <typename T, int PPT, int MODE>
 int launch_tiles_ppt(const void* x_in, const void* R, void* x_out, const double* coeffs, int64_t B,
                      int64_t Bx, int64_t BR, int64_t N, int E, hipStream_t s) {
@@ -451,16 +448,6 @@ int launch_wave(const void* x_in, const void* R, void* x_out, int64_t B, int64_t
     CHX_CHECK_LAUNCH();
     return CHX_OK;
 }
-
-// Beams up to this size take the wave-staged MODE-0 kernel (launch_tiles).
-constexpr int64_t kSmallBeamBytes = (int64_t)14 * 1024 * 1024 + 700 * 1024;
-// In-place element passes on beams up to this size run as MODE 3 (launch_inplace_pass): 7/8 of the 8 x 4 MiB of L2.
-constexpr int64_t kL2ResidentBytes = (int64_t)28 * 1024 * 1024;
-// Calls of chx_track_elementwise with E >= 3 on beams from this size on run passes 1..E-1 column-tiled (launch_coltile_passes).
-// Measured on MI355X, fp32, FODO cell, us per in-place pass, production pass -> column passes (benchmarks/apply_coltile.hip,
-// profiles/r08_coltile.md): 3e5 rows 3.60 -> 3.01, 5e5 6.14 -> 3.48, 1e6 7.37 -> 5.38, 1.6e6 14.5 -> 10.6, 1.6e7 142 -> 113;
-// at 1e5 rows and below both sit on the launch floor (2.6 - 3.0 us, inside each other's spread) and the row passes stay.
-constexpr int64_t kColTileMinBytes = (int64_t)8 * 1024 * 1024;
 
 template <typename T, int MODE>
 int launch_tiles(const void* x_in, const void* R, void* x_out, const double* coeffs, int64_t B,
@@ -498,76 +485,13 @@ int launch_tiles(const void* x_in, const void* R, void* x_out, const double* coe
 // whatever the placement). So the loads allocate in L2 (MODE 3) instead of streaming past it. Measured on MI355X,
 // 1e6 fp32 rows, 100 passes back to back (benchmarks/apply_l2_resident.hip): 9.4 -> 7.7 us per pass, but 11.1 with every
 // tile moved to another XCD each pass. Smaller beams keep the wave-staged kernel, larger ones MODE 0.
-// Calls with E >= 3 on aligned beams of 8 MiB and more do not come here: launch_coltile_passes below.
+// Calls with E >= 3 on aligned beams of 8 MiB and more do not come here: chx_coltile_passes (chx_coltile.hip).
 template <typename T>
 int launch_inplace_pass(void* x, const void* R, int64_t B, int64_t BR, int64_t N, hipStream_t s) {
     const int64_t bytes = B * N * 7 * (int64_t)sizeof(T);
     if (bytes > kSmallBeamBytes && bytes <= kL2ResidentBytes)
         return launch_tiles_ppt<T, tile_cfg<T>::PPT, 3>(x, R, x, nullptr, B, B, BR, N, 1, s);
     return launch_tiles<T, 0>(x, R, x, nullptr, B, B, BR, N, 1, s);
-}
-
-// ---- column-tiled in-place passes (chx_common.h: column tiles) -----------------------------------------------------------
-// Same tiling as apply_tile_kernel: workgroup blockIdx.x takes tile t of batch row b in every pass.
-template <typename T> struct coltile_cfg {
-    static constexpr int TP = tile_cfg<T>::PPT * CHX_BLOCK;          // rows per tile
-    static constexpr int LANES = TP / (16 / (int)sizeof(T));         // lanes of a column pass: 16 bytes of every column each
-};
-
-// pass 1 (TO_COLUMNS) and pass E-1 of a call: [TP][7] -> [7][TP] and back, through LDS
-template <typename T, bool TO_COLUMNS>
-__global__ __launch_bounds__(CHX_BLOCK) void coltile_edge_kernel(T* x, const T* __restrict__ R, int64_t BR, int64_t N) {
-    constexpr int TP = coltile_cfg<T>::TP;
-    __shared__ __attribute__((aligned(16))) T lds[TP * 7];
-    const int64_t tiles_per_row = (N + TP - 1) / TP;
-    const int64_t b = blockIdx.x / tiles_per_row;
-    const int64_t n0 = (blockIdx.x - b * tiles_per_row) * TP;
-    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
-    chx_coltile_edge<T, TP, TO_COLUMNS>(x + (b * N + n0) * 7, R + ((BR == 1) ? 0 : b) * 49, lds, np, true);
-}
-
-// passes 2..E-2: no LDS, no barrier, only the columns the map changed are stored
-template <typename T, bool NT_LOAD>
-__global__ __launch_bounds__(coltile_cfg<T>::LANES) void coltile_pass_kernel(T* x, const T* __restrict__ R, int64_t BR, int64_t N) {
-    constexpr int TP = coltile_cfg<T>::TP;
-    const int64_t tiles_per_row = (N + TP - 1) / TP;
-    const int64_t b = blockIdx.x / tiles_per_row;
-    const int64_t n0 = (blockIdx.x - b * tiles_per_row) * TP;
-    T* g = x + (b * N + n0) * 7;
-    const T* __restrict__ Rb = R + ((BR == 1) ? 0 : b) * 49;
-    if (N - n0 >= TP) chx_coltile_pass<T, TP, NT_LOAD>(g, Rb);
-    else chx_rowtile_pass<T>(g, Rb, (int)(N - n0));
-}
-
-// Passes 1..E-1 of chx_track_elementwise through the column layout: needs E >= 3 and every batch row of x 16-byte aligned.
-template <typename T>
-bool coltile_ok(const void* x, int64_t E, int64_t B, int64_t N) {
-    const int64_t bytes = B * N * 7 * (int64_t)sizeof(T);
-    return E >= 3 && chx_aligned16(x) && (B == 1 || (N * 7 * (int64_t)sizeof(T)) % 16 == 0) &&
-           bytes >= kColTileMinBytes;
-}
-
-template <typename T>
-int launch_coltile_passes(void* x, const void* R, int64_t E, int64_t B, int64_t BR, int64_t N, hipStream_t s) {
-    constexpr int TP = coltile_cfg<T>::TP;
-    const int64_t tiles = ((N + TP - 1) / TP) * B;
-    if (tiles > 0x7fffffffLL) return CHX_ERR_INVALID_ARG;
-    const bool nt_load = B * N * 7 * (int64_t)sizeof(T) > kL2ResidentBytes;
-    const T* Rp = (const T*)R;
-    const int64_t estride = BR * 49;
-    hipLaunchKernelGGL((coltile_edge_kernel<T, true>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (T*)x, Rp + estride, BR, N);
-    for (int64_t e = 2; e < E - 1; ++e) {
-        if (nt_load)
-            hipLaunchKernelGGL((coltile_pass_kernel<T, true>), dim3((unsigned)tiles), dim3(coltile_cfg<T>::LANES), 0, s, (T*)x,
-                               Rp + e * estride, BR, N);
-        else
-            hipLaunchKernelGGL((coltile_pass_kernel<T, false>), dim3((unsigned)tiles), dim3(coltile_cfg<T>::LANES), 0, s, (T*)x,
-                               Rp + e * estride, BR, N);
-    }
-    hipLaunchKernelGGL((coltile_edge_kernel<T, false>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (T*)x, Rp + (E - 1) * estride,
-                       BR, N);
-    CHX_CHECK_LAUNCH();
-    return CHX_OK;
 }
 
 template <typename T>
@@ -661,9 +585,7 @@ extern "C" int chx_track_elementwise(const void* x_in, const void* R, void* x_ou
     hipStream_t s = (hipStream_t)stream;
     // E >= 3: passes 1..E-1 keep every full tile of x_out transposed ([7][TP]) between them and store only the columns a map
     // changed; the last pass leaves x_out as [N][7] rows again (chx_common.h: column tiles)
-    if (st == CHX_OK && (dtype == CHX_F32 ? coltile_ok<float>(x_out, E, B, N) : coltile_ok<double>(x_out, E, B, N)))
-        return dtype == CHX_F32 ? launch_coltile_passes<float>(x_out, R, E, B, BR, N, s)
-                                : launch_coltile_passes<double>(x_out, R, E, B, BR, N, s);
+    if (st == CHX_OK && chx_coltile_ok(x_out, E, B, N, dtype)) return chx_coltile_passes(x_out, R, E, B, BR, N, dtype, s);
     for (int64_t e = 1; e < E && st == CHX_OK; ++e) {
         const void* Re = Rp + (size_t)e * (size_t)BR * 49 * esz;
         st = dtype == CHX_F32 ? launch_inplace_pass<float>(x_out, Re, B, BR, N, s)

@@ -1,0 +1,83 @@
+// chx_coltile.hip — the column-tiled in-place passes of chx_track_elementwise (passes 1..E-1; layout and bodies: chx_common.h,
+// column tiles). A translation unit of its own because it is compiled with kernel-argument preloading
+// (-mllvm -amdgpu-kernarg-preload-count=8, see the Makefile): the 32 bytes of (x, R, BR, N) arrive in scalar registers with the
+// wave instead of through a scalar load that every wave of a 2 - 5 us pass waits for before it can ask for anything else.
+// Measured on MI355X, 1e6 fp32 rows, FODO cell (benchmarks/apply_coltile.hip built with and without the option, alternating;
+// profiles/r09_map_prologue.md): 5.38 -> 4.88 us per pass, bench.py 0.529 - 0.568 -> 0.511 - 0.518 ms per step.
+#include "chx_common.h"
+#include "chx_apply_tiles.h"
+
+namespace {
+
+// ---- column-tiled in-place passes (chx_common.h: column tiles) -----------------------------------------------------------
+// Same tiling as apply_tile_kernel: workgroup blockIdx.x takes tile t of batch row b in every pass.
+template <typename T> struct coltile_cfg {
+    static constexpr int TP = tile_cfg<T>::PPT * CHX_BLOCK;          // rows per tile
+    static constexpr int LANES = TP / (16 / (int)sizeof(T));         // lanes of a column pass: 16 bytes of every column each
+};
+
+// pass 1 (TO_COLUMNS) and pass E-1 of a call: [TP][7] -> [7][TP] and back, through LDS
+template <typename T, bool TO_COLUMNS>
+__global__ __launch_bounds__(CHX_BLOCK) void coltile_edge_kernel(T* x, const T* __restrict__ R, int64_t BR, int64_t N) {
+    constexpr int TP = coltile_cfg<T>::TP;
+    __shared__ __attribute__((aligned(16))) T lds[TP * 7];
+    const int64_t tiles_per_row = (N + TP - 1) / TP;
+    const int64_t b = blockIdx.x / tiles_per_row;
+    const int64_t n0 = (blockIdx.x - b * tiles_per_row) * TP;
+    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
+    chx_coltile_edge<T, TP, TO_COLUMNS>(x + (b * N + n0) * 7, R + ((BR == 1) ? 0 : b) * 49, lds, np, true);
+}
+
+// passes 2..E-2: no LDS, no barrier, only the columns the map changed are stored
+template <typename T, bool NT_LOAD>
+__global__ __launch_bounds__(coltile_cfg<T>::LANES) void coltile_pass_kernel(T* x, const T* __restrict__ R, int64_t BR, int64_t N) {
+    constexpr int TP = coltile_cfg<T>::TP;
+    const int64_t tiles_per_row = (N + TP - 1) / TP;
+    const int64_t b = blockIdx.x / tiles_per_row;
+    const int64_t n0 = (blockIdx.x - b * tiles_per_row) * TP;
+    T* g = x + (b * N + n0) * 7;
+    const T* __restrict__ Rb = R + ((BR == 1) ? 0 : b) * 49;
+    if (N - n0 >= TP) chx_coltile_pass<T, TP, NT_LOAD>(g, Rb);
+    else chx_rowtile_pass<T>(g, Rb, (int)(N - n0));
+}
+
+// Passes 1..E-1 of chx_track_elementwise through the column layout: needs E >= 3 and every batch row of x 16-byte aligned.
+template <typename T>
+bool coltile_ok(const void* x, int64_t E, int64_t B, int64_t N) {
+    const int64_t bytes = B * N * 7 * (int64_t)sizeof(T);
+    return E >= 3 && chx_aligned16(x) && (B == 1 || (N * 7 * (int64_t)sizeof(T)) % 16 == 0) &&
+           bytes >= kColTileMinBytes;
+}
+
+template <typename T>
+int launch_coltile_passes(void* x, const void* R, int64_t E, int64_t B, int64_t BR, int64_t N, hipStream_t s) {
+    constexpr int TP = coltile_cfg<T>::TP;
+    const int64_t tiles = ((N + TP - 1) / TP) * B;
+    if (tiles > 0x7fffffffLL) return CHX_ERR_INVALID_ARG;
+    const bool nt_load = B * N * 7 * (int64_t)sizeof(T) > kL2ResidentBytes;
+    const T* Rp = (const T*)R;
+    const int64_t estride = BR * 49;
+    hipLaunchKernelGGL((coltile_edge_kernel<T, true>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (T*)x, Rp + estride, BR, N);
+    for (int64_t e = 2; e < E - 1; ++e) {
+        if (nt_load)
+            hipLaunchKernelGGL((coltile_pass_kernel<T, true>), dim3((unsigned)tiles), dim3(coltile_cfg<T>::LANES), 0, s, (T*)x,
+                               Rp + e * estride, BR, N);
+        else
+            hipLaunchKernelGGL((coltile_pass_kernel<T, false>), dim3((unsigned)tiles), dim3(coltile_cfg<T>::LANES), 0, s, (T*)x,
+                               Rp + e * estride, BR, N);
+    }
+    hipLaunchKernelGGL((coltile_edge_kernel<T, false>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (T*)x, Rp + (E - 1) * estride,
+                       BR, N);
+    CHX_CHECK_LAUNCH();
+    return CHX_OK;
+}
+
+}  // namespace
+
+bool chx_coltile_ok(const void* x, int64_t E, int64_t B, int64_t N, int dtype) {
+    return dtype == CHX_F32 ? coltile_ok<float>(x, E, B, N) : coltile_ok<double>(x, E, B, N);
+}
+
+int chx_coltile_passes(void* x, const void* R, int64_t E, int64_t B, int64_t BR, int64_t N, int dtype, hipStream_t s) {
+    return dtype == CHX_F32 ? launch_coltile_passes<float>(x, R, E, B, BR, N, s) : launch_coltile_passes<double>(x, R, E, B, BR, N, s);
+}
