@@ -17,6 +17,7 @@ from .accelerator import (  # noqa: F401
     Drift,
     Element,
     HorizontalCorrector,
+    LSCKick,
     Marker,
     PhysicsWarning,
     Quadrupole,

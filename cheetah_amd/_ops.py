@@ -1529,3 +1529,6 @@ from ._ops_wake import _wake_kick_bwd_raw, _wake_kick_raw  # noqa: E402,F401
 # ... and the steady-state CSR kick (the CSRKick element) in _ops_csr.py
 from ._ops_csr import *  # noqa: E402,F401,F403
 from ._ops_csr import _csr_kick_bwd_raw, _csr_kick_raw  # noqa: E402,F401
+# ... and the longitudinal space-charge kick (the LSCKick element) in _ops_lsc.py
+from ._ops_lsc import *  # noqa: E402,F401,F403
+from ._ops_lsc import _lsc_kick_bwd_raw, _lsc_kick_raw  # noqa: E402,F401

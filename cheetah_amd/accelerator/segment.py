@@ -1883,6 +1883,46 @@ class Segment(Element):
                 elements.append(e)
         return self.__class__(elements=elements, name=self.name, metadata=deepcopy(self.metadata))
 
+    def with_lsc_kicks(self, num_bins: int = 200, beam_radius=None, radius_factor: float = 1.7, max_step=None,
+                       except_for=None) -> "Segment":
+        """Every element with a `length` that is anywhere > 0 followed by an `LSCKick(element.length, beam_radius, radius_factor,
+        num_bins)`, nested Segments included. The kick's `effect_length` IS the element's `length` tensor, so in-place edits and
+        gradients follow. With `max_step` (metres) an element longer than that is first split with its own
+        `split(resolution=max_step)` and every piece gets its kick. Names in `except_for` and the collective kicks already there
+        (`LSCKick`, `CSRKick`, `Wakefield`, `SpaceChargeKick`) get none. A kick stands behind its element and sees the outgoing beam:
+        the kick after a `Cavity` uses the energy the beam leaves the cavity with, not the mean energy inside it."""
+        from .csr import CSRKick, check_num_bins
+        from .lsc import LSCKick, check_beam_radius, check_radius_factor
+        from .space_charge_kick import SpaceChargeKick
+        from .wakefield import Wakefield
+
+        owner = "Segment.with_lsc_kicks"
+        check_num_bins(num_bins, owner)
+        check_radius_factor(radius_factor, owner)
+        if beam_radius is not None:
+            check_beam_radius(beam_radius if isinstance(beam_radius, torch.Tensor) else torch.as_tensor(beam_radius), owner)
+        if max_step is not None:
+            step = float(max_step)
+            if not step > 0.0 or step == float("inf"):
+                raise ValueError(f"{owner}: max_step must be a finite length > 0 (metres), got {max_step!r}")
+        except_for = except_for or []
+        elements = []
+        for e in self.elements:
+            if isinstance(e, Segment):
+                elements.append(e.with_lsc_kicks(num_bins, beam_radius, radius_factor, max_step, except_for))
+                continue
+            elements_of_e = [e]
+            if not isinstance(e, (LSCKick, CSRKick, Wakefield, SpaceChargeKick)) and e.name not in except_for \
+                    and bool((e.length > 0).any()):
+                if max_step is not None and bool((e.length > step).any()):
+                    elements_of_e = e.split(torch.as_tensor(step, device=e.length.device, dtype=e.length.dtype))
+                kw = {"device": e.length.device, "dtype": e.length.dtype}
+                elements_of_e = [p for piece in elements_of_e for p in (
+                    piece, LSCKick(piece.length, beam_radius=beam_radius, radius_factor=radius_factor, num_bins=num_bins,
+                                   name=f"{piece.name}_lsc_kick", sanitize_name=False, **kw))]
+            elements += elements_of_e
+        return self.__class__(elements=elements, name=self.name, metadata=deepcopy(self.metadata))
+
     def _no_plot(self, *args, **kwargs):
         raise NotImplementedError("Segment.plot_*: plotting is outside this tracking engine (SURVEY.md section 2); "
                                   "`get_beam_attrs_along_segment` gives the numbers the reference's plots draw")

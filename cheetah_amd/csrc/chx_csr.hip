@@ -6,11 +6,11 @@
 //   F2. wake_deposit_kernel   (chx_grid1d_dev.h) the row header and the fixed-point node deposit D_k (one channel)
 //   F3. csr_toeplitz_kernel   one workgroup per (row, 64 nodes): b_j = a_(j-1) - a_j formed into LDS, the anti-causal sum
 //                             S_k = sum_j b_j D_(k+j) over the nodes behind, its four waves splitting the sources, merged in order
-//   F4. csr_kick_kernel       one thread per particle: gather of the node kicks times the row's scale (formed by F3 from the
-//                             energy, L and theta pointers), delta updated in fp64, rounded once
+//   F4. csr_kick_kernel       (chx_grid1d_dev.h) one thread per particle: gather of the node kicks times the row's scale (formed
+//                             by F3 from the energy, L and theta pointers), delta updated in fp64, rounded once
 // Backward (same pattern): B1 bounds of the gather's cotangents and the per-row partials of d(scale); B2 their fixed-point deposit;
 // B3 the causal correlation (adjoint of the anti-causal sum); B4 one pass over the particles (adjoint of the deposit and of the
-// node coordinate).
+// node coordinate). The particle passes B1, B2, B4 are shared with chx_lsc.hip through chx_grid1d_dev.h.
 #include "chx_grid1d_dev.h"
 
 namespace {
@@ -44,9 +44,6 @@ CsrWs csr_ws(void* base, int64_t B, int64_t N, int M) {
     w.bytes = o;
     return w;
 }
-
-// The row kicks at all: surviving particles and a node spacing h > 0.
-__device__ __forceinline__ bool csr_live(const double* st) { return st[0] != 0.0 && st[2] > 0.0; }
 
 // The row's scale |Z| L^(1/3) |theta|^(2/3) / p0c in fp64; p0c = beta gamma m c^2 as `Beam.p0c` (wake_scale in _ops_wake.py).
 template <typename T>
@@ -96,7 +93,7 @@ __global__ __launch_bounds__(kWB) void csr_toeplitz_kernel(int M, const T* __res
     double* st = state + b * csr_state_row(M);
     double* bt = lds;
     double* acc = lds + 2 * M + 256;
-    const bool live = csr_live(st);
+    const bool live = node_live(st);
     if (blockIdx.x == 0 && threadIdx.x == 0) st[kHdr - 1] = csr_scale(energy, Be, length, Bl, angle, Ba, mass, absz, b);
     if (live) csr_b_table(M, M - k0, bt, lds + M + 256);
     const unsigned long long* gq = grid + b * M;
@@ -125,29 +122,7 @@ __global__ __launch_bounds__(kWB) void csr_toeplitz_kernel(int M, const T* __res
 template <typename T>
 __global__ __launch_bounds__(kWB) void csr_kick_kernel(const T* __restrict__ x, int64_t Bx, int64_t N, int M,
                                                        const double* __restrict__ state, T* __restrict__ out) {
-    const int64_t b = blockIdx.y;
-    const int64_t n = (int64_t)blockIdx.x * kWB + threadIdx.x;
-    if (n >= N) return;
-    const T* xr = x + ((Bx == 1 ? 0 : b) * N + n) * 7;
-    T* o = out + (b * N + n) * 7;
-    T v[7];
-#pragma unroll
-    for (int c = 0; c < 7; ++c) v[c] = xr[c];
-    const double* st = state + b * csr_state_row(M);
-    if (csr_live(st)) {
-        int k;
-        double f;
-        bool in;
-        wake_node((double)v[4], st[1], st[2], M, k, f, in);
-        // no field (a scale of 0: theta = 0 or L = 0; both nodes 0: no charge) leaves delta's bits as they are, NaN tau included
-        const double sc = st[kHdr - 1], n0 = st[kHdr + k], n1 = st[kHdr + k + 1];
-        if (sc != 0.0 && (n0 != 0.0 || n1 != 0.0)) {
-            const double dv = sc * ((1.0 - f) * n0 + f * n1);
-            if (dv != 0.0) v[5] = (T)((double)v[5] + dv);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 7; ++c) o[c] = v[c];
+    node_kick_particle(x, Bx, N, M, state, csr_state_row(M), out);
 }
 
 // ---- B1: bound of the gather's cotangents a = scale g_delta; partials of d(scale) = sum g_delta dE(u) -------------------------------
@@ -155,35 +130,7 @@ template <typename T>
 __global__ __launch_bounds__(kWB) void csr_bwd_range_kernel(const T* __restrict__ x, int64_t Bx, int64_t N, int G, int M,
                                                             const double* __restrict__ state, const T* __restrict__ gout,
                                                             double* __restrict__ bpart, unsigned long long* __restrict__ ggrid) {
-    __shared__ double red[4 * 4];
-    const int64_t b = blockIdx.y;
-    const int g = blockIdx.x;
-    unsigned long long* gr = ggrid + b * M;
-    for (int64_t i = (int64_t)g * kWB + threadIdx.x; i < M; i += (int64_t)G * kWB) gr[i] = 0ull;
-    const double* st = state + b * csr_state_row(M);
-    const double* node = st + kHdr;
-    const int64_t chunk = (N + G - 1) / G, n0 = g * chunk, n1 = n0 + chunk < N ? n0 + chunk : N;
-    double lo = 0.0, hi = 0.0, s[2] = {0.0, 0.0};
-    if (csr_live(st)) {
-        const double sc = st[kHdr - 1];
-        const T* xb = x + (Bx == 1 ? 0 : b) * N * 7;
-        const T* gb = gout + b * N * 7;
-        for (int64_t n = n0 + threadIdx.x; n < n1; n += kWB) {
-            int k;
-            double f;
-            bool in;
-            wake_node((double)xb[n * 7 + 4], st[1], st[2], M, k, f, in);
-            if (isnan(f)) continue;
-            const double g5 = (double)gb[n * 7 + 5];
-            s[0] += fabs(sc * g5);
-            s[1] += g5 * ((1.0 - f) * node[k] + f * node[k + 1]);
-        }
-    }
-    block_reduce<2>(lo, hi, s, red);
-    if (threadIdx.x == 0) {
-        double* p = bpart + (b * G + g) * kPart;
-        p[0] = s[0]; p[1] = s[1]; p[2] = p[3] = p[4] = p[5] = p[6] = p[7] = 0.0;
-    }
+    node_bwd_range(x, Bx, N, G, M, state, csr_state_row(M), gout, bpart, ggrid);
 }
 
 // ---- B2: fixed-point deposit of the gather's cotangents, as F2; workgroup 0 writes d(scale) and the backward header -----------------
@@ -194,50 +141,7 @@ __global__ __launch_bounds__(kWB) void csr_bwd_deposit_kernel(const T* __restric
                                                               double* __restrict__ bhdr, double* __restrict__ d_scale,
                                                               unsigned long long* __restrict__ ggrid) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long hist[];
-    __shared__ double red[4 * 4];
-    __shared__ double S;
-    const int64_t b = blockIdx.y;
-    const int g = blockIdx.x;
-    const double* st = state + b * csr_state_row(M);
-    double lo = 0.0, hi = 0.0, s[2] = {0.0, 0.0};
-    for (int gg = threadIdx.x; gg < G; gg += kWB) {
-        const double* p = bpart + (b * G + gg) * kPart;
-        s[0] += p[0]; s[1] += p[1];
-    }
-    block_reduce<2>(lo, hi, s, red);
-    if (threadIdx.x == 0) {
-        S = fixed_scale(s[0]);
-        if (g == 0) {
-            d_scale[b] = s[1];
-            bhdr[b * kHdr] = st[0];
-            bhdr[b * kHdr + 1] = S;
-        }
-    }
-    __syncthreads();
-    if (!csr_live(st)) return;
-    const double S0 = S;
-    for (int i = threadIdx.x; i < M; i += kWB) hist[i] = 0ull;
-    __syncthreads();
-    const T* xb = x + (Bx == 1 ? 0 : b) * N * 7;
-    const T* gb = gout + b * N * 7;
-    const double sc = st[kHdr - 1];
-    const int64_t chunk = (N + G - 1) / G, n0 = g * chunk, n1 = n0 + chunk < N ? n0 + chunk : N;
-    for (int64_t n = n0 + threadIdx.x; n < n1; n += kWB) {
-        int k;
-        double f;
-        bool in;
-        wake_node((double)xb[n * 7 + 4], st[1], st[2], M, k, f, in);
-        if (isnan(f)) continue;
-        const double a = sc * (double)gb[n * 7 + 5];
-        atomicAdd(&hist[k], to_fixed((1.0 - f) * a, S0));
-        atomicAdd(&hist[k + 1], to_fixed(f * a, S0));
-    }
-    __syncthreads();
-    unsigned long long* gr = ggrid + b * M;
-    for (int i = threadIdx.x; i < M; i += kWB) {
-        const unsigned long long v = hist[i];
-        if (v) atomicAdd(&gr[i], v);
-    }
+    node_bwd_deposit(x, Bx, N, G, M, state, csr_state_row(M), gout, bpart, bhdr, d_scale, ggrid, hist);
 }
 
 // ---- B3: adjoint of F3, GD_m = 3^(2/3) k_e h^(-4/3) sum_{k <= m} b_(m-k) GV_k ------------------------------------------------------
@@ -253,7 +157,7 @@ __global__ __launch_bounds__(kWB) void csr_bwd_toeplitz_kernel(int M, const doub
     double* bt = lds;
     double* acc = lds + 2 * M + 256;
     const int mmax = m0 + kNodeBlock < M ? m0 + kNodeBlock : M;     // sources m < mmax: lags up to mmax - 1
-    const bool live = csr_live(st);
+    const bool live = node_live(st);
     if (live) csr_b_table(M, mmax, bt, lds + M + 256);
     const unsigned long long* gg = ggrid + b * M;
     const double SV = bhdr[b * kHdr + 1], h = st[2];
@@ -283,38 +187,7 @@ __global__ __launch_bounds__(kWB) void csr_bwd_particles_kernel(const T* __restr
                                                                 int64_t N, int M, const double* __restrict__ state,
                                                                 const double* __restrict__ adj, const T* __restrict__ gout,
                                                                 T* __restrict__ dX, T* __restrict__ dC) {
-    const int64_t b = blockIdx.y;
-    const int64_t n = (int64_t)blockIdx.x * kWB + threadIdx.x;
-    if (n >= N) return;
-    const RowPtrs<T> r = row_ptrs(x, q, w, Bx, Bq, Bw, N, b);
-    const T* gr = gout + (b * N + n) * 7;
-    double gv[7];
-#pragma unroll
-    for (int c = 0; c < 7; ++c) gv[c] = (double)gr[c];
-    const double* st = state + b * csr_state_row(M);
-    double dc = 0.0;
-    if (csr_live(st)) {
-        const double tau = (double)r.x[n * 7 + 4];
-        int k;
-        double f;
-        bool in;
-        wake_node(tau, st[1], st[2], M, k, f, in);
-        const double* node = st + kHdr;
-        const double* ad = adj + b * M;
-        const double sc = st[kHdr - 1];
-        double df = sc * gv[5] * (node[k + 1] - node[k]);
-        const double wn = (double)r.w[n];
-        if (wn > 0.0 && isfinite(tau)) {
-            const double c = fabs((double)r.q[n]) * wn;
-            dc = (1.0 - f) * ad[k] + f * ad[k + 1];
-            df += c * (ad[k + 1] - ad[k]);
-        }
-        if (in) gv[4] += df / st[2];
-    }
-    T* o = dX + (b * N + n) * 7;
-#pragma unroll
-    for (int c = 0; c < 7; ++c) o[c] = (T)gv[c];
-    if (dC) dC[b * N + n] = (T)dc;
+    node_bwd_particle(x, q, w, Bx, Bq, Bw, N, M, state, csr_state_row(M), adj, gout, dX, dC);
 }
 
 int check_csr(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M,

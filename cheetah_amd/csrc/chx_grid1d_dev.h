@@ -1,5 +1,5 @@
 // chx_grid1d_dev.h — device code shared by the kicks that bin the beam's charge on M nodes in tau (chx_wake.hip,
-// chx_csr.hip): the node coordinate, 64-bit fixed-point deposits, fixed-order reductions, and the two particle passes that
+// chx_csr.hip, chx_lsc.hip): the node coordinate, 64-bit fixed-point deposits, fixed-order reductions, and the two particle passes that
 // find the row's tau range (F1) and deposit the line density (F2). Per batch row, every grid quantity in fp64.
 #pragma once
 #include "chx_common.h"
@@ -211,6 +211,172 @@ __global__ __launch_bounds__(kWB) void wake_deposit_kernel(const T* __restrict__
         const unsigned long long v = hist[i];
         if (v) atomicAdd(&gr[i], v);
     }
+}
+
+// ---- the particle passes shared by the kicks whose state row is [header | M node kicks | ...] with the row's scale in the header's
+// last slot (chx_csr.hip, chx_lsc.hip): the gather-kick F4 and the backward passes B1, B2, B4; state_row doubles per row ----------
+
+// The row kicks at all: surviving particles and a node spacing h > 0.
+__device__ __forceinline__ bool node_live(const double* st) { return st[0] != 0.0 && st[2] > 0.0; }
+
+// F4, one thread per particle: gather of the node kicks times the row's scale, delta updated in fp64, rounded once.
+template <typename T>
+__device__ __forceinline__ void node_kick_particle(const T* __restrict__ x, int64_t Bx, int64_t N, int M,
+                                                   const double* __restrict__ state, int64_t state_row, T* __restrict__ out) {
+    const int64_t b = blockIdx.y;
+    const int64_t n = (int64_t)blockIdx.x * kWB + threadIdx.x;
+    if (n >= N) return;
+    const T* xr = x + ((Bx == 1 ? 0 : b) * N + n) * 7;
+    T* o = out + (b * N + n) * 7;
+    T v[7];
+#pragma unroll
+    for (int c = 0; c < 7; ++c) v[c] = xr[c];
+    const double* st = state + b * state_row;
+    if (node_live(st)) {
+        int k;
+        double f;
+        bool in;
+        wake_node((double)v[4], st[1], st[2], M, k, f, in);
+        // no field (a scale of 0; both nodes 0: no charge) leaves delta's bits as they are, NaN tau included
+        const double sc = st[kHdr - 1], n0 = st[kHdr + k], n1 = st[kHdr + k + 1];
+        if (sc != 0.0 && (n0 != 0.0 || n1 != 0.0)) {
+            const double dv = sc * ((1.0 - f) * n0 + f * n1);
+            if (dv != 0.0) v[5] = (T)((double)v[5] + dv);
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 7; ++c) o[c] = v[c];
+}
+
+// B1: bound of the gather's cotangents a = scale g_delta; partials of d(scale) = sum g_delta dE(u); zeroes the cotangents' grid.
+template <typename T>
+__device__ __forceinline__ void node_bwd_range(const T* __restrict__ x, int64_t Bx, int64_t N, int G, int M,
+                                               const double* __restrict__ state, int64_t state_row, const T* __restrict__ gout,
+                                               double* __restrict__ bpart, unsigned long long* __restrict__ ggrid) {
+    __shared__ double red[4 * 4];
+    const int64_t b = blockIdx.y;
+    const int g = blockIdx.x;
+    unsigned long long* gr = ggrid + b * M;
+    for (int64_t i = (int64_t)g * kWB + threadIdx.x; i < M; i += (int64_t)G * kWB) gr[i] = 0ull;
+    const double* st = state + b * state_row;
+    const double* node = st + kHdr;
+    const int64_t chunk = (N + G - 1) / G, n0 = g * chunk, n1 = n0 + chunk < N ? n0 + chunk : N;
+    double lo = 0.0, hi = 0.0, s[2] = {0.0, 0.0};
+    if (node_live(st)) {
+        const double sc = st[kHdr - 1];
+        const T* xb = x + (Bx == 1 ? 0 : b) * N * 7;
+        const T* gb = gout + b * N * 7;
+        for (int64_t n = n0 + threadIdx.x; n < n1; n += kWB) {
+            int k;
+            double f;
+            bool in;
+            wake_node((double)xb[n * 7 + 4], st[1], st[2], M, k, f, in);
+            if (isnan(f)) continue;
+            const double g5 = (double)gb[n * 7 + 5];
+            s[0] += fabs(sc * g5);
+            s[1] += g5 * ((1.0 - f) * node[k] + f * node[k + 1]);
+        }
+    }
+    block_reduce<2>(lo, hi, s, red);
+    if (threadIdx.x == 0) {
+        double* p = bpart + (b * G + g) * kPart;
+        p[0] = s[0]; p[1] = s[1]; p[2] = p[3] = p[4] = p[5] = p[6] = p[7] = 0.0;
+    }
+}
+
+// B2: fixed-point deposit of the gather's cotangents, as F2 (hist: M integers of dynamic LDS); workgroup 0 writes d(scale) and
+// the backward header (valid, S of the cotangent deposit).
+template <typename T>
+__device__ __forceinline__ void node_bwd_deposit(const T* __restrict__ x, int64_t Bx, int64_t N, int G, int M,
+                                                 const double* __restrict__ state, int64_t state_row, const T* __restrict__ gout,
+                                                 const double* __restrict__ bpart, double* __restrict__ bhdr,
+                                                 double* __restrict__ d_scale, unsigned long long* __restrict__ ggrid,
+                                                 unsigned long long* hist) {
+    __shared__ double red[4 * 4];
+    __shared__ double S;
+    const int64_t b = blockIdx.y;
+    const int g = blockIdx.x;
+    const double* st = state + b * state_row;
+    double lo = 0.0, hi = 0.0, s[2] = {0.0, 0.0};
+    for (int gg = threadIdx.x; gg < G; gg += kWB) {
+        const double* p = bpart + (b * G + gg) * kPart;
+        s[0] += p[0]; s[1] += p[1];
+    }
+    block_reduce<2>(lo, hi, s, red);
+    if (threadIdx.x == 0) {
+        S = fixed_scale(s[0]);
+        if (g == 0) {
+            d_scale[b] = s[1];
+            bhdr[b * kHdr] = st[0];
+            bhdr[b * kHdr + 1] = S;
+        }
+    }
+    __syncthreads();
+    if (!node_live(st)) return;
+    const double S0 = S;
+    for (int i = threadIdx.x; i < M; i += kWB) hist[i] = 0ull;
+    __syncthreads();
+    const T* xb = x + (Bx == 1 ? 0 : b) * N * 7;
+    const T* gb = gout + b * N * 7;
+    const double sc = st[kHdr - 1];
+    const int64_t chunk = (N + G - 1) / G, n0 = g * chunk, n1 = n0 + chunk < N ? n0 + chunk : N;
+    for (int64_t n = n0 + threadIdx.x; n < n1; n += kWB) {
+        int k;
+        double f;
+        bool in;
+        wake_node((double)xb[n * 7 + 4], st[1], st[2], M, k, f, in);
+        if (isnan(f)) continue;
+        const double a = sc * (double)gb[n * 7 + 5];
+        atomicAdd(&hist[k], to_fixed((1.0 - f) * a, S0));
+        atomicAdd(&hist[k + 1], to_fixed(f * a, S0));
+    }
+    __syncthreads();
+    unsigned long long* gr = ggrid + b * M;
+    for (int i = threadIdx.x; i < M; i += kWB) {
+        const unsigned long long v = hist[i];
+        if (v) atomicAdd(&gr[i], v);
+    }
+}
+
+// B4, one thread per particle: adjoint of the deposit (adj[B][M]: cotangents of the deposits) and of the node coordinate.
+template <typename T>
+__device__ __forceinline__ void node_bwd_particle(const T* __restrict__ x, const T* __restrict__ q, const T* __restrict__ w,
+                                                  int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int M,
+                                                  const double* __restrict__ state, int64_t state_row,
+                                                  const double* __restrict__ adj, const T* __restrict__ gout, T* __restrict__ dX,
+                                                  T* __restrict__ dC) {
+    const int64_t b = blockIdx.y;
+    const int64_t n = (int64_t)blockIdx.x * kWB + threadIdx.x;
+    if (n >= N) return;
+    const RowPtrs<T> r = row_ptrs(x, q, w, Bx, Bq, Bw, N, b);
+    const T* gr = gout + (b * N + n) * 7;
+    double gv[7];
+#pragma unroll
+    for (int c = 0; c < 7; ++c) gv[c] = (double)gr[c];
+    const double* st = state + b * state_row;
+    double dc = 0.0;
+    if (node_live(st)) {
+        const double tau = (double)r.x[n * 7 + 4];
+        int k;
+        double f;
+        bool in;
+        wake_node(tau, st[1], st[2], M, k, f, in);
+        const double* node = st + kHdr;
+        const double* ad = adj + b * M;
+        const double sc = st[kHdr - 1];
+        double df = sc * gv[5] * (node[k + 1] - node[k]);
+        const double wn = (double)r.w[n];
+        if (wn > 0.0 && isfinite(tau)) {
+            const double c = fabs((double)r.q[n]) * wn;
+            dc = (1.0 - f) * ad[k] + f * ad[k + 1];
+            df += c * (ad[k + 1] - ad[k]);
+        }
+        if (in) gv[4] += df / st[2];
+    }
+    T* o = dX + (b * N + n) * 7;
+#pragma unroll
+    for (int c = 0; c < 7; ++c) o[c] = (T)gv[c];
+    if (dC) dC[b * N + n] = (T)dc;
 }
 
 // Lane l's double, broadcast to the whole wave (the Toeplitz sums over the nodes: one source tile of 64 nodes per load).

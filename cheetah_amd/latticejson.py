@@ -101,9 +101,11 @@ def parse_element(name: str, lattice_dict: dict, device=None, dtype=None):
 
     cls_name, params = lattice_dict["elements"][name]
     cls = getattr(accelerator, cls_name)
+    plain = getattr(cls, "_plain_features", ())   # numbers the constructor takes as Python values (LSCKick.radius_factor)
     converted = {
         key: (parse_element(value, lattice_dict, device=device, dtype=dtype)
-              if isinstance(value, str) and value in lattice_dict["elements"] else _feature(value, device, dtype))
+              if isinstance(value, str) and value in lattice_dict["elements"]
+              else value if key in plain else _feature(value, device, dtype))
         for key, value in params.items()
     }
     # unlike the reference (latticejson.py:207) the factory kwargs are forwarded, so defaulted tensors of files that

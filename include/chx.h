@@ -330,6 +330,31 @@ int chx_csr_kick(const void* x, const void* q, const void* w, const void* energy
 int chx_csr_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M,
                      int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale, void* workspace,
                      size_t workspace_bytes, void* stream);
+/* ---- longitudinal space charge (LSCKick element): per batch row b, the surviving particles' grid and node-based linear deposit D_k
+ * (coulomb) exactly as chx_wake_kick's and chx_csr_kick's (same tau_lo, node spacing h, u, k, f, clamping, dead particles, NaN tau);
+ * the on-axis field of a uniformly charged disc of radius a and Lorentz factor gamma, integrated exactly against the hat functions:
+ * rho = a / (gamma h), P(v) = v / (|v| + sqrt(v^2 + rho^2)) + asinh(v / rho), c^_0 = 0, c^_(-j) = -c^_j, c^_j = -(P(j+1) - 2 P(j) +
+ * P(j-1)) / 2; V_k = sum_{j=-k}^{M-1-k} c^_j D_(k+j) (two-sided: charge behind a witness, at larger tau, pushes it forward); every
+ * particle (dead ones too; NaN tau -> NaN) gets delta += S ((1 - f) V_k + f V_(k+1)) with S = |Z| 2 k_e L / (gamma^2 h^2 p0c) (fp64,
+ * rounded once; where the field is zero — L = 0, both nodes 0 — delta keeps its bits, NaN tau included). energy[Be], length[Bl] (L),
+ * radius[Ba] (a) are device arrays of the beam's dtype (each 1 or B rows); gamma, p0c, S and rho are formed on the device, in fp64. A
+ * row whose radius is not > 0 or not finite gets NaN in delta. A row without surviving particles or with h = 0 is copied bit for bit.
+ * out[B][N][7], state[B][CHX_LSC_STATE_DOUBLES(M)] (row header as chx_wake_kick's with S in its last slot, the M node sums V_k, rho, a
+ * free slot, the M deposits D_k). x, q, w (dtype, [Bx][N][7], [Bq][N], [Bw][N]). Deterministic (64-bit fixed-point deposit, fixed-order
+ * sums). 2 <= M <= CHX_WAKE_MAX_BINS. workspace: chx_lsc_workspace_bytes(B, N, M) (also for the backward pass).
+ * chx_lsc_kick_bwd: given d_out[B][N][7] (dtype) and the forward's state -> dX[B][N][7] (delta's cotangent passes through), dC[B][N]
+ * (dtype; gradient with respect to c = |q| w, 0 for particles that do not deposit; may be NULL), d_scale[B] and d_rho[B] (fp64,
+ * gradients with respect to the row's S and rho: the caller chains them to energy, L and a). The node grid is a constant (no gradient
+ * through tau_lo, h). Rows of broadcast inputs are NOT reduced — the caller sums. */
+#define CHX_LSC_STATE_DOUBLES(M) (CHX_WAKE_STATE_HEADER + 2 + 2 * (int64_t)(M))
+size_t chx_lsc_workspace_bytes(int64_t B, int64_t N, int32_t M);
+int chx_lsc_kick(const void* x, const void* q, const void* w, const void* energy, const void* length, const void* radius,
+                 double mass_eV, double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl,
+                 int64_t Ba, int64_t N, int32_t M, int dtype, void* out, double* state, void* workspace, size_t workspace_bytes,
+                 void* stream);
+int chx_lsc_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M,
+                     int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale, double* d_rho,
+                     void* workspace, size_t workspace_bytes, void* stream);
 /* Backward of chx_moments(y), y_n = R x_n, with respect to the MAP R[BR][7][7] (dtype) when the particles x carry no
  * gradient: mu' = A mu + b, cov' = A C A^T (element.py:180-191 + utils/statistics.py:4-62), so
  * dR[B][7][7] (double) = [2 G A C + g_mu mu^T | g_mu; 0] from d_out[B][29] and the INCOMING beam's chx_moments
