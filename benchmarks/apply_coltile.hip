@@ -25,11 +25,19 @@
 // registers with the wave), every kernel of this file takes its arguments that way: the two builds, alternating, are the measurement
 // behind that option for chx_coltile.hip.
 //
+// r10 (profiles/r10_const_column.md): whole calls, pass 0 included, of the production structure against
+//   part 1         the pass that enters the layout writes one word per tile (column 6 all 1), the column passes read six columns
+//                  where it is set (k_enter, k_col16_flag: kernel for kernel coltile_enter_kernel / coltile_pass_flag_kernel)
+//   part 2         pass 0 writes the column tiles itself (k_enter_first), pass 1 is an ordinary column pass
+//   part 1 + 2     both
+// Part 1 is in the library; part 2 moved nothing beyond the spreads at any size and lives here only.
+// us per pass = the whole call / 100; `r10 [rows]` for the three maps at one size, `r10sweep` for the FODO cell over the sizes.
+//
 // Build (after libchx.so) and run:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -Icheetah_amd/csrc -Iinclude benchmarks/apply_coltile.hip \
 //         -Lcheetah_amd -lchx -L/opt/rocm/lib -lhipfft -Wl,-rpath,$PWD/cheetah_amd -o apply_coltile
 //   (the second build: the same line with -mllvm -amdgpu-kernarg-preload-count=8 and -o apply_coltile_preload)
-//   ./apply_coltile ab [rows]; ./apply_coltile sweep
+//   ./apply_coltile ab [rows]; ./apply_coltile sweep; ./apply_coltile r10 [rows]; ./apply_coltile r10sweep
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdio>
@@ -93,6 +101,44 @@ __global__ __launch_bounds__(TP / 4) void k_col16_prod(float* x, const float* __
     const float* __restrict__ Rb = R + ((BR == 1) ? 0 : b) * 49;
     if (N - n0 >= TP) chx_coltile_pass<float, TP, NT_LOAD, NT_STORE>(g, Rb);
     else chx_rowtile_pass<float>(g, Rb, (int)(N - n0));
+}
+
+// ---- r10: the kernels chx_coltile.hip launches when chx_track_elementwise is given scratch ----
+template <bool NT_LOAD>
+__global__ __launch_bounds__(TP / 4) void k_col16_flag(float* x, const float* __restrict__ R, unsigned* flags, int64_t N, int64_t BR) {
+    const int64_t tiles_per_row = (N + TP - 1) / TP;
+    const int64_t b = blockIdx.x / tiles_per_row;
+    const int64_t n0 = (blockIdx.x - b * tiles_per_row) * TP;
+    float* g = x + (b * N + n0) * 7;
+    const float* __restrict__ Rb = R + ((BR == 1) ? 0 : b) * 49;
+    if (N - n0 >= TP) chx_coltile_pass<float, TP, NT_LOAD, true, true>(g, Rb, flags + blockIdx.x);
+    else chx_rowtile_pass<float>(g, Rb, (int)(N - n0));
+}
+
+// pass 1 in place: coltile_enter_kernel
+__global__ __launch_bounds__(CHX_BLOCK) void k_enter(float* x, const float* __restrict__ R, unsigned* flags, int64_t N, int64_t BR) {
+    __shared__ __attribute__((aligned(16))) float lds[TP * 7];
+    const int64_t tiles_per_row = (N + TP - 1) / TP;
+    const int64_t b = blockIdx.x / tiles_per_row;
+    const int64_t n0 = (blockIdx.x - b * tiles_per_row) * TP;
+    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
+    float* g = x + (b * N + n0) * 7;
+    chx_coltile_enter<float, TP>(g, g, R + ((BR == 1) ? 0 : b) * 49, lds, np, true, false, flags + blockIdx.x);
+}
+
+// part 2, not in the library: pass 0 from the input of the call (shared by the batch rows when Bx == 1) straight into column tiles,
+// with apply_tile_kernel's alignment handling. in_flags: bit 0 = x_in 16-byte aligned, bit 1 = nt loads.
+__global__ __launch_bounds__(CHX_BLOCK) void k_enter_first(const float* x_in, const float* __restrict__ R, float* x_out, unsigned* flags,
+                                                           int64_t N, int64_t BR, int64_t Bx, int in_flags) {
+    __shared__ __attribute__((aligned(16))) float lds[TP * 7];
+    const int64_t tiles_per_row = (N + TP - 1) / TP;
+    const int64_t b = blockIdx.x / tiles_per_row;
+    const int64_t n0 = (blockIdx.x - b * tiles_per_row) * TP;
+    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
+    const int64_t in_row = (Bx == 1) ? 0 : b;
+    const bool in_vec = (in_flags & 1) && (((in_row * N * 7 * (int64_t)sizeof(float)) & 15) == 0);
+    chx_coltile_enter<float, TP>(x_in + (in_row * N + n0) * 7, x_out + (b * N + n0) * 7, R + ((BR == 1) ? 0 : b) * 49, lds, np, in_vec,
+                                 (in_flags & 2) != 0, flags + blockIdx.x);
 }
 
 // ---- r09, measured and not taken: the map requested before the particles, in one piece (profiles/r09_map_prologue.md) ----
@@ -440,13 +486,103 @@ int main(int argc, char** argv) {
         CK(hipFree(x0)); CK(hipFree(ref)); CK(hipFree(buf));
     };
 
+    // r10: whole calls (pass 0 + E - 1 in-place passes), us per pass = call / E
+    auto run_r10 = [&](long N, bool sweep) {
+        const unsigned tiles = (unsigned)((N + TP - 1) / TP);
+        const long bytes = N * 28;
+        const bool nt = bytes > 28L * 1024 * 1024;   // kL2ResidentBytes
+        std::vector<float> hx(N * 7);
+        for (long i = 0; i < N * 7; ++i) hx[i] = i % 7 == 6 ? 1.f : ((float)((i * 2654435761u) % 1000) * 1e-3f - 0.4995f) * 1e-3f;
+        float *x0, *ref, *buf;
+        unsigned* flags;
+        CK(hipMalloc(&x0, bytes)); CK(hipMalloc(&ref, bytes)); CK(hipMalloc(&buf, bytes)); CK(hipMalloc(&flags, tiles * 4));
+        CK(hipMemcpy(x0, hx.data(), bytes, hipMemcpyHostToDevice));
+        std::vector<float> ha(N * 7), hb(N * 7);
+        const int64_t Nl = N, one = 1;
+        const dim3 g(tiles), b16(TP / 4), b256(CHX_BLOCK);
+        // 0: production; 1: part 1; 2: part 2; 3: parts 1 and 2
+        auto call = [&](int v, float* out, const float* R) {
+            const bool first = v >= 2, flagged = v == 1 || v == 3;
+            int e = 1;
+            if (first) hipLaunchKernelGGL(k_enter_first, g, b256, 0, 0, x0, R, out, flags, Nl, one, one, 3);
+            else {
+                if (chx_apply_affine7(x0, R, out, 1, 1, 1, N, CHX_F32, nullptr) != CHX_OK) { printf("chx_apply_affine7 failed\n"); exit(1); }
+                if (flagged) hipLaunchKernelGGL(k_enter, g, b256, 0, 0, out, R + 49, flags, Nl, one);
+                else hipLaunchKernelGGL(k_edge_prod<true>, g, b256, 0, 0, out, R + 49, one, Nl);
+                e = 2;
+            }
+            for (; e < E - 1; ++e) {
+                const float* Re = R + e * 49;
+                if (flagged) {
+                    if (nt) hipLaunchKernelGGL(k_col16_flag<true>, g, b16, 0, 0, out, Re, flags, Nl, one);
+                    else hipLaunchKernelGGL(k_col16_flag<false>, g, b16, 0, 0, out, Re, flags, Nl, one);
+                } else {
+                    if (nt) hipLaunchKernelGGL((k_col16_prod<true, true>), g, b16, 0, 0, out, Re, one, Nl);
+                    else hipLaunchKernelGGL((k_col16_prod<false, true>), g, b16, 0, 0, out, Re, one, Nl);
+                }
+            }
+            hipLaunchKernelGGL(k_edge_prod<false>, g, b256, 0, 0, out, R + (E - 1) * 49, one, Nl);
+        };
+        const char* names[4] = {"production: row pass 0, edge pass, column passes", "part 1: flags, six-column passes",
+                                "part 2: pass 0 writes column tiles", "parts 1 + 2"};
+        for (int m = 0; m < (sweep ? 1 : 3); ++m) {
+            printf("N=%ld rows fp32 (%.1f MiB), whole call of %d passes, maps: %s\n", N, bytes / 1048576.0, E, map_name[m]);
+            const float* R = dR[m];
+            Stats st[4];
+            float runs[4][8];
+            for (int v = 0; v < 4; ++v) { st[v] = Stats{0.f, 1e30f, 0.f}; call(v, buf, R); }
+            CK(hipDeviceSynchronize());
+            // The first call behind a synchronise costs 150 - 250 us more than the same call later, whichever variant it is (seen run by
+            // run in profiles/r10_const_column.md): one untimed call takes it. The starting variant rotates from run to run, so
+            // that whatever else depends on the position in the sequence does not always meet the same variant.
+            call(3, buf, R);
+            for (int r = 0; r < reps; ++r)
+                for (int i = 0; i < 4; ++i) {
+                    const int v = (i + r) % 4;
+                    CK(hipEventRecord(t0, 0));
+                    call(v, buf, R);
+                    CK(hipEventRecord(t1, 0));
+                    CK(hipEventSynchronize(t1));
+                    float ms;
+                    CK(hipEventElapsedTime(&ms, t0, t1));
+                    const float us = ms * 1e3f / E;
+                    runs[v][r] = us;
+                    st[v].mean += us / reps;
+                    st[v].lo = us < st[v].lo ? us : st[v].lo;
+                    st[v].hi = us > st[v].hi ? us : st[v].hi;
+                }
+            // the row structure: nt loads, nt stores, rows, in every pass
+            for (int e = 0; e < E; ++e) hipLaunchKernelGGL(k_rows<true>, g, b256, 0, 0, e ? ref : x0, R + e * 49, ref, N);
+            CK(hipDeviceSynchronize());
+            CK(hipMemcpy(ha.data(), ref, bytes, hipMemcpyDeviceToHost));
+            for (int v = 0; v < 4; ++v) {
+                CK(hipMemset(flags, v & 1 ? 0xff : 0, tiles * 4));
+                call(v, buf, R);
+                CK(hipDeviceSynchronize());
+                CK(hipMemcpy(hb.data(), buf, bytes, hipMemcpyDeviceToHost));
+                long bad = 0;
+                for (long i = 0; i < N * 7; ++i) bad += memcmp(&ha[i], &hb[i], 4) != 0;
+                printf("  %-58s %7.3f us/pass (min %7.3f max %7.3f)  mismatches=%ld\n", names[v], st[v].mean, st[v].lo, st[v].hi, bad);
+                printf("      runs in order:");
+                for (int r = 0; r < reps; ++r) printf(" %.3f", runs[v][r]);
+                printf("\n");
+                fflush(stdout);
+            }
+        }
+        CK(hipFree(x0)); CK(hipFree(ref)); CK(hipFree(buf)); CK(hipFree(flags));
+    };
+
+    if (!strcmp(mode, "r10")) run_r10(argc > 2 ? atol(argv[2]) : 1000000, false);
+    else if (!strcmp(mode, "r10sweep")) {
+        for (long N : {300000L, 500000L, 600000L, 800000L, 1000000L, 1048576L, 1300000L, 1600000L, 3000000L, 3600000L, 16000000L}) run_r10(N, true);
+    } else
     if (!strcmp(mode, "ab")) run_size(argc > 2 ? atol(argv[2]) : 1000000, false);
     else if (!strcmp(mode, "sweep")) {
         if (argc > 2) run_size(atol(argv[2]), true);
         else
             for (long N : {20000L, 50000L, 100000L, 300000L, 500000L, 800000L, 1000000L, 1048576L, 1300000L, 1600000L, 3000000L, 16000000L}) run_size(N, true);
     } else {
-        printf("usage: apply_coltile ab [rows] | sweep [rows]\n");
+        printf("usage: apply_coltile ab [rows] | sweep [rows] | r10 [rows] | r10sweep\n");
         return 2;
     }
     for (int m = 0; m < 3; ++m) CK(hipFree(dR[m]));

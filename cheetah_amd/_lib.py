@@ -95,6 +95,7 @@ SIGNATURES = {
     "chx_apply_affine7": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p]),
     "chx_apply_bwd_workspace_bytes": (c_size_t, [c_i64, c_i64]),
     "chx_apply_affine7_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_size_t, c_void_p]),
+    "chx_track_elementwise_scratch_bytes": (c_size_t, [c_i64, c_i64, c_int]),
     "chx_track_elementwise": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p]),
     "chx_track_fused": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p]),
     "chx_cavity_coeffs": (c_int, [c_void_p, c_void_p, c_double, c_double, c_i64, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p]),

@@ -608,7 +608,10 @@ def track_elementwise(particles, maps: torch.Tensor, fused: bool = False) -> tor
         check(lib.chx_track_fused(ptr(x), ptr(maps), ptr(out), E, B, Bx, BR, N, dtype_code(x.dtype), stream_ptr()),
               "chx_track_fused")
     else:
-        check(lib.chx_track_elementwise(ptr(x), ptr(maps), ptr(out), None, E, B, Bx, BR, N,
+        # one word per column tile (chx.h: scratch); from the caching allocator, so stream-ordered and capturable
+        nbytes = lib.chx_track_elementwise_scratch_bytes(B, N, dtype_code(x.dtype))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+        check(lib.chx_track_elementwise(ptr(x), ptr(maps), ptr(out), ptr(scratch) if nbytes else None, E, B, Bx, BR, N,
                                         dtype_code(x.dtype), stream_ptr()), "chx_track_elementwise")
     return out.reshape(*batch_shape, N, 7)
 

@@ -16,7 +16,8 @@
 //    pass, element-wise and fused kernels, so those agree bit for bit);
 //  * between the first and the last in-place pass of chx_track_elementwise the full tiles are held transposed ([7][TP]):
 //    a lane then moves 16 bytes per column without LDS, and a column a map leaves as it was is not stored
-//    (coltile_edge_kernel, coltile_pass_kernel in chx_coltile.hip; the layout never leaves the call).
+//    (coltile_edge_kernel, coltile_pass_kernel in chx_coltile.hip; the layout never leaves the call); with one word of scratch per
+//    tile the seventh column, the constant 1, is not read either where pass 1 found nothing else in it.
 #include <cstdlib>
 #include <type_traits>
 
@@ -567,25 +568,30 @@ extern "C" int chx_track_fused(const void* x_in, const void* R, void* x_out, int
                             : launch_tiles<double, 1>(x_in, R, x_out, nullptr, B, Bx, BR, N, (int)E, s);
 }
 
+extern "C" size_t chx_track_elementwise_scratch_bytes(int64_t B, int64_t N, int dtype) {
+    if (dtype != CHX_F32 && dtype != CHX_F64) return 0;
+    return chx_coltile_scratch_bytes(B, N, dtype);
+}
+
 extern "C" int chx_track_elementwise(const void* x_in, const void* R, void* x_out, void* scratch,
                                      int64_t E, int64_t B, int64_t Bx, int64_t BR, int64_t N,
                                      int dtype, void* stream) {
     int st = check_common(x_in, R, x_out, B, Bx, BR, N, dtype);
     if (st != CHX_OK) return st;
     if (E < 1) return CHX_ERR_INVALID_ARG;
+    if (reinterpret_cast<uintptr_t>(scratch) % sizeof(unsigned)) return CHX_ERR_MISALIGNED;
     const size_t esz = dtype == CHX_F32 ? 4 : 8;
     const char* Rp = (const char*)R;
     // pass 0 goes x_in -> x_out, every later pass updates x_out IN PLACE: a workgroup reads its whole tile into LDS before
     // it writes the same rows back, and no other workgroup touches them. Measured on MI355X at 1e6 particles: 8.9 us per
     // pass in place vs 9.3 us ping-ponging between x_out and scratch (half the footprint in L2 / Infinity Cache); in place
     // the beam can also stay in the XCDs' L2s from pass to pass (launch_inplace_pass).
-    // `scratch` is kept in the signature for ABI stability and is not used.
-    (void)scratch;
     st = chx_apply_affine7(x_in, Rp, x_out, B, Bx, BR, N, dtype, stream);
     hipStream_t s = (hipStream_t)stream;
     // E >= 3: passes 1..E-1 keep every full tile of x_out transposed ([7][TP]) between them and store only the columns a map
-    // changed; the last pass leaves x_out as [N][7] rows again (chx_common.h: column tiles)
-    if (st == CHX_OK && chx_coltile_ok(x_out, E, B, N, dtype)) return chx_coltile_passes(x_out, R, E, B, BR, N, dtype, s);
+    // changed; the last pass leaves x_out as [N][7] rows again (chx_common.h: column tiles). With `scratch` (one word per tile)
+    // pass 1 records which tiles hold nothing but 1 in column 6, and the column passes do not read that column there.
+    if (st == CHX_OK && chx_coltile_ok(x_out, E, B, N, dtype)) return chx_coltile_passes(x_out, R, scratch, E, B, BR, N, dtype, s);
     for (int64_t e = 1; e < E && st == CHX_OK; ++e) {
         const void* Re = Rp + (size_t)e * (size_t)BR * 49 * esz;
         st = dtype == CHX_F32 ? launch_inplace_pass<float>(x_out, Re, B, BR, N, s)

@@ -16,6 +16,13 @@ constexpr int64_t kL2ResidentBytes = (int64_t)28 * 1024 * 1024;
 // at 1e5 rows and below both sit on the launch floor (2.6 - 3.0 us, inside each other's spread) and the row passes stay.
 constexpr int64_t kColTileMinBytes = (int64_t)8 * 1024 * 1024;
 
-// chx_coltile.hip: passes 1..E-1 of chx_track_elementwise through the column layout (needs chx_coltile_ok)
+// Pass 0 of such a call stays the row pass above at every size: a pass 0 that writes the column tiles itself (chx_coltile_enter from
+// x_in, which makes pass 1 an ordinary column pass) was measured in benchmarks/apply_coltile.hip (r10, part 2), us per pass of a
+// whole 100-pass call with / without it: 1e6 rows 4.88 / 4.84, 1.3e6 8.03 / 7.90, 3e6 18.77 / 18.86, 1.6e7 102.9 / 103.2
+// (profiles/r10_const_column.md): inside the spreads everywhere, so there is no size threshold for it here.
+
+// chx_coltile.hip: passes 1..E-1 of chx_track_elementwise through the column layout (needs chx_coltile_ok). flags: NULL, or
+// chx_coltile_scratch_bytes() bytes, one word per tile (column 6 of the tile is all 1: the column passes do not read it).
 bool chx_coltile_ok(const void* x, int64_t E, int64_t B, int64_t N, int dtype);
-int chx_coltile_passes(void* x, const void* R, int64_t E, int64_t B, int64_t BR, int64_t N, int dtype, hipStream_t s);
+size_t chx_coltile_scratch_bytes(int64_t B, int64_t N, int dtype);
+int chx_coltile_passes(void* x, const void* R, void* flags, int64_t E, int64_t B, int64_t BR, int64_t N, int dtype, hipStream_t s);

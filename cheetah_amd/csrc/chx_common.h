@@ -314,8 +314,10 @@ __device__ __forceinline__ void wave_tile_store(T* __restrict__ g, const T* __re
 // ---- column tiles: the in-place element passes of chx_track_elementwise between its first and its last one ---------------
 // A full tile of TP rows (TP * 7 values, the same bytes in every pass) holds its rows transposed, [7][TP] instead of [TP][7].
 // A lane then owns 16 bytes of consecutive rows in each of the seven columns, needs no LDS and no barrier, and a column that a
-// map leaves as it was (px, py, delta and the 1 behind a drift) is a store the wave does not issue. Shared with
-// benchmarks/apply_coltile.hip, which times exactly these bodies.
+// map leaves as it was (px, py, delta and the 1 behind a drift) is a store the wave does not issue. Column 6 of every beam
+// this library makes is the constant 1 and every element's map leaves it so: given one word of scratch per tile, the entering
+// pass records where that holds and the column passes there do not read the column either (chx_coltile_pass, FLAGGED).
+// Shared with benchmarks/apply_coltile.hip, which times exactly these bodies.
 typedef unsigned chx_v4u __attribute__((ext_vector_type(4)));
 template <typename T> struct chx_col16;   // V: 16 bytes of one column, P: two rows of it (one packed FMA per step in float32)
 template <> struct chx_col16<float> { using V = chx_v4f; using P = chx_v2f; };
@@ -337,15 +339,33 @@ __device__ __forceinline__ void chx_map7(const T* __restrict__ R, const X (&x)[7
 // of the wave holds a result whose bits differ from what it loaded: memory already holds exactly the bits a skipped store would
 // have written, so the tile is bit for bit what storing everything leaves (NaN payloads, infinities and -0.0 included).
 // g is read and written: no __restrict__. NT_LOAD: the beam does not stay in L2 from pass to pass, stream past it.
-template <typename T, int TP, bool NT_LOAD, bool NT_STORE = true>
-__device__ __forceinline__ void chx_coltile_pass(T* g, const T* __restrict__ R) {
+// FLAGGED: *flag (one word per tile, written by chx_coltile_enter) says that column 6 of the tile, the affine coordinate, is
+// all (T)1 in memory. The six loads of columns 0..5 leave first, then the flag is read (a uniform address: a scalar load behind
+// the vector loads); where it is set the seventh load, 16 bytes per lane through the L2 queue that bounds the pass, is not
+// issued and x[6] is the constant. The constant goes through an empty asm so that both arms run the same fma chain (no
+// fma(r, 1, acc) folded into an add): identical inputs to identical instructions, identical bits. A wave whose column 6 comes
+// out other than it went in (a map whose last row is not e6, a NaN or inf in another column against a zero of row 6) stores
+// it as ever and clears the flag; a wave that saw no difference leaves the 1s in memory, which is what it would have stored.
+// Two waves of a tile may both clear it, and a wave may read the flag before or after the other wave's clear: its own 16
+// bytes per lane of column 6 are in memory either way. The flag is not set again within a call.
+template <typename T, int TP, bool NT_LOAD, bool NT_STORE = true, bool FLAGGED = false>
+__device__ __forceinline__ void chx_coltile_pass(T* g, const T* __restrict__ R, unsigned* flag = nullptr) {
     using V = typename chx_col16<T>::V;
     using P = typename chx_col16<T>::P;
     constexpr int LANES = TP / (16 / (int)sizeof(T));
+    constexpr int NLOAD = FLAGGED ? 6 : 7;
     V* gv = reinterpret_cast<V*>(g) + threadIdx.x;
     V x[7], y[7];
 #pragma unroll
-    for (int j = 0; j < 7; ++j) x[j] = NT_LOAD ? __builtin_nontemporal_load(gv + j * LANES) : gv[j * LANES];
+    for (int j = 0; j < NLOAD; ++j) x[j] = NT_LOAD ? __builtin_nontemporal_load(gv + j * LANES) : gv[j * LANES];
+    unsigned flagged = 0;
+    if constexpr (FLAGGED) {
+        flagged = *flag;
+        T one = (T)1;
+        asm("" : "+v"(one));
+        x[6] = (V)one;
+        if (!flagged) x[6] = NT_LOAD ? __builtin_nontemporal_load(gv + 6 * LANES) : gv[6 * LANES];
+    }
     if constexpr (sizeof(T) == 4) {
         P lo[7], hi[7], ylo[7], yhi[7];
 #pragma unroll
@@ -363,6 +383,7 @@ __device__ __forceinline__ void chx_coltile_pass(T* g, const T* __restrict__ R) 
         if (__any((d.x | d.y | d.z | d.w) != 0u)) {
             if (NT_STORE) __builtin_nontemporal_store(y[j], gv + j * LANES);
             else gv[j * LANES] = y[j];
+            if (FLAGGED && j == 6 && flagged && (threadIdx.x & 63) == 0) *flag = 0u;
         }
     }
 }
@@ -412,6 +433,60 @@ __device__ __forceinline__ void chx_coltile_edge(T* g, const T* __restrict__ R, 
     }
     __syncthreads();
     tile_store<T, TP>(g, lds, np * 7, vec_ok, true);
+}
+
+// The pass that enters the column layout and says what it left there, CHX_BLOCK lanes: chx_coltile_edge<T, TP, true> with *flag
+// written for the tile, every call, so that the flags need no initialising: 1 iff every value of column 6 the tile now holds has
+// the bits of (T)1. Wave 0 reads that column back from the LDS image behind the last barrier (32 bytes per lane), one lane stores
+// the word. The whole of column 6 goes to memory whatever the flag says. A tile that is not full stays rows, and its flag, which
+// no pass reads, is 0. The library runs it in place (gin == gout: pass 1, the rows just written come from L2); with gin the input
+// of the call it is a pass 0 that writes column tiles (in_vec / nt_in as in apply_tile_kernel), which benchmarks/apply_coltile.hip
+// measured and the library does not use (chx_apply_tiles.h).
+template <typename T, int TP>
+__device__ __forceinline__ void chx_coltile_enter(const T* gin, T* gout, const T* __restrict__ R, T* lds, int np, bool in_vec,
+                                                  bool nt_in, unsigned* flag) {
+    using V = typename chx_col16<T>::V;
+    constexpr int PPT = TP / CHX_BLOCK;
+    const bool full = np == TP;
+    tile_load<T, TP>(gin, lds, np * 7, in_vec, nt_in);
+    __syncthreads();
+    T y[PPT][7];
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        const int p = threadIdx.x + k * CHX_BLOCK;
+        if (p < np) {
+            T x[7];
+#pragma unroll
+            for (int j = 0; j < 7; ++j) x[j] = lds[p * 7 + j];
+            chx_map7<T, T>(R, x, y[k]);
+        }
+    }
+    if (full) __syncthreads();   // the layout changes: every lane has read its rows before another lane's results land on them
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) {
+        const int p = threadIdx.x + k * CHX_BLOCK;
+        if (p < np) {
+#pragma unroll
+            for (int j = 0; j < 7; ++j) lds[full ? j * TP + p : p * 7 + j] = y[k][j];
+        }
+    }
+    __syncthreads();
+    tile_store<T, TP>(gout, lds, np * 7, true, true);
+    if (threadIdx.x < 64) {
+        bool ones = full;
+        if (full) {
+            constexpr int NV = TP * (int)sizeof(T) / 16 / 64;   // 16-byte pieces of column 6 per lane of one wave
+            const V* c6 = reinterpret_cast<const V*>(lds + 6 * TP);
+            const V one = (V)(T)1;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) {
+                const chx_v4u d = __builtin_bit_cast(chx_v4u, c6[threadIdx.x + i * 64]) ^ __builtin_bit_cast(chx_v4u, one);
+                ones = ones && (d.x | d.y | d.z | d.w) == 0u;
+            }
+        }
+        const bool all_ones = __all(ones);
+        if (threadIdx.x == 0) *flag = all_ones ? 1u : 0u;
+    }
 }
 
 static inline int chx_grid_for(int64_t work_items, int per_block, int cap) {

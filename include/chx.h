@@ -190,12 +190,21 @@ int chx_apply_affine7_bwd(const void* dY, const void* R, const void* X, void* dX
 
 /* Element-by-element tracking of a run of E linear elements WITHOUT merging the maps
  * (`for e in elements: beam = e.track(beam)`, segment.py:571-572): E apply passes
- * pass 0 writes x_out, later passes update x_out in place (tile-local read-then-write); `scratch` is ignored (kept for
- * ABI stability, may be NULL). x_out must not alias x_in, which is only read.
+ * pass 0 writes x_out, later passes update x_out in place (tile-local read-then-write). x_out must not alias x_in, which is
+ * only read.
+ * `scratch`: NULL, or at least chx_track_elementwise_scratch_bytes(B, N, dtype) bytes of device memory (4-byte aligned; the
+ * function returns 0 where no call of these extents uses scratch, and then any pointer is ignored). It needs no initialising
+ * and holds nothing of use after the call: one word per tile of the column layout below, in which the pass that enters the
+ * layout records that the tile's seventh coordinate is 1 in every row — true of every beam this library makes, and kept so by
+ * every map whose last row is (0,...,0,1) — so that the passes in between do not read that column; a pass whose map makes it
+ * anything else stores the column and withdraws the word. The results are bit for bit those of a call with scratch == NULL,
+ * whatever the beam and the maps hold.
+ * (An additive export: CHX_ABI_VERSION stays as it is, as for every function added without changing an existing one.)
  * With E >= 3, 16-byte aligned batch rows and 8 MiB of particles or more, the full tiles of x_out (512 float32 / 256 float64
  * rows) are held transposed, [7][rows], between pass 1 and pass E-1, and a pass in between stores only the coordinates whose
  * bits its map changed. Pass E-1 writes rows again: x_out holds [B][N][7] rows, bit for bit those of E plain passes, once the
  * call's last kernel has run (stream order, as for any output); it must not be read on another stream before that. */
+size_t chx_track_elementwise_scratch_bytes(int64_t B, int64_t N, int dtype);
 int chx_track_elementwise(const void* x_in, const void* R /*[E][BR][7][7]*/, void* x_out,
                           void* scratch, int64_t E, int64_t B, int64_t Bx, int64_t BR,
                           int64_t N, int dtype, void* stream);
