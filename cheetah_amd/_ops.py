@@ -1526,12 +1526,5 @@ from ._ops_deposit import _cic_args, _cic_deposit_raw, _hist_args, _launch_cic  
 # ... and the slice statistics (ParticleBeam.slice_statistics) in _ops_slices.py
 from ._ops_slices import *  # noqa: E402,F401,F403
 from ._ops_slices import _slice_moments_bwd_raw, _slice_moments_raw  # noqa: E402,F401
-# ... and the wakefield kick (the Wakefield element) in _ops_wake.py
-from ._ops_wake import *  # noqa: E402,F401,F403
-from ._ops_wake import _wake_kick_bwd_raw, _wake_kick_raw  # noqa: E402,F401
-# ... and the steady-state CSR kick (the CSRKick element) in _ops_csr.py
-from ._ops_csr import *  # noqa: E402,F401,F403
-from ._ops_csr import _csr_kick_bwd_raw, _csr_kick_raw  # noqa: E402,F401
-# ... and the longitudinal space-charge kick (the LSCKick element) in _ops_lsc.py
-from ._ops_lsc import *  # noqa: E402,F401,F403
-from ._ops_lsc import _lsc_kick_bwd_raw, _lsc_kick_raw  # noqa: E402,F401
+# ... and the kicks from the beam binned on nodes in tau (the Wakefield, CSRKick and LSCKick elements) in _ops_grid1d.py
+from ._ops_grid1d import *  # noqa: E402,F401,F403

@@ -1,0 +1,291 @@
+"""The kicks of `cheetah_amd._ops` that bin the surviving particles' charge on M nodes in tau and kick every particle with what a sum
+over the nodes gives at its node coordinate: the short-range wake (Wakefield: causal convolution with the sampled wake, kicks to
+delta, px, py), the steady-state CSR (CSRKick: the anti-causal Toeplitz sum with the exactly integrated (z - z')^(-1/3) kernel) and
+the longitudinal space charge (LSCKick: the two-sided Toeplitz sum with the on-axis field of a charged disc). Each is one
+`chx_*_kick` call (four launches, deterministic, no host synchronisation) and an autograd node whose backward is `chx_*_kick_bwd`.
+The CSR and LSC kicks form their per-row factors on the device from the energy, length and angle / radius; they share one node.
+
+Part of `_ops` (which re-exports every name here). Imported at the END of `_ops`, whose helpers it uses."""
+from __future__ import annotations
+
+from operator import attrgetter
+from typing import Callable, NamedTuple
+
+import torch
+
+from . import _lib
+from ._ops import MAX_GRID_ROWS, aligned, bshapes, check, dtype_code, flat_bcast, numel, ptr, require_device, stream_ptr, workspace
+
+__all__ = ["WAKE_MAX_BINS", "CSR_MAX_BINS", "LSC_MAX_BINS", "WakeKick", "wake_kick", "wake_scale", "csr_kick", "csr_scale", "lsc_kick",
+           "lsc_scale_rho"]
+
+#: CHX_WAKE_MAX_BINS of include/chx.h: the deposit's per-workgroup LDS histograms hold up to 3 channels of M 64-bit nodes; one grid
+#: and one deposit for the three kicks
+WAKE_MAX_BINS = CSR_MAX_BINS = LSC_MAX_BINS = 4096
+#: k_e = 1 / (4 pi eps0), V m / C (chx_grid1d_dev.h)
+_K_E = 8.9875517923e9
+
+
+class _Kick(NamedTuple):
+    """What the shared callers need to know about a kick; built once at import."""
+    owner: str                  # the element's name in messages
+    workspace: str              # C entry points
+    forward: str
+    backward: str
+    state_doubles: tuple        # (s0, s1): s0 + s1 M doubles per batch row of the state the forward pass leaves for the backward pass
+    cotangents: int             # per-row float64 cotangents the backward call returns (d_scale[, d_rho])
+    factors: Callable | None    # (e, L, a, state, mass_eV, abs_z) -> the per-row factors, for the chain rule of the settings
+
+
+def _kick(owner: str, tag: str, state_doubles, cotangents: int, factors=None) -> _Kick:
+    return _Kick(owner, f"chx_{tag}_workspace_bytes", f"chx_{tag}_kick", f"chx_{tag}_kick_bwd", state_doubles, cotangents, factors)
+
+
+_shape = attrgetter("shape")
+
+
+def _rows(t: torch.Tensor, batch_shape, B: int, dtype):
+    """A setting as flat rows of the beam's dtype: (1,) view of a single value (an in-place edit reaches the kernel) or (B,)."""
+    t = t.to(dtype)
+    if t.numel() == 1:
+        return t.reshape(1)
+    return t.expand(batch_shape).reshape(B).contiguous()
+
+
+def _beam_rows(kick: _Kick, particles, charges, survival, *row_settings, others=()):
+    """The beam as flat rows: x (Bx, N, 7) aligned, q (Bq, N), w (Bw, N) in the particles' dtype, and the batch shape (broadcast of
+    the particles', charges', survival probabilities' and row settings' batch shapes) with its number of rows B. `others`: further
+    tensors (or None) that must live on the device."""
+    require_device(particles, charges, survival, *row_settings, *others)
+    dt = particles.dtype
+    batch_shape = bshapes(particles.shape[:-2], charges.shape[:-1], survival.shape[:-1], *map(_shape, row_settings))
+    B = numel(batch_shape)
+    if B > MAX_GRID_ROWS:
+        raise ValueError(f"{kick.owner}: at most {MAX_GRID_ROWS} batch rows per kick, got {B}")
+    x, _ = flat_bcast(particles, batch_shape, 2)
+    q, _ = flat_bcast(charges.to(dt), batch_shape, 1)
+    w, _ = flat_bcast(survival.to(dt), batch_shape, 1)
+    return aligned(x), q.contiguous(), w.contiguous(), batch_shape, B
+
+
+def _kick_raw(kick: _Kick, x, q, w, head, tail, B: int, N: int, M: int):
+    """The forward entry point on flat inputs x (Bx, N, 7), q (Bq, N), w (Bw, N) -> (out (B, N, 7), state (B, state_doubles)
+    float64), state_doubles = s0 + s1 M. `head`: the kick's own arguments between w and B, `tail`: those between Bw and N."""
+    lib = _lib.lib()
+    ws_bytes = getattr(lib, kick.workspace)(B, N, M)
+    ws = workspace(ws_bytes, x.device)
+    out = torch.empty((B, N, 7), dtype=x.dtype, device=x.device)
+    state = torch.empty((B, kick.state_doubles[0] + kick.state_doubles[1] * M), dtype=torch.float64, device=x.device)
+    check(getattr(lib, kick.forward)(ptr(x), ptr(q), ptr(w), *head, B, x.shape[0], q.shape[0], w.shape[0], *tail, N, M,
+                                     dtype_code(x.dtype), ptr(out), ptr(state), ptr(ws), ws_bytes, stream_ptr()), kick.forward)
+    return out, state
+
+
+def _kick_bwd_raw(kick: _Kick, x, q, w, head, state, d_out, B: int, N: int, M: int, need_c: bool, extra=()):
+    """The backward entry point: (dX (B, N, 7), dC (B, N) | None, the per-row cotangents (B,) float64); rows of broadcast inputs not
+    summed. `extra`: the kick's own gradient outputs (or None) behind the per-row cotangents."""
+    kw = {"dtype": x.dtype, "device": x.device}
+    dX = torch.empty((B, N, 7), **kw)
+    dC = torch.empty((B, N), **kw) if need_c else None
+    d_rows = [torch.empty((B,), dtype=torch.float64, device=x.device) for _ in range(kick.cotangents)]
+    lib = _lib.lib()
+    ws_bytes = getattr(lib, kick.workspace)(B, N, M)
+    ws = workspace(ws_bytes, x.device)
+    check(getattr(lib, kick.backward)(ptr(x), ptr(q), ptr(w), *head, B, x.shape[0], q.shape[0], w.shape[0], N, M, dtype_code(x.dtype),
+                                      ptr(state), ptr(d_out), ptr(dX), ptr(dC), *map(ptr, d_rows), *map(ptr, extra),
+                                      ptr(ws), ws_bytes, stream_ptr()), kick.backward)
+    return dX, dC, d_rows
+
+
+def _beam_grads(dX, dC, x, q, w, B: int, need):
+    """(dX, dq, dw) from the backward call's dX and dC (through c = |q| w), as `need`[0:3] asks, rows of broadcast inputs summed."""
+    dq = dw = None
+    if need[1]:
+        dq = dC * w * torch.sign(q)
+        if q.shape[0] == 1 and B > 1:
+            dq = dq.sum(dim=0, keepdim=True)
+    if need[2]:
+        dw = dC * q.abs()
+        if w.shape[0] == 1 and B > 1:
+            dw = dw.sum(dim=0, keepdim=True)
+    if need[0] and x.shape[0] == 1 and B > 1:
+        dX = dX.sum(dim=0, keepdim=True)
+    return (dX if need[0] else None), dq, dw
+
+
+def _gamma_beta(energy: torch.Tensor, mass_eV: float):
+    """(gamma, beta) of the reference energy in float64."""
+    gamma = energy.to(torch.float64) / mass_eV
+    beta = torch.where(gamma.abs() > 0, (1 - gamma.square().reciprocal()).clamp_min(0).sqrt(), torch.ones_like(gamma))
+    return gamma, beta
+
+
+def _p0c(energy: torch.Tensor, mass_eV: float) -> torch.Tensor:
+    """p0c = beta gamma m c^2 of the reference energy in float64, as `Beam.p0c`."""
+    gamma, beta = _gamma_beta(energy, mass_eV)
+    return beta * gamma * mass_eV
+
+
+# ---- the wake --------------------------------------------------------------------------------------------------------------------
+_WAKE = _kick("Wakefield", "wake", (8, 6), 1)      # CHX_WAKE_STATE_DOUBLES
+
+
+def _wake_head(scale, wl, wt, h):
+    """scale (B,), wl, wt (L,) or None, h (1,), all float64."""
+    return ptr(scale), ptr(wl), 0 if wl is None else wl.numel(), ptr(wt), 0 if wt is None else wt.numel(), ptr(h)
+
+
+class WakeKick(torch.autograd.Function):
+    """out (B, N, 7) = chx_wake_kick(x, q, w, scale, wl, wt); backward = chx_wake_kick_bwd: gradients of the particles, the charges
+    and survival probabilities (through c = |q| w), the per-row scale factor |Z| / p0c and both tables (summed over the rows). The
+    node grid (tau range) and the wake spacing h are constants."""
+
+    @staticmethod
+    def forward(ctx, x, q, w, scale, wl, wt, h, B, M):
+        out, state = _kick_raw(_WAKE, x, q, w, _wake_head(scale, wl, wt, h), (), B, x.shape[1], M)
+        ctx.save_for_backward(x, q, w, scale, wl, wt, h, state)
+        ctx.B, ctx.M = B, M
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        x, q, w, scale, wl, wt, h, state = ctx.saved_tensors
+        B, M, N = ctx.B, ctx.M, x.shape[1]
+        need = ctx.needs_input_grad
+        f64 = {"dtype": torch.float64, "device": x.device}
+        d_wl = torch.empty((wl.numel(),), **f64) if need[4] and wl is not None else None
+        d_wt = torch.empty((wt.numel(),), **f64) if need[5] and wt is not None else None
+        dX, dC, (d_scale,) = _kick_bwd_raw(_WAKE, x, q, w, _wake_head(scale, wl, wt, h), state, d_out.contiguous().to(x.dtype), B, N, M,
+                                           need[1] or need[2], (d_wl, d_wt))
+        return *_beam_grads(dX, dC, x, q, w, B, need), (d_scale if need[3] else None), d_wl, d_wt, None, None, None
+
+
+def wake_scale(energy: torch.Tensor, mass_eV: float, abs_charge_number: float, factor: torch.Tensor) -> torch.Tensor:
+    """factor |Z| / p0c in float64 (p0c as `Beam.p0c`), broadcast of the two shapes."""
+    return factor.to(torch.float64) * abs_charge_number / _p0c(energy, mass_eV)
+
+
+def wake_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Tensor, energy: torch.Tensor, mass_eV: float,
+              abs_charge_number: float, factor: torch.Tensor, longitudinal_wake, transverse_wake, wake_spacing: torch.Tensor,
+              num_bins: int) -> torch.Tensor:
+    """The wake kick of a beam of any batch shape (broadcast of the particles', charges', survival probabilities', energy's and
+    factor's batch shapes) -> particles (*batch, N, 7). `longitudinal_wake` / `transverse_wake`: 1-D tables (V/C, V/(C m)) or
+    None; `wake_spacing`: 0-d tensor h (metres between table entries). Differentiable with respect to the particles, charges,
+    survival probabilities, energy, factor and both tables."""
+    x, q, w, batch_shape, B = _beam_rows(_WAKE, particles, charges, survival, energy, factor,
+                                         others=(wake_spacing, longitudinal_wake, transverse_wake))
+    N = particles.shape[-2]
+    scale = wake_scale(energy, mass_eV, abs_charge_number, factor).expand(batch_shape).reshape(B).contiguous()
+    wl = None if longitudinal_wake is None else longitudinal_wake.to(torch.float64).contiguous()
+    wt = None if transverse_wake is None else transverse_wake.to(torch.float64).contiguous()
+    h = wake_spacing.detach().to(torch.float64).reshape(1)
+    grads = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, q, w, scale, wl, wt))
+    if grads:
+        out = WakeKick.apply(x, q, w, scale, wl, wt, h, B, num_bins)
+    else:
+        out, _ = _kick_raw(_WAKE, x, q, w, _wake_head(scale, wl, wt, h), (), B, N, num_bins)
+    return out.reshape(*batch_shape, N, 7)
+
+
+# ---- the kicks with per-row settings: CSR and LSC ------------------------------------------------------------------------------------
+def _safe_pow(v: torch.Tensor, p: float) -> torch.Tensor:
+    """v^p for v > 0, 0 at v = 0 with a zero gradient there (the kick is 0 at L = 0 or theta = 0), NaN for v < 0."""
+    pos = v > 0
+    r = torch.where(pos, v, torch.ones_like(v)).pow(p)
+    return torch.where(pos, r, torch.where(v == 0, torch.zeros_like(v), torch.full_like(v, float("nan"))))
+
+
+def csr_scale(energy: torch.Tensor, mass_eV: float, abs_charge_number: float, length: torch.Tensor,
+              angle: torch.Tensor) -> torch.Tensor:
+    """|Z| L^(1/3) |theta|^(2/3) / p0c in float64 (p0c as `Beam.p0c`), broadcast of the three shapes: the factor the kernels form on
+    the device, restated here for the chain rule of the backward pass."""
+    p0c = _p0c(energy, mass_eV)
+    return abs_charge_number * _safe_pow(length.to(torch.float64), 1 / 3) * _safe_pow(angle.to(torch.float64).abs(), 2 / 3) / p0c
+
+
+def lsc_scale_rho(energy: torch.Tensor, mass_eV: float, abs_charge_number: float, length: torch.Tensor, radius: torch.Tensor,
+                  h: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """(S, rho) = (|Z| 2 k_e L / (gamma^2 h^2 p0c), a / (gamma h)) in float64 (p0c as `Beam.p0c`), broadcast of the four shapes: the
+    factors the kernels form on the device, restated here for the chain rule of the backward pass. `h` is the node spacing of the
+    forward's state header, a constant; a row without a grid (h = 0) has S = 0 and a constant rho."""
+    gamma, beta = _gamma_beta(energy, mass_eV)
+    grid = h > 0
+    hs = torch.where(grid, h, torch.ones_like(h))
+    # p0c is formed here, behind gamma^2: autograd adds the energy's gradient contributions in the order the operations were
+    # recorded, and that sum is not associative
+    S = abs_charge_number * 2 * _K_E * length.to(torch.float64) / (gamma.square() * hs.square() * (beta * gamma * mass_eV))
+    rho = radius.to(torch.float64) / (gamma * hs)
+    return torch.where(grid, S, torch.zeros_like(S)), torch.where(grid, rho, torch.ones_like(rho))
+
+
+_CSR = _kick("CSRKick", "csr", (8, 1), 1,                                           # CHX_CSR_STATE_DOUBLES
+             lambda e, L, a, state, mass_eV, abs_z: (csr_scale(e, mass_eV, abs_z, L, a),))
+_LSC = _kick("LSCKick", "lsc", (8 + 2, 2), 2,                                       # CHX_LSC_STATE_DOUBLES
+             lambda e, L, a, state, mass_eV, abs_z: lsc_scale_rho(e, mass_eV, abs_z, L, a, state[:, 2]))
+
+
+def _settings_args(e, L, a, mass_eV: float, abs_z: float):
+    return (ptr(e), ptr(L), ptr(a), mass_eV, abs_z), (e.shape[0], L.shape[0], a.shape[0])
+
+
+class _SettingsKick(torch.autograd.Function):
+    """out (B, N, 7) = chx_{csr,lsc}_kick(x, q, w, energy e, length L, angle or radius a), the settings (1,) or (B,) in the beam
+    dtype; backward = the kick's _bwd call: gradients of the particles, the charges and survival probabilities (through c = |q| w),
+    and of e, L and a through the per-row cotangents of the kick's factors. The node grid (tau range) is a constant."""
+
+    @staticmethod
+    def forward(ctx, kick, x, q, w, e, L, a, mass_eV, abs_z, B, M):
+        out, state = _kick_raw(kick, x, q, w, *_settings_args(e, L, a, mass_eV, abs_z), B, x.shape[1], M)
+        ctx.save_for_backward(x, q, w, e, L, a, state)
+        ctx.kick, ctx.B, ctx.M, ctx.mass_eV, ctx.abs_z = kick, B, M, mass_eV, abs_z
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        x, q, w, e, L, a, state = ctx.saved_tensors
+        kick, B, M, N = ctx.kick, ctx.B, ctx.M, x.shape[1]
+        need = ctx.needs_input_grad[1:]
+        dX, dC, d_rows = _kick_bwd_raw(kick, x, q, w, (), state, d_out.contiguous().to(x.dtype), B, N, M, need[1] or need[2])
+        settings = [None, None, None]
+        wanted = [i for i in range(3) if need[3 + i]]
+        if wanted:
+            with torch.enable_grad():
+                leaves = [t.detach().requires_grad_(need[3 + i]) for i, t in enumerate((e, L, a))]
+                factors = kick.factors(*leaves, state, ctx.mass_eV, ctx.abs_z)
+                # a factor need not see every setting (the LSC's S does not see the radius, its rho does not see L): only what
+                # carries a graph goes into the chain rule
+                outs = [(o.expand(B), d) for o, d in zip(factors, d_rows) if o.requires_grad]
+                grads = torch.autograd.grad([o for o, _ in outs], [leaves[i] for i in wanted], [d for _, d in outs])
+            for i, g in zip(wanted, grads):
+                settings[i] = g.to(x.dtype)
+        return None, *_beam_grads(dX, dC, x, q, w, B, need), *settings, None, None, None, None
+
+
+def _settings_kick(kick: _Kick, particles, charges, survival, energy, mass_eV, abs_charge_number, length, third, num_bins):
+    x, q, w, batch_shape, B = _beam_rows(kick, particles, charges, survival, energy, length, third)
+    N = particles.shape[-2]
+    dt = particles.dtype
+    e, L, a = _rows(energy, batch_shape, B, dt), _rows(length, batch_shape, B, dt), _rows(third, batch_shape, B, dt)
+    grads = torch.is_grad_enabled() and any(t.requires_grad for t in (x, q, w, e, L, a))
+    if grads:
+        out = _SettingsKick.apply(kick, x, q, w, e, L, a, float(mass_eV), float(abs_charge_number), B, num_bins)
+    else:
+        out, _ = _kick_raw(kick, x, q, w, *_settings_args(e, L, a, float(mass_eV), float(abs_charge_number)), B, N, num_bins)
+    return out.reshape(*batch_shape, N, 7)
+
+
+def csr_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Tensor, energy: torch.Tensor, mass_eV: float,
+             abs_charge_number: float, length: torch.Tensor, angle: torch.Tensor, num_bins: int) -> torch.Tensor:
+    """The steady-state CSR kick of an arc of length `length` and bend angle `angle` on a beam of any batch shape (broadcast of the
+    particles', charges', survival probabilities', energy's, length's and angle's batch shapes) -> particles (*batch, N, 7).
+    Differentiable with respect to the particles, charges, survival probabilities, energy, length and angle."""
+    return _settings_kick(_CSR, particles, charges, survival, energy, mass_eV, abs_charge_number, length, angle, num_bins)
+
+
+def lsc_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Tensor, energy: torch.Tensor, mass_eV: float,
+             abs_charge_number: float, length: torch.Tensor, radius: torch.Tensor, num_bins: int) -> torch.Tensor:
+    """The longitudinal space-charge kick of a straight section of length `length` on a beam of disc radius `radius` and of any batch
+    shape (broadcast of the particles', charges', survival probabilities', energy's, length's and radius' batch shapes) ->
+    particles (*batch, N, 7). Differentiable with respect to the particles, charges, survival probabilities, energy, length and
+    radius."""
+    return _settings_kick(_LSC, particles, charges, survival, energy, mass_eV, abs_charge_number, length, radius, num_bins)

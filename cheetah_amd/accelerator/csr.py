@@ -19,35 +19,13 @@ graph, differentiable with respect to the particles, charges, survival probabili
 
 from __future__ import annotations
 
-import numbers
-
 import torch
 
 from .. import _ops
-from ..particles.particle_beam import ParticleBeam
-from ..sharding import _ACTIVE_GROUP as _SHARDING_STACK
-from .element import Element
+from ._binned_kick import BinnedKick, _as_tensor, check_effect_length, check_num_bins
 
 
-def _as_tensor(v, device, dtype):
-    if isinstance(v, torch.Tensor):
-        return v
-    return torch.as_tensor(v, device=device, dtype=dtype if dtype is not None else torch.get_default_dtype())
-
-
-def check_num_bins(num_bins, owner: str = "CSRKick") -> int:
-    if isinstance(num_bins, bool) or not isinstance(num_bins, numbers.Integral) or not 2 <= int(num_bins) <= _ops.CSR_MAX_BINS:
-        raise ValueError(f"{owner}: num_bins must be an integer in 2 ... {_ops.CSR_MAX_BINS}, got {num_bins!r}")
-    return int(num_bins)
-
-
-def check_num_kicks(num_kicks, owner: str) -> int:
-    if isinstance(num_kicks, bool) or not isinstance(num_kicks, numbers.Integral) or int(num_kicks) < 1:
-        raise ValueError(f"{owner}: num_kicks must be an integer >= 1, got {num_kicks!r}")
-    return int(num_kicks)
-
-
-class CSRKick(Element):
+class CSRKick(BinnedKick):
     """Steady-state CSR of an arc of a bend, as one zero-length energy kick.
 
     Limits of the model: steady state only (no entrance or exit transients, no CSR in the drifts behind a bend); 1-D (a line
@@ -61,13 +39,14 @@ class CSRKick(Element):
     :param num_bins: number of nodes M of the grid in tau, 2 <= M <= 4096.
     """
 
+    _follows = "the CSR kick"
+
     def __init__(self, effect_length, angle, num_bins: int = 200, name=None, sanitize_name=None, metadata=None, device=None,
                  dtype=None):
-        num_bins = check_num_bins(num_bins)
+        num_bins = check_num_bins(num_bins, "CSRKick")
         effect_length = _as_tensor(effect_length, device, dtype)
         angle = _as_tensor(angle, device, dtype)
-        if not bool(torch.isfinite(effect_length.detach()).all() & (effect_length.detach() >= 0).all()):
-            raise ValueError(f"CSRKick: effect_length must be finite and >= 0 (metres), got {effect_length!r}")
+        check_effect_length(effect_length, "CSRKick")
         if not bool(torch.isfinite(angle.detach()).all()):
             raise ValueError(f"CSRKick: angle must be finite (rad), got {angle!r}")
         fk = {"device": device if device is not None else effect_length.device,
@@ -77,27 +56,10 @@ class CSRKick(Element):
         self.register_buffer_or_parameter("effect_length", effect_length)
         self.register_buffer_or_parameter("angle", angle)
 
-    @property
-    def is_skippable(self) -> bool:
-        return False
-
-    def first_order_transfer_map(self, energy, species):
-        raise NotImplementedError("CSRKick has no linear transfer map")
-
-    def track(self, incoming: ParticleBeam) -> ParticleBeam:
-        if not isinstance(incoming, ParticleBeam):
-            raise TypeError("CSRKick tracking needs a ParticleBeam: the CSR kick follows the beam's current profile, which a "
-                            f"{type(incoming).__name__} does not carry")
-        if _SHARDING_STACK:
-            raise NotImplementedError("CSRKick tracking of a particle-sharded beam (inside sharding.particle_sharded) is not "
-                                      "implemented: the tau range and the deposited grid of all ranks are not merged yet; gather "
-                                      "the particles on one rank first")
-        species = incoming.species
-        out = _ops.csr_kick(incoming.particles, incoming.particle_charges, incoming.survival_probabilities, incoming.energy,
-                            species.mass_eV_float, abs(species.num_elementary_charges_float), self.effect_length, self.angle,
-                            self.num_bins)
-        return ParticleBeam(out, incoming.energy, particle_charges=incoming.particle_charges,
-                            survival_probabilities=incoming.survival_probabilities, s=incoming.s, species=species)
+    def _kick(self, incoming, species):
+        return _ops.csr_kick(incoming.particles, incoming.particle_charges, incoming.survival_probabilities, incoming.energy,
+                             species.mass_eV_float, abs(species.num_elementary_charges_float), self.effect_length, self.angle,
+                             self.num_bins)
 
     @property
     def defining_features(self) -> list[str]:

@@ -89,7 +89,8 @@ class Dipole(Element):
         spread along the arc. Only the first piece keeps the entrance face (dipole_e1, fringe_integral, the entrance fringe of
         `fringe_at`) and only the last keeps the exit face; k1, tilt, gap, gap_exit, fringe_type and tracking_method are kept.
         An RBend becomes Dipole pieces with its effective face angles. A bend of zero angle is returned unchanged, as [self]."""
-        from .csr import CSRKick, check_num_bins, check_num_kicks
+        from ._binned_kick import check_num_bins, check_num_kicks
+        from .csr import CSRKick
 
         n = check_num_kicks(num_kicks, "Dipole.split_for_csr")
         num_bins = check_num_bins(num_bins, "Dipole.split_for_csr")

@@ -30,10 +30,7 @@ import math
 import torch
 
 from .. import _ops
-from ..particles.particle_beam import ParticleBeam
-from ..sharding import _ACTIVE_GROUP as _SHARDING_STACK
-from .csr import _as_tensor, check_num_bins
-from .element import Element
+from ._binned_kick import BinnedKick, _as_tensor, check_effect_length, check_num_bins
 
 
 def check_radius_factor(radius_factor, owner: str = "LSCKick") -> float:
@@ -52,7 +49,7 @@ def check_beam_radius(beam_radius, owner: str = "LSCKick") -> None:
         raise ValueError(f"{owner}: beam_radius must be finite and > 0 (metres), got {beam_radius!r}")
 
 
-class LSCKick(Element):
+class LSCKick(BinnedKick):
     """Longitudinal space charge of a straight section, as one zero-length energy kick.
 
     Limits of the model: 1-D (the on-axis field of a transversely uniform disc for every particle: no transverse forces, no
@@ -72,14 +69,14 @@ class LSCKick(Element):
 
     #: LatticeJSON: read back as the Python number it was written as, not as a tensor of the file's dtype
     _plain_features = ("radius_factor",)
+    _follows = "the LSC kick"
 
     def __init__(self, effect_length, beam_radius=None, radius_factor: float = 1.7, num_bins: int = 200, name=None,
                  sanitize_name=None, metadata=None, device=None, dtype=None):
         num_bins = check_num_bins(num_bins, "LSCKick")
         radius_factor = check_radius_factor(radius_factor)
         effect_length = _as_tensor(effect_length, device, dtype)
-        if not bool(torch.isfinite(effect_length.detach()).all() & (effect_length.detach() >= 0).all()):
-            raise ValueError(f"LSCKick: effect_length must be finite and >= 0 (metres), got {effect_length!r}")
+        check_effect_length(effect_length, "LSCKick")
         if beam_radius is not None:
             beam_radius = _as_tensor(beam_radius, device, dtype)
             check_beam_radius(beam_radius)
@@ -91,31 +88,14 @@ class LSCKick(Element):
         self.register_buffer_or_parameter("effect_length", effect_length)
         self.register_buffer_or_parameter("beam_radius", beam_radius)
 
-    @property
-    def is_skippable(self) -> bool:
-        return False
-
-    def first_order_transfer_map(self, energy, species):
-        raise NotImplementedError("LSCKick has no linear transfer map")
-
-    def track(self, incoming: ParticleBeam) -> ParticleBeam:
-        if not isinstance(incoming, ParticleBeam):
-            raise TypeError("LSCKick tracking needs a ParticleBeam: the LSC kick follows the beam's current profile, which a "
-                            f"{type(incoming).__name__} does not carry")
-        if _SHARDING_STACK:
-            raise NotImplementedError("LSCKick tracking of a particle-sharded beam (inside sharding.particle_sharded) is not "
-                                      "implemented: the tau range and the deposited grid of all ranks are not merged yet; gather "
-                                      "the particles on one rank first")
-        species = incoming.species
+    def _kick(self, incoming, species):
         radius = self.beam_radius
         if radius is None:
             _ops.require_device(incoming.particles)
             radius = (self.radius_factor / 2) * (incoming.sigma_x + incoming.sigma_y)
-        out = _ops.lsc_kick(incoming.particles, incoming.particle_charges, incoming.survival_probabilities, incoming.energy,
-                            species.mass_eV_float, abs(species.num_elementary_charges_float), self.effect_length, radius,
-                            self.num_bins)
-        return ParticleBeam(out, incoming.energy, particle_charges=incoming.particle_charges,
-                            survival_probabilities=incoming.survival_probabilities, s=incoming.s, species=species)
+        return _ops.lsc_kick(incoming.particles, incoming.particle_charges, incoming.survival_probabilities, incoming.energy,
+                             species.mass_eV_float, abs(species.num_elementary_charges_float), self.effect_length, radius,
+                             self.num_bins)
 
     @property
     def defining_features(self) -> list[str]:

@@ -1867,7 +1867,7 @@ class Segment(Element):
     def with_csr_kicks(self, num_kicks: int, num_bins: int = 200, except_for=None) -> "Segment":
         """Every bending Dipole (and RBend) split by `Dipole.split_for_csr(num_kicks, num_bins)` into pieces with steady-state CSR
         kicks between them, nested Segments included; other elements, bends of zero angle and names in `except_for` unchanged."""
-        from .csr import check_num_bins, check_num_kicks
+        from ._binned_kick import check_num_bins, check_num_kicks
         from .dipole import Dipole
 
         check_num_kicks(num_kicks, "Segment.with_csr_kicks")
@@ -1891,7 +1891,8 @@ class Segment(Element):
         `split(resolution=max_step)` and every piece gets its kick. Names in `except_for` and the collective kicks already there
         (`LSCKick`, `CSRKick`, `Wakefield`, `SpaceChargeKick`) get none. A kick stands behind its element and sees the outgoing beam:
         the kick after a `Cavity` uses the energy the beam leaves the cavity with, not the mean energy inside it."""
-        from .csr import CSRKick, check_num_bins
+        from ._binned_kick import check_num_bins
+        from .csr import CSRKick
         from .lsc import LSCKick, check_beam_radius, check_radius_factor
         from .space_charge_kick import SpaceChargeKick
         from .wakefield import Wakefield

@@ -14,23 +14,13 @@ respect to the particles, charges, survival probabilities, the beam energy, `fac
 
 from __future__ import annotations
 
-import numbers
-
 import torch
 
 from .. import _ops
-from ..particles.particle_beam import ParticleBeam
-from ..sharding import _ACTIVE_GROUP as _SHARDING_STACK
-from .element import Element
+from ._binned_kick import BinnedKick, _as_tensor, check_num_bins
 
 
-def _as_tensor(v, device, dtype):
-    if v is None or isinstance(v, torch.Tensor):
-        return v
-    return torch.as_tensor(v, device=device, dtype=dtype if dtype is not None else torch.get_default_dtype())
-
-
-class Wakefield(Element):
+class Wakefield(BinnedKick):
     """Short-range wakefield of a structure as one zero-length kick.
 
     :param wake_spacing: scalar tensor h > 0 (m): entry n of a table is the wake at s = n h behind the source.
@@ -42,10 +32,11 @@ class Wakefield(Element):
     :param num_bins: number of nodes M of the grid in tau, 2 <= M <= 4096.
     """
 
+    _follows = "the wake"
+
     def __init__(self, wake_spacing, longitudinal_wake=None, transverse_wake=None, factor=None, num_bins: int = 200, name=None,
                  sanitize_name=None, metadata=None, device=None, dtype=None):
-        if isinstance(num_bins, bool) or not isinstance(num_bins, numbers.Integral) or not 2 <= int(num_bins) <= _ops.WAKE_MAX_BINS:
-            raise ValueError(f"Wakefield: num_bins must be an integer in 2 ... {_ops.WAKE_MAX_BINS}, got {num_bins!r}")
+        num_bins = check_num_bins(num_bins, "Wakefield")
         longitudinal_wake = _as_tensor(longitudinal_wake, device, dtype)
         transverse_wake = _as_tensor(transverse_wake, device, dtype)
         for label, table in (("longitudinal_wake", longitudinal_wake), ("transverse_wake", transverse_wake)):
@@ -62,35 +53,18 @@ class Wakefield(Element):
             raise ValueError(f"Wakefield: wake_spacing must be a positive scalar (metres), got {wake_spacing!r}")
         super().__init__(name=name, sanitize_name=sanitize_name, metadata=metadata, **fk)
         empty = lambda t: t if t is not None and t.numel() > 0 else torch.zeros(0, **fk)  # noqa: E731
-        self.num_bins = int(num_bins)
+        self.num_bins = num_bins
         self.register_buffer_or_parameter("wake_spacing", wake_spacing)
         self.register_buffer_or_parameter("longitudinal_wake", empty(longitudinal_wake))
         self.register_buffer_or_parameter("transverse_wake", empty(transverse_wake))
         self.register_buffer_or_parameter("factor", _as_tensor(factor, fk["device"], fk["dtype"]) if factor is not None
                                           else torch.ones((), **fk))
 
-    @property
-    def is_skippable(self) -> bool:
-        return False
-
-    def first_order_transfer_map(self, energy, species):
-        raise NotImplementedError("Wakefield has no linear transfer map")
-
-    def track(self, incoming: ParticleBeam) -> ParticleBeam:
-        if not isinstance(incoming, ParticleBeam):
-            raise TypeError("Wakefield tracking needs a ParticleBeam: the wake follows the beam's current profile, which a "
-                            f"{type(incoming).__name__} does not carry")
-        if _SHARDING_STACK:
-            raise NotImplementedError("Wakefield tracking of a particle-sharded beam (inside sharding.particle_sharded) is not "
-                                      "implemented: the tau range and the deposited grid of all ranks are not merged yet; gather "
-                                      "the particles on one rank first")
+    def _kick(self, incoming, species):
         wl, wt = self.longitudinal_wake, self.transverse_wake
-        species = incoming.species
-        out = _ops.wake_kick(incoming.particles, incoming.particle_charges, incoming.survival_probabilities, incoming.energy,
-                             species.mass_eV_float, abs(species.num_elementary_charges_float), self.factor,
-                             wl if wl.numel() > 0 else None, wt if wt.numel() > 0 else None, self.wake_spacing, self.num_bins)
-        return ParticleBeam(out, incoming.energy, particle_charges=incoming.particle_charges,
-                            survival_probabilities=incoming.survival_probabilities, s=incoming.s, species=species)
+        return _ops.wake_kick(incoming.particles, incoming.particle_charges, incoming.survival_probabilities, incoming.energy,
+                              species.mass_eV_float, abs(species.num_elementary_charges_float), self.factor,
+                              wl if wl.numel() > 0 else None, wt if wt.numel() > 0 else None, self.wake_spacing, self.num_bins)
 
     @property
     def defining_features(self) -> list[str]:

@@ -6,55 +6,31 @@
 //   F2. wake_deposit_kernel   (chx_grid1d_dev.h) the row header and the fixed-point node deposit D_k (one channel)
 //   F3. csr_toeplitz_kernel   one workgroup per (row, 64 nodes): b_j = a_(j-1) - a_j formed into LDS, the anti-causal sum
 //                             S_k = sum_j b_j D_(k+j) over the nodes behind, its four waves splitting the sources, merged in order
-//   F4. csr_kick_kernel       (chx_grid1d_dev.h) one thread per particle: gather of the node kicks times the row's scale (formed
+//   F4. node_kick_kernel      (chx_grid1d_dev.h) one thread per particle: gather of the node kicks times the row's scale (formed
 //                             by F3 from the energy, L and theta pointers), delta updated in fp64, rounded once
-// Backward (same pattern): B1 bounds of the gather's cotangents and the per-row partials of d(scale); B2 their fixed-point deposit;
-// B3 the causal correlation (adjoint of the anti-causal sum); B4 one pass over the particles (adjoint of the deposit and of the
-// node coordinate). The particle passes B1, B2, B4 are shared with chx_lsc.hip through chx_grid1d_dev.h.
-#include "chx_grid1d_dev.h"
+// Backward (same pattern): B1 node_bwd_range_kernel, bounds of the gather's cotangents and the per-row partials of d(scale); B2
+// node_bwd_deposit_kernel, their fixed-point deposit; B3 csr_bwd_toeplitz_kernel, the causal correlation (adjoint of the anti-causal
+// sum); B4 node_bwd_particles_kernel, one pass over the particles (adjoint of the deposit and of the node coordinate). Only F3 and
+// B3 are this file's: the particle passes, the argument check, the workspace and the launchers are chx_grid1d_dev.h and
+// chx_grid1d_host.h, shared with chx_wake.hip and chx_lsc.hip.
+#include "chx_grid1d_host.h"
 
 namespace {
 
-constexpr double kCoulomb = 8.9875517923e9;   // k_e = 1 / (4 pi eps0), V m / C
-
 __host__ __device__ inline int64_t csr_state_row(int M) { return CHX_CSR_STATE_DOUBLES(M); }
 
-struct CsrWs {
-    double* part;               // [B][G][kPart] forward partials
-    unsigned long long* grid;   // [B][M] fixed-point deposit
-    double* bpart;              // [B][G][kPart] backward partials
-    double* bhdr;               // [B][kHdr] backward header: valid, S of the cotangent deposit
-    unsigned long long* ggrid;  // [B][M] fixed-point cotangents of the node kicks
-    double* adj;                // [B][M] cotangents of the deposits
-    size_t bytes;
-};
+Grid1dWs csr_ws(void* base, int64_t B, int64_t N, int M) { return grid1d_ws(base, B, N, M, 1, 0); }
 
-CsrWs csr_ws(void* base, int64_t B, int64_t N, int M) {
-    CsrWs w;
-    char* p = (char*)base;
-    size_t o = 0;
-    auto take = [&](size_t nbytes) { char* r = p ? p + o : nullptr; o += al256(nbytes); return r; };
-    const int G = wake_groups(N);
-    w.part = (double*)take((size_t)(B * G * kPart) * 8);
-    w.grid = (unsigned long long*)take((size_t)(B * M) * 8);
-    w.bpart = (double*)take((size_t)(B * G * kPart) * 8);
-    w.bhdr = (double*)take((size_t)(B * kHdr) * 8);
-    w.ggrid = (unsigned long long*)take((size_t)(B * M) * 8);
-    w.adj = (double*)take((size_t)(B * M) * 8);
-    w.bytes = o;
-    return w;
-}
-
-// The row's scale |Z| L^(1/3) |theta|^(2/3) / p0c in fp64; p0c = beta gamma m c^2 as `Beam.p0c` (wake_scale in _ops_wake.py).
+// The row's scale |Z| L^(1/3) |theta|^(2/3) / p0c in fp64; p0c = beta gamma m c^2 as `Beam.p0c`.
 template <typename T>
 __device__ __forceinline__ double csr_scale(const T* energy, int64_t Be, const T* length, int64_t Bl, const T* angle, int64_t Ba,
                                             double mass, double absz, int64_t b) {
     const double e = (double)energy[Be == 1 ? 0 : b], L = (double)length[Bl == 1 ? 0 : b], th = (double)angle[Ba == 1 ? 0 : b];
-    const double gamma = e / mass;
-    const double beta = fabs(gamma) > 0.0 ? sqrt(fmax(1.0 - 1.0 / (gamma * gamma), 0.0)) : 1.0;
+    double gamma;
+    const double p0c = ref_p0c(e, mass, gamma);
     const double lf = L > 0.0 ? cbrt(L) : (L == 0.0 ? 0.0 : __longlong_as_double(0x7ff8000000000000LL));
     const double c = cbrt(fabs(th));
-    return absz * lf * (c * c) / (beta * gamma * mass);
+    return absz * lf * (c * c) / p0c;
 }
 
 // a_j = (j+1)^(2/3) - j^(2/3) without the cancellation.
@@ -118,32 +94,6 @@ __global__ __launch_bounds__(kWB) void csr_toeplitz_kernel(int M, const T* __res
     }
 }
 
-// ---- F4 ----------------------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(kWB) void csr_kick_kernel(const T* __restrict__ x, int64_t Bx, int64_t N, int M,
-                                                       const double* __restrict__ state, T* __restrict__ out) {
-    node_kick_particle(x, Bx, N, M, state, csr_state_row(M), out);
-}
-
-// ---- B1: bound of the gather's cotangents a = scale g_delta; partials of d(scale) = sum g_delta dE(u) -------------------------------
-template <typename T>
-__global__ __launch_bounds__(kWB) void csr_bwd_range_kernel(const T* __restrict__ x, int64_t Bx, int64_t N, int G, int M,
-                                                            const double* __restrict__ state, const T* __restrict__ gout,
-                                                            double* __restrict__ bpart, unsigned long long* __restrict__ ggrid) {
-    node_bwd_range(x, Bx, N, G, M, state, csr_state_row(M), gout, bpart, ggrid);
-}
-
-// ---- B2: fixed-point deposit of the gather's cotangents, as F2; workgroup 0 writes d(scale) and the backward header -----------------
-template <typename T>
-__global__ __launch_bounds__(kWB) void csr_bwd_deposit_kernel(const T* __restrict__ x, int64_t Bx, int64_t N, int G, int M,
-                                                              const double* __restrict__ state,
-                                                              const T* __restrict__ gout, const double* __restrict__ bpart,
-                                                              double* __restrict__ bhdr, double* __restrict__ d_scale,
-                                                              unsigned long long* __restrict__ ggrid) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long hist[];
-    node_bwd_deposit(x, Bx, N, G, M, state, csr_state_row(M), gout, bpart, bhdr, d_scale, ggrid, hist);
-}
-
 // ---- B3: adjoint of F3, GD_m = 3^(2/3) k_e h^(-4/3) sum_{k <= m} b_(m-k) GV_k ------------------------------------------------------
 // One workgroup per (row, 64 sources m0 ... m0 + 63); wave v takes the target tiles k0 = 64 (v + 4 i) <= m0 + 63. Lag m - k of
 // target k0 + j: bt index 128 + m - k0 - j in [2, M + 190].
@@ -180,106 +130,67 @@ __global__ __launch_bounds__(kWB) void csr_bwd_toeplitz_kernel(int M, const doub
     }
 }
 
-// ---- B4: one pass over the particles ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(kWB) void csr_bwd_particles_kernel(const T* __restrict__ x, const T* __restrict__ q,
-                                                                const T* __restrict__ w, int64_t Bx, int64_t Bq, int64_t Bw,
-                                                                int64_t N, int M, const double* __restrict__ state,
-                                                                const double* __restrict__ adj, const T* __restrict__ gout,
-                                                                T* __restrict__ dX, T* __restrict__ dC) {
-    node_bwd_particle(x, q, w, Bx, Bq, Bw, N, M, state, csr_state_row(M), adj, gout, dX, dC);
-}
-
-int check_csr(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M,
-              int dtype, const double* state) {
-    if (!x || !q || !w || !state || B < 1 || B > 65535 || N < 1 || N > 0x7fffffffLL || M < 2 || M > CHX_WAKE_MAX_BINS)
-        return CHX_ERR_INVALID_ARG;
-    if (!chx_bcast_ok(Bx, B) || !chx_bcast_ok(Bq, B) || !chx_bcast_ok(Bw, B)) return CHX_ERR_INVALID_ARG;
-    if (dtype != CHX_F32 && dtype != CHX_F64) return CHX_ERR_DTYPE;
-    if (!chx_aligned16(x)) return CHX_ERR_MISALIGNED;
-    return CHX_OK;
-}
-
 template <typename T>
 int csr_kick_t(const T* x, const T* q, const T* w, const T* energy, const T* length, const T* angle, double mass, double absz,
                int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Ba, int64_t N, int M, T* out,
-               double* state, const CsrWs& ws, hipStream_t s) {
-    const int G = wake_groups(N);
+               double* state, const Grid1dWs& ws, hipStream_t s) {
     if (!lds_ok(csr_toeplitz_kernel<T>, toeplitz_lds(M))) return CHX_ERR_LAUNCH;
-    hipLaunchKernelGGL(wake_range_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, G, M, 0,
-                       (int64_t)M, ws.part, ws.grid);
+    int st = launch_deposit(x, q, w, B, Bx, Bq, Bw, N, M, 0, 1, 1, csr_state_row(M), state, ws, s);
+    if (st != CHX_OK) return st;
+    hipLaunchKernelGGL(csr_toeplitz_kernel<T>, grid_nodes(M, B), dim3(kWB), toeplitz_lds(M), s, M, energy, Be, length, Bl, angle, Ba,
+                       mass, absz, ws.grid, state);
     CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(wake_deposit_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), (size_t)M * 8, s, x, q, w, Bx, Bq, Bw, N, G,
-                       M, 0, 1, csr_state_row(M), (int64_t)M, ws.part, state, ws.grid);
-    CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(csr_toeplitz_kernel<T>, dim3((unsigned)((M + kNodeBlock - 1) / kNodeBlock), (unsigned)B), dim3(kWB),
-                       toeplitz_lds(M), s, M, energy, Be, length, Bl, angle, Ba, mass, absz, ws.grid, state);
-    CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(csr_kick_kernel<T>, dim3((unsigned)((N + kWB - 1) / kWB), (unsigned)B), dim3(kWB), 0, s, x, Bx, N, M, state,
-                       out);
-    CHX_CHECK_LAUNCH();
-    return CHX_OK;
+    return launch_node_kick(x, B, Bx, N, M, csr_state_row(M), state, out, s);
 }
 
 template <typename T>
 int csr_kick_bwd_t(const T* x, const T* q, const T* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int M,
-                   const double* state, const T* gout, T* dX, T* dC, double* d_scale, const CsrWs& ws, hipStream_t s) {
-    const int G = wake_groups(N);
+                   const double* state, const T* gout, T* dX, T* dC, double* d_scale, const Grid1dWs& ws, hipStream_t s) {
     if (!lds_ok(csr_bwd_toeplitz_kernel, toeplitz_lds(M))) return CHX_ERR_LAUNCH;
-    hipLaunchKernelGGL(csr_bwd_range_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), 0, s, x, Bx, N, G, M, state, gout,
-                       ws.bpart, ws.ggrid);
+    int st = launch_node_bwd_deposit(x, B, Bx, N, M, csr_state_row(M), state, gout, d_scale, ws, s);
+    if (st != CHX_OK) return st;
+    hipLaunchKernelGGL(csr_bwd_toeplitz_kernel, grid_nodes(M, B), dim3(kWB), toeplitz_lds(M), s, M, state, ws.bhdr, ws.ggrid, ws.adj);
     CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(csr_bwd_deposit_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), (size_t)M * 8, s, x, Bx, N, G, M, state,
-                       gout, ws.bpart, ws.bhdr, d_scale, ws.ggrid);
-    CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(csr_bwd_toeplitz_kernel, dim3((unsigned)((M + kNodeBlock - 1) / kNodeBlock), (unsigned)B), dim3(kWB),
-                       toeplitz_lds(M), s, M, state, ws.bhdr, ws.ggrid, ws.adj);
-    CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(csr_bwd_particles_kernel<T>, dim3((unsigned)((N + kWB - 1) / kWB), (unsigned)B), dim3(kWB), 0, s, x, q, w, Bx,
-                       Bq, Bw, N, M, state, ws.adj, gout, dX, dC);
+    hipLaunchKernelGGL(node_bwd_particles_kernel<T>, grid_particles(N, B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, M, state,
+                       csr_state_row(M), ws.adj, gout, dX, dC);
     CHX_CHECK_LAUNCH();
     return CHX_OK;
 }
 
 }  // namespace
 
-extern "C" size_t chx_csr_workspace_bytes(int64_t B, int64_t N, int32_t M) {
-    if (B < 1 || N < 1 || M < 2 || M > CHX_WAKE_MAX_BINS) return 0;
-    return csr_ws(nullptr, B, N, M).bytes;
-}
+extern "C" size_t chx_csr_workspace_bytes(int64_t B, int64_t N, int32_t M) { return csr_ws(nullptr, B, N, M).bytes; }
 
 extern "C" int chx_csr_kick(const void* x, const void* q, const void* w, const void* energy, const void* length, const void* angle,
                             double mass_eV, double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl,
                             int64_t Ba, int64_t N, int32_t M, int dtype, void* out, double* state, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    const int st = check_csr(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
+    const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!energy || !length || !angle || !(mass_eV > 0.0) || !chx_bcast_ok(Be, B) || !chx_bcast_ok(Bl, B) || !chx_bcast_ok(Ba, B) ||
         !out)
         return CHX_ERR_INVALID_ARG;
     if (!chx_aligned16(out)) return CHX_ERR_MISALIGNED;
-    const CsrWs ws = csr_ws(workspace, B, N, M);
+    const Grid1dWs ws = csr_ws(workspace, B, N, M);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == CHX_F32)
-        return csr_kick_t<float>((const float*)x, (const float*)q, (const float*)w, (const float*)energy, (const float*)length,
-                                 (const float*)angle, mass_eV, abs_charge, B, Bx, Bq, Bw, Be, Bl, Ba, N, M, (float*)out, state, ws, s);
-    return csr_kick_t<double>((const double*)x, (const double*)q, (const double*)w, (const double*)energy, (const double*)length,
-                              (const double*)angle, mass_eV, abs_charge, B, Bx, Bq, Bw, Be, Bl, Ba, N, M, (double*)out, state, ws, s);
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return csr_kick_t<T>((const T*)x, (const T*)q, (const T*)w, (const T*)energy, (const T*)length, (const T*)angle, mass_eV,
+                             abs_charge, B, Bx, Bq, Bw, Be, Bl, Ba, N, M, (T*)out, state, ws, (hipStream_t)stream);
+    });
 }
 
 extern "C" int chx_csr_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
                                 int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
                                 void* workspace, size_t workspace_bytes, void* stream) {
-    const int st = check_csr(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
+    const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!d_out || !dX || !d_scale) return CHX_ERR_INVALID_ARG;
-    const CsrWs ws = csr_ws(workspace, B, N, M);
+    const Grid1dWs ws = csr_ws(workspace, B, N, M);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == CHX_F32)
-        return csr_kick_bwd_t<float>((const float*)x, (const float*)q, (const float*)w, B, Bx, Bq, Bw, N, M, state,
-                                     (const float*)d_out, (float*)dX, (float*)dC, d_scale, ws, s);
-    return csr_kick_bwd_t<double>((const double*)x, (const double*)q, (const double*)w, B, Bx, Bq, Bw, N, M, state,
-                                  (const double*)d_out, (double*)dX, (double*)dC, d_scale, ws, s);
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return csr_kick_bwd_t<T>((const T*)x, (const T*)q, (const T*)w, B, Bx, Bq, Bw, N, M, state, (const T*)d_out, (T*)dX, (T*)dC,
+                                 d_scale, ws, (hipStream_t)stream);
+    });
 }

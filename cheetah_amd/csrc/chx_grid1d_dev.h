@@ -1,6 +1,9 @@
 // chx_grid1d_dev.h — device code shared by the kicks that bin the beam's charge on M nodes in tau (chx_wake.hip,
-// chx_csr.hip, chx_lsc.hip): the node coordinate, 64-bit fixed-point deposits, fixed-order reductions, and the two particle passes that
-// find the row's tau range (F1) and deposit the line density (F2). Per batch row, every grid quantity in fp64.
+// chx_csr.hip, chx_lsc.hip): the node coordinate, 64-bit fixed-point deposits, fixed-order reductions, the two particle passes that
+// find the row's tau range (F1, wake_range_kernel) and deposit the line density (F2, wake_deposit_kernel), and the particle passes
+// of the single-channel kicks (CSR, LSC): the gather-kick F4 (node_kick_kernel) and the backward passes B1 (node_bwd_range_kernel),
+// B2 (node_bwd_deposit_kernel) and B4 (node_bwd_particles_kernel), which take the doubles per state row as an argument. Per batch
+// row, every grid quantity in fp64. The host side of the same layer (argument check, workspace, launchers) is chx_grid1d_host.h.
 #pragma once
 #include "chx_common.h"
 
@@ -13,6 +16,7 @@ constexpr int kMaxG = 1024;                   // workgroups per row of a particl
 constexpr int kPart = 8;                      // doubles per workgroup partial
 constexpr int kHdr = CHX_WAKE_STATE_HEADER;   // state row header: valid, tau_lo, D, S[3] (fixed-point scales), tau_hi, free slot
 constexpr int kNodeBlock = 64;                // nodes per workgroup of the convolution kernels (one per lane)
+constexpr double kCoulomb = 8.9875517923e9;   // k_e = 1 / (4 pi eps0), V m / C
 
 inline int wake_groups(int64_t N) {
     const int64_t g = (N + 2047) / 2048;
@@ -110,6 +114,13 @@ __device__ void wake_row_header(const double* __restrict__ part, int G, int M, d
         hdr[7] = 0.0;
     }
     __syncthreads();
+}
+
+// p0c = beta gamma m c^2 of a reference energy as `Beam.p0c` (energy and mass in eV), and gamma = energy / mass.
+__device__ __forceinline__ double ref_p0c(double energy, double mass, double& gamma) {
+    gamma = energy / mass;
+    const double beta = fabs(gamma) > 0.0 ? sqrt(fmax(1.0 - 1.0 / (gamma * gamma), 0.0)) : 1.0;
+    return beta * gamma * mass;
 }
 
 template <typename T> struct RowPtrs {
@@ -213,16 +224,16 @@ __global__ __launch_bounds__(kWB) void wake_deposit_kernel(const T* __restrict__
     }
 }
 
-// ---- the particle passes shared by the kicks whose state row is [header | M node kicks | ...] with the row's scale in the header's
-// last slot (chx_csr.hip, chx_lsc.hip): the gather-kick F4 and the backward passes B1, B2, B4; state_row doubles per row ----------
+// ---- the particle passes of the kicks whose state row is [header | M node kicks | ...] with the row's scale in the header's last
+// slot (chx_csr.hip, chx_lsc.hip): the gather-kick F4 and the backward passes B1, B2, B4; state_row doubles per row ---------------
 
 // The row kicks at all: surviving particles and a node spacing h > 0.
 __device__ __forceinline__ bool node_live(const double* st) { return st[0] != 0.0 && st[2] > 0.0; }
 
 // F4, one thread per particle: gather of the node kicks times the row's scale, delta updated in fp64, rounded once.
 template <typename T>
-__device__ __forceinline__ void node_kick_particle(const T* __restrict__ x, int64_t Bx, int64_t N, int M,
-                                                   const double* __restrict__ state, int64_t state_row, T* __restrict__ out) {
+__global__ __launch_bounds__(kWB) void node_kick_kernel(const T* __restrict__ x, int64_t Bx, int64_t N, int M,
+                                                        const double* __restrict__ state, int64_t state_row, T* __restrict__ out) {
     const int64_t b = blockIdx.y;
     const int64_t n = (int64_t)blockIdx.x * kWB + threadIdx.x;
     if (n >= N) return;
@@ -250,9 +261,10 @@ __device__ __forceinline__ void node_kick_particle(const T* __restrict__ x, int6
 
 // B1: bound of the gather's cotangents a = scale g_delta; partials of d(scale) = sum g_delta dE(u); zeroes the cotangents' grid.
 template <typename T>
-__device__ __forceinline__ void node_bwd_range(const T* __restrict__ x, int64_t Bx, int64_t N, int G, int M,
-                                               const double* __restrict__ state, int64_t state_row, const T* __restrict__ gout,
-                                               double* __restrict__ bpart, unsigned long long* __restrict__ ggrid) {
+__global__ __launch_bounds__(kWB) void node_bwd_range_kernel(const T* __restrict__ x, int64_t Bx, int64_t N, int G, int M,
+                                                             const double* __restrict__ state, int64_t state_row,
+                                                             const T* __restrict__ gout, double* __restrict__ bpart,
+                                                             unsigned long long* __restrict__ ggrid) {
     __shared__ double red[4 * 4];
     const int64_t b = blockIdx.y;
     const int g = blockIdx.x;
@@ -287,11 +299,12 @@ __device__ __forceinline__ void node_bwd_range(const T* __restrict__ x, int64_t 
 // B2: fixed-point deposit of the gather's cotangents, as F2 (hist: M integers of dynamic LDS); workgroup 0 writes d(scale) and
 // the backward header (valid, S of the cotangent deposit).
 template <typename T>
-__device__ __forceinline__ void node_bwd_deposit(const T* __restrict__ x, int64_t Bx, int64_t N, int G, int M,
-                                                 const double* __restrict__ state, int64_t state_row, const T* __restrict__ gout,
-                                                 const double* __restrict__ bpart, double* __restrict__ bhdr,
-                                                 double* __restrict__ d_scale, unsigned long long* __restrict__ ggrid,
-                                                 unsigned long long* hist) {
+__global__ __launch_bounds__(kWB) void node_bwd_deposit_kernel(const T* __restrict__ x, int64_t Bx, int64_t N, int G, int M,
+                                                               const double* __restrict__ state, int64_t state_row,
+                                                               const T* __restrict__ gout, const double* __restrict__ bpart,
+                                                               double* __restrict__ bhdr, double* __restrict__ d_scale,
+                                                               unsigned long long* __restrict__ ggrid) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long hist[];   // [M]
     __shared__ double red[4 * 4];
     __shared__ double S;
     const int64_t b = blockIdx.y;
@@ -338,7 +351,8 @@ __device__ __forceinline__ void node_bwd_deposit(const T* __restrict__ x, int64_
     }
 }
 
-// B4, one thread per particle: adjoint of the deposit (adj[B][M]: cotangents of the deposits) and of the node coordinate.
+// B4, one thread per particle: adjoint of the deposit (adj[B][M]: cotangents of the deposits) and of the node coordinate. A device
+// function under node_bwd_particles_kernel, so that a kick with more to do in this pass wraps it in a kernel of its own.
 template <typename T>
 __device__ __forceinline__ void node_bwd_particle(const T* __restrict__ x, const T* __restrict__ q, const T* __restrict__ w,
                                                   int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int M,
@@ -379,17 +393,19 @@ __device__ __forceinline__ void node_bwd_particle(const T* __restrict__ x, const
     if (dC) dC[b * N + n] = (T)dc;
 }
 
+template <typename T>
+__global__ __launch_bounds__(kWB) void node_bwd_particles_kernel(const T* __restrict__ x, const T* __restrict__ q,
+                                                                 const T* __restrict__ w, int64_t Bx, int64_t Bq, int64_t Bw,
+                                                                 int64_t N, int M, const double* __restrict__ state,
+                                                                 int64_t state_row, const double* __restrict__ adj,
+                                                                 const T* __restrict__ gout, T* __restrict__ dX, T* __restrict__ dC) {
+    node_bwd_particle(x, q, w, Bx, Bq, Bw, N, M, state, state_row, adj, gout, dX, dC);
+}
+
 // Lane l's double, broadcast to the whole wave (the Toeplitz sums over the nodes: one source tile of 64 nodes per load).
 __device__ __forceinline__ double readlane_d(double v, int l) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), l), hi = __builtin_amdgcn_readlane(__double2hiint(v), l);
     return __hiloint2double(hi, lo);
-}
-
-// Dynamic LDS above 64 KiB (M > ~2700 nodes) must be requested per kernel (gfx950: 160 KiB per workgroup).
-template <typename K>
-bool lds_ok(K kern, size_t bytes) {
-    return bytes <= 64 * 1024 ||
-           hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
 }
 
 }  // namespace

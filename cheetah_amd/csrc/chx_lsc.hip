@@ -8,15 +8,17 @@
 //   F3. lsc_toeplitz_kernel   one workgroup per (row, 64 nodes): P and c^_j for the lags 0 ... M - 1 formed into LDS, the two-sided sum
 //                             V_k = sum_j c^_j D_(k+j) over the source tiles on both sides of the block with the lag's sign, its four
 //                             waves splitting the tiles, merged in order; workgroup 0 stores the row's scale S and rho
-//   F4. lsc_kick_kernel       (chx_grid1d_dev.h) one thread per particle: gather of the node sums times S, delta rounded once
-// Backward (the CSR kick's pattern): B1 bounds of the gather's cotangents and the per-row partials of d(S); B2 their fixed-point
-// deposit; B3 the adjoint correlation (two-sided, the opposite sign) with c^ for the deposits' cotangents and with d c^ / d rho
-// against the forward's deposits for d(rho); B4 one pass over the particles.
-#include "chx_grid1d_dev.h"
+//   F4. node_kick_kernel      (chx_grid1d_dev.h) one thread per particle: gather of the node sums times S, delta rounded once
+// Backward (the CSR kick's pattern): B1 node_bwd_range_kernel, bounds of the gather's cotangents and the per-row partials of d(S);
+// B2 node_bwd_deposit_kernel, their fixed-point deposit; B3 lsc_bwd_toeplitz_kernel, the adjoint correlation (two-sided, the
+// opposite sign) with c^ for the deposits' cotangents and with d c^ / d rho against the forward's deposits for d(rho); B4
+// lsc_bwd_particles_kernel, one pass over the particles (node_bwd_particle of chx_grid1d_dev.h) that also sums d(rho). Only F3, B3
+// and that sum are this file's: the particle passes, the argument check, the workspace and the launchers are chx_grid1d_dev.h and
+// chx_grid1d_host.h, shared with chx_wake.hip and chx_csr.hip.
+#include "chx_grid1d_host.h"
 
 namespace {
 
-constexpr double kCoulomb = 8.9875517923e9;   // k_e = 1 / (4 pi eps0), V m / C
 constexpr int kMaxBlocks = CHX_WAKE_MAX_BINS / kNodeBlock;
 
 __host__ __device__ inline int64_t lsc_state_row(int M) { return CHX_LSC_STATE_DOUBLES(M); }
@@ -24,33 +26,8 @@ __host__ __device__ inline int64_t lsc_state_row(int M) { return CHX_LSC_STATE_D
 __host__ __device__ inline int lsc_rho_slot(int M) { return kHdr + M; }
 __host__ __device__ inline int lsc_dep_slot(int M) { return kHdr + M + 2; }
 
-struct LscWs {
-    double* part;               // [B][G][kPart] forward partials
-    unsigned long long* grid;   // [B][M] fixed-point deposit
-    double* bpart;              // [B][G][kPart] backward partials
-    double* bhdr;               // [B][kHdr] backward header: valid, S of the cotangent deposit
-    unsigned long long* ggrid;  // [B][M] fixed-point cotangents of the node sums
-    double* adj;                // [B][M] cotangents of the deposits
-    double* rpart;              // [B][kMaxBlocks] partials of d(rho), one per workgroup of B3
-    size_t bytes;
-};
-
-LscWs lsc_ws(void* base, int64_t B, int64_t N, int M) {
-    LscWs w;
-    char* p = (char*)base;
-    size_t o = 0;
-    auto take = [&](size_t nbytes) { char* r = p ? p + o : nullptr; o += al256(nbytes); return r; };
-    const int G = wake_groups(N);
-    w.part = (double*)take((size_t)(B * G * kPart) * 8);
-    w.grid = (unsigned long long*)take((size_t)(B * M) * 8);
-    w.bpart = (double*)take((size_t)(B * G * kPart) * 8);
-    w.bhdr = (double*)take((size_t)(B * kHdr) * 8);
-    w.ggrid = (unsigned long long*)take((size_t)(B * M) * 8);
-    w.adj = (double*)take((size_t)(B * M) * 8);
-    w.rpart = (double*)take((size_t)(B * kMaxBlocks) * 8);
-    w.bytes = o;
-    return w;
-}
+// The workspace's own block: rpart[B][kMaxBlocks], the partials of d(rho), one per workgroup of B3.
+Grid1dWs lsc_ws(void* base, int64_t B, int64_t N, int M) { return grid1d_ws(base, B, N, M, 1, (size_t)(B * kMaxBlocks) * 8); }
 
 // The row's scale S = |Z| 2 k_e L / (gamma^2 h^2 p0c) and rho = a / (gamma h) in fp64; p0c = beta gamma m c^2 as `Beam.p0c`. A radius
 // that is not > 0 or not finite gives NaN for both (a line charge has no finite on-axis field).
@@ -58,10 +35,10 @@ template <typename T>
 __device__ __forceinline__ void lsc_scales(const T* energy, int64_t Be, const T* length, int64_t Bl, const T* radius, int64_t Ba,
                                            double mass, double absz, double h, int64_t b, double& S, double& rho) {
     const double e = (double)energy[Be == 1 ? 0 : b], L = (double)length[Bl == 1 ? 0 : b], a = (double)radius[Ba == 1 ? 0 : b];
-    const double gamma = e / mass;
-    const double beta = fabs(gamma) > 0.0 ? sqrt(fmax(1.0 - 1.0 / (gamma * gamma), 0.0)) : 1.0;
+    double gamma;
+    const double p0c = ref_p0c(e, mass, gamma);
     if (a > 0.0 && isfinite(a)) {
-        S = absz * 2.0 * kCoulomb * L / (gamma * gamma * h * h * (beta * gamma * mass));
+        S = absz * 2.0 * kCoulomb * L / (gamma * gamma * h * h * p0c);
         rho = a / (gamma * h);
     } else {
         S = rho = __longlong_as_double(0x7ff8000000000000LL);
@@ -154,31 +131,6 @@ __global__ __launch_bounds__(kWB) void lsc_toeplitz_kernel(int M, const T* __res
     }
 }
 
-// ---- F4 ----------------------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(kWB) void lsc_kick_kernel(const T* __restrict__ x, int64_t Bx, int64_t N, int M,
-                                                       const double* __restrict__ state, T* __restrict__ out) {
-    node_kick_particle(x, Bx, N, M, state, lsc_state_row(M), out);
-}
-
-// ---- B1, B2 ------------------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(kWB) void lsc_bwd_range_kernel(const T* __restrict__ x, int64_t Bx, int64_t N, int G, int M,
-                                                            const double* __restrict__ state, const T* __restrict__ gout,
-                                                            double* __restrict__ bpart, unsigned long long* __restrict__ ggrid) {
-    node_bwd_range(x, Bx, N, G, M, state, lsc_state_row(M), gout, bpart, ggrid);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kWB) void lsc_bwd_deposit_kernel(const T* __restrict__ x, int64_t Bx, int64_t N, int G, int M,
-                                                              const double* __restrict__ state,
-                                                              const T* __restrict__ gout, const double* __restrict__ bpart,
-                                                              double* __restrict__ bhdr, double* __restrict__ d_scale,
-                                                              unsigned long long* __restrict__ ggrid) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long hist[];
-    node_bwd_deposit(x, Bx, N, G, M, state, lsc_state_row(M), gout, bpart, bhdr, d_scale, ggrid, hist);
-}
-
 // ---- B3: adjoint of F3, GD_m = sum_k sgn(m - k) c^_|m-k| GV_k, and the workgroup's partial of d(rho) = sum_m D_m sum_k sgn(m - k)
 // (d c^ / d rho)_|m-k| GV_k. One workgroup per (row, 64 sources m0 ... m0 + 63); wave v takes the target tiles k0 = 64 (v + 4 i) < M.
 __global__ __launch_bounds__(kWB) void lsc_bwd_toeplitz_kernel(int M, const double* __restrict__ state, const double* __restrict__ bhdr,
@@ -265,97 +217,69 @@ __global__ __launch_bounds__(kWB) void lsc_bwd_particles_kernel(const T* __restr
     node_bwd_particle(x, q, w, Bx, Bq, Bw, N, M, state, lsc_state_row(M), adj, gout, dX, dC);
 }
 
-int check_lsc(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M,
-              int dtype, const double* state) {
-    if (!x || !q || !w || !state || B < 1 || B > 65535 || N < 1 || N > 0x7fffffffLL || M < 2 || M > CHX_WAKE_MAX_BINS)
-        return CHX_ERR_INVALID_ARG;
-    if (!chx_bcast_ok(Bx, B) || !chx_bcast_ok(Bq, B) || !chx_bcast_ok(Bw, B)) return CHX_ERR_INVALID_ARG;
-    if (dtype != CHX_F32 && dtype != CHX_F64) return CHX_ERR_DTYPE;
-    if (!chx_aligned16(x)) return CHX_ERR_MISALIGNED;
-    return CHX_OK;
-}
-
 template <typename T>
 int lsc_kick_t(const T* x, const T* q, const T* w, const T* energy, const T* length, const T* radius, double mass, double absz,
                int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Ba, int64_t N, int M, T* out,
-               double* state, const LscWs& ws, hipStream_t s) {
-    const int G = wake_groups(N);
+               double* state, const Grid1dWs& ws, hipStream_t s) {
     if (!lds_ok(lsc_toeplitz_kernel<T>, lsc_lds(M, 1))) return CHX_ERR_LAUNCH;
-    hipLaunchKernelGGL(wake_range_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, G, M, 0,
-                       (int64_t)M, ws.part, ws.grid);
+    int st = launch_deposit(x, q, w, B, Bx, Bq, Bw, N, M, 0, 1, 1, lsc_state_row(M), state, ws, s);
+    if (st != CHX_OK) return st;
+    hipLaunchKernelGGL(lsc_toeplitz_kernel<T>, grid_nodes(M, B), dim3(kWB), lsc_lds(M, 1), s, M, energy, Be, length, Bl, radius, Ba,
+                       mass, absz, ws.grid, state);
     CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(wake_deposit_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), (size_t)M * 8, s, x, q, w, Bx, Bq, Bw, N, G,
-                       M, 0, 1, lsc_state_row(M), (int64_t)M, ws.part, state, ws.grid);
-    CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(lsc_toeplitz_kernel<T>, dim3((unsigned)((M + kNodeBlock - 1) / kNodeBlock), (unsigned)B), dim3(kWB),
-                       lsc_lds(M, 1), s, M, energy, Be, length, Bl, radius, Ba, mass, absz, ws.grid, state);
-    CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(lsc_kick_kernel<T>, dim3((unsigned)((N + kWB - 1) / kWB), (unsigned)B), dim3(kWB), 0, s, x, Bx, N, M, state,
-                       out);
-    CHX_CHECK_LAUNCH();
-    return CHX_OK;
+    return launch_node_kick(x, B, Bx, N, M, lsc_state_row(M), state, out, s);
 }
 
 template <typename T>
 int lsc_kick_bwd_t(const T* x, const T* q, const T* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int M,
-                   const double* state, const T* gout, T* dX, T* dC, double* d_scale, double* d_rho, const LscWs& ws,
+                   const double* state, const T* gout, T* dX, T* dC, double* d_scale, double* d_rho, const Grid1dWs& ws,
                    hipStream_t s) {
-    const int G = wake_groups(N);
     if (!lds_ok(lsc_bwd_toeplitz_kernel, lsc_lds(M, 2))) return CHX_ERR_LAUNCH;
-    hipLaunchKernelGGL(lsc_bwd_range_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), 0, s, x, Bx, N, G, M, state, gout,
-                       ws.bpart, ws.ggrid);
+    int st = launch_node_bwd_deposit(x, B, Bx, N, M, lsc_state_row(M), state, gout, d_scale, ws, s);
+    if (st != CHX_OK) return st;
+    hipLaunchKernelGGL(lsc_bwd_toeplitz_kernel, grid_nodes(M, B), dim3(kWB), lsc_lds(M, 2), s, M, state, ws.bhdr, ws.ggrid, ws.adj,
+                       ws.extra);
     CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(lsc_bwd_deposit_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), (size_t)M * 8, s, x, Bx, N, G, M, state,
-                       gout, ws.bpart, ws.bhdr, d_scale, ws.ggrid);
-    CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(lsc_bwd_toeplitz_kernel, dim3((unsigned)((M + kNodeBlock - 1) / kNodeBlock), (unsigned)B), dim3(kWB),
-                       lsc_lds(M, 2), s, M, state, ws.bhdr, ws.ggrid, ws.adj, ws.rpart);
-    CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(lsc_bwd_particles_kernel<T>, dim3((unsigned)((N + kWB - 1) / kWB), (unsigned)B), dim3(kWB), 0, s, x, q, w, Bx,
-                       Bq, Bw, N, M, state, ws.adj, ws.rpart, gout, dX, dC, d_rho);
+    hipLaunchKernelGGL(lsc_bwd_particles_kernel<T>, grid_particles(N, B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, M, state, ws.adj,
+                       ws.extra, gout, dX, dC, d_rho);
     CHX_CHECK_LAUNCH();
     return CHX_OK;
 }
 
 }  // namespace
 
-extern "C" size_t chx_lsc_workspace_bytes(int64_t B, int64_t N, int32_t M) {
-    if (B < 1 || N < 1 || M < 2 || M > CHX_WAKE_MAX_BINS) return 0;
-    return lsc_ws(nullptr, B, N, M).bytes;
-}
+extern "C" size_t chx_lsc_workspace_bytes(int64_t B, int64_t N, int32_t M) { return lsc_ws(nullptr, B, N, M).bytes; }
 
 extern "C" int chx_lsc_kick(const void* x, const void* q, const void* w, const void* energy, const void* length, const void* radius,
                             double mass_eV, double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl,
                             int64_t Ba, int64_t N, int32_t M, int dtype, void* out, double* state, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    const int st = check_lsc(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
+    const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!energy || !length || !radius || !(mass_eV > 0.0) || !chx_bcast_ok(Be, B) || !chx_bcast_ok(Bl, B) || !chx_bcast_ok(Ba, B) ||
         !out)
         return CHX_ERR_INVALID_ARG;
     if (!chx_aligned16(out)) return CHX_ERR_MISALIGNED;
-    const LscWs ws = lsc_ws(workspace, B, N, M);
+    const Grid1dWs ws = lsc_ws(workspace, B, N, M);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == CHX_F32)
-        return lsc_kick_t<float>((const float*)x, (const float*)q, (const float*)w, (const float*)energy, (const float*)length,
-                                 (const float*)radius, mass_eV, abs_charge, B, Bx, Bq, Bw, Be, Bl, Ba, N, M, (float*)out, state, ws, s);
-    return lsc_kick_t<double>((const double*)x, (const double*)q, (const double*)w, (const double*)energy, (const double*)length,
-                              (const double*)radius, mass_eV, abs_charge, B, Bx, Bq, Bw, Be, Bl, Ba, N, M, (double*)out, state, ws, s);
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return lsc_kick_t<T>((const T*)x, (const T*)q, (const T*)w, (const T*)energy, (const T*)length, (const T*)radius, mass_eV,
+                             abs_charge, B, Bx, Bq, Bw, Be, Bl, Ba, N, M, (T*)out, state, ws, (hipStream_t)stream);
+    });
 }
 
 extern "C" int chx_lsc_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
                                 int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
                                 double* d_rho, void* workspace, size_t workspace_bytes, void* stream) {
-    const int st = check_lsc(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
+    const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!d_out || !dX || !d_scale || !d_rho) return CHX_ERR_INVALID_ARG;
-    const LscWs ws = lsc_ws(workspace, B, N, M);
+    const Grid1dWs ws = lsc_ws(workspace, B, N, M);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == CHX_F32)
-        return lsc_kick_bwd_t<float>((const float*)x, (const float*)q, (const float*)w, B, Bx, Bq, Bw, N, M, state,
-                                     (const float*)d_out, (float*)dX, (float*)dC, d_scale, d_rho, ws, s);
-    return lsc_kick_bwd_t<double>((const double*)x, (const double*)q, (const double*)w, B, Bx, Bq, Bw, N, M, state,
-                                  (const double*)d_out, (double*)dX, (double*)dC, d_scale, d_rho, ws, s);
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return lsc_kick_bwd_t<T>((const T*)x, (const T*)q, (const T*)w, B, Bx, Bq, Bw, N, M, state, (const T*)d_out, (T*)dX, (T*)dC,
+                                 d_scale, d_rho, ws, (hipStream_t)stream);
+    });
 }

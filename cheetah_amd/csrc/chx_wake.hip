@@ -12,40 +12,18 @@
 // Backward (same pattern): B1 bounds of the cotangents and the per-row partials of d(scale); B2 deposit of the gather's
 // cotangents; B3 the anti-causal correlation (adjoint of the convolution) and B4 the correlation for the sampled wakes' gradient;
 // B5 one pass over the particles (adjoint of the deposit and of the node coordinate); B6 the tables' gradient (adjoint of the
-// sampling), one thread per table entry. F1 and F2 live in chx_grid1d_dev.h, shared with the CSR kick (chx_csr.hip).
-#include "chx_grid1d_dev.h"
+// sampling), one thread per table entry. F1 and F2 live in chx_grid1d_dev.h; the argument check, the workspace, the dtype dispatch
+// and the launcher of F1 and F2 in chx_grid1d_host.h, all shared with the CSR and LSC kicks (chx_csr.hip, chx_lsc.hip). The
+// three-channel passes F4, B1, B2 and B5 are this file's own.
+#include "chx_grid1d_host.h"
 
 namespace {
 
 __host__ __device__ inline int64_t state_row(int M) { return CHX_WAKE_STATE_DOUBLES(M); }
 
-struct WakeWs {
-    double* part;               // [B][G][kPart] forward partials
-    unsigned long long* grid;   // [B][3][M] fixed-point deposit (Q, X, Y)
-    double* bpart;              // [B][G][kPart] backward partials
-    double* bhdr;               // [B][kHdr] backward header: valid, S[3] of the cotangent deposit
-    unsigned long long* ggrid;  // [B][3][M] fixed-point cotangents of the node kicks (GV, GUx, GUy)
-    double* adj;                // [B][3][M] cotangents of the deposits (GQ, GX, GY)
-    double* dsamp;              // [B][2][M] cotangents of the sampled wakes (longitudinal, transverse)
-    size_t bytes;
-};
-
-WakeWs wake_ws(void* base, int64_t B, int64_t N, int M) {
-    WakeWs w;
-    char* p = (char*)base;
-    size_t o = 0;
-    auto take = [&](size_t nbytes) { char* r = p ? p + o : nullptr; o += al256(nbytes); return r; };
-    const int G = wake_groups(N);
-    w.part = (double*)take((size_t)(B * G * kPart) * 8);
-    w.grid = (unsigned long long*)take((size_t)(B * 3 * M) * 8);
-    w.bpart = (double*)take((size_t)(B * G * kPart) * 8);
-    w.bhdr = (double*)take((size_t)(B * kHdr) * 8);
-    w.ggrid = (unsigned long long*)take((size_t)(B * 3 * M) * 8);
-    w.adj = (double*)take((size_t)(B * 3 * M) * 8);
-    w.dsamp = (double*)take((size_t)(B * 2 * M) * 8);
-    w.bytes = o;
-    return w;
-}
+// Three deposit channels (Q, X, Y); the workspace's own block: dsamp[B][2][M], the cotangents of the sampled wakes (longitudinal,
+// transverse).
+Grid1dWs wake_ws(void* base, int64_t B, int64_t N, int M) { return grid1d_ws(base, B, N, M, 3, (size_t)(B * 2 * M) * 8); }
 
 // Position of node n in the table: p = n D / h; false beyond the last entry (the wake is 0 there), else entry j and fraction t
 // of the linear interpolation (1 - t) T[j] + t T[j + 1] (a table of one entry: j = 0, t = 0).
@@ -483,18 +461,13 @@ __global__ __launch_bounds__(kWB) void wake_bwd_tables_kernel(int64_t B, int M, 
     dT[j] = s;
 }
 
+// The table conditions of the wake on top of check_grid1d.
 int check_wake(const void* x, const void* q, const void* w, const double* scale, const double* wl, int64_t Ll, const double* wt,
                int64_t Lt, const double* h, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M, int dtype,
                const double* state) {
-    if (!x || !q || !w || !scale || !h || !state || B < 1 || B > 65535 || N < 1 || N > 0x7fffffffLL || M < 2 ||
-        M > CHX_WAKE_MAX_BINS || Ll < 0 || Lt < 0 || (Ll == 0 && Lt == 0) || (Ll > 0 && !wl) || (Lt > 0 && !wt))
-        return CHX_ERR_INVALID_ARG;
-    if (!chx_bcast_ok(Bx, B) || !chx_bcast_ok(Bq, B) || !chx_bcast_ok(Bw, B)) return CHX_ERR_INVALID_ARG;
-    if (dtype != CHX_F32 && dtype != CHX_F64) return CHX_ERR_DTYPE;
-    if (!chx_aligned16(x)) return CHX_ERR_MISALIGNED;
-    return CHX_OK;
+    if (!scale || !h || Ll < 0 || Lt < 0 || (Ll == 0 && Lt == 0) || (Ll > 0 && !wl) || (Lt > 0 && !wt)) return CHX_ERR_INVALID_ARG;
+    return check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
 }
-
 
 inline size_t conv_lds(int M) { return ((size_t)2 * (64 + M) + 4 * 3 * 64) * sizeof(double); }
 inline size_t samples_lds(int M) { return ((size_t)3 * (M + 128) + 4 * 2 * 64) * sizeof(double); }
@@ -502,17 +475,12 @@ inline size_t samples_lds(int M) { return ((size_t)3 * (M + 128) + 4 * 2 * 64) *
 template <typename T>
 int wake_kick_t(const T* x, const T* q, const T* w, const double* scale, const double* wl, int64_t Ll, const double* wt, int64_t Lt,
                 const double* h, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int M, T* out, double* state,
-                const WakeWs& ws, hipStream_t s) {
-    const int G = wake_groups(N);
+                const Grid1dWs& ws, hipStream_t s) {
     const int has_l = Ll > 0, has_t = Lt > 0;
     const int ch0 = has_l ? 0 : 1, nch = has_t ? 3 - ch0 : 1;
-    if (!lds_ok(wake_deposit_kernel<T>, (size_t)nch * M * 8) || !lds_ok(wake_conv_kernel, conv_lds(M))) return CHX_ERR_LAUNCH;
-    hipLaunchKernelGGL(wake_range_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, G, M, has_t,
-                       3 * (int64_t)M, ws.part, ws.grid);
-    CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(wake_deposit_kernel<T>, dim3((unsigned)G, (unsigned)B), dim3(kWB), (size_t)nch * M * 8, s, x, q, w, Bx, Bq, Bw,
-                       N, G, M, ch0, nch, state_row(M), 3 * (int64_t)M, ws.part, state, ws.grid);
-    CHX_CHECK_LAUNCH();
+    if (!lds_ok(wake_conv_kernel, conv_lds(M))) return CHX_ERR_LAUNCH;
+    int st = launch_deposit(x, q, w, B, Bx, Bq, Bw, N, M, ch0, nch, 3, state_row(M), state, ws, s);
+    if (st != CHX_OK) return st;
     hipLaunchKernelGGL(wake_conv_kernel, dim3((unsigned)((M + kNodeBlock - 1) / kNodeBlock), (unsigned)B), dim3(kWB), conv_lds(M), s,
                        wl, Ll, wt, Lt, h, M, ws.grid, state);
     CHX_CHECK_LAUNCH();
@@ -525,7 +493,7 @@ int wake_kick_t(const T* x, const T* q, const T* w, const double* scale, const d
 template <typename T>
 int wake_kick_bwd_t(const T* x, const T* q, const T* w, const double* scale, const double* wl, int64_t Ll, const double* wt,
                     int64_t Lt, const double* h, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int M, const double* state,
-                    const T* gout, T* dX, T* dC, double* d_scale, double* d_wl, double* d_wt, const WakeWs& ws, hipStream_t s) {
+                    const T* gout, T* dX, T* dC, double* d_scale, double* d_wl, double* d_wt, const Grid1dWs& ws, hipStream_t s) {
     const int G = wake_groups(N);
     const int has_l = Ll > 0, has_t = Lt > 0;
     const int ch0 = has_l ? 0 : 1, nch = has_t ? 3 - ch0 : 1;
@@ -544,16 +512,16 @@ int wake_kick_bwd_t(const T* x, const T* q, const T* w, const double* scale, con
     CHX_CHECK_LAUNCH();
     if (d_wl || d_wt) {
         hipLaunchKernelGGL(wake_bwd_table_samples_kernel, dim3(nb, (unsigned)B), dim3(kWB), samples_lds(M), s, has_l, has_t, M, state,
-                           ws.bhdr, ws.ggrid, ws.dsamp);
+                           ws.bhdr, ws.ggrid, ws.extra);
         CHX_CHECK_LAUNCH();
         if (d_wl && has_l) {
             hipLaunchKernelGGL(wake_bwd_tables_kernel, dim3((unsigned)((Ll + kWB - 1) / kWB)), dim3(kWB), 0, s, B, M, Ll, 0, h, state,
-                               ws.dsamp, d_wl);
+                               ws.extra, d_wl);
             CHX_CHECK_LAUNCH();
         }
         if (d_wt && has_t) {
             hipLaunchKernelGGL(wake_bwd_tables_kernel, dim3((unsigned)((Lt + kWB - 1) / kWB)), dim3(kWB), 0, s, B, M, Lt, 1, h, state,
-                               ws.dsamp, d_wt);
+                               ws.extra, d_wt);
             CHX_CHECK_LAUNCH();
         }
     }
@@ -565,10 +533,7 @@ int wake_kick_bwd_t(const T* x, const T* q, const T* w, const double* scale, con
 
 }  // namespace
 
-extern "C" size_t chx_wake_workspace_bytes(int64_t B, int64_t N, int32_t M) {
-    if (B < 1 || N < 1 || M < 2 || M > CHX_WAKE_MAX_BINS) return 0;
-    return wake_ws(nullptr, B, N, M).bytes;
-}
+extern "C" size_t chx_wake_workspace_bytes(int64_t B, int64_t N, int32_t M) { return wake_ws(nullptr, B, N, M).bytes; }
 
 extern "C" int chx_wake_kick(const void* x, const void* q, const void* w, const double* scale, const double* wl, int64_t Ll,
                              const double* wt, int64_t Lt, const double* h, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
@@ -577,14 +542,13 @@ extern "C" int chx_wake_kick(const void* x, const void* q, const void* w, const 
     if (st != CHX_OK) return st;
     if (!out) return CHX_ERR_INVALID_ARG;
     if (!chx_aligned16(out)) return CHX_ERR_MISALIGNED;
-    const WakeWs ws = wake_ws(workspace, B, N, M);
+    const Grid1dWs ws = wake_ws(workspace, B, N, M);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == CHX_F32)
-        return wake_kick_t<float>((const float*)x, (const float*)q, (const float*)w, scale, wl, Ll, wt, Lt, h, B, Bx, Bq, Bw, N, M,
-                                  (float*)out, state, ws, s);
-    return wake_kick_t<double>((const double*)x, (const double*)q, (const double*)w, scale, wl, Ll, wt, Lt, h, B, Bx, Bq, Bw, N, M,
-                               (double*)out, state, ws, s);
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return wake_kick_t<T>((const T*)x, (const T*)q, (const T*)w, scale, wl, Ll, wt, Lt, h, B, Bx, Bq, Bw, N, M, (T*)out, state, ws,
+                              (hipStream_t)stream);
+    });
 }
 
 extern "C" int chx_wake_kick_bwd(const void* x, const void* q, const void* w, const double* scale, const double* wl, int64_t Ll,
@@ -594,12 +558,11 @@ extern "C" int chx_wake_kick_bwd(const void* x, const void* q, const void* w, co
     const int st = check_wake(x, q, w, scale, wl, Ll, wt, Lt, h, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!d_out || !dX || !d_scale) return CHX_ERR_INVALID_ARG;
-    const WakeWs ws = wake_ws(workspace, B, N, M);
+    const Grid1dWs ws = wake_ws(workspace, B, N, M);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    if (dtype == CHX_F32)
-        return wake_kick_bwd_t<float>((const float*)x, (const float*)q, (const float*)w, scale, wl, Ll, wt, Lt, h, B, Bx, Bq, Bw, N, M,
-                                      state, (const float*)d_out, (float*)dX, (float*)dC, d_scale, d_wl, d_wt, ws, s);
-    return wake_kick_bwd_t<double>((const double*)x, (const double*)q, (const double*)w, scale, wl, Ll, wt, Lt, h, B, Bx, Bq, Bw, N,
-                                   M, state, (const double*)d_out, (double*)dX, (double*)dC, d_scale, d_wl, d_wt, ws, s);
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return wake_kick_bwd_t<T>((const T*)x, (const T*)q, (const T*)w, scale, wl, Ll, wt, Lt, h, B, Bx, Bq, Bw, N, M, state,
+                                  (const T*)d_out, (T*)dX, (T*)dC, d_scale, d_wl, d_wt, ws, (hipStream_t)stream);
+    });
 }
