@@ -25,6 +25,7 @@ from .accelerator import (  # noqa: F401
     Screen,
     Segment,
     Sextupole,
+    TransientCSRKick,
     TransverseDeflectingCavity,
     Solenoid,
     SpaceChargeKick,

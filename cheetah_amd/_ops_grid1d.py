@@ -1,9 +1,11 @@
 """The kicks of `cheetah_amd._ops` that bin the surviving particles' charge on M nodes in tau and kick every particle with what a sum
 over the nodes gives at its node coordinate: the short-range wake (Wakefield: causal convolution with the sampled wake, kicks to
-delta, px, py), the steady-state CSR (CSRKick: the anti-causal Toeplitz sum with the exactly integrated (z - z')^(-1/3) kernel) and
-the longitudinal space charge (LSCKick: the two-sided Toeplitz sum with the on-axis field of a charged disc). Each is one
+delta, px, py), the steady-state CSR (CSRKick: the anti-causal Toeplitz sum with the exactly integrated (z - z')^(-1/3) kernel), its
+entrance transient (TransientCSRKick: the same sum with the table of the slippage length reached inside the bend) and the
+longitudinal space charge (LSCKick: the two-sided Toeplitz sum with the on-axis field of a charged disc). Each is one
 `chx_*_kick` call (four launches, deterministic, no host synchronisation) and an autograd node whose backward is `chx_*_kick_bwd`.
-The CSR and LSC kicks form their per-row factors on the device from the energy, length and angle / radius; they share one node.
+The CSR and LSC kicks form their per-row factors on the device from the energy and their further settings (length, angle, radius,
+distance); they share one node.
 
 Part of `_ops` (which re-exports every name here). Imported at the END of `_ops`, whose helpers it uses."""
 from __future__ import annotations
@@ -16,8 +18,8 @@ import torch
 from . import _lib
 from ._ops import MAX_GRID_ROWS, aligned, bshapes, check, dtype_code, flat_bcast, numel, ptr, require_device, stream_ptr, workspace
 
-__all__ = ["WAKE_MAX_BINS", "CSR_MAX_BINS", "LSC_MAX_BINS", "WakeKick", "wake_kick", "wake_scale", "csr_kick", "csr_scale", "lsc_kick",
-           "lsc_scale_rho"]
+__all__ = ["WAKE_MAX_BINS", "CSR_MAX_BINS", "LSC_MAX_BINS", "WakeKick", "wake_kick", "wake_scale", "csr_kick", "csr_scale", "csr_transient_kick",
+           "csr_transient_x", "lsc_kick", "lsc_scale_rho"]
 
 #: CHX_WAKE_MAX_BINS of include/chx.h: the deposit's per-workgroup LDS histograms hold up to 3 channels of M 64-bit nodes; one grid
 #: and one deposit for the three kicks
@@ -34,7 +36,7 @@ class _Kick(NamedTuple):
     backward: str
     state_doubles: tuple        # (s0, s1): s0 + s1 M doubles per batch row of the state the forward pass leaves for the backward pass
     cotangents: int             # per-row float64 cotangents the backward call returns (d_scale[, d_rho])
-    factors: Callable | None    # (e, L, a, state, mass_eV, abs_z) -> the per-row factors, for the chain rule of the settings
+    factors: Callable | None    # (state, mass_eV, abs_z, *settings) -> the per-row factors, for the chain rule of the settings
 
 
 def _kick(owner: str, tag: str, state_doubles, cotangents: int, factors=None) -> _Kick:
@@ -218,59 +220,77 @@ def lsc_scale_rho(energy: torch.Tensor, mass_eV: float, abs_charge_number: float
     return torch.where(grid, S, torch.zeros_like(S)), torch.where(grid, rho, torch.ones_like(rho))
 
 
+def csr_transient_x(length: torch.Tensor, angle: torch.Tensor, distance: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
+    """x = z_L / h = d^3 theta^2 / (24 L^2 h) in float64, broadcast of the four shapes: the slippage length an arc length d into the
+    bend in node spacings, which the kernels form on the device, restated here for the chain rule of the backward pass. `h` is the
+    node spacing of the forward's state header, a constant. Where L, theta or d is 0 or the row has no grid (h = 0) there is no
+    kick: x = 0 with zero gradients."""
+    L, th, d = (t.to(torch.float64) for t in (length, angle, distance))
+    kicks = (L != 0) & (th != 0) & (d != 0) & (h > 0)
+    one = torch.ones((), dtype=torch.float64, device=h.device)
+    Ls, ds, hs = torch.where(kicks, L, one), torch.where(kicks, d, one), torch.where(kicks, h, one)
+    x = ds.pow(3) * th.square() / (24 * Ls.square() * hs)
+    x = torch.where((Ls > 0) & (ds > 0), x, torch.full_like(x, float("nan")))
+    return torch.where(kicks, x, torch.zeros_like(x))
+
+
 _CSR = _kick("CSRKick", "csr", (8, 1), 1,                                           # CHX_CSR_STATE_DOUBLES
-             lambda e, L, a, state, mass_eV, abs_z: (csr_scale(e, mass_eV, abs_z, L, a),))
+             lambda state, mass_eV, abs_z, e, L, a: (csr_scale(e, mass_eV, abs_z, L, a),))
+_CSR_TRANSIENT = _kick("TransientCSRKick", "csr_transient", (8 + 2, 2), 2,          # CHX_CSR_TRANSIENT_STATE_DOUBLES
+                       lambda state, mass_eV, abs_z, e, L, a, d: (csr_scale(e, mass_eV, abs_z, L, a),
+                                                                  csr_transient_x(L, a, d, state[:, 2])))
 _LSC = _kick("LSCKick", "lsc", (8 + 2, 2), 2,                                       # CHX_LSC_STATE_DOUBLES
-             lambda e, L, a, state, mass_eV, abs_z: lsc_scale_rho(e, mass_eV, abs_z, L, a, state[:, 2]))
+             lambda state, mass_eV, abs_z, e, L, a: lsc_scale_rho(e, mass_eV, abs_z, L, a, state[:, 2]))
 
 
-def _settings_args(e, L, a, mass_eV: float, abs_z: float):
-    return (ptr(e), ptr(L), ptr(a), mass_eV, abs_z), (e.shape[0], L.shape[0], a.shape[0])
+def _settings_args(settings, mass_eV: float, abs_z: float):
+    return (*map(ptr, settings), mass_eV, abs_z), tuple(t.shape[0] for t in settings)
 
 
 class _SettingsKick(torch.autograd.Function):
-    """out (B, N, 7) = chx_{csr,lsc}_kick(x, q, w, energy e, length L, angle or radius a), the settings (1,) or (B,) in the beam
-    dtype; backward = the kick's _bwd call: gradients of the particles, the charges and survival probabilities (through c = |q| w),
-    and of e, L and a through the per-row cotangents of the kick's factors. The node grid (tau range) is a constant."""
+    """out (B, N, 7) = chx_{csr,csr_transient,lsc}_kick(x, q, w, *settings): the energy e, the length L and the kick's further
+    settings (angle, radius, distance), each (1,) or (B,) in the beam dtype; backward = the kick's _bwd call: gradients of the
+    particles, the charges and survival probabilities (through c = |q| w), and of the settings through the per-row cotangents of the
+    kick's factors. The node grid (tau range) is a constant."""
 
     @staticmethod
-    def forward(ctx, kick, x, q, w, e, L, a, mass_eV, abs_z, B, M):
-        out, state = _kick_raw(kick, x, q, w, *_settings_args(e, L, a, mass_eV, abs_z), B, x.shape[1], M)
-        ctx.save_for_backward(x, q, w, e, L, a, state)
+    def forward(ctx, kick, mass_eV, abs_z, B, M, x, q, w, *settings):
+        out, state = _kick_raw(kick, x, q, w, *_settings_args(settings, mass_eV, abs_z), B, x.shape[1], M)
+        ctx.save_for_backward(x, q, w, state, *settings)
         ctx.kick, ctx.B, ctx.M, ctx.mass_eV, ctx.abs_z = kick, B, M, mass_eV, abs_z
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        x, q, w, e, L, a, state = ctx.saved_tensors
+        x, q, w, state, *given = ctx.saved_tensors
         kick, B, M, N = ctx.kick, ctx.B, ctx.M, x.shape[1]
-        need = ctx.needs_input_grad[1:]
+        need = ctx.needs_input_grad[5:]
         dX, dC, d_rows = _kick_bwd_raw(kick, x, q, w, (), state, d_out.contiguous().to(x.dtype), B, N, M, need[1] or need[2])
-        settings = [None, None, None]
-        wanted = [i for i in range(3) if need[3 + i]]
+        settings = [None] * len(given)
+        wanted = [i for i in range(len(given)) if need[3 + i]]
         if wanted:
             with torch.enable_grad():
-                leaves = [t.detach().requires_grad_(need[3 + i]) for i, t in enumerate((e, L, a))]
-                factors = kick.factors(*leaves, state, ctx.mass_eV, ctx.abs_z)
+                leaves = [t.detach().requires_grad_(need[3 + i]) for i, t in enumerate(given)]
+                factors = kick.factors(state, ctx.mass_eV, ctx.abs_z, *leaves)
                 # a factor need not see every setting (the LSC's S does not see the radius, its rho does not see L): only what
                 # carries a graph goes into the chain rule
                 outs = [(o.expand(B), d) for o, d in zip(factors, d_rows) if o.requires_grad]
                 grads = torch.autograd.grad([o for o, _ in outs], [leaves[i] for i in wanted], [d for _, d in outs])
             for i, g in zip(wanted, grads):
                 settings[i] = g.to(x.dtype)
-        return None, *_beam_grads(dX, dC, x, q, w, B, need), *settings, None, None, None, None
+        return None, None, None, None, None, *_beam_grads(dX, dC, x, q, w, B, need), *settings
 
 
-def _settings_kick(kick: _Kick, particles, charges, survival, energy, mass_eV, abs_charge_number, length, third, num_bins):
-    x, q, w, batch_shape, B = _beam_rows(kick, particles, charges, survival, energy, length, third)
+def _settings_kick(kick: _Kick, particles, charges, survival, mass_eV, abs_charge_number, settings, num_bins):
+    """`settings`: the energy, the length and the kick's further settings, in the order of the C entry point."""
+    x, q, w, batch_shape, B = _beam_rows(kick, particles, charges, survival, *settings)
     N = particles.shape[-2]
-    dt = particles.dtype
-    e, L, a = _rows(energy, batch_shape, B, dt), _rows(length, batch_shape, B, dt), _rows(third, batch_shape, B, dt)
-    grads = torch.is_grad_enabled() and any(t.requires_grad for t in (x, q, w, e, L, a))
+    rows = tuple(_rows(t, batch_shape, B, particles.dtype) for t in settings)
+    grads = torch.is_grad_enabled() and any(t.requires_grad for t in (x, q, w, *rows))
     if grads:
-        out = _SettingsKick.apply(kick, x, q, w, e, L, a, float(mass_eV), float(abs_charge_number), B, num_bins)
+        out = _SettingsKick.apply(kick, float(mass_eV), float(abs_charge_number), B, num_bins, x, q, w, *rows)
     else:
-        out, _ = _kick_raw(kick, x, q, w, *_settings_args(e, L, a, float(mass_eV), float(abs_charge_number)), B, N, num_bins)
+        out, _ = _kick_raw(kick, x, q, w, *_settings_args(rows, float(mass_eV), float(abs_charge_number)), B, N, num_bins)
     return out.reshape(*batch_shape, N, 7)
 
 
@@ -279,7 +299,19 @@ def csr_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Ten
     """The steady-state CSR kick of an arc of length `length` and bend angle `angle` on a beam of any batch shape (broadcast of the
     particles', charges', survival probabilities', energy's, length's and angle's batch shapes) -> particles (*batch, N, 7).
     Differentiable with respect to the particles, charges, survival probabilities, energy, length and angle."""
-    return _settings_kick(_CSR, particles, charges, survival, energy, mass_eV, abs_charge_number, length, angle, num_bins)
+    return _settings_kick(_CSR, particles, charges, survival, mass_eV, abs_charge_number, (energy, length, angle), num_bins)
+
+
+def csr_transient_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Tensor, energy: torch.Tensor, mass_eV: float,
+                       abs_charge_number: float, length: torch.Tensor, angle: torch.Tensor, distance: torch.Tensor,
+                       num_bins: int) -> torch.Tensor:
+    """The CSR kick of an arc of length `length` and bend angle `angle` at the arc length `distance` behind the entrance face of a bend
+    that follows a long straight (the entrance transient; the steady state for a large distance), on a beam of any batch shape
+    (broadcast of the particles', charges', survival probabilities', energy's, length's, angle's and distance's batch shapes) ->
+    particles (*batch, N, 7). Differentiable with respect to the particles, charges, survival probabilities, energy, length, angle
+    and distance."""
+    return _settings_kick(_CSR_TRANSIENT, particles, charges, survival, mass_eV, abs_charge_number,
+                          (energy, length, angle, distance), num_bins)
 
 
 def lsc_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Tensor, energy: torch.Tensor, mass_eV: float,
@@ -288,4 +320,4 @@ def lsc_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Ten
     shape (broadcast of the particles', charges', survival probabilities', energy's, length's and radius' batch shapes) ->
     particles (*batch, N, 7). Differentiable with respect to the particles, charges, survival probabilities, energy, length and
     radius."""
-    return _settings_kick(_LSC, particles, charges, survival, energy, mass_eV, abs_charge_number, length, radius, num_bins)
+    return _settings_kick(_LSC, particles, charges, survival, mass_eV, abs_charge_number, (energy, length, radius), num_bins)

@@ -1,5 +1,6 @@
-"""CSRKick: the steady-state coherent synchrotron radiation (CSR) of a bending magnet's arc, applied as one instantaneous energy kick
-that follows the bunch's current profile. Put kicks into a lattice with `Dipole.split_for_csr` or `Segment.with_csr_kicks`.
+"""CSRKick and TransientCSRKick: the coherent synchrotron radiation (CSR) of a bending magnet's arc, in the steady state and with
+the entrance transient, applied as one instantaneous energy kick that follows the bunch's current profile. Put kicks into a
+lattice with `Dipole.split_for_csr` or `Segment.with_csr_kicks`.
 
 The kick is one `chx_csr_kick` call (`_ops.csr_kick`): per batch row, the surviving particles (survival probability > 0, finite
 tau) are deposited on `num_bins` nodes spanning their tau range, exactly as `Wakefield` deposits them. The line density is taken
@@ -15,7 +16,23 @@ are the particles behind it, and the head gains energy. Per node, with h the nod
 
 with b_0 = -1, b_j = a_(j-1) - a_j, a_j = (j+1)^(2/3) - j^(2/3). Deterministic, no host synchronisation, capturable in a device
 graph, differentiable with respect to the particles, charges, survival probabilities, the beam energy, `effect_length` and
-`angle` (the node grid is a constant)."""
+`angle` (the node grid is a constant).
+
+TransientCSRKick is the same call with the kernel of a bunch that has travelled the arc length d into a bend of radius R behind a
+long straight (Saldin, Schneidmiller, Yurkov, section 3). With the slippage length z_L = d^3 / (24 R^2),
+
+    dE/ds(tau) = (2 Z e / (4 pi eps0 3^(1/3) R^(2/3))) { int_0^{z_L} u^(-1/3) lambda'(tau + u) du
+                                                       - z_L^(-1/3) [lambda(tau + z_L) - lambda(tau + 4 z_L)] }
+
+which is 0 for z_L -> 0 and the steady state for z_L -> inf. On the nodes, with x = z_L / h (`chx_csr_transient_kick`),
+
+    dE_k = |Z| 3^(2/3) k_e L^(1/3) |theta|^(2/3) h^(-4/3) S_k(x)
+    S_k(x) = sum_j a~_j(x) (D_(k+j+1) - D_(k+j)) - (2/3) x^(-1/3) [D~(k + x) - D~(k + 4x)]
+    a~_j(x) = min(j+1, x)^(2/3) - min(j, x)^(2/3)
+
+where D~(y) interpolates the deposits linearly at the real index y and is 0 beyond the last node. For x >= M the sum is CSRKick's
+term for term, and so is the result, bit for bit. Differentiable with respect to `entrance_distance` as well; S is continuous in x
+and its derivative jumps where 4x crosses a node."""
 
 from __future__ import annotations
 
@@ -28,11 +45,11 @@ from ._binned_kick import BinnedKick, _as_tensor, check_effect_length, check_num
 class CSRKick(BinnedKick):
     """Steady-state CSR of an arc of a bend, as one zero-length energy kick.
 
-    Limits of the model: steady state only (no entrance or exit transients, no CSR in the drifts behind a bend); 1-D (a line
-    charge: no transverse forces, no dependence on the transverse size); the arc is taken as long as the formation length
-    (24 sigma_z R^2)^(1/3) or longer, and a shorter arc is overestimated. The deposit is not filtered: at a fixed number of
-    particles N the noise grows with `num_bins` (for a Gaussian bunch of N = 10^6 the pointwise rms error of the kick is about 4 %
-    at M = 200 and 13 % at M = 1000), so choose M for the bunch's structure, not more.
+    Limits of the model: steady state only (no exit transient, no CSR in the drifts behind a bend; `TransientCSRKick` has the
+    entrance transient); 1-D (a line charge: no transverse forces, no dependence on the transverse size); the arc is taken as long
+    as the formation length (24 sigma_z R^2)^(1/3) or longer, and a shorter arc is overestimated. The deposit is not filtered:
+    at a fixed number of particles N the noise grows with `num_bins` (for a Gaussian bunch of N = 10^6 the pointwise rms error of
+    the kick is about 4 % at M = 200 and 13 % at M = 1000), so choose M for the bunch's structure, not more.
 
     :param effect_length: arc length L >= 0 (m) the kick stands for; may carry a batch shape that broadcasts with the beam's.
     :param angle: bend angle theta (rad) of that arc, L / R; may carry a batch shape. The kick scales as L^(1/3) |theta|^(2/3).
@@ -64,3 +81,49 @@ class CSRKick(BinnedKick):
     @property
     def defining_features(self) -> list[str]:
         return super().defining_features + ["effect_length", "angle", "num_bins"]
+
+
+class TransientCSRKick(BinnedKick):
+    """CSR of an arc of a bend at a given arc length behind the bend's entrance face, as one zero-length energy kick: the entrance
+    transient, in which the wake builds up over the formation length, and the steady state behind it.
+
+    Limits of the model: ultra-relativistic; 1-D (a line charge: no transverse forces, no dependence on the transverse size); a
+    long straight in front of the bend (no radiation of an earlier bend catches up with the bunch); no CSR in the drift behind the
+    bend (exit transient). The deposit is not filtered, as in `CSRKick`: choose `num_bins` for the bunch's structure, not more.
+
+    :param effect_length: arc length L >= 0 (m) the kick stands for; may carry a batch shape that broadcasts with the beam's.
+    :param angle: bend angle theta (rad) of that arc; may carry a batch shape. The bend's radius is R = L / |theta|.
+    :param entrance_distance: arc length d >= 0 (m) from the bend's entrance face to the point where the wake is evaluated; may
+        carry a batch shape. At d = 0 there is no kick; for d^3 / (24 R^2) beyond the bunch's length the kick is `CSRKick`'s.
+    :param num_bins: number of nodes M of the grid in tau, 2 <= M <= 4096.
+    """
+
+    _follows = "the CSR kick"
+
+    def __init__(self, effect_length, angle, entrance_distance, num_bins: int = 200, name=None, sanitize_name=None, metadata=None,
+                 device=None, dtype=None):
+        num_bins = check_num_bins(num_bins, "TransientCSRKick")
+        effect_length = _as_tensor(effect_length, device, dtype)
+        angle = _as_tensor(angle, device, dtype)
+        entrance_distance = _as_tensor(entrance_distance, device, dtype)
+        check_effect_length(effect_length, "TransientCSRKick")
+        if not bool(torch.isfinite(angle.detach()).all()):
+            raise ValueError(f"TransientCSRKick: angle must be finite (rad), got {angle!r}")
+        if not bool(torch.isfinite(entrance_distance.detach()).all() & (entrance_distance.detach() >= 0).all()):
+            raise ValueError(f"TransientCSRKick: entrance_distance must be finite and >= 0 (metres), got {entrance_distance!r}")
+        fk = {"device": device if device is not None else effect_length.device,
+              "dtype": dtype if dtype is not None else effect_length.dtype}
+        super().__init__(name=name, sanitize_name=sanitize_name, metadata=metadata, **fk)
+        self.num_bins = num_bins
+        self.register_buffer_or_parameter("effect_length", effect_length)
+        self.register_buffer_or_parameter("angle", angle)
+        self.register_buffer_or_parameter("entrance_distance", entrance_distance)
+
+    def _kick(self, incoming, species):
+        return _ops.csr_transient_kick(incoming.particles, incoming.particle_charges, incoming.survival_probabilities,
+                                       incoming.energy, species.mass_eV_float, abs(species.num_elementary_charges_float),
+                                       self.effect_length, self.angle, self.entrance_distance, self.num_bins)
+
+    @property
+    def defining_features(self) -> list[str]:
+        return super().defining_features + ["effect_length", "angle", "entrance_distance", "num_bins"]

@@ -84,13 +84,15 @@ class Dipole(Element):
     def is_active(self) -> bool:
         return bool((self.angle != 0).any().item())
 
-    def split_for_csr(self, num_kicks: int, num_bins: int = 200) -> list[Element]:
+    def split_for_csr(self, num_kicks: int, num_bins: int = 200, transient: bool = False) -> list[Element]:
         """The bend as `num_kicks` x [Dipole of L / n and theta / n, CSRKick(L / n, theta / n, num_bins)]: steady-state CSR kicks
-        spread along the arc. Only the first piece keeps the entrance face (dipole_e1, fringe_integral, the entrance fringe of
-        `fringe_at`) and only the last keeps the exit face; k1, tilt, gap, gap_exit, fringe_type and tracking_method are kept.
-        An RBend becomes Dipole pieces with its effective face angles. A bend of zero angle is returned unchanged, as [self]."""
+        spread along the arc. With `transient`, piece i gets `TransientCSRKick(L / n, theta / n, entrance_distance=(i + 1/2) L / n,
+        num_bins)` instead: the wake at the piece's midpoint (the midpoint rule) of a bend behind a long straight. Only the first
+        piece keeps the entrance face (dipole_e1, fringe_integral, the entrance fringe of `fringe_at`) and only the last keeps the
+        exit face; k1, tilt, gap, gap_exit, fringe_type and tracking_method are kept. An RBend becomes Dipole pieces with its
+        effective face angles. A bend of zero angle is returned unchanged, as [self]."""
         from ._binned_kick import check_num_bins, check_num_kicks
-        from .csr import CSRKick
+        from .csr import CSRKick, TransientCSRKick
 
         n = check_num_kicks(num_kicks, "Dipole.split_for_csr")
         num_bins = check_num_bins(num_bins, "Dipole.split_for_csr")
@@ -111,7 +113,8 @@ class Dipole(Element):
                 fringe_integral_exit=self.fringe_integral_exit if last else torch.zeros_like(self.fringe_integral_exit),
                 fringe_at=fringe_at, fringe_type=self.fringe_type, tracking_method=self.tracking_method,
                 name=f"{self.name}_csr_{i}", sanitize_name=False, **fk))
-            parts.append(CSRKick(length, angle, num_bins=num_bins, name=f"{self.name}_csr_kick_{i}", sanitize_name=False, **fk))
+            kk = {"num_bins": num_bins, "name": f"{self.name}_csr_kick_{i}", "sanitize_name": False, **fk}
+            parts.append(TransientCSRKick(length, angle, (i + 0.5) * length, **kk) if transient else CSRKick(length, angle, **kk))
         return parts
 
     @property

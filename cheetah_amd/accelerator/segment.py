@@ -1864,9 +1864,10 @@ class Segment(Element):
         merged_elements.append(current)
         return self.__class__(elements=merged_elements, name=self.name, metadata=deepcopy(self.metadata))
 
-    def with_csr_kicks(self, num_kicks: int, num_bins: int = 200, except_for=None) -> "Segment":
-        """Every bending Dipole (and RBend) split by `Dipole.split_for_csr(num_kicks, num_bins)` into pieces with steady-state CSR
-        kicks between them, nested Segments included; other elements, bends of zero angle and names in `except_for` unchanged."""
+    def with_csr_kicks(self, num_kicks: int, num_bins: int = 200, except_for=None, transient: bool = False) -> "Segment":
+        """Every bending Dipole (and RBend) split by `Dipole.split_for_csr(num_kicks, num_bins, transient)` into pieces with
+        steady-state CSR kicks between them (with `transient`: kicks with the entrance transient, every bend taken to follow a long
+        straight), nested Segments included; other elements, bends of zero angle and names in `except_for` unchanged."""
         from ._binned_kick import check_num_bins, check_num_kicks
         from .dipole import Dipole
 
@@ -1876,9 +1877,9 @@ class Segment(Element):
         elements = []
         for e in self.elements:
             if isinstance(e, Segment):
-                elements.append(e.with_csr_kicks(num_kicks, num_bins, except_for))
+                elements.append(e.with_csr_kicks(num_kicks, num_bins, except_for, transient))
             elif isinstance(e, Dipole) and e.name not in except_for:
-                elements += e.split_for_csr(num_kicks, num_bins)
+                elements += e.split_for_csr(num_kicks, num_bins, transient)
             else:
                 elements.append(e)
         return self.__class__(elements=elements, name=self.name, metadata=deepcopy(self.metadata))
@@ -1889,10 +1890,11 @@ class Segment(Element):
         num_bins)`, nested Segments included. The kick's `effect_length` IS the element's `length` tensor, so in-place edits and
         gradients follow. With `max_step` (metres) an element longer than that is first split with its own
         `split(resolution=max_step)` and every piece gets its kick. Names in `except_for` and the collective kicks already there
-        (`LSCKick`, `CSRKick`, `Wakefield`, `SpaceChargeKick`) get none. A kick stands behind its element and sees the outgoing beam:
-        the kick after a `Cavity` uses the energy the beam leaves the cavity with, not the mean energy inside it."""
+        (`LSCKick`, `CSRKick`, `TransientCSRKick`, `Wakefield`, `SpaceChargeKick`) get none. A kick stands behind its element and
+        sees the outgoing beam: the kick after a `Cavity` uses the energy the beam leaves the cavity with, not the mean energy inside
+        it."""
         from ._binned_kick import check_num_bins
-        from .csr import CSRKick
+        from .csr import CSRKick, TransientCSRKick
         from .lsc import LSCKick, check_beam_radius, check_radius_factor
         from .space_charge_kick import SpaceChargeKick
         from .wakefield import Wakefield
@@ -1913,7 +1915,7 @@ class Segment(Element):
                 elements.append(e.with_lsc_kicks(num_bins, beam_radius, radius_factor, max_step, except_for))
                 continue
             elements_of_e = [e]
-            if not isinstance(e, (LSCKick, CSRKick, Wakefield, SpaceChargeKick)) and e.name not in except_for \
+            if not isinstance(e, (LSCKick, CSRKick, TransientCSRKick, Wakefield, SpaceChargeKick)) and e.name not in except_for \
                     and bool((e.length > 0).any()):
                 if max_step is not None and bool((e.length > step).any()):
                     elements_of_e = e.split(torch.as_tensor(step, device=e.length.device, dtype=e.length.dtype))

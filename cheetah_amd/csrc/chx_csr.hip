@@ -13,6 +13,8 @@
 // sum); B4 node_bwd_particles_kernel, one pass over the particles (adjoint of the deposit and of the node coordinate). Only F3 and
 // B3 are this file's: the particle passes, the argument check, the workspace and the launchers are chx_grid1d_dev.h and
 // chx_grid1d_host.h, shared with chx_wake.hip and chx_lsc.hip.
+// The second half of the file is the same kick with the entrance transient (TransientCSRKick element): F3 and B3 with the table of
+// the slippage length reached inside the bend, and B4 wrapped to sum the cotangent of that length.
 #include "chx_grid1d_host.h"
 
 namespace {
@@ -53,10 +55,45 @@ __device__ void csr_b_table(int M, int nlag, double* bt, double* at) {
 
 inline size_t toeplitz_lds(int M) { return ((size_t)2 * M + 256 + 4 * 64) * sizeof(double); }
 
+// A wave's share of the anti-causal sum of node k0 + lane: the source tiles m0 = k0 + 64 (wave + 4 i) < mend; a tile's 64 deposits
+// are loaded one per lane and broadcast with readlane. Lag m - k of source m0 + j: bt index 128 + m0 + j - k in [65, M + 190].
+__device__ __forceinline__ double toeplitz_fwd_sum(const double* bt, const unsigned long long* __restrict__ gq, double SQ, int k0,
+                                                   int mend, int M) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int k = k0 + lane;
+    double v = 0.0;
+    for (int m0 = k0 + wave * 64; m0 < mend; m0 += kWB) {
+        const int m = m0 + lane;
+        const double d = m < M ? from_fixed(gq[m], SQ) : 0.0;
+        const int base = 128 + m0 - k;
+#pragma unroll 16
+        for (int j = 0; j < 64; ++j) v += bt[base + j] * readlane_d(d, j);
+    }
+    return v;
+}
+
+// A wave's share of the adjoint (causal) sum of source m0 + lane: the target tiles k0 = 64 (wave + 4 i) < mmax that reach up to node
+// kmin or beyond (the tiles in front of it only meet lags whose coefficient is zero). Lag m - k of target k0 + j: bt index
+// 128 + m - k0 - j in [65, M + 190] (k0 <= m0).
+__device__ __forceinline__ double toeplitz_bwd_sum(const double* bt, const unsigned long long* __restrict__ gg, double SV, int m0,
+                                                   int mmax, int kmin, int M) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int m = m0 + lane;
+    double v = 0.0;
+    for (int k0 = wave * 64; k0 < mmax; k0 += kWB) {
+        if (k0 + 63 < kmin) continue;
+        const int k = k0 + lane;
+        const double a = k < M ? from_fixed(gg[k], SV) : 0.0;
+        const int base = 128 + m - k0;
+#pragma unroll 16
+        for (int j = 0; j < 64; ++j) v += bt[base - j] * readlane_d(a, j);
+    }
+    return v;
+}
+
 // ---- F3 ----------------------------------------------------------------------------------------------------------------------
 // One workgroup per (row, 64 nodes k0 ... k0 + 63); workgroup 0 stores the row's scale in the last header slot, where F4 and the
-// backward pass read it; wave v takes the source tiles m0 = k0 + 64 (v + 4 i) < M; a tile's 64 deposits
-// are loaded one per lane and broadcast with readlane. Lag m - k of source m0 + j: bt index 128 + m0 + j - k in [65, M + 190].
+// backward pass read it; wave v takes the source tiles m0 = k0 + 64 (v + 4 i) < M (toeplitz_fwd_sum).
 template <typename T>
 __global__ __launch_bounds__(kWB) void csr_toeplitz_kernel(int M, const T* __restrict__ energy, int64_t Be,
                                                            const T* __restrict__ length, int64_t Bl, const T* __restrict__ angle,
@@ -75,17 +112,7 @@ __global__ __launch_bounds__(kWB) void csr_toeplitz_kernel(int M, const T* __res
     const unsigned long long* gq = grid + b * M;
     const double SQ = st[3], h = st[2];
     const int k = k0 + lane;
-    double v = 0.0;
-    if (live) {
-        for (int m0 = k0 + wave * 64; m0 < M; m0 += kWB) {
-            const int m = m0 + lane;
-            const double d = m < M ? from_fixed(gq[m], SQ) : 0.0;
-            const int base = 128 + m0 - k;
-#pragma unroll 16
-            for (int j = 0; j < 64; ++j) v += bt[base + j] * readlane_d(d, j);
-        }
-    }
-    acc[wave * 64 + lane] = v;
+    acc[wave * 64 + lane] = live ? toeplitz_fwd_sum(bt, gq, SQ, k0, M, M) : 0.0;
     __syncthreads();
     if (wave == 0 && k < M) {
         const double s = ((acc[lane] + acc[64 + lane]) + acc[128 + lane]) + acc[192 + lane];
@@ -95,8 +122,7 @@ __global__ __launch_bounds__(kWB) void csr_toeplitz_kernel(int M, const T* __res
 }
 
 // ---- B3: adjoint of F3, GD_m = 3^(2/3) k_e h^(-4/3) sum_{k <= m} b_(m-k) GV_k ------------------------------------------------------
-// One workgroup per (row, 64 sources m0 ... m0 + 63); wave v takes the target tiles k0 = 64 (v + 4 i) <= m0 + 63. Lag m - k of
-// target k0 + j: bt index 128 + m - k0 - j in [2, M + 190].
+// One workgroup per (row, 64 sources m0 ... m0 + 63); wave v takes the target tiles k0 = 64 (v + 4 i) <= m0 + 63 (toeplitz_bwd_sum).
 __global__ __launch_bounds__(kWB) void csr_bwd_toeplitz_kernel(int M, const double* __restrict__ state, const double* __restrict__ bhdr,
                                                                const unsigned long long* __restrict__ ggrid, double* __restrict__ adj) {
     extern __shared__ __attribute__((aligned(16))) double lds[];            // bt[M + 256], at[M], acc[4][64]
@@ -112,17 +138,7 @@ __global__ __launch_bounds__(kWB) void csr_bwd_toeplitz_kernel(int M, const doub
     const unsigned long long* gg = ggrid + b * M;
     const double SV = bhdr[b * kHdr + 1], h = st[2];
     const int m = m0 + lane;
-    double v = 0.0;
-    if (live) {
-        for (int k0 = wave * 64; k0 < mmax; k0 += kWB) {
-            const int k = k0 + lane;
-            const double a = k < M ? from_fixed(gg[k], SV) : 0.0;
-            const int base = 128 + m - k0;
-#pragma unroll 16
-            for (int j = 0; j < 64; ++j) v += bt[base - j] * readlane_d(a, j);
-        }
-    }
-    acc[wave * 64 + lane] = v;
+    acc[wave * 64 + lane] = live ? toeplitz_bwd_sum(bt, gg, SV, m0, mmax, 0, M) : 0.0;
     __syncthreads();
     if (wave == 0 && m < M) {
         const double s = ((acc[lane] + acc[64 + lane]) + acc[128 + lane]) + acc[192 + lane];
@@ -153,6 +169,220 @@ int csr_kick_bwd_t(const T* x, const T* q, const T* w, int64_t B, int64_t Bx, in
     CHX_CHECK_LAUNCH();
     hipLaunchKernelGGL(node_bwd_particles_kernel<T>, grid_particles(N, B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, M, state,
                        csr_state_row(M), ws.adj, gout, dX, dC);
+    CHX_CHECK_LAUNCH();
+    return CHX_OK;
+}
+
+// ==== the entrance transient (TransientCSRKick element) ===========================================================================
+// Saldin, Schneidmiller, Yurkov, NIM A 398 (1997) 373: an arc length d into a bend of radius R behind a long straight the slippage
+// length is z_L = d^3 / (24 R^2), x = z_L / h = d^3 theta^2 / (24 L^2 h) nodes, and
+//   S_k(x) = sum_j a~_j(x) (D_(k+j+1) - D_(k+j)) - (2/3) x^(-1/3) [D~(k + x) - D~(k + 4x)],   a~_j = min(j+1, x)^(2/3) - min(j, x)^(2/3)
+// with D~ the linear interpolation of the deposits (0 beyond node M). As a Toeplitz table: b_j = a~_(j-1) - a~_j, then
+// -(2/3) x^(-1/3) (1 - f, f) at the lags (p, p + 1) and +(2/3) x^(-1/3) (1 - f4, f4) at (p4, p4 + 1), p = floor(x), p4 = floor(4x).
+// For x >= M the table is the steady state's. F3 and B3 below; the particle passes are the shared ones. State row: the header with
+// the row's scale in its last slot | M node kicks | x | a free slot | M deposits D_k.
+constexpr int kCsrMaxBlocks = CHX_WAKE_MAX_BINS / kNodeBlock;
+
+__host__ __device__ inline int64_t csrt_state_row(int M) { return CHX_CSR_TRANSIENT_STATE_DOUBLES(M); }
+__host__ __device__ inline int csrt_x_slot(int M) { return kHdr + M; }
+__host__ __device__ inline int csrt_dep_slot(int M) { return kHdr + M + 2; }
+
+// The workspace's own block: xpart[B][kCsrMaxBlocks], the partials of d(x), one per workgroup of B3.
+Grid1dWs csrt_ws(void* base, int64_t B, int64_t N, int M) { return grid1d_ws(base, B, N, M, 1, (size_t)(B * kCsrMaxBlocks) * 8); }
+
+// The row's x = d^3 theta^2 / (24 L^2 h) in fp64: 0 (no kick) where L, theta or d is 0, NaN for a negative L or d.
+template <typename T>
+__device__ __forceinline__ double csrt_x(const T* length, int64_t Bl, const T* angle, int64_t Ba, const T* distance, int64_t Bd,
+                                         double h, int64_t b) {
+    const double L = (double)length[Bl == 1 ? 0 : b], th = (double)angle[Ba == 1 ? 0 : b], d = (double)distance[Bd == 1 ? 0 : b];
+    if (L == 0.0 || th == 0.0 || d == 0.0) return 0.0;
+    if (L > 0.0 && d > 0.0) return d * d * d * th * th / (24.0 * L * L * h);
+    return __longlong_as_double(0x7ff8000000000000LL);
+}
+
+// x > 0 taken apart: p = floor(x) and p4 = floor(4x) clamped to M in double (x may be 1e30) with the fractions f, f4 (only used
+// below the clamp), cx = (2/3) x^(-1/3), and nl = min(M, p4 + 2): the lags j >= nl have b_j = 0.
+struct CsrLags {
+    int p, p4, nl;
+    double f, f4, cx;
+};
+__device__ __forceinline__ CsrLags csr_lags(double x, int M) {
+    CsrLags g;
+    const double pd = fmin(floor(x), (double)M), p4d = fmin(floor(4.0 * x), (double)M);
+    g.p = (int)pd;
+    g.p4 = (int)p4d;
+    g.f = x - pd;
+    g.f4 = 4.0 * x - p4d;
+    g.nl = g.p4 + 2 < M ? g.p4 + 2 : M;
+    g.cx = 2.0 / (3.0 * cbrt(x));
+    return g;
+}
+
+// LDS table bt[i] = b_(i - 128)(x) for lags 0 <= i - 128 < nlag, zero elsewhere (i < M + 256); scratch at[nlag] for a~_j: csr_a(j)
+// for the full intervals j < p and the same cancellation-free form, (x - p)(x + p) / (x^(4/3) + (x p)^(2/3) + p^(4/3)), for the
+// partial one. Where x and 4x lie between the same two nodes (x < 1/4) the two interpolations are taken together, (f - f4) and
+// (f4 - f), so that b stays accurate as x -> 0, where it goes as x^(2/3).
+__device__ void csrt_b_table(int M, int nlag, double x, const CsrLags& g, double* bt, double* at) {
+    for (int j = threadIdx.x; j < nlag; j += kWB) {
+        double a = 0.0;
+        if (j < g.p) {
+            a = csr_a(j);
+        } else if (j == g.p) {
+            const double pp = (double)j, cxp = cbrt(x * pp);
+            a = (x - pp) * (x + pp) / (x * cbrt(x) + cxp * cxp + pp * cbrt(pp));
+        }
+        at[j] = a;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < M + 256; i += kWB) {
+        const int j = i - 128;
+        double bj = 0.0;
+        if (j >= 0 && j < nlag) {
+            bj = j == 0 ? (g.p > 0 ? -1.0 : -at[0]) : at[j - 1] - at[j];
+            if (g.p4 == g.p) {
+                if (j == g.p) bj += g.cx * (g.f - g.f4);
+                else if (j == g.p + 1) bj += g.cx * (g.f4 - g.f);
+            } else {
+                if (j == g.p) bj -= g.cx * (1.0 - g.f);
+                else if (j == g.p + 1) bj -= g.cx * g.f;
+                if (j == g.p4) bj += g.cx * (1.0 - g.f4);
+                else if (j == g.p4 + 1) bj += g.cx * g.f4;
+            }
+        }
+        bt[i] = bj;
+    }
+    __syncthreads();
+}
+
+// ---- F3 of the transient: csr_toeplitz_kernel with the table of the row's x; workgroup 0 stores the row's scale and x in the state
+// row, where F4 and the backward pass read them. The source tiles behind the last non-zero lag are skipped.
+template <typename T>
+__global__ __launch_bounds__(kWB) void csrt_toeplitz_kernel(int M, const T* __restrict__ energy, int64_t Be,
+                                                            const T* __restrict__ length, int64_t Bl, const T* __restrict__ angle,
+                                                            int64_t Ba, const T* __restrict__ distance, int64_t Bd, double mass,
+                                                            double absz, const unsigned long long* __restrict__ grid,
+                                                            double* __restrict__ state) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];            // bt[M + 256], at[M], acc[4][64]
+    const int64_t b = blockIdx.y;
+    const int k0 = blockIdx.x * kNodeBlock;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* st = state + b * csrt_state_row(M);
+    double* bt = lds;
+    double* acc = lds + 2 * M + 256;
+    const bool live = node_live(st);
+    const double SQ = st[3], h = st[2];
+    const double x = live ? csrt_x(length, Bl, angle, Ba, distance, Bd, h, b) : 0.0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        st[kHdr - 1] = csr_scale(energy, Be, length, Bl, angle, Ba, mass, absz, b);
+        st[csrt_x_slot(M)] = x;
+        st[csrt_x_slot(M) + 1] = 0.0;
+    }
+    const bool ok = live && x > 0.0;
+    const CsrLags g = csr_lags(ok ? x : 1.0, M);
+    if (ok) csrt_b_table(M, M - k0 < g.nl ? M - k0 : g.nl, x, g, bt, lds + M + 256);
+    const unsigned long long* gq = grid + b * M;
+    const int k = k0 + lane;
+    const int mend = k0 + 63 + g.nl < M ? k0 + 63 + g.nl : M;       // sources m >= mend: lags >= nl for every node of the block
+    acc[wave * 64 + lane] = ok ? toeplitz_fwd_sum(bt, gq, SQ, k0, mend, M) : 0.0;
+    __syncthreads();
+    if (wave == 0 && k < M) {
+        const double s = ((acc[lane] + acc[64 + lane]) + acc[128 + lane]) + acc[192 + lane];
+        st[kHdr + k] = ok ? cbrt(9.0) * kCoulomb / (h * cbrt(h)) * s : (live && x != x ? x : 0.0);
+        st[csrt_dep_slot(M) + k] = live ? from_fixed(gq[k], SQ) : 0.0;
+    }
+}
+
+// ---- B3 of the transient: csr_bwd_toeplitz_kernel with the table of the row's x, and the workgroup's partial of d(x) = sum_k GV_k
+// 3^(2/3) k_e h^(-4/3) dS_k/dx over its 64 nodes, dS_k/dx = (2/9) x^(-4/3) [D~(k + x) - D~(k + 4x)] + (8/3) x^(-1/3) (D_(k+p4+1) -
+// D_(k+p4)) (the derivative of the partial a~ cancels against the interpolation's slope at k + x).
+__global__ __launch_bounds__(kWB) void csrt_bwd_toeplitz_kernel(int M, const double* __restrict__ state,
+                                                                const double* __restrict__ bhdr,
+                                                                const unsigned long long* __restrict__ ggrid,
+                                                                double* __restrict__ adj, double* __restrict__ xpart) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];            // bt[M + 256], at[M], acc[4][64]
+    const int64_t b = blockIdx.y;
+    const int m0 = blockIdx.x * kNodeBlock;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double* st = state + b * csrt_state_row(M);
+    double* bt = lds;
+    double* acc = lds + 2 * M + 256;
+    const int mmax = m0 + kNodeBlock < M ? m0 + kNodeBlock : M;     // sources m < mmax: lags up to mmax - 1
+    const bool live = node_live(st);
+    const double x = st[csrt_x_slot(M)];
+    const bool ok = live && x > 0.0;
+    const CsrLags g = csr_lags(ok ? x : 1.0, M);
+    if (ok) csrt_b_table(M, mmax < g.nl ? mmax : g.nl, x, g, bt, lds + M + 256);
+    const unsigned long long* gg = ggrid + b * M;
+    const double SV = bhdr[b * kHdr + 1], h = st[2];
+    const int m = m0 + lane;
+    acc[wave * 64 + lane] = ok ? toeplitz_bwd_sum(bt, gg, SV, m0, mmax, m0 - g.nl + 1, M) : 0.0;
+    __syncthreads();
+    if (wave == 0) {
+        const double nan_x = live && x != x ? x : 0.0;
+        double xp = 0.0;
+        if (m < M) {
+            const double s = ((acc[lane] + acc[64 + lane]) + acc[128 + lane]) + acc[192 + lane];
+            const double factor = cbrt(9.0) * kCoulomb / (h * cbrt(h));
+            adj[b * M + m] = ok ? factor * s : nan_x;
+            xp = nan_x;
+            if (ok && m + g.p < M) {                                // beyond: every deposit dS_m/dx meets is zero
+                const double* D = st + csrt_dep_slot(M);
+                const int i = m + g.p, i4 = m + g.p4;
+                const double d0 = D[i], d1 = i + 1 < M ? D[i + 1] : 0.0;
+                const double e0 = i4 < M ? D[i4] : 0.0, e1 = i4 + 1 < M ? D[i4 + 1] : 0.0;
+                const double diff = g.p4 == g.p ? (g.f - g.f4) * (d1 - d0)
+                                                : ((1.0 - g.f) * d0 + g.f * d1) - (i4 < M ? (1.0 - g.f4) * e0 + g.f4 * e1 : 0.0);
+                const double dsdx = g.cx / (3.0 * x) * diff + 4.0 * g.cx * (e1 - e0);
+                xp = from_fixed(gg[m], SV) * factor * dsdx;
+            }
+        }
+        xp = chx_wave_sum(xp);
+        if (lane == 0) xpart[b * kCsrMaxBlocks + blockIdx.x] = xp;
+    }
+}
+
+// ---- B4 of the transient: one pass over the particles; the first thread of a row adds the workgroups' partials of d(x) in order
+template <typename T>
+__global__ __launch_bounds__(kWB) void csrt_bwd_particles_kernel(const T* __restrict__ x, const T* __restrict__ q,
+                                                                 const T* __restrict__ w, int64_t Bx, int64_t Bq, int64_t Bw,
+                                                                 int64_t N, int M, const double* __restrict__ state,
+                                                                 const double* __restrict__ adj, const double* __restrict__ xpart,
+                                                                 const T* __restrict__ gout, T* __restrict__ dX, T* __restrict__ dC,
+                                                                 double* __restrict__ d_x) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int nb = (M + kNodeBlock - 1) / kNodeBlock;
+        double s = 0.0;
+        for (int i = 0; i < nb; ++i) s += xpart[(int64_t)blockIdx.y * kCsrMaxBlocks + i];
+        d_x[blockIdx.y] = s;
+    }
+    node_bwd_particle(x, q, w, Bx, Bq, Bw, N, M, state, csrt_state_row(M), adj, gout, dX, dC);
+}
+
+template <typename T>
+int csrt_kick_t(const T* x, const T* q, const T* w, const T* energy, const T* length, const T* angle, const T* distance, double mass,
+                double absz, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Ba, int64_t Bd, int64_t N,
+                int M, T* out, double* state, const Grid1dWs& ws, hipStream_t s) {
+    if (!lds_ok(csrt_toeplitz_kernel<T>, toeplitz_lds(M))) return CHX_ERR_LAUNCH;
+    int st = launch_deposit(x, q, w, B, Bx, Bq, Bw, N, M, 0, 1, 1, csrt_state_row(M), state, ws, s);
+    if (st != CHX_OK) return st;
+    hipLaunchKernelGGL(csrt_toeplitz_kernel<T>, grid_nodes(M, B), dim3(kWB), toeplitz_lds(M), s, M, energy, Be, length, Bl, angle, Ba,
+                       distance, Bd, mass, absz, ws.grid, state);
+    CHX_CHECK_LAUNCH();
+    return launch_node_kick(x, B, Bx, N, M, csrt_state_row(M), state, out, s);
+}
+
+template <typename T>
+int csrt_kick_bwd_t(const T* x, const T* q, const T* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int M,
+                    const double* state, const T* gout, T* dX, T* dC, double* d_scale, double* d_x, const Grid1dWs& ws,
+                    hipStream_t s) {
+    if (!lds_ok(csrt_bwd_toeplitz_kernel, toeplitz_lds(M))) return CHX_ERR_LAUNCH;
+    int st = launch_node_bwd_deposit(x, B, Bx, N, M, csrt_state_row(M), state, gout, d_scale, ws, s);
+    if (st != CHX_OK) return st;
+    hipLaunchKernelGGL(csrt_bwd_toeplitz_kernel, grid_nodes(M, B), dim3(kWB), toeplitz_lds(M), s, M, state, ws.bhdr, ws.ggrid, ws.adj,
+                       ws.extra);
+    CHX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(csrt_bwd_particles_kernel<T>, grid_particles(N, B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, M, state, ws.adj,
+                       ws.extra, gout, dX, dC, d_x);
     CHX_CHECK_LAUNCH();
     return CHX_OK;
 }
@@ -192,5 +422,43 @@ extern "C" int chx_csr_kick_bwd(const void* x, const void* q, const void* w, int
         using T = decltype(t);
         return csr_kick_bwd_t<T>((const T*)x, (const T*)q, (const T*)w, B, Bx, Bq, Bw, N, M, state, (const T*)d_out, (T*)dX, (T*)dC,
                                  d_scale, ws, (hipStream_t)stream);
+    });
+}
+
+extern "C" size_t chx_csr_transient_workspace_bytes(int64_t B, int64_t N, int32_t M) { return csrt_ws(nullptr, B, N, M).bytes; }
+
+extern "C" int chx_csr_transient_kick(const void* x, const void* q, const void* w, const void* energy, const void* length,
+                                      const void* angle, const void* distance, double mass_eV, double abs_charge, int64_t B,
+                                      int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Ba, int64_t Bd, int64_t N,
+                                      int32_t M, int dtype, void* out, double* state, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
+    if (st != CHX_OK) return st;
+    if (!energy || !length || !angle || !distance || !(mass_eV > 0.0) || !chx_bcast_ok(Be, B) || !chx_bcast_ok(Bl, B) ||
+        !chx_bcast_ok(Ba, B) || !chx_bcast_ok(Bd, B) || !out)
+        return CHX_ERR_INVALID_ARG;
+    if (!chx_aligned16(out)) return CHX_ERR_MISALIGNED;
+    const Grid1dWs ws = csrt_ws(workspace, B, N, M);
+    if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return csrt_kick_t<T>((const T*)x, (const T*)q, (const T*)w, (const T*)energy, (const T*)length, (const T*)angle,
+                              (const T*)distance, mass_eV, abs_charge, B, Bx, Bq, Bw, Be, Bl, Ba, Bd, N, M, (T*)out, state, ws,
+                              (hipStream_t)stream);
+    });
+}
+
+extern "C" int chx_csr_transient_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                                          int64_t N, int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC,
+                                          double* d_scale, double* d_x, void* workspace, size_t workspace_bytes, void* stream) {
+    const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
+    if (st != CHX_OK) return st;
+    if (!d_out || !dX || !d_scale || !d_x) return CHX_ERR_INVALID_ARG;
+    const Grid1dWs ws = csrt_ws(workspace, B, N, M);
+    if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return csrt_kick_bwd_t<T>((const T*)x, (const T*)q, (const T*)w, B, Bx, Bq, Bw, N, M, state, (const T*)d_out, (T*)dX, (T*)dC,
+                                  d_scale, d_x, ws, (hipStream_t)stream);
     });
 }

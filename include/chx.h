@@ -339,6 +339,27 @@ int chx_csr_kick(const void* x, const void* q, const void* w, const void* energy
 int chx_csr_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M,
                      int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale, void* workspace,
                      size_t workspace_bytes, void* stream);
+/* ---- entrance transient of coherent synchrotron radiation (TransientCSRKick element): chx_csr_kick's deposit, scale, gather and
+ * degenerate cases with the kernel of a bunch that has travelled the arc length d into a bend behind a long straight (Saldin,
+ * Schneidmiller, Yurkov, NIM A 398 (1997) 373): x = z_L / h = d^3 theta^2 / (24 L^2 h) (0, no kick, where L, theta or d is 0; NaN for a
+ * negative L or d), a~_j = min(j+1, x)^(2/3) - min(j, x)^(2/3) (cancellation-free, 0 for j >= x), D~(y) the linear interpolation of
+ * the deposits at the real index y (0 beyond node M),
+ *   S_k = sum_j a~_j (D_(k+j+1) - D_(k+j)) - (2/3) x^(-1/3) [D~(k + x) - D~(k + 4x)],   dE_k = |Z| 3^(2/3) k_e L^(1/3) |theta|^(2/3) h^(-4/3) S_k
+ * summed as a Toeplitz table b_j(x) in chx_csr_kick's order; for x >= M the table, and with it the result, is chx_csr_kick's bit for
+ * bit. distance[Bd] (d) is a device array like length and angle. state[B][CHX_CSR_TRANSIENT_STATE_DOUBLES(M)]: the row header with
+ * the scale in its last slot, the M node kicks, x, a free slot, the M deposits D_k. workspace:
+ * chx_csr_transient_workspace_bytes(B, N, M) (also for the backward pass).
+ * chx_csr_transient_kick_bwd: as chx_csr_kick_bwd, with d_x[B] (fp64) besides d_scale[B]: the gradient with respect to the row's x
+ * (the node spacing h a constant), which the caller chains to L, theta and d; 0 where x = 0. */
+#define CHX_CSR_TRANSIENT_STATE_DOUBLES(M) (CHX_WAKE_STATE_HEADER + 2 + 2 * (int64_t)(M))
+size_t chx_csr_transient_workspace_bytes(int64_t B, int64_t N, int32_t M);
+int chx_csr_transient_kick(const void* x, const void* q, const void* w, const void* energy, const void* length, const void* angle,
+                           const void* distance, double mass_eV, double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                           int64_t Be, int64_t Bl, int64_t Ba, int64_t Bd, int64_t N, int32_t M, int dtype, void* out, double* state,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int chx_csr_transient_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
+                               int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
+                               double* d_x, void* workspace, size_t workspace_bytes, void* stream);
 /* ---- longitudinal space charge (LSCKick element): per batch row b, the surviving particles' grid and node-based linear deposit D_k
  * (coulomb) exactly as chx_wake_kick's and chx_csr_kick's (same tau_lo, node spacing h, u, k, f, clamping, dead particles, NaN tau);
  * the on-axis field of a uniformly charged disc of radius a and Lorentz factor gamma, integrated exactly against the hat functions:
