@@ -273,6 +273,11 @@ SIGNATURES = {
                                   c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "chx_slice_moments_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, ctypes.c_int32,
                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "chx_bunching_workspace_bytes": (c_size_t, [c_i64, c_i64, c_i64]),
+    "chx_bunching": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p,
+                             c_void_p, c_void_p, c_size_t, c_void_p]),
+    "chx_bunching_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_int,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "chx_wake_workspace_bytes": (c_size_t, [c_i64, c_i64, ctypes.c_int32]),
     "chx_wake_kick": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_i64, c_i64, c_i64,
                               c_i64, c_i64, ctypes.c_int32, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

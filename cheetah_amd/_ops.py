@@ -1526,5 +1526,8 @@ from ._ops_deposit import _cic_args, _cic_deposit_raw, _hist_args, _launch_cic  
 # ... and the slice statistics (ParticleBeam.slice_statistics) in _ops_slices.py
 from ._ops_slices import *  # noqa: E402,F401,F403
 from ._ops_slices import _slice_moments_bwd_raw, _slice_moments_raw  # noqa: E402,F401
+# ... and the bunching factor (ParticleBeam.bunching_factor) in _ops_bunching.py
+from ._ops_bunching import *  # noqa: E402,F401,F403
+from ._ops_bunching import _bunching_bwd_raw, _bunching_raw  # noqa: E402,F401
 # ... and the kicks from the beam binned on nodes in tau (the Wakefield, CSRKick and LSCKick elements) in _ops_grid1d.py
 from ._ops_grid1d import *  # noqa: E402,F401,F403

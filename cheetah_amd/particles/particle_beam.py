@@ -362,6 +362,24 @@ class ParticleBeam(Beam):
 
         return slice_statistics(self, num_slices=num_slices, tau_range=tau_range, edges=edges)
 
+    def bunching_factor(self, wavelengths=None, *, wavenumbers=None) -> torch.Tensor:
+        """The bunching factor b(k) = sum a exp(-i k tau) / sum a of the beam at chosen wavelengths (a = charge x survival
+        probability, tau = `particles[..., 4]` in metres): the beam's spectrum, the longitudinal form factor of coherent
+        radiation -> complex128 (*batch, K); `|b|` is `.abs()`.
+
+        Exactly one of `wavelengths` (lambda in metres) and `wavenumbers` (k = 2 pi / lambda in rad/m): a float, a sequence or a
+        tensor (…, K) whose leading dimensions broadcast against the beam's batch shape; constants, never differentiated. With
+        nu = 1 / lambda (or k / (2 pi)) in float64: F = sum a exp(-2 pi i nu tau), Q = sum a, b = F / Q, all sums in float64.
+        A particle with a == 0 contributes exactly 0 whatever its coordinates hold; a row with Q == 0 is NaN; a non-finite tau
+        with a != 0 makes its row NaN. Host-side values must be finite (wavelengths > 0); device tensors are used as given.
+
+        One `chx_bunching` call (a direct sum over particle x wavelength pairs; bitwise reproducible, no host synchronisation,
+        capturable in a device graph); differentiable with respect to tau, the survival probabilities and the charges. Not
+        available inside `sharding.particle_sharded` (NotImplementedError)."""
+        from .bunching import bunching_factor
+
+        return bunching_factor(self, wavelengths, wavenumbers)
+
     def _entry(self, index: int, take_sqrt: bool = False) -> torch.Tensor:
         """One entry of the moment vector (optionally its square root) in the beam's dtype. Under autograd this is ONE node
         (`_MomentEntry`) instead of select -> sqrt -> to, whose three backward nodes cost more host time than the moment

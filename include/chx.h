@@ -287,6 +287,32 @@ int chx_slice_moments_bwd(const void* x, const void* w, const void* q, const voi
                           int64_t Bq, int64_t Be, int64_t N, int32_t S, int dtype, const double* out, const double* d_out,
                           const double* d_charge, void* dX, void* dW, void* dQ, void* workspace, size_t workspace_bytes,
                           void* stream);
+/* ---- bunching factor (ParticleBeam.bunching_factor): per batch row b and spatial frequency nu[Bnu][K] (fp64, TURNS per metre:
+ * nu = 1 / lambda = k / (2 pi), so that no rounding of 2 pi enters the phase), with a_i = q_i w_i and tau column 4 of x:
+ *   F[B][K][2] = sum_i a_i exp(-2 pi i nu tau_i) (re, im),  Q[B] = sum_i a_i      (the bunching factor is F / Q)
+ * The phase is t = nu * tau in fp64, reduced to f = t - rint(t); sin and cos of 2 pi f are evaluated in the beam's precision
+ * (dtype) and accumulated in fp64. A particle with a == 0 contributes exactly 0 whatever its tau holds (a select, not a
+ * product: lost particles keep NaN / inf coordinates); a non-finite tau with a != 0 makes every F of its row NaN.
+ * w, q (dtype, [Bw][N], [Bq][N]) may be NULL (all ones). 1 <= K <= CHX_BUNCHING_K_MAX.
+ * Deterministic: a direct sum over CHX_BUNCHING_CHUNK particles x CHX_BUNCHING_K_TILE frequencies per workgroup, every
+ * frequency one fma chain per wave, the waves and then the chunks added in a fixed order; no float atomics.
+ * workspace: chx_bunching_workspace_bytes(B, N, K) (0 for arguments out of range); the backward pass needs none (its workspace
+ * arguments are accepted and ignored).
+ * chx_bunching_bwd: given dF[B][K][2] and dQ[B] (either may be NULL) -> dTau[B][N], dW[B][N], dQpart[B][N] (dtype; NULL outputs
+ * are not computed; rows of broadcast inputs are NOT reduced — the caller sums). With theta = 2 pi nu_k tau_i:
+ *   dTau_i = a_i sum_k 2 pi nu_k (-dF_re sin theta - dF_im cos theta),  da_i = sum_k (dF_re cos theta - dF_im sin theta) + dQ,
+ *   dQpart_i = da_i w_i,  dW_i = da_i q_i.
+ * A particle with a == 0 gets dTau == 0 exactly; if its tau is not finite as well, the sum over k in da_i is taken as 0. */
+#define CHX_BUNCHING_K_MAX 65536  /* 256 frequency tiles (a grid dimension); F partials: 16 K bytes per chunk and row */
+#define CHX_BUNCHING_CHUNK 2048   /* particles per workgroup: the granule of the ordered merge */
+#define CHX_BUNCHING_K_TILE 256   /* frequencies per workgroup */
+size_t chx_bunching_workspace_bytes(int64_t B, int64_t N, int64_t K);
+int chx_bunching(const void* x, const void* w, const void* q, const double* nu, int64_t B, int64_t Bx, int64_t Bw, int64_t Bq,
+                 int64_t Bnu, int64_t N, int64_t K, int dtype, double* F, double* Q, void* workspace, size_t workspace_bytes,
+                 void* stream);
+int chx_bunching_bwd(const void* x, const void* w, const void* q, const double* nu, int64_t B, int64_t Bx, int64_t Bw, int64_t Bq,
+                     int64_t Bnu, int64_t N, int64_t K, int dtype, const double* dF, const double* dQ, void* dTau, void* dW,
+                     void* dQpart, void* workspace, size_t workspace_bytes, void* stream);
 /* ---- short-range wakefield (Wakefield element): per batch row b, over the SURVIVING particles (w > 0, finite tau; c = |q| w):
  * tau_lo, tau_hi, node spacing D = (tau_hi - tau_lo) / (M - 1); node coordinate u = clamp((tau - tau_lo) / D, 0, M - 1) (0 when
  * D = 0), k = min(floor u, M - 2), f = u - k; node deposits Q_k += (1 - f) c, Q_k+1 += f c (and X, Y with c x, c y when the
