@@ -95,10 +95,12 @@ template <typename T>
 int launch_node_bwd_deposit(const T* x, int64_t B, int64_t Bx, int64_t N, int M, int64_t state_row, const double* state,
                             const T* gout, double* d_scale, const Grid1dWs& ws, hipStream_t s) {
     const int G = wake_groups(N);
+    const size_t lds = (size_t)M * 8;
+    if (!lds_ok(node_bwd_deposit_kernel<T>, lds)) return CHX_ERR_LAUNCH;
     hipLaunchKernelGGL(node_bwd_range_kernel<T>, grid_groups(N, B), dim3(kWB), 0, s, x, Bx, N, G, M, state, state_row, gout, ws.bpart,
                        ws.ggrid);
     CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(node_bwd_deposit_kernel<T>, grid_groups(N, B), dim3(kWB), (size_t)M * 8, s, x, Bx, N, G, M, state, state_row,
+    hipLaunchKernelGGL(node_bwd_deposit_kernel<T>, grid_groups(N, B), dim3(kWB), lds, s, x, Bx, N, G, M, state, state_row,
                        gout, ws.bpart, ws.bhdr, d_scale, ws.ggrid);
     CHX_CHECK_LAUNCH();
     return CHX_OK;

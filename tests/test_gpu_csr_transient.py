@@ -347,7 +347,6 @@ def test_gradients_match_autograd_through_the_restatement(batch, xcase):
         b = r.grad
         scale = b.abs().max()
         assert scale > 0, name
-        print(name, float((a - b).abs().max() / scale))
         assert torch.allclose(a, b, rtol=0, atol=1e-9 * scale), (name, float((a - b).abs().max() / scale))
     # the tau column gets the node coordinate's term
     assert float(got[0][..., 4].abs().max()) > 0
