@@ -89,7 +89,8 @@ __global__ __launch_bounds__(CHX_BLOCK) void k_edge_prod(float* x, const float* 
     const int64_t b = blockIdx.x / tiles_per_row;
     const int64_t n0 = (blockIdx.x - b * tiles_per_row) * TP;
     const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
-    chx_coltile_edge<float, TP, TO_COLUMNS>(x + (b * N + n0) * 7, R + ((BR == 1) ? 0 : b) * 49, lds, np, true);
+    float* g = x + (b * N + n0) * 7;
+    chx_coltile_edge<float, TP, TO_COLUMNS>(g, g, R + ((BR == 1) ? 0 : b) * 49, lds, np, true, false);
 }
 
 template <bool NT_LOAD, bool NT_STORE>
@@ -123,7 +124,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void k_enter(float* x, const float* __re
     const int64_t n0 = (blockIdx.x - b * tiles_per_row) * TP;
     const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
     float* g = x + (b * N + n0) * 7;
-    chx_coltile_enter<float, TP>(g, g, R + ((BR == 1) ? 0 : b) * 49, lds, np, true, false, flags + blockIdx.x);
+    chx_coltile_edge<float, TP, true, true>(g, g, R + ((BR == 1) ? 0 : b) * 49, lds, np, true, false, flags + blockIdx.x);
 }
 
 // part 2, not in the library: pass 0 from the input of the call (shared by the batch rows when Bx == 1) straight into column tiles,
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void k_enter_first(const float* x_in, co
     const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
     const int64_t in_row = (Bx == 1) ? 0 : b;
     const bool in_vec = (in_flags & 1) && (((in_row * N * 7 * (int64_t)sizeof(float)) & 15) == 0);
-    chx_coltile_enter<float, TP>(x_in + (in_row * N + n0) * 7, x_out + (b * N + n0) * 7, R + ((BR == 1) ? 0 : b) * 49, lds, np, in_vec,
+    chx_coltile_edge<float, TP, true, true>(x_in + (in_row * N + n0) * 7, x_out + (b * N + n0) * 7, R + ((BR == 1) ? 0 : b) * 49, lds, np, in_vec,
                                  (in_flags & 2) != 0, flags + blockIdx.x);
 }
 
@@ -198,7 +199,7 @@ __device__ __forceinline__ void r09_tile_of_block(unsigned tiles_per_row, unsign
     }
 }
 
-// y = R x, the fma chain j = 0..6 of apply7 (chx_apply.hip), for one row (X = T) or two rows side by side (X = chx_col16<T>::P);
+// y = R x, the fma chain j = 0..6 of chx_map7 (chx_common.h), for one row (X = T) or two rows side by side (X = chx_col16<T>::P);
 // R: a pointer to the 49 entries or a r09_map_regs
 template <typename T, typename X, typename M>
 __device__ __forceinline__ void r09_map7(const M& R, const X (&x)[7], X (&y)[7]) {

@@ -27,22 +27,6 @@
 
 namespace {
 
-template <typename T> __device__ __forceinline__ T chx_fma(T a, T b, T c);
-template <> __device__ __forceinline__ float chx_fma<float>(float a, float b, float c) { return fmaf(a, b, c); }
-template <> __device__ __forceinline__ double chx_fma<double>(double a, double b, double c) { return fma(a, b, c); }
-
-// y = R x with R row-major 7x7 (49 values). R may live in SGPRs (uniform pointer).
-template <typename T>
-__device__ __forceinline__ void apply7(const T* __restrict__ R, const T (&x)[7], T (&y)[7]) {
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        T acc = R[i * 7] * x[0];
-#pragma unroll
-        for (int j = 1; j < 7; ++j) acc = chx_fma<T>(R[i * 7 + j], x[j], acc);
-        y[i] = acc;
-    }
-}
-
 // Cavity per-particle epilogue (cavity.py:135-151, 220-226), evaluated in fp64.
 // c = [a, b, kbeta0, phi, cosphi, T566, T556, T555]; tau/delta are the INCOMING coordinates.
 template <typename T>
@@ -53,6 +37,82 @@ __device__ __forceinline__ void cavity_epilogue(const double* __restrict__ c, co
     y[5] = (T)dnew;
     y[4] = (T)tnew;
 }
+
+// A lane's PPT particles and the map step on them. float32 with an even PPT: two particles per 64-bit register pair (particle 2 p
+// in .x, 2 p + 1 in .y) FROM LOAD TO STORE, so that a map is 49 v_pk_fma_f32 per pair and nothing else (packed anew per item, the
+// 28 + 28 register moves around every map were as many instructions as the map itself). Per particle every variant is chx_map7's
+// chain: same bits. apply<ORDER>() walks the pairs in one of two orders, each chosen on measurements (the scalar variant has one):
+//   kMapByPair       the whole map pair by pair (apply_tile_kernel MODE 1, lattice_apply_kernel);
+//   kMapByMatrixRow  matrix row by matrix row over ALL pairs, so that a map entry is fetched once per item — pair by pair the compiler,
+//                    short of scalar registers next to the wave kernels' other state, fetched the 49 entries in four pieces per pair,
+//                    each waited for on the spot (apply_shared_wave_kernel; lattice_scan_wave_kernel walks the same order itself).
+// cavity: the item is an active cavity, c its coefficient row — the epilogue on the INCOMING tau, delta of every particle.
+enum chx_map_order { kMapByPair, kMapByMatrixRow };
+
+template <typename T, int PPT, bool PAIRS = (std::is_same<T, float>::value && PPT % 2 == 0)>
+struct LaneRows {
+    T v[PPT][7];
+    __device__ __forceinline__ T get(int k, int j) const { return v[k][j]; }
+    __device__ __forceinline__ void set(int k, int j, T val) { v[k][j] = val; }
+    template <chx_map_order ORDER>
+    __device__ __forceinline__ void apply(const T* __restrict__ R, bool cavity = false, const double* __restrict__ c = nullptr) {
+#pragma unroll
+        for (int k = 0; k < PPT; ++k) {
+            T y[7];
+            chx_map7<T, T>(R, v[k], y);
+            if (cavity) cavity_epilogue<T>(c, v[k], y);
+#pragma unroll
+            for (int j = 0; j < 7; ++j) v[k][j] = y[j];
+        }
+    }
+};
+template <int PPT>
+struct LaneRows<float, PPT, true> {
+    chx_v2f v[PPT / 2][7];
+    __device__ __forceinline__ float get(int k, int j) const { return (k & 1) ? v[k >> 1][j].y : v[k >> 1][j].x; }
+    __device__ __forceinline__ void set(int k, int j, float val) {
+        if (k & 1) v[k >> 1][j].y = val;
+        else v[k >> 1][j].x = val;
+    }
+    // the cavity epilogue on the two particles of a pair: y = R x already formed, x the incoming pair
+    static __device__ __forceinline__ void cavity_pair(const double* __restrict__ c, const chx_v2f (&x)[7], chx_v2f (&y)[7]) {
+        float xa[7], xb[7], ya[7], yb[7];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) {
+            xa[j] = x[j].x; xb[j] = x[j].y;
+            ya[j] = y[j].x; yb[j] = y[j].y;
+        }
+        cavity_epilogue<float>(c, xa, ya);
+        cavity_epilogue<float>(c, xb, yb);
+        y[4] = chx_v2f{ya[4], yb[4]};
+        y[5] = chx_v2f{ya[5], yb[5]};
+    }
+    template <chx_map_order ORDER>
+    __device__ __forceinline__ void apply(const float* __restrict__ R, bool cavity = false, const double* __restrict__ c = nullptr) {
+        chx_v2f y[PPT / 2][7];
+        if constexpr (ORDER == kMapByPair) {
+#pragma unroll
+            for (int pr = 0; pr < PPT / 2; ++pr) {
+                chx_map7<float, chx_v2f>(R, v[pr], y[pr]);
+                if (cavity) cavity_pair(c, v[pr], y[pr]);
+#pragma unroll
+                for (int j = 0; j < 7; ++j) v[pr][j] = y[pr][j];
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 7; ++r) chx_map7_row<float, chx_v2f, PPT / 2>(R, r, v, y);
+            if (cavity) {
+#pragma unroll
+                for (int pr = 0; pr < PPT / 2; ++pr) cavity_pair(c, v[pr], y[pr]);
+            }
+#pragma unroll
+            for (int pr = 0; pr < PPT / 2; ++pr) {
+#pragma unroll
+                for (int j = 0; j < 7; ++j) v[pr][j] = y[pr][j];
+            }
+        }
+    }
+};
 
 // ---- generic multi-map kernel -------------------------------------------------------------
 // MODE 0: x_out = R[0] x_in                      (single pass)
@@ -70,21 +130,13 @@ __global__ __launch_bounds__(CHX_BLOCK) void apply_tile_kernel(
     constexpr int TP = PPT * CHX_BLOCK;
     __shared__ __attribute__((aligned(16))) T lds[TP * 7];
 
-    // tiles are laid out per batch row so that a tile never straddles two rows:
-    // tiles_per_row = ceil(N / TP); blockIdx.x = b * tiles_per_row + t
-    const int64_t tiles_per_row = (N + TP - 1) / TP;
-    const int64_t b = blockIdx.x / tiles_per_row;
-    const int64_t t = blockIdx.x - b * tiles_per_row;
-    const int64_t n0 = t * TP;
-    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
-
+    const chx_tile<TP> tc = chx_tile_coords<TP>(N);
+    const int64_t b = tc.b;
+    const int np = tc.np();
     const int64_t in_row = (Bx == 1) ? 0 : b;
-    const T* gin = x_in + (in_row * N + n0) * 7;
-    T* gout = x_out + (b * N + n0) * 7;
-    // vector path needs the tile start 16-B aligned: base aligned (checked on host) and
-    // (row*N + n0)*7*sizeof(T) % 16 == 0. n0*7*sizeof(T) is a multiple of 16 by construction.
-    const bool in_vec = in_vec_ok && (((in_row * N * 7 * (int64_t)sizeof(T)) & 15) == 0);
-    const bool out_vec = out_vec_ok && (((b * N * 7 * (int64_t)sizeof(T)) & 15) == 0);
+    const T* gin = x_in + (in_row * N + tc.n0) * 7;
+    T* gout = x_out + (b * N + tc.n0) * 7;
+    const bool in_vec = CHX_TILE_VEC_OK(T, in_vec_ok, in_row, N), out_vec = CHX_TILE_VEC_OK(T, out_vec_ok, b, N);
 
     // streaming pass: bypass L2 allocation unless the input row is shared by several batch rows (re-read by others) or the
     // pass runs in place on an L2-resident beam (MODE 3)
@@ -94,83 +146,29 @@ __global__ __launch_bounds__(CHX_BLOCK) void apply_tile_kernel(
 
     const int64_t rb = (BR == 1) ? 0 : b;
     if (MODE == 1) {
-        // fused run: all PPT rows of the lane stay in registers; the element loop is OUTSIDE the row loop so
-        // that every map is fetched into SGPRs once per lane and reused for PPT x 49 FMAs
-        if constexpr (std::is_same<T, float>::value && (PPT % 2 == 0)) {
-            // fp32: two particles of the lane share one 64-bit register pair, so every step of the fmaf chain is ONE
-            // v_pk_fma_f32 for both (the map entry is a scalar operand): 49 packed FMAs per pair and element, the
-            // same per-particle operation order as apply7 -> bit-identical results, twice the FMA issue rate
-            chx_v2f xp[PPT / 2][7];
-#pragma unroll
-            for (int q = 0; q < PPT / 2; ++q) {
-                const int p0 = threadIdx.x + (2 * q) * CHX_BLOCK, p1 = p0 + CHX_BLOCK;
-#pragma unroll
-                for (int j = 0; j < 7; ++j) {
-                    xp[q][j].x = (p0 < np) ? lds[p0 * 7 + j] : 0.f;
-                    xp[q][j].y = (p1 < np) ? lds[p1 * 7 + j] : 0.f;
-                }
-            }
-            for (int e = 0; e < E; ++e) {
-                const float* __restrict__ Re = R + ((int64_t)e * BR + rb) * 49;
-#pragma unroll
-                for (int q = 0; q < PPT / 2; ++q) {
-                    chx_v2f y[7];
-#pragma unroll
-                    for (int i = 0; i < 7; ++i) {
-                        chx_v2f acc = xp[q][0] * Re[i * 7];
-#pragma unroll
-                        for (int j = 1; j < 7; ++j) {
-                            const chx_v2f r = {Re[i * 7 + j], Re[i * 7 + j]};
-                            acc = __builtin_elementwise_fma(r, xp[q][j], acc);
-                        }
-                        y[i] = acc;
-                    }
-#pragma unroll
-                    for (int j = 0; j < 7; ++j) xp[q][j] = y[j];
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < PPT / 2; ++q) {
-                const int p0 = threadIdx.x + (2 * q) * CHX_BLOCK, p1 = p0 + CHX_BLOCK;
-#pragma unroll
-                for (int j = 0; j < 7; ++j) {
-                    if (p0 < np) lds[p0 * 7 + j] = xp[q][j].x;
-                    if (p1 < np) lds[p1 * 7 + j] = xp[q][j].y;
-                }
-            }
-            __syncthreads();
-            tile_store<T, TP>(gout, lds, np * 7, out_vec, true);
-            return;
-        }
-        T xs[PPT][7];
+        // fused run: all PPT rows of the lane stay in registers (LaneRows: float32 pairs as packed FMAs, twice the FMA issue rate);
+        // the element loop is OUTSIDE the row loop so that every map is fetched into SGPRs once per lane and reused for PPT x 49 FMAs
+        LaneRows<T, PPT> x;
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
             const int p = threadIdx.x + k * CHX_BLOCK;
 #pragma unroll
-            for (int j = 0; j < 7; ++j) xs[k][j] = (p < np) ? lds[p * 7 + j] : (T)0;
+            for (int j = 0; j < 7; ++j) x.set(k, j, (p < np) ? lds[p * 7 + j] : (T)0);
         }
-        for (int e = 0; e < E; ++e) {
-            const T* __restrict__ Re = R + ((int64_t)e * BR + rb) * 49;
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) {
-                T y[7];
-                apply7<T>(Re, xs[k], y);
-#pragma unroll
-                for (int j = 0; j < 7; ++j) xs[k][j] = y[j];
-            }
-        }
+        for (int e = 0; e < E; ++e) x.template apply<kMapByPair>(R + ((int64_t)e * BR + rb) * 49);
 #pragma unroll
         for (int k = 0; k < PPT; ++k) {
             const int p = threadIdx.x + k * CHX_BLOCK;
             if (p < np) {
 #pragma unroll
-                for (int j = 0; j < 7; ++j) lds[p * 7 + j] = xs[k][j];
+                for (int j = 0; j < 7; ++j) lds[p * 7 + j] = x.get(k, j);
             }
         }
         __syncthreads();
         tile_store<T, TP>(gout, lds, np * 7, out_vec, true);
         return;
     }
+    const T* __restrict__ Rb = R + rb * 49;
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
         const int p = threadIdx.x + k * CHX_BLOCK;
@@ -178,18 +176,8 @@ __global__ __launch_bounds__(CHX_BLOCK) void apply_tile_kernel(
             T x[7], y[7];
 #pragma unroll
             for (int j = 0; j < 7; ++j) x[j] = lds[p * 7 + j];
-            if (MODE == 1) {
-                for (int e = 0; e < E; ++e) {
-                    const T* __restrict__ Re = R + ((int64_t)e * BR + rb) * 49;
-                    apply7<T>(Re, x, y);
-#pragma unroll
-                    for (int j = 0; j < 7; ++j) x[j] = y[j];
-                }
-            } else {
-                const T* __restrict__ Rb = R + rb * 49;
-                apply7<T>(Rb, x, y);
-                if (MODE == 2) cavity_epilogue<T>(coeffs + b * CHX_CAV_NCOEF, x, y);
-            }
+            chx_map7<T, T>(Rb, x, y);
+            if (MODE == 2) cavity_epilogue<T>(coeffs + b * CHX_CAV_NCOEF, x, y);
 #pragma unroll
             for (int j = 0; j < 7; ++j) lds[p * 7 + j] = y[j];
         }
@@ -206,38 +194,18 @@ template <typename T, int PPT, int THREADS = CHX_BLOCK>
 __global__ __launch_bounds__(THREADS) void apply_wave_kernel(const T* __restrict__ x_in, const T* __restrict__ R,
                                                                T* __restrict__ x_out, int64_t B, int64_t Bx, int64_t BR,
                                                                int64_t N) {
-    using V = typename chx_vec16<T>::type;
-    constexpr int VN = chx_vec16<T>::n;
     constexpr int TP = PPT * THREADS;
-    constexpr int WP = PPT * 64, WE = WP * 7, WV = WE / VN;
+    constexpr int WP = PPT * 64, WE = WP * 7, WV = WE / chx_vec16<T>::n;
     __shared__ __attribute__((aligned(16))) T lds[TP * 7];
-    const int64_t tiles_per_row = (N + TP - 1) / TP;
-    const int64_t b = blockIdx.x / tiles_per_row;
-    const int64_t t = blockIdx.x - b * tiles_per_row;
+    const chx_tile<TP> tc = chx_tile_coords<TP>(N);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t n0 = t * TP + wave * WP;                 // first row of this wave
+    const int64_t n0 = tc.n0 + wave * WP;                  // first row of this wave
     if (n0 >= N) return;
     const int valid = (int)((N - n0 < WP) ? (N - n0) : WP);
-    const int vchunks = valid * 7 / VN;
-    const int64_t in_row = (Bx == 1) ? 0 : b;
-    const T* __restrict__ gin = x_in + (in_row * N + n0) * 7;
-    T* __restrict__ gout = x_out + (b * N + n0) * 7;
     T* wl = lds + wave * WE;
-    const bool nt_in = !(Bx == 1 && B > 1);
-    {
-        const V* __restrict__ gv = reinterpret_cast<const V*>(gin);
-        V* lv = reinterpret_cast<V*>(wl);
-#pragma unroll
-        for (int c = 0; c < (WV + 63) / 64; ++c) {
-            const int v = c * 64 + lane;
-            if (v < vchunks) lv[v] = nt_in ? chx_nt_load(gv + v) : gv[v];
-        }
-        for (int e = vchunks * VN + lane; e < valid * 7; e += 64) wl[e] = gin[e];
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const T* __restrict__ Rb = R + ((BR == 1) ? 0 : b) * 49;
+    wave_slice_load<T, WV>(x_in + (((Bx == 1) ? 0 : tc.b) * N + n0) * 7, wl, valid * 7, !(Bx == 1 && B > 1));
+    chx_wave_sync();
+    const T* __restrict__ Rb = R + ((BR == 1) ? 0 : tc.b) * 49;
     T y[PPT][7];
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
@@ -245,11 +213,9 @@ __global__ __launch_bounds__(THREADS) void apply_wave_kernel(const T* __restrict
         T x[7];
 #pragma unroll
         for (int j = 0; j < 7; ++j) x[j] = (p < valid) ? wl[p * 7 + j] : (T)0;
-        apply7<T>(Rb, x, y[k]);
+        chx_map7<T, T>(Rb, x, y[k]);
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    chx_wave_sync();
 #pragma unroll
     for (int k = 0; k < PPT; ++k) {
         const int p = k * 64 + lane;
@@ -258,39 +224,9 @@ __global__ __launch_bounds__(THREADS) void apply_wave_kernel(const T* __restrict
             for (int j = 0; j < 7; ++j) wl[p * 7 + j] = y[k][j];
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    {
-        V* __restrict__ gv = reinterpret_cast<V*>(gout);
-        const V* lv = reinterpret_cast<const V*>(wl);
-#pragma unroll
-        for (int c = 0; c < (WV + 63) / 64; ++c) {
-            const int v = c * 64 + lane;
-            if (v < vchunks) chx_nt_store(lv[v], gv + v);
-        }
-        for (int e = vchunks * VN + lane; e < valid * 7; e += 64) gout[e] = wl[e];
-    }
+    chx_wave_sync();
+    wave_slice_store<T, WV, false>(x_out + (tc.b * N + n0) * 7, wl, valid * 7);
 }
-
-// A lane's PPT particles. float32 with an even PPT: two particles per 64-bit register pair (particle 2 p in .x, 2 p + 1 in .y) FROM
-// LOAD TO STORE, so that a map is 49 v_pk_fma_f32 per pair and nothing else (packed anew per item, the 28 + 28 register moves
-// around every map were as many instructions as the map itself).
-template <typename T, int PPT, bool PAIRS = (std::is_same<T, float>::value && PPT % 2 == 0)>
-struct LaneRows {
-    T v[PPT][7];
-    __device__ __forceinline__ T get(int k, int j) const { return v[k][j]; }
-    __device__ __forceinline__ void set(int k, int j, T val) { v[k][j] = val; }
-};
-template <int PPT>
-struct LaneRows<float, PPT, true> {
-    chx_v2f v[PPT / 2][7];
-    __device__ __forceinline__ float get(int k, int j) const { return (k & 1) ? v[k >> 1][j].y : v[k >> 1][j].x; }
-    __device__ __forceinline__ void set(int k, int j, float val) {
-        if (k & 1) v[k >> 1][j].y = val;
-        else v[k >> 1][j].x = val;
-    }
-};
 
 // ---- shared-input kernel (Bx == 1, B > 1): one x tile, many maps ---------------------------
 // grid = (tiles over N, batch chunks). Each block keeps its particles in registers and loops
@@ -326,7 +262,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void apply_shared_kernel(
             const int p = threadIdx.x + k * CHX_BLOCK;
             if (p < np) {
                 T y[7];
-                apply7<T>(Rb, x[k], y);
+                chx_map7<T, T>(Rb, x[k], y);
 #pragma unroll
                 for (int j = 0; j < 7; ++j) tile[p * 7 + j] = y[j];
             }
@@ -345,12 +281,10 @@ template <typename T, int PPT>
 __global__ __launch_bounds__(CHX_BLOCK) void apply_shared_wave_kernel(
     const T* __restrict__ x_in, const T* __restrict__ R, T* __restrict__ x_out, int64_t B,
     int64_t N, int64_t rows_per_chunk, int in_vec_ok) {
-    using V = typename chx_vec16<T>::type;
-    constexpr int VN = chx_vec16<T>::n;
     constexpr int TP = PPT * CHX_BLOCK;
     constexpr int WP = PPT * 64;                 // particles per wave
     constexpr int WE = WP * 7;                   // elements per wave
-    constexpr int WV = WE / VN;                  // 16-byte chunks per wave
+    constexpr int WV = WE / chx_vec16<T>::n;     // 16-byte chunks per wave
     __shared__ __attribute__((aligned(16))) T lds[TP * 7];
     const int64_t n0 = (int64_t)blockIdx.x * TP;
     const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
@@ -370,56 +304,17 @@ __global__ __launch_bounds__(CHX_BLOCK) void apply_shared_wave_kernel(
     }
     // from here on a wave touches only its own slice
     const int valid = (np - wave * WP < 0) ? 0 : ((np - wave * WP < WP) ? (np - wave * WP) : WP);   // rows of this wave that exist
-    const int vchunks = valid * 7 / VN;           // whole chunks inside the valid rows
     for (int64_t b = b0; b < b1; ++b) {
-        const T* __restrict__ Rb = R + b * 49;
-        if constexpr (std::is_same<T, float>::value && PPT % 2 == 0) {
-            // apply7's fmaf chain for the two particles of a pair in ONE v_pk_fma_f32 per step (same order per particle: same bits)
+        LaneRows<T, PPT> y = x;
+        y.template apply<kMapByMatrixRow>(R + b * 49);
 #pragma unroll
-            for (int r = 0; r < 7; ++r) {
-                chx_v2f y[PPT / 2];
+        for (int k = 0; k < PPT; ++k) {
 #pragma unroll
-                for (int pr = 0; pr < PPT / 2; ++pr) y[pr] = x.v[pr][0] * Rb[r * 7];
-#pragma unroll
-                for (int j = 1; j < 7; ++j) {
-                    const chx_v2f m = {Rb[r * 7 + j], Rb[r * 7 + j]};
-#pragma unroll
-                    for (int pr = 0; pr < PPT / 2; ++pr) y[pr] = __builtin_elementwise_fma(m, x.v[pr][j], y[pr]);
-                }
-#pragma unroll
-                for (int pr = 0; pr < PPT / 2; ++pr) {
-                    wl[((2 * pr) * 64 + lane) * 7 + r] = y[pr].x;
-                    wl[((2 * pr + 1) * 64 + lane) * 7 + r] = y[pr].y;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) {
-                T xi[7], y[7];
-#pragma unroll
-                for (int j = 0; j < 7; ++j) xi[j] = x.get(k, j);
-                apply7<T>(Rb, xi, y);
-#pragma unroll
-                for (int j = 0; j < 7; ++j) wl[(k * 64 + lane) * 7 + j] = y[j];
-            }
+            for (int j = 0; j < 7; ++j) wl[(k * 64 + lane) * 7 + j] = y.get(k, j);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        T* __restrict__ gout = x_out + (b * N + n0 + wave * WP) * 7;
-        V* __restrict__ gv = reinterpret_cast<V*>(gout);
-        const V* lv = reinterpret_cast<const V*>(wl);
-#pragma unroll
-        for (int c = 0; c < (WV + 63) / 64; ++c) {
-            const int v = c * 64 + lane;
-            if (v < vchunks) chx_nt_store(lv[v], gv + v);
-        }
-        if (vchunks < WV) {                       // the last tile of a row: a few elements beyond the last whole chunk
-            for (int e = vchunks * VN + lane; e < valid * 7; e += 64) gout[e] = wl[e];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        chx_wave_sync();
+        wave_slice_store<T, WV>(x_out + (b * N + n0 + wave * WP) * 7, wl, valid * 7);
+        chx_wave_sync();
     }
 }
 
@@ -946,55 +841,13 @@ __global__ __launch_bounds__(CHX_BLOCK) void lattice_apply_kernel(const T* x_in,
         const double* __restrict__ c = STAGED ? coeffs_s + i * CHX_CAV_NCOEF : coeffs_g + mrow * CHX_CAV_NCOEF;
         if constexpr (SCREENS == 3) {
             T y0[7];
-            apply7<T>(R, x0, y0);
+            chx_map7<T, T>(R, x0, y0);
             if (cavity) cavity_epilogue<T>(c, x0, y0);
 #pragma unroll
             for (int j = 0; j < 7; ++j) x0[j] = y0[j];
         }
-        if constexpr (std::is_same<T, float>::value && PPT % 2 == 0) {
-            // the lane's particles two to a register pair, kept that way from load to store: every step of apply7's fmaf chain is ONE
-            // v_pk_fma_f32 for both (same per-particle order -> same bits; at 4e8 particle rows the maps of a stretch are VALU time,
-            // not HBM time)
-#pragma unroll
-            for (int pr = 0; pr < PPT / 2; ++pr) {
-                chx_v2f y[7];
-#pragma unroll
-                for (int r = 0; r < 7; ++r) {
-                    chx_v2f acc = x.v[pr][0] * R[r * 7];
-#pragma unroll
-                    for (int j = 1; j < 7; ++j) {
-                        const chx_v2f m = {R[r * 7 + j], R[r * 7 + j]};
-                        acc = __builtin_elementwise_fma(m, x.v[pr][j], acc);
-                    }
-                    y[r] = acc;
-                }
-                if (cavity) {
-                    T xa[7], xb[7], ya[7], yb[7];
-#pragma unroll
-                    for (int j = 0; j < 7; ++j) {
-                        xa[j] = x.v[pr][j].x; xb[j] = x.v[pr][j].y;
-                        ya[j] = y[j].x; yb[j] = y[j].y;
-                    }
-                    cavity_epilogue<T>(c, xa, ya);
-                    cavity_epilogue<T>(c, xb, yb);
-                    y[4] = chx_v2f{ya[4], yb[4]};
-                    y[5] = chx_v2f{ya[5], yb[5]};
-                }
-#pragma unroll
-                for (int j = 0; j < 7; ++j) x.v[pr][j] = y[j];
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) {
-                T xi[7], y[7];
-#pragma unroll
-                for (int j = 0; j < 7; ++j) xi[j] = x.get(k, j);
-                apply7<T>(R, xi, y);
-                if (cavity) cavity_epilogue<T>(c, xi, y);
-#pragma unroll
-                for (int j = 0; j < 7; ++j) x.set(k, j, y[j]);
-            }
-        }
+        // (float32 pairs: at 4e8 particle rows the maps of a stretch are VALU time, not HBM time)
+        x.template apply<kMapByPair>(R, cavity, c);
     }
     if (survival_out) {
 #pragma unroll
@@ -1035,12 +888,10 @@ __global__ __launch_bounds__(CHX_BLOCK) void lattice_scan_wave_kernel(const T* _
                                                                      const int64_t* __restrict__ ptrs, T* __restrict__ survival_out,
                                                                      int shared_sv, int transport /*monitors behind a linear prefix are
                                                                      evaluated elsewhere (lattice_scan_bpm_transport_kernel)*/) {
-    using V = typename chx_vec16<T>::type;
-    constexpr int VN = chx_vec16<T>::n;
     constexpr int TP = PPT * CHX_BLOCK;
     constexpr int WP = PPT * 64;                 // particles per wave
     constexpr int WE = WP * 7;                   // elements per wave
-    constexpr int WV = WE / VN;                  // 16-byte chunks per wave
+    constexpr int WV = WE / chx_vec16<T>::n;     // 16-byte chunks per wave
     constexpr bool kPairs = std::is_same<T, float>::value && PPT % 2 == 0;
     __shared__ __attribute__((aligned(16))) T lds[TP * 7];
     const int64_t t0 = (int64_t)blockIdx.x * TP;
@@ -1067,7 +918,6 @@ __global__ __launch_bounds__(CHX_BLOCK) void lattice_scan_wave_kernel(const T* _
     }
     // from here on a wave touches only its own slice
     const int valid = (np - wave * WP < 0) ? 0 : ((np - wave * WP < WP) ? (np - wave * WP) : WP);   // particles of this wave that exist
-    const int vchunks = valid * 7 / VN;           // whole chunks inside the valid rows
     const int nw = (int)gridDim.x * (CHX_BLOCK / 64);                    // waves per row
     for (int b = b0; b < b1; ++b) {
         LaneRows<T, PPT> x = x0;
@@ -1140,35 +990,14 @@ __global__ __launch_bounds__(CHX_BLOCK) void lattice_scan_wave_kernel(const T* _
             const bool cavity = CAV && type == 1;
             const double* __restrict__ c = coeffs + mrow * CHX_CAV_NCOEF;
             if constexpr (kPairs) {
-                // every step of apply7's fmaf chain is ONE v_pk_fma_f32 for the two particles of a pair (same per-particle order -> same
-                // bits); matrix row by matrix row over ALL pairs, so that a map entry is fetched once per item (pair by pair the compiler,
-                // short of scalar registers, fetched the 49 entries in four pieces per pair, each waited for on the spot)
+                // (the row loop stands here, not behind LaneRows::apply: through the member this kernel took 23 more vector registers
+                // and lost a wave per SIMD, profiles/map7_refactor.md)
                 chx_v2f y[PPT / 2][7];
 #pragma unroll
-                for (int r = 0; r < 7; ++r) {
-#pragma unroll
-                    for (int pr = 0; pr < PPT / 2; ++pr) y[pr][r] = x.v[pr][0] * R[r * 7];
-#pragma unroll
-                    for (int j = 1; j < 7; ++j) {
-                        const chx_v2f m = {R[r * 7 + j], R[r * 7 + j]};
-#pragma unroll
-                        for (int pr = 0; pr < PPT / 2; ++pr) y[pr][r] = __builtin_elementwise_fma(m, x.v[pr][j], y[pr][r]);
-                    }
-                }
+                for (int r = 0; r < 7; ++r) chx_map7_row<float, chx_v2f, PPT / 2>(R, r, x.v, y);
                 if (cavity) {
 #pragma unroll
-                    for (int pr = 0; pr < PPT / 2; ++pr) {
-                        T xa[7], xb[7], ya[7], yb[7];
-#pragma unroll
-                        for (int j = 0; j < 7; ++j) {
-                            xa[j] = x.v[pr][j].x; xb[j] = x.v[pr][j].y;
-                            ya[j] = y[pr][j].x; yb[j] = y[pr][j].y;
-                        }
-                        cavity_epilogue<T>(c, xa, ya);
-                        cavity_epilogue<T>(c, xb, yb);
-                        y[pr][4] = chx_v2f{ya[4], yb[4]};
-                        y[pr][5] = chx_v2f{ya[5], yb[5]};
-                    }
+                    for (int pr = 0; pr < PPT / 2; ++pr) LaneRows<T, PPT>::cavity_pair(c, x.v[pr], y[pr]);
                 }
 #pragma unroll
                 for (int pr = 0; pr < PPT / 2; ++pr)
@@ -1180,7 +1009,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void lattice_scan_wave_kernel(const T* _
                     T xi[7], y[7];
 #pragma unroll
                     for (int j = 0; j < 7; ++j) xi[j] = x.get(k, j);
-                    apply7<T>(R, xi, y);
+                    chx_map7<T, T>(R, xi, y);
                     if (cavity) cavity_epilogue<T>(c, xi, y);
 #pragma unroll
                     for (int j = 0; j < 7; ++j) x.set(k, j, y[j]);
@@ -1199,23 +1028,9 @@ __global__ __launch_bounds__(CHX_BLOCK) void lattice_scan_wave_kernel(const T* _
 #pragma unroll
             for (int j = 0; j < 7; ++j) wl[(k * 64 + lane) * 7 + j] = x.get(k, j);
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        T* __restrict__ gout = x_out + ((int64_t)b * N + t0 + wave * WP) * 7;
-        V* __restrict__ gv = reinterpret_cast<V*>(gout);
-        const V* lv = reinterpret_cast<const V*>(wl);
-#pragma unroll
-        for (int cidx = 0; cidx < (WV + 63) / 64; ++cidx) {
-            const int v = cidx * 64 + lane;
-            if (v < vchunks) chx_nt_store(lv[v], gv + v);
-        }
-        if (vchunks < WV) {                       // the last tile of a row: a few elements beyond the last whole chunk
-            for (int e = vchunks * VN + lane; e < valid * 7; e += 64) gout[e] = wl[e];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        chx_wave_sync();
+        wave_slice_store<T, WV>(x_out + ((int64_t)b * N + t0 + wave * WP) * 7, wl, valid * 7);
+        chx_wave_sync();
     }
 }
 
@@ -1284,16 +1099,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void lattice_scan_bpm_transport_kernel(c
         }
         if (type != 0) continue;
         const T* __restrict__ R = reinterpret_cast<const T*>(Rs + ((int64_t)i * B + b) * 49);
-        double y[7];
-#pragma unroll
-        for (int r = 0; r < 7; ++r) {
-            double acc = (double)R[r * 7] * v[0];
-#pragma unroll
-            for (int j = 1; j < 7; ++j) acc = fma((double)R[r * 7 + j], v[j], acc);
-            y[r] = acc;
-        }
-#pragma unroll
-        for (int j = 0; j < 7; ++j) v[j] = y[j];
+        chx_map7_inplace<T, double>(R, v);
     }
 }
 

@@ -16,7 +16,7 @@ constexpr int64_t kL2ResidentBytes = (int64_t)28 * 1024 * 1024;
 // at 1e5 rows and below both sit on the launch floor (2.6 - 3.0 us, inside each other's spread) and the row passes stay.
 constexpr int64_t kColTileMinBytes = (int64_t)8 * 1024 * 1024;
 
-// Pass 0 of such a call stays the row pass above at every size: a pass 0 that writes the column tiles itself (chx_coltile_enter from
+// Pass 0 of such a call stays the row pass above at every size: a pass 0 that writes the column tiles itself (chx_coltile_edge from
 // x_in, which makes pass 1 an ordinary column pass) was measured in benchmarks/apply_coltile.hip (r10, part 2), us per pass of a
 // whole 100-pass call with / without it: 1e6 rows 4.88 / 4.84, 1.3e6 8.03 / 7.90, 3e6 18.77 / 18.86, 1.6e7 102.9 / 103.2
 // (profiles/r10_const_column.md): inside the spreads everywhere, so there is no size threshold for it here.

@@ -516,27 +516,19 @@ __device__ __forceinline__ void compose_block(MapOf map_of, int E, int has_init,
     // a follow-up launch continues from the product accumulated so far (wave 0 only)
     if (has_init && wave == 0 && lane < 49) acc = (double)R_row[lane];
     if (lane < 49) cur[wave][lane] = acc;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    chx_wave_sync();
     for (int e = e0; e < e1; ++e) {
         const T* Re = map_of(e);
         if (lane < 49) nxt[wave][lane] = (double)Re[lane];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        chx_wave_sync();
         if (lane < 49) {
             double s = nxt[wave][i * 7] * cur[wave][j];
             for (int k = 1; k < 7; ++k) s = fma(nxt[wave][i * 7 + k], cur[wave][k * 7 + j], s);
             acc = s;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        chx_wave_sync();
         if (lane < 49) cur[wave][lane] = acc;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        chx_wave_sync();
     }
     __syncthreads();
     if (wave == 0) {
@@ -547,13 +539,9 @@ __device__ __forceinline__ void compose_block(MapOf map_of, int E, int has_init,
                 for (int k = 1; k < 7; ++k) s = fma(cur[w][i * 7 + k], cur[0][k * 7 + j], s);
                 acc = s;
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            chx_wave_sync();
             if (lane < 49) cur[0][lane] = acc;
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            chx_wave_sync();
         }
         if (lane < 49) R_row[lane] = (T)acc;
     }
@@ -1555,18 +1543,14 @@ __global__ __launch_bounds__(64) void compose_prefix_kernel(const T* __restrict_
     for (int e = 0; e < E; ++e) {
         const T* Me = maps + ((int64_t)e * Bm + (Bm == 1 ? 0 : b)) * 49;
         if (lane < 49) { cur[lane] = acc; nxt[lane] = (double)Me[lane]; }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        chx_wave_sync();
         if (lane < 49) {
             double s = nxt[i * 7] * cur[j];
             for (int k = 1; k < 7; ++k) s = fma(nxt[i * 7 + k], cur[k * 7 + j], s);
             acc = s;
             out[((int64_t)e * B + b) * 49 + lane] = (T)acc;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        chx_wave_sync();
     }
 }
 

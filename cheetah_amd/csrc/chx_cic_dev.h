@@ -54,7 +54,7 @@ __device__ __forceinline__ void screen_extent_axis(int resolution, T pixel_size,
 
 // cloud_in_cell.py:150-172 (1-D), :262-311 (3-D): in-extent mask, bin-space position, floor, frac
 // Rmap (optional): a 7x7 map applied to the particle on the fly — coordinate cols[d] of R x, evaluated as the fma chain of
-// chx_apply_affine7 (bit-identical to tracking first and depositing afterwards), without the tracked particles ever
+// chx_apply_affine7 (chx_map7) (bit-identical to tracking first and depositing afterwards), without the tracked particles ever
 // being written (chx_cic_deposit_mapped: Screen images of a scan of lattice settings).
 template <typename T>
 __device__ __forceinline__ CicPoint<T> cic_locate(const CicDev& a, const T* __restrict__ x,
@@ -76,10 +76,7 @@ __device__ __forceinline__ CicPoint<T> cic_locate(const CicDev& a, const T* __re
         if (d < a.ndim) {
             T v;
             if (Rmap) {
-                const T* Rr = Rmap + a.cols[d] * 7;
-                v = Rr[0] * row[0];
-#pragma unroll
-                for (int j = 1; j < 7; ++j) v = fma(Rr[j], row[j], v);
+                v = chx_map7_one_row<T, T>(Rmap + a.cols[d] * 7, row);
             } else {
                 v = x[xrow * 7 + a.cols[d]];
             }

@@ -24,24 +24,21 @@ template <typename T, bool TO_COLUMNS>
 __global__ __launch_bounds__(CHX_BLOCK) void coltile_edge_kernel(T* x, const T* __restrict__ R, int64_t BR, int64_t N) {
     constexpr int TP = coltile_cfg<T>::TP;
     __shared__ __attribute__((aligned(16))) T lds[TP * 7];
-    const int64_t tiles_per_row = (N + TP - 1) / TP;
-    const int64_t b = blockIdx.x / tiles_per_row;
-    const int64_t n0 = (blockIdx.x - b * tiles_per_row) * TP;
-    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
-    chx_coltile_edge<T, TP, TO_COLUMNS>(x + (b * N + n0) * 7, R + ((BR == 1) ? 0 : b) * 49, lds, np, true);
+    const chx_tile<TP> tc = chx_tile_coords<TP>(N);
+    const int np = tc.np();
+    T* g = x + (tc.b * N + tc.n0) * 7;
+    chx_coltile_edge<T, TP, TO_COLUMNS>(g, g, R + ((BR == 1) ? 0 : tc.b) * 49, lds, np, true, false);
 }
 
 // passes 2..E-2: no LDS, no barrier, only the columns the map changed are stored
 template <typename T, bool NT_LOAD>
 __global__ __launch_bounds__(coltile_cfg<T>::LANES) void coltile_pass_kernel(T* x, const T* __restrict__ R, int64_t BR, int64_t N) {
     constexpr int TP = coltile_cfg<T>::TP;
-    const int64_t tiles_per_row = (N + TP - 1) / TP;
-    const int64_t b = blockIdx.x / tiles_per_row;
-    const int64_t n0 = (blockIdx.x - b * tiles_per_row) * TP;
-    T* g = x + (b * N + n0) * 7;
-    const T* __restrict__ Rb = R + ((BR == 1) ? 0 : b) * 49;
-    if (N - n0 >= TP) chx_coltile_pass<T, TP, NT_LOAD>(g, Rb);
-    else chx_rowtile_pass<T>(g, Rb, (int)(N - n0));
+    const chx_tile<TP> tc = chx_tile_coords<TP>(N);
+    T* g = x + (tc.b * N + tc.n0) * 7;
+    const T* __restrict__ Rb = R + ((BR == 1) ? 0 : tc.b) * 49;
+    if (tc.full()) chx_coltile_pass<T, TP, NT_LOAD>(g, Rb);
+    else chx_rowtile_pass<T>(g, Rb, (int)(N - tc.n0));
 }
 
 // ---- the same with one word of scratch per tile (chx_track_elementwise_scratch_bytes): flags[blockIdx.x] != 0 says that column
@@ -53,26 +50,22 @@ template <typename T, bool NT_LOAD>
 __global__ __launch_bounds__(coltile_cfg<T>::LANES) void coltile_pass_flag_kernel(T* x, const T* __restrict__ R, unsigned* flags,
                                                                                   int64_t N, int64_t BR) {
     constexpr int TP = coltile_cfg<T>::TP;
-    const int64_t tiles_per_row = (N + TP - 1) / TP;
-    const int64_t b = blockIdx.x / tiles_per_row;
-    const int64_t n0 = (blockIdx.x - b * tiles_per_row) * TP;
-    T* g = x + (b * N + n0) * 7;
-    const T* __restrict__ Rb = R + ((BR == 1) ? 0 : b) * 49;
-    if (N - n0 >= TP) chx_coltile_pass<T, TP, NT_LOAD, true, true>(g, Rb, flags + blockIdx.x);
-    else chx_rowtile_pass<T>(g, Rb, (int)(N - n0));
+    const chx_tile<TP> tc = chx_tile_coords<TP>(N);
+    T* g = x + (tc.b * N + tc.n0) * 7;
+    const T* __restrict__ Rb = R + ((BR == 1) ? 0 : tc.b) * 49;
+    if (tc.full()) chx_coltile_pass<T, TP, NT_LOAD, true, true>(g, Rb, flags + blockIdx.x);
+    else chx_rowtile_pass<T>(g, Rb, (int)(N - tc.n0));
 }
 
-// pass 1 with scratch: coltile_edge_kernel<T, true> that also writes the tile's flag (chx_common.h: chx_coltile_enter, in place)
+// pass 1 with scratch: coltile_edge_kernel<T, true> that also writes the tile's flag (chx_common.h: chx_coltile_edge with FLAG, in place)
 template <typename T>
 __global__ __launch_bounds__(CHX_BLOCK) void coltile_enter_kernel(T* x, const T* __restrict__ R, unsigned* flags, int64_t N, int64_t BR) {
     constexpr int TP = coltile_cfg<T>::TP;
     __shared__ __attribute__((aligned(16))) T lds[TP * 7];
-    const int64_t tiles_per_row = (N + TP - 1) / TP;
-    const int64_t b = blockIdx.x / tiles_per_row;
-    const int64_t n0 = (blockIdx.x - b * tiles_per_row) * TP;
-    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
-    T* g = x + (b * N + n0) * 7;
-    chx_coltile_enter<T, TP>(g, g, R + ((BR == 1) ? 0 : b) * 49, lds, np, true, false, flags + blockIdx.x);
+    const chx_tile<TP> tc = chx_tile_coords<TP>(N);
+    const int np = tc.np();
+    T* g = x + (tc.b * N + tc.n0) * 7;
+    chx_coltile_edge<T, TP, true, true>(g, g, R + ((BR == 1) ? 0 : tc.b) * 49, lds, np, true, false, flags + blockIdx.x);
 }
 
 // Passes 1..E-1 of chx_track_elementwise through the column layout: needs E >= 3 and every batch row of x 16-byte aligned.

@@ -311,6 +311,69 @@ __device__ __forceinline__ void wave_tile_store(T* __restrict__ g, const T* __re
     }
 }
 
+// The same two transfers UNROLLED, for a wave's whole slice of WV 16-byte chunks (WV compile time) of which `valid_elem` elements
+// exist: every chunk of a lane is requested before the first is waited for, then the few elements behind the last whole chunk (the
+// ragged end of a batch row). Both pairs exist on purpose: the rolled one above takes any length and an unaligned slice (scalar
+// fallback) and costs no registers beyond one chunk — what tile_load / tile_store were measured to want; this one needs the slice
+// 16-byte aligned in global memory and is what apply_wave_kernel, apply_shared_wave_kernel and lattice_scan_wave_kernel were
+// tuned with: a wave that stages on its own has no other wave's barrier to wait at, so the depth of its own requests is its overlap.
+// Stores are non-temporal; loads when `nt`.
+template <typename T, int WV>
+__device__ __forceinline__ void wave_slice_load(const T* __restrict__ g, T* __restrict__ wl, int valid_elem, bool nt) {
+    using V = typename chx_vec16<T>::type;
+    constexpr int VN = chx_vec16<T>::n;
+    const int lane = threadIdx.x & 63, vchunks = valid_elem / VN;
+    const V* __restrict__ gv = reinterpret_cast<const V*>(g);
+    V* lv = reinterpret_cast<V*>(wl);
+#pragma unroll
+    for (int c = 0; c < (WV + 63) / 64; ++c) {
+        const int v = c * 64 + lane;
+        if (v < vchunks) lv[v] = nt ? chx_nt_load(gv + v) : gv[v];
+    }
+    for (int e = vchunks * VN + lane; e < valid_elem; e += 64) wl[e] = g[e];
+}
+
+// TAIL_TEST: the scalar tail sits behind a test of its own for "the slice is whole" (the row loops of the shared-beam kernels were
+// tuned with it; apply_wave_kernel, one slice per wave, without: either way costs the other a wave per SIMD in registers).
+template <typename T, int WV, bool TAIL_TEST = true>
+__device__ __forceinline__ void wave_slice_store(T* __restrict__ g, const T* __restrict__ wl, int valid_elem) {
+    using V = typename chx_vec16<T>::type;
+    constexpr int VN = chx_vec16<T>::n;
+    const int lane = threadIdx.x & 63, vchunks = valid_elem / VN;
+    V* __restrict__ gv = reinterpret_cast<V*>(g);
+    const V* lv = reinterpret_cast<const V*>(wl);
+#pragma unroll
+    for (int c = 0; c < (WV + 63) / 64; ++c) {
+        const int v = c * 64 + lane;
+        if (v < vchunks) chx_nt_store(lv[v], gv + v);
+    }
+    if (!TAIL_TEST || vchunks < WV) {             // the last tile of a row: a few elements beyond the last whole chunk
+        for (int e = vchunks * VN + lane; e < valid_elem; e += 64) g[e] = wl[e];
+    }
+}
+
+// ---- tile coordinates: workgroup blockIdx.x takes tile t of batch row b of x[B][N][7], tiles of TP rows laid out per batch row so
+// that a tile never straddles two rows (blockIdx.x = b * ceil(N / TP) + t).
+template <int TP>
+struct chx_tile {
+    int64_t N, tiles_per_row, b, t, n0;   // n0: first row of the tile within its batch row
+    // rows of the tile that exist (< TP only in the last tile of a batch row)
+    __device__ __forceinline__ int np() const { return (int)((N - n0 < TP) ? (N - n0) : TP); }
+    __device__ __forceinline__ bool full() const { return N - n0 >= TP; }
+};
+template <int TP>
+__device__ __forceinline__ chx_tile<TP> chx_tile_coords(int64_t N) {
+    const int64_t tiles_per_row = (N + TP - 1) / TP;
+    const int64_t b = blockIdx.x / tiles_per_row;
+    const int64_t t = blockIdx.x - b * tiles_per_row;
+    return {N, tiles_per_row, b, t, t * TP};
+}
+// The vector path of tile_load / tile_store needs the tile start 16-byte aligned: the base (base_ok, checked on the host) and
+// row * N * 7 * sizeof(T) for the tile's batch row (the input's row is 0 for one beam shared by the batch); n0 * 7 * sizeof(T) is
+// a multiple of 16 by construction. A macro, not a function: behind a call the compiler orders and branches the prologue of
+// every kernel that uses it differently (profiles/map7_refactor.md), and this text is what the kernels always held.
+#define CHX_TILE_VEC_OK(T, base_ok, row, N) ((base_ok) && ((((row) * (N) * 7 * (int64_t)sizeof(T)) & 15) == 0))
+
 // ---- column tiles: the in-place element passes of chx_track_elementwise between its first and its last one ---------------
 // A full tile of TP rows (TP * 7 values, the same bytes in every pass) holds its rows transposed, [7][TP] instead of [TP][7].
 // A lane then owns 16 bytes of consecutive rows in each of the seven columns, needs no LDS and no barrier, and a column that a
@@ -323,23 +386,59 @@ template <typename T> struct chx_col16;   // V: 16 bytes of one column, P: two r
 template <> struct chx_col16<float> { using V = chx_v4f; using P = chx_v2f; };
 template <> struct chx_col16<double> { using V = chx_v2d; using P = chx_v2d; };
 
-// y = R x, the fma chain j = 0..6 of apply7 (chx_apply.hip), for one row (X = T) or two rows side by side (X = chx_col16<T>::P)
-template <typename T, typename X>
-__device__ __forceinline__ void chx_map7(const T* __restrict__ R, const X (&x)[7], X (&y)[7]) {
+// ---- THE first-order map step: y = R x with R row-major 7x7. Row i is R_i0 * x_0 first, then six fused multiply-adds j = 1..6,
+// in the storage dtype: the one spelling of that chain in the library, so that every kernel that sends a particle through a map
+// — single pass, fused, element by element, column tiles, lattice stretches, scans, the chains of chx_nonlinear.hip and
+// chx_spacecharge.hip, the moments of chx_moments.hip, the mapped deposits of chx_cic_dev.h — writes the same bits. X = T: one particle; X = chx_v2f with T = float: two
+// particles side by side, every step ONE v_pk_fma_f32 (the map entry a scalar operand); X = double with T = float: float32-rounded
+// maps on fp64 coordinates. R may live in SGPRs (uniform pointer).
+// Row i for NX operands side by side: every map entry is fetched once and used for all of them (LaneRows, kMapByMatrixRow).
+template <typename T, typename X, int NX>
+__device__ __forceinline__ void chx_map7_row(const T* __restrict__ R, int i, const X (&x)[NX][7], X (&y)[NX][7]) {
 #pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        X acc = x[0] * R[i * 7];
+    for (int n = 0; n < NX; ++n) y[n][i] = x[n][0] * R[i * 7];
 #pragma unroll
-        for (int j = 1; j < 7; ++j) acc = __builtin_elementwise_fma((X)R[i * 7 + j], x[j], acc);
-        y[i] = acc;
+    for (int j = 1; j < 7; ++j) {
+        const X m = (X)R[i * 7 + j];
+#pragma unroll
+        for (int n = 0; n < NX; ++n) y[n][i] = __builtin_elementwise_fma(m, x[n][j], y[n][i]);
     }
+}
+// ROWS < 7: only the first rows of the map (the moments take six coordinates)
+template <typename T, typename X, int ROWS = 7>
+__device__ __forceinline__ void chx_map7(const T* __restrict__ R, const X (&x)[7], X (&y)[ROWS]) {
+    X x1[1][7], y1[1][7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) x1[0][j] = x[j];
+#pragma unroll
+    for (int i = 0; i < ROWS; ++i) {
+        chx_map7_row<T, X, 1>(R, i, x1, y1);
+        y[i] = y1[0][i];
+    }
+}
+// one row alone, Rrow = R + 7 i with i a run-time index (the coordinates a deposit takes of a mapped particle, chx_cic_dev.h)
+template <typename T, typename X>
+__device__ __forceinline__ X chx_map7_one_row(const T* __restrict__ Rrow, const X (&x)[7]) {
+    X x1[1][7], y1[1][7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) x1[0][j] = x[j];
+    chx_map7_row<T, X, 1>(Rrow, 0, x1, y1);
+    return y1[0][0];
+}
+// in place
+template <typename T, typename X>
+__device__ __forceinline__ void chx_map7_inplace(const T* __restrict__ R, X (&x)[7]) {
+    X y[7];
+    chx_map7<T, X>(R, x, y);
+#pragma unroll
+    for (int j = 0; j < 7; ++j) x[j] = y[j];
 }
 
 // One column pass over a full column tile at g, TP / (16 / sizeof(T)) lanes per workgroup. Column i goes back only if some lane
 // of the wave holds a result whose bits differ from what it loaded: memory already holds exactly the bits a skipped store would
 // have written, so the tile is bit for bit what storing everything leaves (NaN payloads, infinities and -0.0 included).
 // g is read and written: no __restrict__. NT_LOAD: the beam does not stay in L2 from pass to pass, stream past it.
-// FLAGGED: *flag (one word per tile, written by chx_coltile_enter) says that column 6 of the tile, the affine coordinate, is
+// FLAGGED: *flag (one word per tile, written by chx_coltile_edge, FLAG) says that column 6 of the tile, the affine coordinate, is
 // all (T)1 in memory. The six loads of columns 0..5 leave first, then the flag is read (a uniform address: a scalar load behind
 // the vector loads); where it is set the seventh load, 16 bytes per lane through the L2 queue that bounds the pass, is not
 // issued and x[6] is the constant. The constant goes through an empty asm so that both arms run the same fma chain (no
@@ -403,13 +502,23 @@ __device__ __forceinline__ void chx_rowtile_pass(T* g, const T* __restrict__ R, 
 
 // The pass that enters (TO_COLUMNS) or leaves the column layout, CHX_BLOCK lanes: the tile's bytes go through LDS as in every
 // LDS-staged pass, the lane reads its rows in the layout the tile came in and writes them in the one it leaves in. A tile that is
-// not full is [np][7] on both sides.
-template <typename T, int TP, bool TO_COLUMNS>
-__device__ __forceinline__ void chx_coltile_edge(T* g, const T* __restrict__ R, T* lds, int np, bool vec_ok) {
+// not full is [np][7] on both sides. The library runs it in place (gin == gout, in_vec true, nt_in false: the rows just written
+// come from L2); with gin the input of the call an entering pass is a pass 0 that writes column tiles (in_vec / nt_in as in
+// apply_tile_kernel), which benchmarks/apply_coltile.hip measured and the library does not use (chx_apply_tiles.h).
+// gout must be 16-byte aligned (the column layout exists only on aligned batch rows, chx_coltile_ok): the store always takes the
+// vector path, only the input side has an alignment argument.
+// FLAG (entering only): the pass also says what it left there — *flag is written for the tile, every call, so that the flags need
+// no initialising: 1 iff every value of column 6 the tile now holds has the bits of (T)1. Wave 0 reads that column back from the
+// LDS image behind the last barrier (32 bytes per lane), one lane stores the word. The whole of column 6 goes to memory whatever
+// the flag says. A tile that is not full stays rows, and its flag, which no pass reads, is 0.
+template <typename T, int TP, bool TO_COLUMNS, bool FLAG = false>
+__device__ __forceinline__ void chx_coltile_edge(const T* gin, T* gout, const T* __restrict__ R, T* lds, int np, bool in_vec,
+                                                 bool nt_in, unsigned* flag = nullptr) {
+    static_assert(TO_COLUMNS || !FLAG, "only the entering pass writes a flag");
     constexpr int PPT = TP / CHX_BLOCK;
     const bool full = np == TP;
     const bool in_cols = full && !TO_COLUMNS, out_cols = full && TO_COLUMNS;
-    tile_load<T, TP>(g, lds, np * 7, vec_ok, false);
+    tile_load<T, TP>(gin, lds, np * 7, in_vec, nt_in);
     __syncthreads();
     T y[PPT][7];
 #pragma unroll
@@ -432,60 +541,24 @@ __device__ __forceinline__ void chx_coltile_edge(T* g, const T* __restrict__ R, 
         }
     }
     __syncthreads();
-    tile_store<T, TP>(g, lds, np * 7, vec_ok, true);
-}
-
-// The pass that enters the column layout and says what it left there, CHX_BLOCK lanes: chx_coltile_edge<T, TP, true> with *flag
-// written for the tile, every call, so that the flags need no initialising: 1 iff every value of column 6 the tile now holds has
-// the bits of (T)1. Wave 0 reads that column back from the LDS image behind the last barrier (32 bytes per lane), one lane stores
-// the word. The whole of column 6 goes to memory whatever the flag says. A tile that is not full stays rows, and its flag, which
-// no pass reads, is 0. The library runs it in place (gin == gout: pass 1, the rows just written come from L2); with gin the input
-// of the call it is a pass 0 that writes column tiles (in_vec / nt_in as in apply_tile_kernel), which benchmarks/apply_coltile.hip
-// measured and the library does not use (chx_apply_tiles.h).
-template <typename T, int TP>
-__device__ __forceinline__ void chx_coltile_enter(const T* gin, T* gout, const T* __restrict__ R, T* lds, int np, bool in_vec,
-                                                  bool nt_in, unsigned* flag) {
-    using V = typename chx_col16<T>::V;
-    constexpr int PPT = TP / CHX_BLOCK;
-    const bool full = np == TP;
-    tile_load<T, TP>(gin, lds, np * 7, in_vec, nt_in);
-    __syncthreads();
-    T y[PPT][7];
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        const int p = threadIdx.x + k * CHX_BLOCK;
-        if (p < np) {
-            T x[7];
-#pragma unroll
-            for (int j = 0; j < 7; ++j) x[j] = lds[p * 7 + j];
-            chx_map7<T, T>(R, x, y[k]);
-        }
-    }
-    if (full) __syncthreads();   // the layout changes: every lane has read its rows before another lane's results land on them
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        const int p = threadIdx.x + k * CHX_BLOCK;
-        if (p < np) {
-#pragma unroll
-            for (int j = 0; j < 7; ++j) lds[full ? j * TP + p : p * 7 + j] = y[k][j];
-        }
-    }
-    __syncthreads();
     tile_store<T, TP>(gout, lds, np * 7, true, true);
-    if (threadIdx.x < 64) {
-        bool ones = full;
-        if (full) {
-            constexpr int NV = TP * (int)sizeof(T) / 16 / 64;   // 16-byte pieces of column 6 per lane of one wave
-            const V* c6 = reinterpret_cast<const V*>(lds + 6 * TP);
-            const V one = (V)(T)1;
+    if constexpr (FLAG) {
+        using V = typename chx_col16<T>::V;
+        if (threadIdx.x < 64) {
+            bool ones = full;
+            if (full) {
+                constexpr int NV = TP * (int)sizeof(T) / 16 / 64;   // 16-byte pieces of column 6 per lane of one wave
+                const V* c6 = reinterpret_cast<const V*>(lds + 6 * TP);
+                const V one = (V)(T)1;
 #pragma unroll
-            for (int i = 0; i < NV; ++i) {
-                const chx_v4u d = __builtin_bit_cast(chx_v4u, c6[threadIdx.x + i * 64]) ^ __builtin_bit_cast(chx_v4u, one);
-                ones = ones && (d.x | d.y | d.z | d.w) == 0u;
+                for (int i = 0; i < NV; ++i) {
+                    const chx_v4u d = __builtin_bit_cast(chx_v4u, c6[threadIdx.x + i * 64]) ^ __builtin_bit_cast(chx_v4u, one);
+                    ones = ones && (d.x | d.y | d.z | d.w) == 0u;
+                }
             }
+            const bool all_ones = __all(ones);
+            if (threadIdx.x == 0) *flag = all_ones ? 1u : 0u;
         }
-        const bool all_ones = __all(ones);
-        if (threadIdx.x == 0) *flag = all_ones ? 1u : 0u;
     }
 }
 

@@ -362,21 +362,14 @@ __global__ void transpose_maps_kernel(const T* __restrict__ R, int64_t B, T* __r
 // (bit-identical y), the accumulation in fp64.
 constexpr int kTM = 29;
 
-template <typename T> __device__ __forceinline__ T tm_fma(T a, T b, T c);
-template <> __device__ __forceinline__ float tm_fma<float>(float a, float b, float c) { return fmaf(a, b, c); }
-template <> __device__ __forceinline__ double tm_fma<double>(double a, double b, double c) { return fma(a, b, c); }
-
 template <typename T>
 __device__ __forceinline__ void tm_accumulate(const T (&R)[42], const T (&x)[7], double w, const double (&c)[6],
                                               double (&a)[kTM]) {
+    T y[6];
+    chx_map7<T, T, 6>(R, x, y);
     double d[6];
 #pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        T y = R[i * 7] * x[0];
-#pragma unroll
-        for (int j = 1; j < 7; ++j) y = tm_fma<T>(R[i * 7 + j], x[j], y);
-        d[i] = (double)y - c[i];
-    }
+    for (int i = 0; i < 6; ++i) d[i] = (double)y[i] - c[i];
     a[0] += w;
     a[1] += w * w;
     int k = 8;
@@ -507,17 +500,10 @@ __global__ __launch_bounds__(CHX_BLOCK) void track_moments_rows_f32_kernel(const
 #pragma unroll
                 for (int j = 0; j < 7; ++j) xv[j] = xs[p * 7 + j];
                 const chx_v2f wv = ws[p];
-                chx_v2f d[6];
+                chx_v2f y[6], d[6];
+                chx_map7<float, chx_v2f, 6>(R, xv, y);              // the fma chain of chx_apply_affine7, two particles wide
 #pragma unroll
-                for (int i = 0; i < 6; ++i) {
-                    chx_v2f y = xv[0] * R[i * 7];                  // the fma chain of chx_apply_affine7, two particles wide
-#pragma unroll
-                    for (int j = 1; j < 7; ++j) {
-                        const chx_v2f r = {R[i * 7 + j], R[i * 7 + j]};
-                        y = __builtin_elementwise_fma(r, xv[j], y);
-                    }
-                    d[i] = y - chx_v2f{cf[i], cf[i]};
-                }
+                for (int i = 0; i < 6; ++i) d[i] = y[i] - chx_v2f{cf[i], cf[i]};
                 a[0] = a[0] + wv;
                 a[1] = __builtin_elementwise_fma(wv, wv, a[1]);
                 int k = 8;

@@ -302,14 +302,11 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_kernel(const T* __restrict__ x_
     __shared__ double cst_[C_N + 1];
     __shared__ C cstc_[C_N + 1];
 
-    const int64_t tiles_per_row = (N + TP - 1) / TP;
-    const int64_t b = blockIdx.x / tiles_per_row;
-    const int64_t t = blockIdx.x - b * tiles_per_row;
-    const int64_t n0 = t * TP;
-    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
+    const chx_tile<TP> tc = chx_tile_coords<TP>(N);
+    const int64_t b = tc.b, t = tc.t, n0 = tc.n0;
+    const int np = tc.np();
     const int64_t in_row = (Bx == 1) ? 0 : b;
-    const bool in_vec = in_vec_ok && (((in_row * N * 7 * (int64_t)sizeof(T)) & 15) == 0);
-    const bool out_vec = out_vec_ok && (((b * N * 7 * (int64_t)sizeof(T)) & 15) == 0);
+    const bool in_vec = CHX_TILE_VEC_OK(T, in_vec_ok, in_row, N), out_vec = CHX_TILE_VEC_OK(T, out_vec_ok, b, N);
 
     if (threadIdx.x == 0) {
         const T Eb = energy[(Be == 1) ? 0 : b];
@@ -479,14 +476,11 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_mixed_kernel(const float* __res
     constexpr int TP = CHX_BLOCK;
     __shared__ __attribute__((aligned(16))) float lds[TP * 7];
     __shared__ double cst_[C_MIXED_N];
-    const int64_t tiles_per_row = (N + TP - 1) / TP;
-    const int64_t b = blockIdx.x / tiles_per_row;
-    const int64_t t = blockIdx.x - b * tiles_per_row;
-    const int64_t n0 = t * TP;
-    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
+    const chx_tile<TP> tc = chx_tile_coords<TP>(N);
+    const int64_t b = tc.b, t = tc.t, n0 = tc.n0;
+    const int np = tc.np();
     const int64_t in_row = (Bx == 1) ? 0 : b;
-    const bool in_vec = in_vec_ok && (((in_row * N * 7 * (int64_t)sizeof(float)) & 15) == 0);
-    const bool out_vec = out_vec_ok && (((b * N * 7 * (int64_t)sizeof(float)) & 15) == 0);
+    const bool in_vec = CHX_TILE_VEC_OK(float, in_vec_ok, in_row, N), out_vec = CHX_TILE_VEC_OK(float, out_vec_ok, b, N);
     tile_load<float, TP>(x_in + (in_row * N + n0) * 7, lds, np * 7, in_vec, !(Bx == 1 && B > 1));   // rows first: the constants
     if (threadIdx.x == 0) {                                                                          // are formed under the loads
         const float Eb = energy[(Be == 1) ? 0 : b];
@@ -530,12 +524,10 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_bwd_kernel(const T* __restrict_
     __shared__ Dual cd[C_N + 1];
     __shared__ double red[CHX_BLOCK / 64];
 
-    const int64_t tiles_per_row = (N + TP - 1) / TP;
-    const int64_t b = blockIdx.x / tiles_per_row;
-    const int64_t t = blockIdx.x - b * tiles_per_row;
-    const int64_t n = t * TP + threadIdx.x;
+    const chx_tile<TP> tc = chx_tile_coords<TP>(N);
+    const int64_t b = tc.b, t = tc.t, in_row = (Bx == 1) ? 0 : b;
+    const int64_t n = tc.n0 + threadIdx.x;
     const bool live = n < N;
-    const int64_t in_row = (Bx == 1) ? 0 : b;
     const T Eb = energy[(Be == 1) ? 0 : b];
     const T* par = params + ((Bp == 1) ? 0 : b) * P;
 
@@ -592,7 +584,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_bwd_kernel(const T* __restrict_
             if (threadIdx.x == 0) {
                 double tot = 0.0;
                 for (int w = 0; w < CHX_BLOCK / 64; ++w) tot += red[w];
-                partials[(b * tiles_per_row + t) * (P + 1) + k] = tot;
+                partials[(b * tc.tiles_per_row + t) * (P + 1) + k] = tot;
             }
             __syncthreads();
         }
@@ -848,17 +840,11 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel(const float* x_in,
         const int32_t* w = reinterpret_cast<const int32_t*>(c + kDkdMeta);
         const int kind = w[0], steps = w[1];
         if (kind == kDkdLinear) {
-            // a merged run of linear elements: apply7's arithmetic on all seven coordinates, as chx_apply_affine7 does it
+            // a merged run of linear elements: chx_map7 on all seven coordinates, as chx_apply_affine7 does it
             const float* __restrict__ R = reinterpret_cast<const float*>(c);
             const float x[7] = {v[0], v[1], v[2], v[3], v[4], v[5], v6};
             float y[7];
-#pragma unroll
-            for (int i = 0; i < 7; ++i) {
-                float acc = R[i * 7] * x[0];
-#pragma unroll
-                for (int j = 1; j < 7; ++j) acc = fmaf(R[i * 7 + j], x[j], acc);
-                y[i] = acc;
-            }
+            chx_map7<float, float>(R, x, y);
 #pragma unroll
             for (int j = 0; j < 6; ++j) v[j] = y[j];
             v6 = y[6];
@@ -900,13 +886,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel_f64(const double* 
         if (kind == kDkdLinear) {
             const double x[7] = {v[0], v[1], v[2], v[3], v[4], v[5], v6};
             double y[7];
-#pragma unroll
-            for (int i = 0; i < 7; ++i) {
-                double acc = c[i * 7] * x[0];
-#pragma unroll
-                for (int j = 1; j < 7; ++j) acc = fma(c[i * 7 + j], x[j], acc);
-                y[i] = acc;
-            }
+            chx_map7<double, double>(c, x, y);
 #pragma unroll
             for (int j = 0; j < 6; ++j) v[j] = y[j];
             v6 = y[6];
@@ -1236,22 +1216,13 @@ __device__ __forceinline__ void so_step_pattern(const float* __restrict__ U, chx
     so_eval_pattern<P>(u, x, probe);
 }
 
-// a first-order map between two second-order elements: apply7's order (R_i0 x_0, then six multiply-adds), both particles of
+// a first-order map between two second-order elements: chx_map7 (R_i0 x_0, then six multiply-adds), both particles of
 // the lane at once — the values chx_apply_affine7 writes
 __device__ __forceinline__ void so_step_linear(const float* __restrict__ U, chx_v2f (&x)[7]) {
     float r[49];
 #pragma unroll
     for (int k = 0; k < 49; ++k) r[k] = U[kSoPacked + k];
-    chx_v2f y[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        chx_v2f acc = x[0] * r[i * 7];
-#pragma unroll
-        for (int j = 1; j < 7; ++j) acc = __builtin_elementwise_fma(chx_v2f{r[i * 7 + j], r[i * 7 + j]}, x[j], acc);
-        y[i] = acc;
-    }
-#pragma unroll
-    for (int j = 0; j < 7; ++j) x[j] = y[j];
+    chx_map7_inplace<float, chx_v2f>(r, x);
 }
 
 __device__ __forceinline__ void so_step_groups(const float* __restrict__ U, chx_v2f (&x)[7], chx_v2f probe) {
@@ -1366,18 +1337,7 @@ __device__ __forceinline__ void so_step_groups_f64(const double* __restrict__ U,
     for (int j = 0; j < 7; ++j) x[j] = y[j];
 }
 
-__device__ __forceinline__ void so_step_linear_f64(const double* __restrict__ U, double (&x)[7]) {
-    double y[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        double acc = U[kSoPacked + i * 7] * x[0];
-#pragma unroll
-        for (int j = 1; j < 7; ++j) acc = fma(U[kSoPacked + i * 7 + j], x[j], acc);
-        y[i] = acc;
-    }
-#pragma unroll
-    for (int j = 0; j < 7; ++j) x[j] = y[j];
-}
+__device__ __forceinline__ void so_step_linear_f64(const double* __restrict__ U, double (&x)[7]) { chx_map7_inplace<double, double>(U + kSoPacked, x); }
 
 __global__ __launch_bounds__(CHX_BLOCK) void so_chain_kernel_f64(const double* x_in, const double* __restrict__ coef, int E, double* x_out,
                                                                  int64_t N, int in_vec_ok, int out_vec_ok) {
@@ -1581,14 +1541,11 @@ __global__ __launch_bounds__(CHX_BLOCK) void second_order_kernel(const T* __rest
     __shared__ __attribute__((aligned(16))) T lds[TP * 7];
     __shared__ T U[7 * 28];  // arithmetic in the storage dtype, like the reference's einsum
 
-    const int64_t tiles_per_row = (N + TP - 1) / TP;
-    const int64_t b = blockIdx.x / tiles_per_row;
-    const int64_t t = blockIdx.x - b * tiles_per_row;
-    const int64_t n0 = t * TP;
-    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
+    const chx_tile<TP> tc = chx_tile_coords<TP>(N);
+    const int64_t b = tc.b, n0 = tc.n0;
+    const int np = tc.np();
     const int64_t in_row = (Bx == 1) ? 0 : b;
-    const bool in_vec = in_vec_ok && (((in_row * N * 7 * (int64_t)sizeof(T)) & 15) == 0);
-    const bool out_vec = out_vec_ok && (((b * N * 7 * (int64_t)sizeof(T)) & 15) == 0);
+    const bool in_vec = CHX_TILE_VEC_OK(T, in_vec_ok, in_row, N), out_vec = CHX_TILE_VEC_OK(T, out_vec_ok, b, N);
 
     if (threadIdx.x < 7 * 28) {
         const int i = threadIdx.x / 28;
@@ -1646,14 +1603,11 @@ void second_order_pk_kernel(const float* __restrict__ x_in, const float* __restr
     constexpr int TP = 2 * CHX_BLOCK;
     __shared__ __attribute__((aligned(16))) float lds[TP * 7];
     __shared__ __attribute__((aligned(16))) float U[7 * 28];   // rows of 28 = seven 16-byte groups: read as ds_read_b128
-    const int64_t tiles_per_row = (N + TP - 1) / TP;
-    const int64_t b = blockIdx.x / tiles_per_row;
-    const int64_t t = blockIdx.x - b * tiles_per_row;
-    const int64_t n0 = t * TP;
-    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
+    const chx_tile<TP> tc = chx_tile_coords<TP>(N);
+    const int64_t b = tc.b, n0 = tc.n0;
+    const int np = tc.np();
     const int64_t in_row = (Bx == 1) ? 0 : b;
-    const bool in_vec = in_vec_ok && (((in_row * N * 7 * (int64_t)sizeof(float)) & 15) == 0);
-    const bool out_vec = out_vec_ok && (((b * N * 7 * (int64_t)sizeof(float)) & 15) == 0);
+    const bool in_vec = CHX_TILE_VEC_OK(float, in_vec_ok, in_row, N), out_vec = CHX_TILE_VEC_OK(float, out_vec_ok, b, N);
     tile_load<float, TP>(x_in + (in_row * N + n0) * 7, lds, np * 7, in_vec, !(Bx == 1 && B > 1));
     if (threadIdx.x < 7 * 28) {
         // U[i][(j,k)], j <= k: T_ijk + T_ikj folded (element.py:207-217 sums over all j, k)

@@ -302,18 +302,7 @@ __device__ __forceinline__ void sc_kick_row32(const ScKickCtx32& c, const float 
 }
 
 // the linear run behind a kick on the kicked row, the fma chain of chx_apply_affine7 (bit-identical to a second pass)
-__device__ __forceinline__ void sc_post_map32(const float* __restrict__ R, float (&x)[7]) {
-    float y[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        float acc = R[i * 7] * x[0];
-#pragma unroll
-        for (int j = 1; j < 7; ++j) acc = fmaf(R[i * 7 + j], x[j], acc);
-        y[i] = acc;
-    }
-#pragma unroll
-    for (int i = 0; i < 7; ++i) x[i] = y[i];
-}
+__device__ __forceinline__ void sc_post_map32(const float* __restrict__ R, float (&x)[7]) { chx_map7_inplace<float, float>(R, x); }
 
 // CHX_SC_GATHER_FP64=1: float32 beams take the float64 particle step of rounds 1-5 again (A/B runs, bisecting)
 static bool sc_gather_fp64() {
@@ -499,13 +488,9 @@ __global__ __launch_bounds__(CHX_BLOCK) void sc_particle_kernel(
                     T xk[7];
 #pragma unroll
                     for (int j = 0; j < 7; ++j) xk[j] = (T)v[j];
+                    chx_map7_inplace<T, T>(R, xk);
 #pragma unroll
-                    for (int i = 0; i < 7; ++i) {
-                        T acc = R[i * 7] * xk[0];
-#pragma unroll
-                        for (int j = 1; j < 7; ++j) acc = fma(R[i * 7 + j], xk[j], acc);
-                        lds[p * 7 + i] = acc;
-                    }
+                    for (int j = 0; j < 7; ++j) lds[p * 7 + j] = xk[j];
                 } else {
 #pragma unroll
                     for (int j = 0; j < 7; ++j) lds[p * 7 + j] = (T)v[j];
@@ -991,13 +976,7 @@ __device__ __forceinline__ void sc_kick_finish(const ScKickCtx<T>& c, double (&s
         T xk[7];
 #pragma unroll
         for (int j = 0; j < 7; ++j) xk[j] = (T)v[j];
-#pragma unroll
-        for (int i = 0; i < 7; ++i) {
-            T acc = c.post_map[i * 7] * xk[0];
-#pragma unroll
-            for (int j = 1; j < 7; ++j) acc = fma(c.post_map[i * 7 + j], xk[j], acc);
-            out[i] = acc;
-        }
+        chx_map7<T, T>(c.post_map, xk, out);
     } else {
 #pragma unroll
         for (int j = 0; j < 7; ++j) out[j] = (T)v[j];
