@@ -30,6 +30,7 @@ from .accelerator import (  # noqa: F401
     Solenoid,
     SpaceChargeKick,
     Superimposed,
+    SynchrotronRadiationKick,
     Undulator,
     VerticalCorrector,
     Wakefield,

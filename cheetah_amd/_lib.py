@@ -29,6 +29,7 @@ c_i32_p = ctypes.POINTER(ctypes.c_int32)
 c_u8_p = ctypes.POINTER(ctypes.c_uint8)
 c_vpp = ctypes.POINTER(ctypes.c_void_p)
 c_double_p = ctypes.POINTER(ctypes.c_double)
+c_u32, c_u64 = ctypes.c_uint32, ctypes.c_uint64
 
 
 class ChxError(RuntimeError):
@@ -302,6 +303,13 @@ SIGNATURES = {
                              c_void_p]),
     "chx_lsc_kick_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, ctypes.c_int32, c_int, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "chx_sr_workspace_bytes": (c_size_t, [c_i64, c_i64]),
+    "chx_sr_kick": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_int, c_u32, c_u32, c_void_p, c_i64, c_i64,
+                            c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_void_p]),
+    "chx_sr_kick_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_int, c_u32, c_u32, c_void_p, c_i64,
+                                c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_size_t, c_void_p]),
+    "chx_sr_normals": (c_int, [c_u32, c_u32, c_u64, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
     "chx_run_vjp_workspace_bytes": (c_size_t, [c_i64]),
     "chx_run_vjp": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_size_t, c_void_p]),

@@ -13,4 +13,5 @@ from .screen import Screen  # noqa: F401
 from .segment import Segment  # noqa: F401
 from .space_charge_kick import SpaceChargeKick  # noqa: F401
 from .superimposed import Superimposed  # noqa: F401
+from .synchrotron_radiation import SynchrotronRadiationKick  # noqa: F401
 from .wakefield import Wakefield  # noqa: F401

@@ -99,6 +99,18 @@ class Dipole(Element):
         if not bool((self.angle != 0).any()):
             return [self]
         fk = {"device": self.angle.device, "dtype": self.angle.dtype}
+        parts = []
+        for i, piece in enumerate(self._arc_pieces(n, "csr")):
+            parts.append(piece)
+            kk = {"num_bins": num_bins, "name": f"{self.name}_csr_kick_{i}", "sanitize_name": False, **fk}
+            parts.append(TransientCSRKick(piece.length, piece.angle, (i + 0.5) * piece.length, **kk) if transient
+                         else CSRKick(piece.length, piece.angle, **kk))
+        return parts
+
+    def _arc_pieces(self, n: int, tag: str) -> list["Dipole"]:
+        """The bend as n Dipoles of L / n and theta / n named `{name}_{tag}_{i}`, which share one length and one angle tensor: only the
+        first keeps the entrance face and only the last the exit face (see `split_for_csr`)."""
+        fk = {"device": self.angle.device, "dtype": self.angle.dtype}
         length, angle = self.length / n, self.angle / n
         entrance, exit_ = self.fringe_at in ("both", "entrance"), self.fringe_at in ("both", "exit")
         parts = []
@@ -112,9 +124,31 @@ class Dipole(Element):
                 fringe_integral=self.fringe_integral if first else torch.zeros_like(self.fringe_integral),
                 fringe_integral_exit=self.fringe_integral_exit if last else torch.zeros_like(self.fringe_integral_exit),
                 fringe_at=fringe_at, fringe_type=self.fringe_type, tracking_method=self.tracking_method,
-                name=f"{self.name}_csr_{i}", sanitize_name=False, **fk))
-            kk = {"num_bins": num_bins, "name": f"{self.name}_csr_kick_{i}", "sanitize_name": False, **fk}
-            parts.append(TransientCSRKick(length, angle, (i + 0.5) * length, **kk) if transient else CSRKick(length, angle, **kk))
+                name=f"{self.name}_{tag}_{i}", sanitize_name=False, **fk))
+        return parts
+
+    def split_for_radiation(self, num_kicks: int, quantum_excitation: bool = True, seed: int = 0,
+                            first_stream: int = 0) -> list[Element]:
+        """The bend as `num_kicks` x [Dipole of L / n and theta / n, SynchrotronRadiationKick(L / n, theta / n, quantum_excitation,
+        seed, stream=first_stream + i)]: the incoherent radiation spread along the arc, every kick with a stream of its own. The
+        pieces are `split_for_csr`'s (faces, k1, tilt, gaps, fringe_type and tracking_method likewise), named `{name}_sr_{i}` with
+        the kicks `{name}_sr_kick_{i}`. A bend of zero angle is returned unchanged, as [self]."""
+        from ._binned_kick import check_num_kicks
+        from .synchrotron_radiation import SynchrotronRadiationKick, check_key_word
+
+        owner = "Dipole.split_for_radiation"
+        n = check_num_kicks(num_kicks, owner)
+        seed = check_key_word(seed, "seed", owner)
+        first_stream = check_key_word(first_stream, "first_stream", owner)
+        check_key_word(first_stream + n - 1, "first_stream + num_kicks - 1", owner)
+        if not bool((self.angle != 0).any()):
+            return [self]
+        fk = {"device": self.angle.device, "dtype": self.angle.dtype}
+        parts = []
+        for i, piece in enumerate(self._arc_pieces(n, "sr")):
+            parts.append(piece)
+            parts.append(SynchrotronRadiationKick(piece.length, piece.angle, quantum_excitation=quantum_excitation, seed=seed,
+                                                  stream=first_stream + i, name=f"{self.name}_sr_kick_{i}", sanitize_name=False, **fk))
         return parts
 
     @property

@@ -1884,6 +1884,36 @@ class Segment(Element):
                 elements.append(e)
         return self.__class__(elements=elements, name=self.name, metadata=deepcopy(self.metadata))
 
+    def with_radiation_kicks(self, num_kicks: int = 1, quantum_excitation: bool = True, seed: int = 0, except_for=None) -> "Segment":
+        """Every bending Dipole (and RBend) split by `Dipole.split_for_radiation(num_kicks, quantum_excitation, seed, first_stream)`
+        into pieces with incoherent synchrotron-radiation kicks between them, nested Segments included; other elements, bends of zero
+        angle and names in `except_for` unchanged. The kicks' `stream` counts 0, 1, 2, ... in lattice order, so no two kicks of the
+        lattice draw the same deviates. Applied with `num_kicks=1` to the result of `with_csr_kicks` it puts one radiation kick behind
+        every CSR piece."""
+        from ._binned_kick import check_num_kicks
+        from .synchrotron_radiation import check_key_word
+
+        check_num_kicks(num_kicks, "Segment.with_radiation_kicks")
+        check_key_word(seed, "seed", "Segment.with_radiation_kicks")
+        return self._with_radiation_kicks(num_kicks, quantum_excitation, seed, except_for or [], 0)[0]
+
+    def _with_radiation_kicks(self, num_kicks, quantum_excitation, seed, except_for, stream):
+        """(the segment with the kicks, the first stream not used yet)"""
+        from .dipole import Dipole
+
+        elements = []
+        for e in self.elements:
+            if isinstance(e, Segment):
+                e, stream = e._with_radiation_kicks(num_kicks, quantum_excitation, seed, except_for, stream)
+                elements.append(e)
+            elif isinstance(e, Dipole) and e.name not in except_for:
+                parts = e.split_for_radiation(num_kicks, quantum_excitation, seed, stream)
+                stream += len(parts) // 2
+                elements += parts
+            else:
+                elements.append(e)
+        return self.__class__(elements=elements, name=self.name, metadata=deepcopy(self.metadata)), stream
+
     def with_lsc_kicks(self, num_bins: int = 200, beam_radius=None, radius_factor: float = 1.7, max_step=None,
                        except_for=None) -> "Segment":
         """Every element with a `length` that is anywhere > 0 followed by an `LSCKick(element.length, beam_radius, radius_factor,

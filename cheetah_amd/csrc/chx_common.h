@@ -14,6 +14,11 @@
     } while (0)
 
 static inline bool chx_bcast_ok(int64_t b, int64_t B) { return b == 1 || b == B; }
+// f(T{}) with T = float or double as the dtype says: f is a generic lambda that casts the entry point's pointers to T.
+template <typename F>
+int dispatch_dtype(int dtype, F&& f) {
+    return dtype == CHX_F32 ? f(float{}) : f(double{});
+}
 static __host__ __device__ inline bool chx_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // 16-byte vector type per element type: float -> 4 lanes, double -> 2 lanes.

@@ -48,12 +48,6 @@ Grid1dWs grid1d_ws(void* base, int64_t B, int64_t N, int M, int channels, size_t
     return w;
 }
 
-// f(T{}) with T = float or double as the dtype says: f is a generic lambda that casts the entry point's pointers to T.
-template <typename F>
-int dispatch_dtype(int dtype, F&& f) {
-    return dtype == CHX_F32 ? f(float{}) : f(double{});
-}
-
 // Dynamic LDS above 64 KiB (M > ~2700 nodes) must be requested per kernel (gfx950: 160 KiB per workgroup).
 template <typename K>
 bool lds_ok(K kern, size_t bytes) {

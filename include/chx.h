@@ -411,6 +411,36 @@ int chx_lsc_kick(const void* x, const void* q, const void* w, const void* energy
 int chx_lsc_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M,
                      int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale, double* d_rho,
                      void* workspace, size_t workspace_bytes, void* stream);
+/* ---- incoherent synchrotron radiation (SynchrotronRadiationKick element): the classical energy loss and the quantum excitation
+ * (Gaussian approximation) of an arc of length L and bend angle theta, as one zero-length kick. Per batch row b, in fp64, with gamma0 =
+ * energy / mass_eV, P0 = beta0 gamma0 (beta0 as `Beam.p0c`), r_c = abs_charge^2 r_e m_e / m, lambda_c = hbar c / mc^2:
+ *   a = (2/3) r_c theta^2 / L,   b = 55 / (24 sqrt 3) r_c lambda_c |theta|^3 / L^2   (both 0 where L = 0 or theta = 0, NaN for L < 0)
+ * and per particle n, in fp64 whatever the dtype, rounded once on the store:
+ *   g = gamma0 + delta P0, pi = sqrt(g^2 - 1), g' = g - a P0^2 pi g - sqrt(b P0^3 g^7 / pi^3) xi,
+ *   delta' = delta + (g' - g) / P0, px' = px pi' / pi, py' = py pi' / pi with pi' = sqrt(g'^2 - 1).
+ * x, y, tau and the seventh column keep their bits; a row with a = b = 0 keeps every bit. A particle with a non-finite delta, px or
+ * py, or with g' <= 1, gets NaN in delta', px', py'. quantum_excitation = 0: the xi term is absent and nothing is drawn.
+ * xi = sqrt(-2 ln u1) cospi(2 u2), u1 = (((w0 2^32 + w1) >> 11) + 1/2) 2^-53, u2 likewise from (w2, w3), with (w0 .. w3) =
+ * Philox4x32-10(counter = (n, b, call_lo, call_hi), key = (seed, rng_stream)), the standard multipliers and Weyl constants: xi of
+ * particle n does not depend on N, the launch geometry or the dtype. call_index: ONE int64 in device memory, read by the kernel (a
+ * captured graph follows it); the caller advances it. energy[Be], length[Bl], angle[Ba]: device arrays of the beam's dtype, each 1 or
+ * B rows. x[Bx][N][7], out[B][N][7] (16-byte aligned). 1 <= B <= 65535, 1 <= N < 2^32, mass_eV > 0. Deterministic.
+ * chx_sr_kick_bwd: the same arguments and d_out[B][N][7] (dtype) -> dX[B][N][7] and the per-row cotangents d_gamma[B], d_a[B], d_b[B]
+ * (fp64) of (gamma0, a, b), P0 = sqrt(gamma0^2 - 1) folded into gamma0's: the caller chains them to energy, L and theta. xi is drawn
+ * again from the same counter. The rows' sums are formed in a fixed order (per-workgroup partials in the workspace, then one
+ * workgroup per row): bitwise reproducible, no float atomics. Rows of a broadcast x are NOT reduced — the caller sums. A particle
+ * whose output is NaN has zero gradient. workspace: chx_sr_workspace_bytes(B, N) (0 for a shape out of range).
+ * chx_sr_normals: the draw itself, words_out[B][N][4] (uint32, 16-byte aligned) and xi_out[B][N] (fp64), `call` by value. */
+size_t chx_sr_workspace_bytes(int64_t B, int64_t N);
+int chx_sr_kick(const void* x, const void* energy, const void* length, const void* angle, double mass_eV, double abs_charge,
+                int quantum_excitation, uint32_t seed, uint32_t rng_stream, const int64_t* call_index, int64_t B, int64_t Bx,
+                int64_t Be, int64_t Bl, int64_t Ba, int64_t N, int dtype, void* out, void* stream);
+int chx_sr_kick_bwd(const void* x, const void* energy, const void* length, const void* angle, double mass_eV, double abs_charge,
+                    int quantum_excitation, uint32_t seed, uint32_t rng_stream, const int64_t* call_index, int64_t B, int64_t Bx,
+                    int64_t Be, int64_t Bl, int64_t Ba, int64_t N, int dtype, const void* d_out, void* dX, double* d_gamma,
+                    double* d_a, double* d_b, void* workspace, size_t workspace_bytes, void* stream);
+int chx_sr_normals(uint32_t seed, uint32_t rng_stream, uint64_t call, int64_t B, int64_t N, uint32_t* words_out, double* xi_out,
+                   void* stream);
 /* Backward of chx_moments(y), y_n = R x_n, with respect to the MAP R[BR][7][7] (dtype) when the particles x carry no
  * gradient: mu' = A mu + b, cov' = A C A^T (element.py:180-191 + utils/statistics.py:4-62), so
  * dR[B][7][7] (double) = [2 G A C + g_mu mu^T | g_mu; 0] from d_out[B][29] and the INCOMING beam's chx_moments
