@@ -11,6 +11,7 @@ from .accelerator import (  # noqa: F401
     Aperture,
     Cavity,
     CombinedCorrector,
+    CSRDriftKick,
     CSRKick,
     CustomTransferMap,
     Dipole,

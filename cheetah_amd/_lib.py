@@ -297,6 +297,13 @@ SIGNATURES = {
                                        c_void_p, c_void_p, c_size_t, c_void_p]),
     "chx_csr_transient_kick_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, ctypes.c_int32, c_int,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "chx_csr_drift_workspace_bytes": (c_size_t, [c_i64, c_i64, ctypes.c_int32]),
+    "chx_csr_drift_kick": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double,
+                                   c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, ctypes.c_int32, c_int,
+                                   c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "chx_csr_drift_kick_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64, ctypes.c_int32, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_size_t, c_void_p]),
     "chx_lsc_workspace_bytes": (c_size_t, [c_i64, c_i64, ctypes.c_int32]),
     "chx_lsc_kick": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_i64, c_i64, c_i64,
                              c_i64, c_i64, c_i64, c_i64, c_i64, ctypes.c_int32, c_int, c_void_p, c_void_p, c_void_p, c_size_t,

@@ -1,7 +1,8 @@
 """The kicks of `cheetah_amd._ops` that bin the surviving particles' charge on M nodes in tau and kick every particle with what a sum
 over the nodes gives at its node coordinate: the short-range wake (Wakefield: causal convolution with the sampled wake, kicks to
 delta, px, py), the steady-state CSR (CSRKick: the anti-causal Toeplitz sum with the exactly integrated (z - z')^(-1/3) kernel), its
-entrance transient (TransientCSRKick: the same sum with the table of the slippage length reached inside the bend) and the
+entrance transient (TransientCSRKick: the same sum with the table of the slippage length reached inside the bend), the CSR in the
+drift behind a bend (CSRDriftKick: the same sum with the table of the radiation that left the bend and catches up) and the
 longitudinal space charge (LSCKick: the two-sided Toeplitz sum with the on-axis field of a charged disc). Each is one
 `chx_*_kick` call (four launches, deterministic, no host synchronisation) and an autograd node whose backward is `chx_*_kick_bwd`.
 The CSR and LSC kicks form their per-row factors on the device from the energy and their further settings (length, angle, radius,
@@ -19,7 +20,7 @@ from . import _lib
 from ._ops import MAX_GRID_ROWS, aligned, bshapes, check, dtype_code, flat_bcast, numel, ptr, require_device, stream_ptr, workspace
 
 __all__ = ["WAKE_MAX_BINS", "CSR_MAX_BINS", "LSC_MAX_BINS", "WakeKick", "wake_kick", "wake_scale", "csr_kick", "csr_scale", "csr_transient_kick",
-           "csr_transient_x", "lsc_kick", "lsc_scale_rho"]
+           "csr_transient_x", "csr_drift_kick", "csr_drift_factors", "lsc_kick", "lsc_scale_rho"]
 
 #: CHX_WAKE_MAX_BINS of include/chx.h: the deposit's per-workgroup LDS histograms hold up to 3 channels of M 64-bit nodes; one grid
 #: and one deposit for the three kicks
@@ -234,11 +235,32 @@ def csr_transient_x(length: torch.Tensor, angle: torch.Tensor, distance: torch.T
     return torch.where(kicks, x, torch.zeros_like(x))
 
 
+def csr_drift_factors(energy: torch.Tensor, mass_eV: float, abs_charge_number: float, length: torch.Tensor, bend_length: torch.Tensor,
+                      bend_angle: torch.Tensor, distance: torch.Tensor, h: torch.Tensor):
+    """(scale, xh, phi, kappa) = (|Z| L / p0c, x |theta| / L_b, |theta|, 24 h |theta| / L_b) in float64 (p0c as `Beam.p0c`), broadcast
+    of the shapes: the scale and the three shape numbers of the CSR wake a distance x behind a bend of length L_b and angle theta,
+    which the kernels form on the device, restated here for the chain rule of the backward pass. `h` is the node spacing of the
+    forward's state header, a constant. Where L, L_b or theta is 0 or the row has no grid (h = 0) there is no kick: all four are 0
+    with zero gradients."""
+    L, Lb, th, d = (t.to(torch.float64) for t in (length, bend_length, bend_angle, distance))
+    kicks = (L != 0) & (Lb != 0) & (th != 0) & (h > 0)
+    one = torch.ones((), dtype=torch.float64, device=h.device)
+    Ls, Lbs, hs = torch.where(kicks, L, one), torch.where(kicks, Lb, one), torch.where(kicks, h, one)
+    phi = th.abs()
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=h.device)
+    valid = (Ls > 0) & (Lbs > 0) & (d >= 0)
+    zero = torch.zeros((), dtype=torch.float64, device=h.device)
+    factors = (abs_charge_number * Ls / _p0c(energy, mass_eV), d * phi / Lbs, phi, 24 * hs * phi / Lbs)
+    return tuple(torch.where(kicks, torch.where(valid, f, nan), zero) for f in factors)
+
+
 _CSR = _kick("CSRKick", "csr", (8, 1), 1,                                           # CHX_CSR_STATE_DOUBLES
              lambda state, mass_eV, abs_z, e, L, a: (csr_scale(e, mass_eV, abs_z, L, a),))
 _CSR_TRANSIENT = _kick("TransientCSRKick", "csr_transient", (8 + 2, 2), 2,          # CHX_CSR_TRANSIENT_STATE_DOUBLES
                        lambda state, mass_eV, abs_z, e, L, a, d: (csr_scale(e, mass_eV, abs_z, L, a),
                                                                   csr_transient_x(L, a, d, state[:, 2])))
+_CSR_DRIFT = _kick("CSRDriftKick", "csr_drift", (8 + 4, 2), 4,                         # CHX_CSR_DRIFT_STATE_DOUBLES
+                   lambda state, mass_eV, abs_z, e, L, Lb, a, d: csr_drift_factors(e, mass_eV, abs_z, L, Lb, a, d, state[:, 2]))
 _LSC = _kick("LSCKick", "lsc", (8 + 2, 2), 2,                                       # CHX_LSC_STATE_DOUBLES
              lambda state, mass_eV, abs_z, e, L, a: lsc_scale_rho(e, mass_eV, abs_z, L, a, state[:, 2]))
 
@@ -248,7 +270,7 @@ def _settings_args(settings, mass_eV: float, abs_z: float):
 
 
 class _SettingsKick(torch.autograd.Function):
-    """out (B, N, 7) = chx_{csr,csr_transient,lsc}_kick(x, q, w, *settings): the energy e, the length L and the kick's further
+    """out (B, N, 7) = chx_{csr,csr_transient,csr_drift,lsc}_kick(x, q, w, *settings): the energy e, the length L and the kick's further
     settings (angle, radius, distance), each (1,) or (B,) in the beam dtype; backward = the kick's _bwd call: gradients of the
     particles, the charges and survival probabilities (through c = |q| w), and of the settings through the per-row cotangents of the
     kick's factors. The node grid (tau range) is a constant."""
@@ -312,6 +334,18 @@ def csr_transient_kick(particles: torch.Tensor, charges: torch.Tensor, survival:
     and distance."""
     return _settings_kick(_CSR_TRANSIENT, particles, charges, survival, mass_eV, abs_charge_number,
                           (energy, length, angle, distance), num_bins)
+
+
+def csr_drift_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Tensor, energy: torch.Tensor, mass_eV: float,
+                   abs_charge_number: float, length: torch.Tensor, bend_length: torch.Tensor, bend_angle: torch.Tensor,
+                   distance: torch.Tensor, num_bins: int) -> torch.Tensor:
+    """The CSR kick of a piece of drift of length `length` at the distance `distance` behind the exit face of a bend of arc length
+    `bend_length` and angle `bend_angle` (the radiation emitted inside that bend catching up with the bunch), on a beam of any batch
+    shape (broadcast of the particles', charges', survival probabilities', energy's and the four settings' batch shapes) ->
+    particles (*batch, N, 7). Differentiable with respect to the particles, charges, survival probabilities, energy and the four
+    settings."""
+    return _settings_kick(_CSR_DRIFT, particles, charges, survival, mass_eV, abs_charge_number,
+                          (energy, length, bend_length, bend_angle, distance), num_bins)
 
 
 def lsc_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Tensor, energy: torch.Tensor, mass_eV: float,

@@ -1,5 +1,5 @@
 from .cavity import Cavity  # noqa: F401
-from .csr import CSRKick, TransientCSRKick  # noqa: F401
+from .csr import CSRDriftKick, CSRKick, TransientCSRKick  # noqa: F401
 from .correctors import CombinedCorrector, HorizontalCorrector, VerticalCorrector  # noqa: F401
 from .custom_transfer_map import CustomTransferMap  # noqa: F401
 from .dipole import Dipole, RBend  # noqa: F401

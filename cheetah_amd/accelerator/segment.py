@@ -26,6 +26,7 @@ are applied back to back by `chx_track_elementwise` / `chx_track_fused` from a s
 from __future__ import annotations
 
 import ctypes
+import numbers
 import os
 import weakref
 from copy import deepcopy
@@ -1864,25 +1865,71 @@ class Segment(Element):
         merged_elements.append(current)
         return self.__class__(elements=merged_elements, name=self.name, metadata=deepcopy(self.metadata))
 
-    def with_csr_kicks(self, num_kicks: int, num_bins: int = 200, except_for=None, transient: bool = False) -> "Segment":
+    def with_csr_kicks(self, num_kicks: int, num_bins: int = 200, except_for=None, transient: bool = False, drift_kicks: int = 0,
+                       max_distance=None) -> "Segment":
         """Every bending Dipole (and RBend) split by `Dipole.split_for_csr(num_kicks, num_bins, transient)` into pieces with
         steady-state CSR kicks between them (with `transient`: kicks with the entrance transient, every bend taken to follow a long
-        straight), nested Segments included; other elements, bends of zero angle and names in `except_for` unchanged."""
-        from ._binned_kick import check_num_bins, check_num_kicks
-        from .dipole import Dipole
+        straight), nested Segments included; other elements, bends of zero angle and names in `except_for` unchanged.
 
-        check_num_kicks(num_kicks, "Segment.with_csr_kicks")
-        check_num_bins(num_bins, "Segment.with_csr_kicks")
-        except_for = except_for or []
+        With `drift_kicks` = n >= 1 the elements behind a split bend, in lattice order and through nested Segments, get
+        `CSRDriftKick`s of that bend (its `length` and `angle` tensors) until the next bending Dipole or the end of the lattice: a
+        `Drift` of length L > 0 becomes n x [Drift(L / n), CSRDriftKick(L / n, bend L, bend theta, x0 + (i + 1/2) L / n)] named
+        `{drift}_csr_drift_{i}` and `{drift}_csr_drift_kick_{i}`, x0 the distance from the bend's exit face to the drift; any other
+        element with a length > 0 is kept whole and followed by one kick for its length at its mid-distance
+        (`{element}_csr_drift_kick`); elements of zero length pass unchanged. A bend in `except_for` ends the run without kicks, and
+        so does an element that starts beyond `max_distance` (metres, compared on the largest batch entry)."""
+        from ._binned_kick import check_num_bins, check_num_kicks
+
+        owner = "Segment.with_csr_kicks"
+        check_num_kicks(num_kicks, owner)
+        check_num_bins(num_bins, owner)
+        if isinstance(drift_kicks, bool) or not isinstance(drift_kicks, numbers.Integral) or int(drift_kicks) < 0:
+            raise ValueError(f"{owner}: drift_kicks must be an integer >= 0, got {drift_kicks!r}")
+        if max_distance is not None and not float(max_distance) >= 0.0:
+            raise ValueError(f"{owner}: max_distance must be a length >= 0 (metres), got {max_distance!r}")
+        limit = None if max_distance is None else float(max_distance)
+        return self._with_csr_kicks(num_kicks, num_bins, except_for or [], transient, int(drift_kicks), limit, None)[0]
+
+    def _with_csr_kicks(self, num_kicks, num_bins, except_for, transient, drift_kicks, max_distance, behind):
+        """(the segment with the kicks, the state of the drift kicks behind it). `behind`: None, or (length, angle, distance) of the
+        last split bend: its two tensors and the distance travelled since its exit face."""
+        from .csr import CSRDriftKick
+        from .dipole import Dipole
+        from .drift import Drift
+
         elements = []
         for e in self.elements:
             if isinstance(e, Segment):
-                elements.append(e.with_csr_kicks(num_kicks, num_bins, except_for, transient))
-            elif isinstance(e, Dipole) and e.name not in except_for:
-                elements += e.split_for_csr(num_kicks, num_bins, transient)
-            else:
+                e, behind = e._with_csr_kicks(num_kicks, num_bins, except_for, transient, drift_kicks, max_distance, behind)
                 elements.append(e)
-        return self.__class__(elements=elements, name=self.name, metadata=deepcopy(self.metadata))
+                continue
+            if isinstance(e, Dipole) and e.is_active:
+                if e.name in except_for:
+                    elements.append(e)
+                    behind = None
+                else:
+                    elements += e.split_for_csr(num_kicks, num_bins, transient)
+                    behind = (e.length, e.angle, torch.zeros_like(e.length)) if drift_kicks else None
+                continue
+            if behind is not None and max_distance is not None and float(behind[2].detach().max()) > max_distance:
+                behind = None
+            if behind is None or not bool((e.length > 0).any()):
+                elements.append(e)
+                continue
+            bend_length, bend_angle, x0 = behind
+            kk = {"num_bins": num_bins, "sanitize_name": False, "device": e.length.device, "dtype": e.length.dtype}
+            if isinstance(e, Drift):
+                piece = e.length / drift_kicks
+                for i in range(drift_kicks):
+                    elements.append(Drift(piece, tracking_method=e.tracking_method, name=f"{e.name}_csr_drift_{i}", sanitize_name=False,
+                                          device=e.length.device, dtype=e.length.dtype))
+                    elements.append(CSRDriftKick(piece, bend_length, bend_angle, x0 + (i + 0.5) * piece,
+                                                 name=f"{e.name}_csr_drift_kick_{i}", **kk))
+            else:
+                elements += [e, CSRDriftKick(e.length, bend_length, bend_angle, x0 + 0.5 * e.length,
+                                             name=f"{e.name}_csr_drift_kick", **kk)]
+            behind = (bend_length, bend_angle, x0 + e.length)
+        return self.__class__(elements=elements, name=self.name, metadata=deepcopy(self.metadata)), behind
 
     def with_radiation_kicks(self, num_kicks: int = 1, quantum_excitation: bool = True, seed: int = 0, except_for=None) -> "Segment":
         """Every bending Dipole (and RBend) split by `Dipole.split_for_radiation(num_kicks, quantum_excitation, seed, first_stream)`
@@ -1920,11 +1967,11 @@ class Segment(Element):
         num_bins)`, nested Segments included. The kick's `effect_length` IS the element's `length` tensor, so in-place edits and
         gradients follow. With `max_step` (metres) an element longer than that is first split with its own
         `split(resolution=max_step)` and every piece gets its kick. Names in `except_for` and the collective kicks already there
-        (`LSCKick`, `CSRKick`, `TransientCSRKick`, `Wakefield`, `SpaceChargeKick`) get none. A kick stands behind its element and
+        (`LSCKick`, `CSRKick`, `TransientCSRKick`, `CSRDriftKick`, `Wakefield`, `SpaceChargeKick`) get none. A kick stands behind its element and
         sees the outgoing beam: the kick after a `Cavity` uses the energy the beam leaves the cavity with, not the mean energy inside
         it."""
         from ._binned_kick import check_num_bins
-        from .csr import CSRKick, TransientCSRKick
+        from .csr import CSRDriftKick, CSRKick, TransientCSRKick
         from .lsc import LSCKick, check_beam_radius, check_radius_factor
         from .space_charge_kick import SpaceChargeKick
         from .wakefield import Wakefield
@@ -1945,7 +1992,7 @@ class Segment(Element):
                 elements.append(e.with_lsc_kicks(num_bins, beam_radius, radius_factor, max_step, except_for))
                 continue
             elements_of_e = [e]
-            if not isinstance(e, (LSCKick, CSRKick, TransientCSRKick, Wakefield, SpaceChargeKick)) and e.name not in except_for \
+            if not isinstance(e, (LSCKick, CSRKick, TransientCSRKick, CSRDriftKick, Wakefield, SpaceChargeKick)) and e.name not in except_for \
                     and bool((e.length > 0).any()):
                 if max_step is not None and bool((e.length > step).any()):
                     elements_of_e = e.split(torch.as_tensor(step, device=e.length.device, dtype=e.length.dtype))

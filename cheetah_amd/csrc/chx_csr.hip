@@ -14,7 +14,9 @@
 // B3 are this file's: the particle passes, the argument check, the workspace and the launchers are chx_grid1d_dev.h and
 // chx_grid1d_host.h, shared with chx_wake.hip and chx_lsc.hip.
 // The second half of the file is the same kick with the entrance transient (TransientCSRKick element): F3 and B3 with the table of
-// the slippage length reached inside the bend, and B4 wrapped to sum the cotangent of that length.
+// the slippage length reached inside the bend, and B4 wrapped to sum the cotangent of that length. The third part is the kick in the
+// drift behind the bend (CSRDriftKick element): F3 and B3 with the table of the radiation that left the bend and catches up.
+#include "chx_dual.h"
 #include "chx_grid1d_host.h"
 
 namespace {
@@ -387,6 +389,340 @@ int csrt_kick_bwd_t(const T* x, const T* q, const T* w, int64_t B, int64_t Bx, i
     return CHX_OK;
 }
 
+// ==== the drift behind a bend (CSRDriftKick element) ==============================================================================
+// Stupakov and Emma, EPAC 2002, case D: a bunch a distance x behind the exit face of a bend of radius R and angle phi sees the
+// radiation emitted inside that bend. With xh = x / R, kappa = 24 h / R, the retarded angle psi(u) the root of
+// psi^3 (psi + 4 xh) / (psi + xh) = 24 u / R and y = u(phi) / h = phi^3 (phi + 4 xh) / (kappa (phi + xh)) nodes,
+//   S_k = (1 / (2 h^2)) { sum_j [G(psi_(j+1)) - G(psi_j)] (D_(k+j+1) - D_(k+j)) - kappa / (3 (phi + 2 xh)) D~(k + y) }
+//   G(psi) = psi^2 / 2 + xh^2 psi / (psi + xh) - xh^2 log1p(psi / xh),   psi_j = min(psi(j h), phi)
+// (the deposits beyond node M are 0, as in the kicks above), delta_k += (|Z| k_e L / p0c) S_k. As a Toeplitz table: b_0 = -g_0,
+// b_j = g_(j-1) - g_j with g_j = G(psi_(j+1)) - G(psi_j), then -beta (1 - f, f) at the lags (p, p + 1), p = floor(y), f = y - p,
+// beta = kappa / (3 (phi + 2 xh)). At xh = 0 and y >= M this is the steady state's table. F3 and B3 below; the particle passes are
+// the shared ones. State row: the header with the row's scale |Z| L / p0c in its last slot | M node kicks | xh, phi, kappa, a free
+// slot | M deposits D_k.
+constexpr int kCsrdPar = 4;                    // doubles per workgroup partial of B3: d(xh), d(phi), d(kappa), a free slot
+
+__host__ __device__ inline int64_t csrd_state_row(int M) { return CHX_CSR_DRIFT_STATE_DOUBLES(M); }
+__host__ __device__ inline int csrd_par_slot(int M) { return kHdr + M; }
+__host__ __device__ inline int csrd_dep_slot(int M) { return kHdr + M + 4; }
+
+// The workspace's own block: part[B][kCsrMaxBlocks][kCsrdPar], the partials of the shape numbers' cotangents, one per workgroup of B3.
+Grid1dWs csrd_ws(void* base, int64_t B, int64_t N, int M) {
+    return grid1d_ws(base, B, N, M, 1, (size_t)(B * kCsrMaxBlocks * kCsrdPar) * 8);
+}
+
+// The row's scale |Z| L / p0c and its shape numbers xh = x |theta| / L_b, phi = |theta|, kappa = 24 h |theta| / L_b in fp64: all 0
+// (no kick) where L, L_b or theta is 0, NaN for a negative L, L_b or x.
+struct CsrdRow {
+    double scale, xh, phi, kappa;
+};
+template <typename T>
+__device__ __forceinline__ CsrdRow csrd_row(const T* energy, int64_t Be, const T* length, int64_t Bl, const T* bend_length, int64_t Bbl,
+                                            const T* bend_angle, int64_t Bba, const T* distance, int64_t Bd, double mass, double absz,
+                                            double h, int64_t b) {
+    const double e = (double)energy[Be == 1 ? 0 : b], L = (double)length[Bl == 1 ? 0 : b];
+    const double Lb = (double)bend_length[Bbl == 1 ? 0 : b], th = (double)bend_angle[Bba == 1 ? 0 : b];
+    const double d = (double)distance[Bd == 1 ? 0 : b];
+    CsrdRow r = {0.0, 0.0, 0.0, 0.0};
+    if (L == 0.0 || Lb == 0.0 || th == 0.0) return r;
+    if (L > 0.0 && Lb > 0.0 && d >= 0.0) {
+        double gamma;
+        r.scale = absz * L / ref_p0c(e, mass, gamma);
+        r.phi = fabs(th);
+        r.xh = d * r.phi / Lb;
+        r.kappa = 24.0 * h * r.phi / Lb;
+    } else {
+        r.scale = r.xh = r.phi = r.kappa = __longlong_as_double(0x7ff8000000000000LL);
+    }
+    return r;
+}
+
+// The table's arithmetic is written once for double (F3, B3's table) and Dual (B3's derivatives). The entries G(psi_j) grow with j
+// while their second differences b_j shrink, so a table that differs in the last bit of its entries differs by far more than that
+// in the node sums of a long table (1e-12 of the largest kick and more at M = 4096). The double instance is therefore a fixed
+// sequence of IEEE additions, multiplications and divisions (libchx is built without contraction into fused multiply-adds) that
+// gives the same bits wherever it is restated: no library cbrt for Newton's start and no library log1p, which differ by an ulp
+// from one platform to the next (a start one ulp apart ends on a neighbouring fixed point of the iteration in hundreds of entries).
+
+// log1p(x) for x > -1/2 from IEEE operations and the exact frexp: 1 + x = m 2^e with m in [sqrt(1/2), sqrt(2)),
+// log m = 2 s (1 + z / 3 + ... + z^11 / 23), s = (m - 1) / (m + 1), z = s^2 <= 0.0295, ln 2 in two parts, and the rounding of 1 + x
+// put back to first order.
+__device__ __forceinline__ double csrd_log1p(double x) {
+    const double u = 1.0 + x;
+    int e;
+    double m = frexp(u, &e);
+    if (m < 0.70710678118654757) {
+        m = 2.0 * m;
+        e -= 1;
+    }
+    const double s = (m - 1.0) / (m + 1.0), z = s * s;
+    double p = 1.0 / 23.0;
+    for (int n = 10; n >= 0; --n) p = 1.0 / (double)(2 * n + 1) + z * p;
+    return (double)e * 6.93147180369123816490e-01 + (2.0 * s * p + ((double)e * 1.90821492927058770002e-10 + (x - (u - 1.0)) / u));
+}
+__device__ __forceinline__ Dual csrd_log1p(Dual x) { return mk(csrd_log1p(x.v), x.d / (1.0 + x.v)); }
+
+// G(psi; xh). Below psi / xh = 1/4 the closed form cancels to O(r^3): there the series xh^2 sum_(n=3)^(32) (-1)^(n+1) (1 - 1/n) r^n,
+// in Horner's form (summed from the small terms to the large ones).
+template <typename S>
+__device__ __forceinline__ S csrd_G(S psi, S xh) {
+    if (val(xh) == 0.0) return 0.5 * psi * psi;
+    const S r = psi / xh;
+    if (val(r) < 0.25) {
+        S acc = cst<S>(-(1.0 - 1.0 / 32.0));
+        for (int n = 31; n >= 3; --n) {
+            const double c = 1.0 - 1.0 / (double)n;
+            acc = ((n & 1) ? c : -c) + r * acc;
+        }
+        return xh * xh * (r * r * r * acc);
+    }
+    return (0.5 * psi * psi + xh * xh * psi / (psi + xh)) - xh * xh * csrd_log1p(r);
+}
+
+// One Newton step for the root of psi^3 (psi + 4 xh) / (psi + xh) = c, over a common denominator (one division). The left side
+// is convex in psi, so the steps from above the root come down to it monotonically.
+template <typename S>
+__device__ __forceinline__ S csrd_newton(S psi, S c, S xh) {
+    const S a = psi + xh;
+    const S n = psi * psi * psi * (psi + 4.0 * xh) - c * a;
+    const S w = psi * (psi + 2.0 * xh);
+    return psi - n * a / (3.0 * w * w);
+}
+
+// The root for c > 0: it lies in [(c / 4)^(1/3), c^(1/3)]; 12 steps from the power of two at or above the upper end (c = m 2^e
+// with m < 1: 2^ceil(e / 3)), the same count in every lane.
+__device__ __forceinline__ double csrd_root(double c, double xh) {
+    int e;
+    frexp(c, &e);
+    double psi = ldexp(1.0, e >= 0 ? (e + 2) / 3 : -((-e) / 3));
+    for (int i = 0; i < 12; ++i) psi = csrd_newton(psi, c, xh);
+    return psi;
+}
+
+// t_i = G(psi_i), psi_i = min(psi(i h), phi) (phi itself for i > p = floor(y)), t_0 = 0. One more Newton step from the converged
+// root, taken in S, carries the root's implicit derivative.
+template <typename S>
+__device__ __forceinline__ S csrd_t(int i, int p, S xh, S phi, S kappa) {
+    if (i <= 0) return cst<S>(0.0);
+    if (i > p) return csrd_G(phi, xh);
+    const double psi0 = csrd_root((double)i * val(kappa), val(xh));
+    S psi = csrd_newton(cst<S>(psi0), (double)i * kappa, xh);
+    if (val(psi) > val(phi)) psi = phi;
+    return csrd_G(psi, xh);
+}
+
+// y > 0 taken apart: p = floor(y) clamped to M in double (y may be 1e30) with the fraction f (only used below the clamp), and
+// nl = min(M, p + 2): the lags j >= nl have b_j = 0.
+struct CsrdLags {
+    int p, nl;
+};
+__device__ __forceinline__ CsrdLags csrd_lags(double y, int M) {
+    CsrdLags g;
+    g.p = (int)fmin(floor(y), (double)M);
+    g.nl = g.p + 2 < M ? g.p + 2 : M;
+    return g;
+}
+template <typename S>
+__device__ __forceinline__ S csrd_y(S xh, S phi, S kappa) {
+    return phi * phi * phi * (phi + 4.0 * xh) / (kappa * (phi + xh));
+}
+template <typename S>
+__device__ __forceinline__ S csrd_beta(S xh, S phi, S kappa) {
+    return kappa / (3.0 * (phi + 2.0 * xh));
+}
+// b_j from t_(j-1), t_j, t_(j+1) and the boundary term's interpolation weights.
+template <typename S>
+__device__ __forceinline__ S csrd_b(int j, int p, S tm, S t0, S tp, S beta, S y) {
+    S bj = (t0 - tm) - (tp - t0);
+    if (j == p) bj = bj - beta * (1.0 - (y - (double)p));
+    else if (j == p + 1) bj = bj - beta * (y - (double)p);
+    return bj;
+}
+
+// LDS table bt[i] = b_(i - 128) for lags 0 <= i - 128 < nlag <= nl, zero elsewhere (i < M + 256); scratch at[nlag] for t_(j+1).
+__device__ void csrd_b_table(int M, int nlag, const CsrdRow& r, const CsrdLags& g, double* bt, double* at) {
+    for (int j = threadIdx.x; j < nlag; j += kWB) at[j] = csrd_t<double>(j + 1, g.p, r.xh, r.phi, r.kappa);
+    __syncthreads();
+    const double beta = csrd_beta(r.xh, r.phi, r.kappa), y = csrd_y(r.xh, r.phi, r.kappa);
+    for (int i = threadIdx.x; i < M + 256; i += kWB) {
+        const int j = i - 128;
+        double bj = 0.0;
+        if (j >= 0 && j < nlag) bj = csrd_b<double>(j, g.p, j > 1 ? at[j - 2] : 0.0, j > 0 ? at[j - 1] : 0.0, at[j], beta, y);
+        bt[i] = bj;
+    }
+    __syncthreads();
+}
+
+// toeplitz_fwd_sum with the sources in fp64 (B3: the deposits the forward pass left in the state row).
+__device__ __forceinline__ double toeplitz_fwd_sum_d(const double* bt, const double* __restrict__ D, int k0, int mend, int M) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int k = k0 + lane;
+    double v = 0.0;
+    for (int m0 = k0 + wave * 64; m0 < mend; m0 += kWB) {
+        const int m = m0 + lane;
+        const double d = m < M ? D[m] : 0.0;
+        const int base = 128 + m0 - k;
+#pragma unroll 16
+        for (int j = 0; j < 64; ++j) v += bt[base + j] * readlane_d(d, j);
+    }
+    return v;
+}
+
+// ---- F3 of the drift: csr_toeplitz_kernel with the row's table; workgroup 0 stores the row's scale and shape numbers in the state
+// row, where F4 and the backward pass read them. The source tiles behind the last non-zero lag are skipped.
+template <typename T>
+__global__ __launch_bounds__(kWB) void csrd_toeplitz_kernel(int M, const T* __restrict__ energy, int64_t Be,
+                                                            const T* __restrict__ length, int64_t Bl,
+                                                            const T* __restrict__ bend_length, int64_t Bbl,
+                                                            const T* __restrict__ bend_angle, int64_t Bba,
+                                                            const T* __restrict__ distance, int64_t Bd, double mass, double absz,
+                                                            const unsigned long long* __restrict__ grid,
+                                                            double* __restrict__ state) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];            // bt[M + 256], at[M], acc[4][64]
+    const int64_t b = blockIdx.y;
+    const int k0 = blockIdx.x * kNodeBlock;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    double* st = state + b * csrd_state_row(M);
+    double* bt = lds;
+    double* acc = lds + 2 * M + 256;
+    const bool live = node_live(st);
+    const double SQ = st[3], h = st[2];
+    const CsrdRow r = csrd_row(energy, Be, length, Bl, bend_length, Bbl, bend_angle, Bba, distance, Bd, mass, absz, live ? h : 0.0, b);
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        st[kHdr - 1] = r.scale;
+        st[csrd_par_slot(M)] = r.xh;
+        st[csrd_par_slot(M) + 1] = r.phi;
+        st[csrd_par_slot(M) + 2] = r.kappa;
+        st[csrd_par_slot(M) + 3] = 0.0;
+    }
+    const bool ok = live && r.kappa > 0.0;
+    const CsrdLags g = csrd_lags(ok ? csrd_y(r.xh, r.phi, r.kappa) : 1.0, M);
+    if (ok) csrd_b_table(M, M - k0 < g.nl ? M - k0 : g.nl, r, g, bt, lds + M + 256);
+    const unsigned long long* gq = grid + b * M;
+    const int k = k0 + lane;
+    const int mend = k0 + 63 + g.nl < M ? k0 + 63 + g.nl : M;       // sources m >= mend: lags >= nl for every node of the block
+    acc[wave * 64 + lane] = ok ? toeplitz_fwd_sum(bt, gq, SQ, k0, mend, M) : 0.0;
+    __syncthreads();
+    if (wave == 0 && k < M) {
+        const double s = ((acc[lane] + acc[64 + lane]) + acc[128 + lane]) + acc[192 + lane];
+        st[kHdr + k] = ok ? kCoulomb / (2.0 * h * h) * s : (live && r.kappa != r.kappa ? r.kappa : 0.0);
+        st[csrd_dep_slot(M) + k] = live ? from_fixed(gq[k], SQ) : 0.0;
+    }
+}
+
+// ---- B3 of the drift: csr_bwd_toeplitz_kernel with the row's table, and the workgroup's partials of the shape numbers'
+// cotangents: d(p) = (k_e / (2 h^2)) sum_j (db_j / dp) C_j over its 64 lags j, C_j = sum_k GV_k D_(k+j) the correlation of the node
+// kicks' cotangents with the deposits (the same Toeplitz sum, the cotangents as its table); wave v < 3 takes the derivative with
+// respect to xh, phi, kappa as dual numbers through the root and G, the lags p and p + 1 of the boundary term held fixed.
+__global__ __launch_bounds__(kWB) void csrd_bwd_toeplitz_kernel(int M, const double* __restrict__ state,
+                                                                const double* __restrict__ bhdr,
+                                                                const unsigned long long* __restrict__ ggrid,
+                                                                double* __restrict__ adj, double* __restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) double lds[];            // bt[M + 256], at[M], acc[4][64]
+    const int64_t b = blockIdx.y;
+    const int m0 = blockIdx.x * kNodeBlock;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const double* st = state + b * csrd_state_row(M);
+    double* bt = lds;
+    double* acc = lds + 2 * M + 256;
+    const int mmax = m0 + kNodeBlock < M ? m0 + kNodeBlock : M;     // sources m < mmax: lags up to mmax - 1
+    const bool live = node_live(st);
+    CsrdRow r;
+    r.scale = st[kHdr - 1];
+    r.xh = st[csrd_par_slot(M)];
+    r.phi = st[csrd_par_slot(M) + 1];
+    r.kappa = st[csrd_par_slot(M) + 2];
+    const bool ok = live && r.kappa > 0.0;
+    const double nan_row = live && r.kappa != r.kappa ? r.kappa : 0.0;
+    const CsrdLags g = csrd_lags(ok ? csrd_y(r.xh, r.phi, r.kappa) : 1.0, M);
+    if (ok) csrd_b_table(M, mmax < g.nl ? mmax : g.nl, r, g, bt, lds + M + 256);
+    const unsigned long long* gg = ggrid + b * M;
+    const double SV = bhdr[b * kHdr + 1], h = st[2];
+    const double factor = kCoulomb / (2.0 * h * h);
+    const int m = m0 + lane;
+    acc[wave * 64 + lane] = ok ? toeplitz_bwd_sum(bt, gg, SV, m0, mmax, m0 - g.nl + 1, M) : 0.0;
+    __syncthreads();
+    if (wave == 0 && m < M) {
+        const double s = ((acc[lane] + acc[64 + lane]) + acc[128 + lane]) + acc[192 + lane];
+        adj[b * M + m] = ok ? factor * s : nan_row;
+    }
+    // the lags j = m0 + lane of this workgroup; those from nl on have b_j = 0 for every value of the shape numbers
+    const bool lags = ok && m0 < g.nl;
+    __syncthreads();
+    if (lags) {
+        for (int i = threadIdx.x; i < M + 256; i += kWB) {
+            const int k = i - 128;
+            bt[i] = (k >= 0 && k < M) ? from_fixed(gg[k], SV) : 0.0;
+        }
+    }
+    __syncthreads();
+    acc[wave * 64 + lane] = lags ? toeplitz_fwd_sum_d(bt, st + csrd_dep_slot(M), m0, M, M) : 0.0;
+    __syncthreads();
+    if (wave < 3) {
+        double dp = wave == 0 ? nan_row : 0.0;
+        if (lags && m < g.nl) {
+            const double cj = ((acc[lane] + acc[64 + lane]) + acc[128 + lane]) + acc[192 + lane];
+            const Dual xh = mk(r.xh, wave == 0 ? 1.0 : 0.0), phi = mk(r.phi, wave == 1 ? 1.0 : 0.0),
+                       kappa = mk(r.kappa, wave == 2 ? 1.0 : 0.0);
+            const Dual bj = csrd_b<Dual>(m, g.p, csrd_t<Dual>(m - 1, g.p, xh, phi, kappa), csrd_t<Dual>(m, g.p, xh, phi, kappa),
+                                         csrd_t<Dual>(m + 1, g.p, xh, phi, kappa), csrd_beta(xh, phi, kappa), csrd_y(xh, phi, kappa));
+            dp = factor * bj.d * cj;
+        }
+        dp = chx_wave_sum(dp);
+        if (lane == 0) part[(b * kCsrMaxBlocks + blockIdx.x) * kCsrdPar + wave] = dp;
+    }
+}
+
+// ---- B4 of the drift: one pass over the particles; the first thread of a row adds the workgroups' partials in order
+template <typename T>
+__global__ __launch_bounds__(kWB) void csrd_bwd_particles_kernel(const T* __restrict__ x, const T* __restrict__ q,
+                                                                 const T* __restrict__ w, int64_t Bx, int64_t Bq, int64_t Bw,
+                                                                 int64_t N, int M, const double* __restrict__ state,
+                                                                 const double* __restrict__ adj, const double* __restrict__ part,
+                                                                 const T* __restrict__ gout, T* __restrict__ dX, T* __restrict__ dC,
+                                                                 double* __restrict__ d_xh, double* __restrict__ d_phi,
+                                                                 double* __restrict__ d_kappa) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const int nb = (M + kNodeBlock - 1) / kNodeBlock;
+        double s[3] = {0.0, 0.0, 0.0};
+        for (int i = 0; i < nb; ++i)
+            for (int c = 0; c < 3; ++c) s[c] += part[((int64_t)blockIdx.y * kCsrMaxBlocks + i) * kCsrdPar + c];
+        d_xh[blockIdx.y] = s[0];
+        d_phi[blockIdx.y] = s[1];
+        d_kappa[blockIdx.y] = s[2];
+    }
+    node_bwd_particle(x, q, w, Bx, Bq, Bw, N, M, state, csrd_state_row(M), adj, gout, dX, dC);
+}
+
+template <typename T>
+int csrd_kick_t(const T* x, const T* q, const T* w, const T* energy, const T* length, const T* bend_length, const T* bend_angle,
+                const T* distance, double mass, double absz, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl,
+                int64_t Bbl, int64_t Bba, int64_t Bd, int64_t N, int M, T* out, double* state, const Grid1dWs& ws, hipStream_t s) {
+    if (!lds_ok(csrd_toeplitz_kernel<T>, toeplitz_lds(M))) return CHX_ERR_LAUNCH;
+    int st = launch_deposit(x, q, w, B, Bx, Bq, Bw, N, M, 0, 1, 1, csrd_state_row(M), state, ws, s);
+    if (st != CHX_OK) return st;
+    hipLaunchKernelGGL(csrd_toeplitz_kernel<T>, grid_nodes(M, B), dim3(kWB), toeplitz_lds(M), s, M, energy, Be, length, Bl, bend_length,
+                       Bbl, bend_angle, Bba, distance, Bd, mass, absz, ws.grid, state);
+    CHX_CHECK_LAUNCH();
+    return launch_node_kick(x, B, Bx, N, M, csrd_state_row(M), state, out, s);
+}
+
+template <typename T>
+int csrd_kick_bwd_t(const T* x, const T* q, const T* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int M,
+                    const double* state, const T* gout, T* dX, T* dC, double* d_scale, double* d_xh, double* d_phi, double* d_kappa,
+                    const Grid1dWs& ws, hipStream_t s) {
+    if (!lds_ok(csrd_bwd_toeplitz_kernel, toeplitz_lds(M))) return CHX_ERR_LAUNCH;
+    int st = launch_node_bwd_deposit(x, B, Bx, N, M, csrd_state_row(M), state, gout, d_scale, ws, s);
+    if (st != CHX_OK) return st;
+    hipLaunchKernelGGL(csrd_bwd_toeplitz_kernel, grid_nodes(M, B), dim3(kWB), toeplitz_lds(M), s, M, state, ws.bhdr, ws.ggrid, ws.adj,
+                       ws.extra);
+    CHX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(csrd_bwd_particles_kernel<T>, grid_particles(N, B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, M, state, ws.adj,
+                       ws.extra, gout, dX, dC, d_xh, d_phi, d_kappa);
+    CHX_CHECK_LAUNCH();
+    return CHX_OK;
+}
+
 }  // namespace
 
 extern "C" size_t chx_csr_workspace_bytes(int64_t B, int64_t N, int32_t M) { return csr_ws(nullptr, B, N, M).bytes; }
@@ -460,5 +796,44 @@ extern "C" int chx_csr_transient_kick_bwd(const void* x, const void* q, const vo
         using T = decltype(t);
         return csrt_kick_bwd_t<T>((const T*)x, (const T*)q, (const T*)w, B, Bx, Bq, Bw, N, M, state, (const T*)d_out, (T*)dX, (T*)dC,
                                   d_scale, d_x, ws, (hipStream_t)stream);
+    });
+}
+
+extern "C" size_t chx_csr_drift_workspace_bytes(int64_t B, int64_t N, int32_t M) { return csrd_ws(nullptr, B, N, M).bytes; }
+
+extern "C" int chx_csr_drift_kick(const void* x, const void* q, const void* w, const void* energy, const void* length,
+                                  const void* bend_length, const void* bend_angle, const void* distance, double mass_eV,
+                                  double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Bbl,
+                                  int64_t Bba, int64_t Bd, int64_t N, int32_t M, int dtype, void* out, double* state, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
+    if (st != CHX_OK) return st;
+    if (!energy || !length || !bend_length || !bend_angle || !distance || !(mass_eV > 0.0) || !chx_bcast_ok(Be, B) ||
+        !chx_bcast_ok(Bl, B) || !chx_bcast_ok(Bbl, B) || !chx_bcast_ok(Bba, B) || !chx_bcast_ok(Bd, B) || !out)
+        return CHX_ERR_INVALID_ARG;
+    if (!chx_aligned16(out)) return CHX_ERR_MISALIGNED;
+    const Grid1dWs ws = csrd_ws(workspace, B, N, M);
+    if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return csrd_kick_t<T>((const T*)x, (const T*)q, (const T*)w, (const T*)energy, (const T*)length, (const T*)bend_length,
+                              (const T*)bend_angle, (const T*)distance, mass_eV, abs_charge, B, Bx, Bq, Bw, Be, Bl, Bbl, Bba, Bd, N, M,
+                              (T*)out, state, ws, (hipStream_t)stream);
+    });
+}
+
+extern "C" int chx_csr_drift_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                                      int64_t N, int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC,
+                                      double* d_scale, double* d_xh, double* d_phi, double* d_kappa, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
+    if (st != CHX_OK) return st;
+    if (!d_out || !dX || !d_scale || !d_xh || !d_phi || !d_kappa) return CHX_ERR_INVALID_ARG;
+    const Grid1dWs ws = csrd_ws(workspace, B, N, M);
+    if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
+    return dispatch_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        return csrd_kick_bwd_t<T>((const T*)x, (const T*)q, (const T*)w, B, Bx, Bq, Bw, N, M, state, (const T*)d_out, (T*)dX, (T*)dC,
+                                  d_scale, d_xh, d_phi, d_kappa, ws, (hipStream_t)stream);
     });
 }

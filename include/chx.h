@@ -386,6 +386,33 @@ int chx_csr_transient_kick(const void* x, const void* q, const void* w, const vo
 int chx_csr_transient_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
                                int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
                                double* d_x, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- coherent synchrotron radiation in the drift behind a bend (CSRDriftKick element): chx_csr_kick's deposit, gather and
+ * degenerate cases with the wake of the radiation that was emitted inside a bend of length L_b and angle theta and catches up with the
+ * bunch a distance x behind the bend's exit face (Stupakov and Emma, EPAC 2002, case D). With R = L_b / |theta|, phi = |theta|,
+ * xh = x / R, kappa = 24 h / R, psi(u) the root of psi^3 (psi + 4 xh) / (psi + xh) = 24 u / R (12 Newton steps from the power of
+ * two at or above (24 u / R)^(1/3) and one more), psi_j = min(psi(j h), phi), y = phi^3 (phi + 4 xh) / (kappa (phi + xh)) and
+ * G(psi) = psi^2 / 2 + xh^2 psi / (psi + xh) - xh^2 log1p(psi / xh) (below psi / xh = 1/4 its series from the cubic term on),
+ * the table a fixed sequence of IEEE operations (its own log1p; no library function),
+ *   S_k = (1 / (2 h^2)) { sum_j [G(psi_(j+1)) - G(psi_j)] (D_(k+j+1) - D_(k+j)) - kappa / (3 (phi + 2 xh)) D~(k + y) },
+ *   delta_k += (|Z| k_e L / p0c) S_k
+ * with D~ the linear interpolation of the deposits at a real index and every deposit beyond node M equal to 0, summed as a Toeplitz
+ * table in chx_csr_kick's order. length[Bl] (L, the piece of drift the kick stands for), bend_length[Bbl], bend_angle[Bba] and
+ * distance[Bd] (x) are device arrays like chx_csr_kick's; no kick (the bits kept) where L, L_b or theta is 0, NaN for a negative L,
+ * L_b or x. state[B][CHX_CSR_DRIFT_STATE_DOUBLES(M)]: the row header with the scale |Z| L / p0c in its last slot, the M node kicks
+ * k_e S_k, then xh, phi, kappa, a free slot, the M deposits D_k. workspace: chx_csr_drift_workspace_bytes(B, N, M) (also for the
+ * backward pass).
+ * chx_csr_drift_kick_bwd: as chx_csr_kick_bwd, with d_xh[B], d_phi[B], d_kappa[B] (fp64) besides d_scale[B]: the gradients with
+ * respect to the row's three shape numbers (the node spacing h and the lags floor(y), floor(y) + 1 constants), which the caller
+ * chains to L_b, theta and x; 0 where there is no kick. */
+#define CHX_CSR_DRIFT_STATE_DOUBLES(M) (CHX_WAKE_STATE_HEADER + 4 + 2 * (int64_t)(M))
+size_t chx_csr_drift_workspace_bytes(int64_t B, int64_t N, int32_t M);
+int chx_csr_drift_kick(const void* x, const void* q, const void* w, const void* energy, const void* length, const void* bend_length,
+                       const void* bend_angle, const void* distance, double mass_eV, double abs_charge, int64_t B, int64_t Bx,
+                       int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Bbl, int64_t Bba, int64_t Bd, int64_t N, int32_t M,
+                       int dtype, void* out, double* state, void* workspace, size_t workspace_bytes, void* stream);
+int chx_csr_drift_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
+                           int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
+                           double* d_xh, double* d_phi, double* d_kappa, void* workspace, size_t workspace_bytes, void* stream);
 /* ---- longitudinal space charge (LSCKick element): per batch row b, the surviving particles' grid and node-based linear deposit D_k
  * (coulomb) exactly as chx_wake_kick's and chx_csr_kick's (same tau_lo, node spacing h, u, k, f, clamping, dead particles, NaN tau);
  * the on-axis field of a uniformly charged disc of radius a and Lorentz factor gamma, integrated exactly against the hat functions:
