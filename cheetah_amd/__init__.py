@@ -18,6 +18,7 @@ from .accelerator import (  # noqa: F401
     Drift,
     Element,
     HorizontalCorrector,
+    LaserModulator,
     LSCKick,
     Marker,
     PhysicsWarning,
@@ -35,6 +36,7 @@ from .accelerator import (  # noqa: F401
     Undulator,
     VerticalCorrector,
     Wakefield,
+    laser_modulation_amplitude,
 )
 from .particles import BeamSlices, ParameterBeam, ParticleBeam, Species  # noqa: F401
 from . import converters, graph, latticejson, track_methods, utils  # noqa: F401,E402

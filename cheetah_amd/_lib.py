@@ -317,6 +317,10 @@ SIGNATURES = {
                                 c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_size_t, c_void_p]),
     "chx_sr_normals": (c_int, [c_u32, c_u32, c_u64, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
+    "chx_laser_workspace_bytes": (c_size_t, [c_i64, c_i64]),
+    "chx_laser_kick": (c_int, [c_void_p] * 10 + [c_double] + [c_i64] * 12 + [c_int, c_void_p, c_void_p]),
+    "chx_laser_kick_bwd": (c_int, [c_void_p] * 10 + [c_double] + [c_i64] * 12 + [c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                                                c_size_t, c_void_p]),
     "chx_run_vjp_workspace_bytes": (c_size_t, [c_i64]),
     "chx_run_vjp": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_size_t, c_void_p]),

@@ -1533,3 +1533,5 @@ from ._ops_bunching import _bunching_bwd_raw, _bunching_raw  # noqa: E402,F401
 from ._ops_grid1d import *  # noqa: E402,F401,F403
 # ... and the incoherent synchrotron-radiation kick (the SynchrotronRadiationKick element) in _ops_sr.py
 from ._ops_sr import *  # noqa: E402,F401,F403
+# ... and the laser energy modulation in an undulator (the LaserModulator element) in _ops_laser.py
+from ._ops_laser import *  # noqa: E402,F401,F403

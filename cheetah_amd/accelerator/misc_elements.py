@@ -77,6 +77,48 @@ class Undulator(Element):
     def is_skippable(self) -> bool:
         return True
 
+    def resonant_wavelength(self, energy, species=None) -> torch.Tensor:
+        """The wavelength lambda_u (1 + K^2 / 2) / (2 gamma0^2) of the undulator's fundamental on axis for a beam of reference
+        energy `energy` (eV), K^2 = kx^2 + ky^2; `species=None` is an electron."""
+        from ..particles.species import electron_mass_eV
+
+        energy = torch.as_tensor(energy, dtype=self.period.dtype, device=self.period.device)
+        gamma = energy / (electron_mass_eV if species is None else species.mass_eV.to(energy.device))
+        return self.period * (1 + (self.kx.square() + self.ky.square()) / 2) / (2 * gamma.square())
+
+    def with_laser(self, peak_power, laser_sigma, energy, wavelength=None, phase=0.0, offset_x=0.0, offset_y=0.0, pulse_sigma=None,
+                   pulse_center=0.0, num_kicks: int = 1):
+        """The undulator with a laser in it, as a `Segment` of `num_kicks` x [Undulator of L / 2n, LaserModulator, Undulator of
+        L / 2n]: the energy modulation of a laser of peak power `peak_power` (W) and rms intensity size `laser_sigma` (m) on a beam
+        of electrons of reference energy `energy` (eV), every kick with the amplitude `laser_modulation_amplitude` gives for L / n.
+        `wavelength=None` takes the resonant one. For a planar undulator: K is the one non-zero of `kx`, `ky`. The pieces are
+        named `{name}_laser_{j}`, the kicks `{name}_laser_kick_{i}`; the pieces' total map is the undulator's own."""
+        from ._binned_kick import check_num_kicks
+        from .laser_modulator import LaserModulator, laser_modulation_amplitude
+        from .segment import Segment
+
+        owner = "Undulator.with_laser"
+        n = check_num_kicks(num_kicks, owner)
+        has_kx, has_ky = bool((self.kx != 0).any()), bool((self.ky != 0).any())
+        if has_kx == has_ky:
+            raise ValueError(f"{owner}: a planar undulator has exactly one of kx and ky non-zero, got kx={self.kx!r}, ky={self.ky!r}")
+        K = self.kx if has_kx else self.ky
+        fk = {"device": self.length.device, "dtype": self.length.dtype}
+        t = lambda v: v if v is None or isinstance(v, torch.Tensor) else torch.as_tensor(v, **fk)  # noqa: E731
+        energy = t(energy)
+        if wavelength is None:
+            wavelength = self.resonant_wavelength(energy)
+        amplitude = laser_modulation_amplitude(t(peak_power), K, self.length / n, t(laser_sigma), energy)
+        elements = []
+        for i in range(n):
+            halves = [Undulator(self.length / (2 * n), period=self.period, kx=self.kx, ky=self.ky, name=f"{self.name}_laser_{2 * i + j}",
+                                sanitize_name=False, **fk) for j in range(2)]
+            kick = LaserModulator(amplitude, t(wavelength), t(laser_sigma), phase=t(phase), offset_x=t(offset_x), offset_y=t(offset_y),
+                                  pulse_sigma=t(pulse_sigma), pulse_center=t(pulse_center), name=f"{self.name}_laser_kick_{i}",
+                                  sanitize_name=False, **fk)
+            elements += [halves[0], kick, halves[1]]
+        return Segment(elements, name=self.name, sanitize_name=False)
+
     @property
     def defining_features(self) -> list[str]:
         return super().defining_features + ["length", "period", "kx", "ky"]

@@ -468,6 +468,37 @@ int chx_sr_kick_bwd(const void* x, const void* energy, const void* length, const
                     double* d_a, double* d_b, void* workspace, size_t workspace_bytes, void* stream);
 int chx_sr_normals(uint32_t seed, uint32_t rng_stream, uint64_t call, int64_t B, int64_t N, uint32_t* words_out, double* xi_out,
                    void* stream);
+/* ---- laser energy modulation in an undulator (LaserModulator element; Huang et al., PRSTAB 7, 074401 (2004), eq. 8), as one
+ * zero-length kick. Per batch row b, in fp64, with gamma0 = energy / mass_eV, P0 = beta0 gamma0 (as chx_sr_kick forms them), the
+ * amplitude A (eV), the wavelength lambda, the phase phi, the rms size sigma_r of the laser intensity, the laser axis (x0, y0), the rms
+ * length sigma_t of the intensity envelope and its centre tau0:
+ *   a = A / (P0 mass_eV), nu = 1 / lambda, phi_t = phi / fl(2 pi), g = 1 / (4 sigma_r^2), h = 1 / (4 sigma_t^2)
+ * (h = 0 for pulse_sigma = NULL: no envelope), and per particle n, in fp64 whatever the dtype, rounded once on the store, with
+ * u = x - x0, v = y - y0, w = tau - tau0:
+ *   t = fl(fl(tau nu) + phi_t) (turns; product and sum rounded separately), f = t - rint(t), Ex = exp(-g (u^2 + v^2) - h w^2),
+ *   delta' = delta + a Ex sin(2 pi f), the sine as sincospi(2 f).
+ * Every other column keeps its bits; a row with a = 0 keeps every bit. A particle whose x, y, tau or delta is not finite gets a
+ * non-finite delta' (NaN, or the non-finite delta itself) and nothing else of it changes. energy[Be], amplitude[Ba], wavelength[Bw],
+ * phase[Bp], laser_sigma[Bs], offset_x[Bx0], offset_y[By0], pulse_sigma[Bps] (or NULL), pulse_center[Bpc]: device arrays of the
+ * beam's dtype, each 1 or B rows. x[Bx][N][7], out[B][N][7] (16-byte aligned). 1 <= B <= 65535, 1 <= N < 2^32, mass_eV > 0.
+ * chx_laser_kick_bwd: the same arguments and d_out[B][N][7] (dtype) -> dX[B][N][7] and d_rows[B][8] (fp64), the per-row cotangents of
+ * (a, nu, phi_t, g, x0, y0, h, tau0): the caller chains them to the energy and the eight settings. With G the cotangent of delta',
+ * S = a Ex and (s, c) = sincospi(2 f): dX = d_out, x's adds -2 g u G S s, y's -2 g v G S s, tau's G S (2 pi nu c - 2 h w s); G_a =
+ * sum G Ex s, G_nu = sum 2 pi tau G S c, G_phit = sum 2 pi G S c, G_g = -sum G S s (u^2 + v^2), G_x0 = sum 2 g u G S s, G_y0 = sum
+ * 2 g v G S s, G_h = -sum G S s w^2, G_tau0 = sum 2 h w G S s. The rows' sums are formed in a fixed order (per-workgroup partials in
+ * the workspace, then one workgroup per row): bitwise reproducible, no float atomics. Rows of a broadcast x are NOT reduced — the
+ * caller sums. A particle whose delta' is not finite has zero gradient in the delta column and adds nothing. workspace:
+ * chx_laser_workspace_bytes(B, N) (0 for a shape out of range). */
+size_t chx_laser_workspace_bytes(int64_t B, int64_t N);
+int chx_laser_kick(const void* x, const void* energy, const void* amplitude, const void* wavelength, const void* phase,
+                   const void* laser_sigma, const void* offset_x, const void* offset_y, const void* pulse_sigma,
+                   const void* pulse_center, double mass_eV, int64_t B, int64_t Bx, int64_t Be, int64_t Ba, int64_t Bw, int64_t Bp,
+                   int64_t Bs, int64_t Bx0, int64_t By0, int64_t Bps, int64_t Bpc, int64_t N, int dtype, void* out, void* stream);
+int chx_laser_kick_bwd(const void* x, const void* energy, const void* amplitude, const void* wavelength, const void* phase,
+                       const void* laser_sigma, const void* offset_x, const void* offset_y, const void* pulse_sigma,
+                       const void* pulse_center, double mass_eV, int64_t B, int64_t Bx, int64_t Be, int64_t Ba, int64_t Bw,
+                       int64_t Bp, int64_t Bs, int64_t Bx0, int64_t By0, int64_t Bps, int64_t Bpc, int64_t N, int dtype,
+                       const void* d_out, void* dX, double* d_rows, void* workspace, size_t workspace_bytes, void* stream);
 /* Backward of chx_moments(y), y_n = R x_n, with respect to the MAP R[BR][7][7] (dtype) when the particles x carry no
  * gradient: mu' = A mu + b, cov' = A C A^T (element.py:180-191 + utils/statistics.py:4-62), so
  * dR[B][7][7] (double) = [2 G A C + g_mu mu^T | g_mu; 0] from d_out[B][29] and the INCOMING beam's chx_moments
