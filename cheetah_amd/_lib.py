@@ -321,6 +321,11 @@ SIGNATURES = {
     "chx_laser_kick": (c_int, [c_void_p] * 10 + [c_double] + [c_i64] * 12 + [c_int, c_void_p, c_void_p]),
     "chx_laser_kick_bwd": (c_int, [c_void_p] * 10 + [c_double] + [c_i64] * 12 + [c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                                                 c_size_t, c_void_p]),
+    "chx_quiet_sequence": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_int, c_int, c_void_p, c_void_p]),
+    "chx_density_workspace_bytes": (c_size_t, [c_i64, c_i64]),
+    "chx_density_modulate": (c_int, [c_void_p] * 4 + [c_i64] * 7 + [c_int, c_void_p, c_void_p]),
+    "chx_density_modulate_bwd": (c_int, [c_void_p] * 4 + [c_i64] * 7 + [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                         c_void_p]),
     "chx_run_vjp_workspace_bytes": (c_size_t, [c_i64]),
     "chx_run_vjp": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_size_t, c_void_p]),

@@ -1535,3 +1535,7 @@ from ._ops_grid1d import *  # noqa: E402,F401,F403
 from ._ops_sr import *  # noqa: E402,F401,F403
 # ... and the laser energy modulation in an undulator (the LaserModulator element) in _ops_laser.py
 from ._ops_laser import *  # noqa: E402,F401,F403
+# ... and the quiet-start deviates (ParticleBeam.from_distribution(quiet_start=True)) in _ops_quiet.py
+from ._ops_quiet import *  # noqa: E402,F401,F403
+# ... and the seeded density modulation (ParticleBeam.with_density_modulation) in _ops_density.py
+from ._ops_density import *  # noqa: E402,F401,F403

@@ -21,6 +21,7 @@ from .beam import Beam
 from .species import Species
 
 _COORDS = ["x", "px", "y", "py", "tau", "p"]
+_QUIET_BASES = (5, 7, 11, 13, 2, 3)                           # Halton bases of a quiet start's columns, in _COORDS' order
 speed_of_light = 299792458.0
 
 
@@ -95,16 +96,32 @@ class ParticleBeam(Beam):
     # ------------------------------------------------------------------ factories (input generation)
     @classmethod
     def from_distribution(cls, mu, cov, num_particles=100_000, energy=None, total_charge=None, s=None,
-                          species=None, device=None, dtype=None) -> "ParticleBeam":
+                          species=None, device=None, dtype=None, quiet_start: bool = False,
+                          sequence_offset: int = 0) -> "ParticleBeam":
         """Random particles matched to (mu, cov) (particle_beam.py:355-432). Input factory: generated
-        with torch's RNG on `device`; not part of the tracking hot path."""
+        with torch's RNG on `device`; not part of the tracking hot path.
+
+        `quiet_start=True`: the (N, 6) block of normal deviates is not drawn but taken from the Halton sequence
+        (`_ops.quiet_sequence`, one `chx_quiet_sequence` launch), the columns (x, px, y, py, tau, p) in the bases (5, 7, 11, 13, 2,
+        3): the longitudinal plane gets the two most uniform ones. The block goes through the same whitening and colouring, is
+        shared by all batch rows of `cov`, and the beam stays differentiable in `mu` and `cov`. Such a beam's bunching factor lies
+        far below the 1 / sqrt(N) of a drawn one, and it is the same beam on every call, whatever torch's seed. Row n has the
+        sequence index `sequence_offset` + 1 + n (0 <= sequence_offset, sequence_offset + N < 2^40; ValueError otherwise): the ranks
+        of a particle-sharded beam pass `sequence_offset = rank * N_local`, so that together they hold one sequence."""
+        if quiet_start:
+            _ops.check_sequence_range(num_particles, sequence_offset)
         factory_kwargs = {"device": device, "dtype": dtype}
         species = species.to(**factory_kwargs) if species is not None else Species("electron", **factory_kwargs)
         energy = energy if energy is not None else torch.tensor(1e8, **factory_kwargs)
         total_charge = total_charge if total_charge is not None else species.charge_coulomb * num_particles
         particle_charges = (torch.ones((*total_charge.shape, num_particles), **factory_kwargs)
                             * total_charge.unsqueeze(-1) / num_particles)
-        z = torch.randn(num_particles, 6, **factory_kwargs)
+        if quiet_start:
+            z = _ops.quiet_sequence(num_particles, _QUIET_BASES, offset=sequence_offset, normal=True,
+                                    dtype=dtype if dtype is not None else torch.get_default_dtype(),
+                                    device=device if device is not None else torch.get_default_device())
+        else:
+            z = torch.randn(num_particles, 6, **factory_kwargs)
         # whiten the sample, then colour it with chol(cov) and shift to mu (utils/statistics.py:91-143)
         z = z - z.mean(dim=0, keepdim=True)
         c = (z.mT @ z) / (num_particles - 1)
@@ -120,8 +137,12 @@ class ParticleBeam(Beam):
                         sigma_p=None, cov_xpx=None, cov_ypy=None, cov_taup=None, cov_xp=None, cov_pxp=None, cov_yp=None,
                         cov_pyp=None, cov_xy=None, cov_xpy=None, cov_xtau=None, cov_pxy=None, cov_pxpy=None,
                         cov_pxtau=None, cov_ytau=None, cov_pytau=None, energy=None, total_charge=None, s=None,
-                        species=None, device=None, dtype=None) -> "ParticleBeam":
-        """Gaussian beam from its means, sigmas and any of the 15 covariances; defaults as particle_beam.py:108-353."""
+                        species=None, device=None, dtype=None, quiet_start: bool = False,
+                        sequence_offset: int = 0) -> "ParticleBeam":
+        """Gaussian beam from its means, sigmas and any of the 15 covariances; defaults as particle_beam.py:108-353.
+        `quiet_start`, `sequence_offset`: as `from_distribution`."""
+        if quiet_start:
+            _ops.check_sequence_range(num_particles, sequence_offset)
         fk = {"device": device, "dtype": dtype}
         d = lambda v, default: v if v is not None else torch.tensor(default, **fk)  # noqa: E731
         mus = torch.broadcast_tensors(d(mu_x, 0.0), d(mu_px, 0.0), d(mu_y, 0.0), d(mu_py, 0.0), d(mu_tau, 0.0),
@@ -141,14 +162,19 @@ class ParticleBeam(Beam):
             cov[..., i, j] = c
             cov[..., j, i] = c
         return cls.from_distribution(mean, cov, num_particles=num_particles, energy=energy,
-                                     total_charge=total_charge, s=s, species=species, device=device, dtype=dtype)
+                                     total_charge=total_charge, s=s, species=species, device=device, dtype=dtype,
+                                     quiet_start=quiet_start, sequence_offset=sequence_offset)
 
     @classmethod
     def from_twiss(cls, num_particles=100_000, beta_x=None, alpha_x=None, emittance_x=None, beta_y=None,
                    alpha_y=None, emittance_y=None, dispersion_x=None, dispersion_px=None, dispersion_y=None,
                    dispersion_py=None, energy=None, sigma_tau=None, sigma_p=None, cov_taup=None, total_charge=None,
-                   s=None, species=None, device=None, dtype=None) -> "ParticleBeam":
-        """Gaussian beam from Twiss parameters and dispersion (particle_beam.py:434-560)."""
+                   s=None, species=None, device=None, dtype=None, quiet_start: bool = False,
+                   sequence_offset: int = 0) -> "ParticleBeam":
+        """Gaussian beam from Twiss parameters and dispersion (particle_beam.py:434-560). `quiet_start`, `sequence_offset`: as
+        `from_distribution`."""
+        if quiet_start:
+            _ops.check_sequence_range(num_particles, sequence_offset)
         fk = {"device": device, "dtype": dtype}
         d = lambda v, default: v if v is not None else torch.tensor(default, **fk)  # noqa: E731
         beta_x, alpha_x, emittance_x = d(beta_x, 0.0), d(alpha_x, 0.0), d(emittance_x, 7.1971891e-13)
@@ -165,7 +191,7 @@ class ParticleBeam(Beam):
             sigma_tau=sigma_tau, sigma_p=sigma_p, cov_xpx=-emittance_x * alpha_x + dx * dpx * sp2,
             cov_ypy=-emittance_y * alpha_y + dy * dpy * sp2, cov_taup=cov_taup, cov_xp=dx * sp2, cov_pxp=dpx * sp2,
             cov_yp=dy * sp2, cov_pyp=dpy * sp2, energy=d(energy, 1e8), total_charge=total_charge, s=s, species=species,
-            device=device, dtype=dtype)
+            device=device, dtype=dtype, quiet_start=quiet_start, sequence_offset=sequence_offset)
 
     @classmethod
     def uniform_3d_ellipsoid(cls, num_particles=100_000, radius_x=None, radius_y=None, radius_tau=None,
@@ -379,6 +405,31 @@ class ParticleBeam(Beam):
         from .bunching import bunching_factor
 
         return bunching_factor(self, wavelengths, wavenumbers)
+
+    def with_density_modulation(self, wavelengths, amplitudes, phases=0.0) -> "ParticleBeam":
+        """A beam whose longitudinal density is this one's times 1 + sum_m A_m cos(2 pi tau / lambda_m + phi_m), for up to 8 modes:
+        the seed of a microbunching-gain calculation, gain = b_out / b_in. Every particle's tau moves to the root tau' of
+
+            tau' + sum_m A_m lambda_m / (2 pi) sin(2 pi tau' / lambda_m + phi_m) = tau,
+
+        which is exact for a uniform envelope; for a bunch of rms length sigma the bunching factor at k_m = 2 pi / lambda_m becomes
+        b(k_m) = (A_m / 2) exp(i phi_m) (1 + O((k_m sigma)^-2)) in the sign convention of `bunching_factor`. On a quiet-start beam
+        (`from_distribution(quiet_start=True)`) nothing else is left at that wavelength.
+
+        `wavelengths`, `amplitudes`, `phases`: floats, sequences or tensors (…, K), one value per mode (a single value stands for
+        all modes), whose leading dimensions broadcast against the beam's batch shape; at most 65 535 batch rows. The root is
+        unique only for sum |A_m| < 1. Host-side values are checked (ValueError for sum |A_m| >= 1, wavelengths <= 0, non-finite
+        values, more than 8 modes, lengths that differ); device tensors are used as given, and a row with sum |A_m| >= 1 gets NaN
+        in tau'. Float64 arithmetic whatever the beam dtype, the phase reduced in turns, so thousands of wavelengths along the
+        bunch cost no digits; a safeguarded Newton iteration of at most 32 steps. Every coordinate but tau keeps its bits, a row
+        with all A_m = 0 keeps all of them, a non-finite tau stays as it is.
+
+        One `chx_density_modulate` call (bitwise reproducible, no host synchronisation, capturable in a device graph: an in-place
+        edit of a device-resident setting is followed); differentiable with respect to the particles, the amplitudes, the
+        wavelengths and the phases."""
+        from .modulation import with_density_modulation
+
+        return with_density_modulation(self, wavelengths, amplitudes, phases)
 
     def _entry(self, index: int, take_sqrt: bool = False) -> torch.Tensor:
         """One entry of the moment vector (optionally its square root) in the beam's dtype. Under autograd this is ONE node

@@ -499,6 +499,40 @@ int chx_laser_kick_bwd(const void* x, const void* energy, const void* amplitude,
                        const void* pulse_center, double mass_eV, int64_t B, int64_t Bx, int64_t Be, int64_t Ba, int64_t Bw,
                        int64_t Bp, int64_t Bs, int64_t Bx0, int64_t By0, int64_t Bps, int64_t Bpc, int64_t N, int dtype,
                        const void* d_out, void* dX, double* d_rows, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- quiet-start deviates: out[N][D] (dtype) holds the Halton sequence in the D bases bases[D] (a HOST array read during the call;
+ * distinct primes <= 19), as uniforms in (0, 1) (normal = 0) or as standard-normal deviates. Row n has the index i = offset + 1 + n;
+ * index 0 is never used. 1 <= D <= CHX_QUIET_MAX_DIMS, N >= 1, offset >= 0, offset + N < 2^40 (CHX_ERR_INVALID_ARG otherwise, before
+ * any device work). Radical inverse: in unsigned 64-bit integers the digits of i are peeled off in base b, r = r b + digit and
+ * p = p b per digit; u = (double)r / (double)p, one IEEE division (r, p < 2^53: the same bits on any machine). Normal deviates, in
+ * fp64: s = min(u, 1 - u), z = -+ sqrt(2) erfcinv(2 s), negative for u < 1/2, exactly 0 at u = 1/2. A float32 output is the fp64 value
+ * rounded once on the store. One launch; bitwise reproducible; rows [a, b) of one call equal a call with offset + a. */
+#define CHX_QUIET_MAX_DIMS 8
+int chx_quiet_sequence(const int* bases, int64_t D, int64_t N, int64_t offset, int normal, int dtype, void* out, void* stream);
+/* ---- seeded density modulation (ParticleBeam.with_density_modulation): the longitudinal density times 1 + sum_m A_m cos(2 pi tau /
+ * lambda_m + phi_m), 1 <= K <= CHX_DENSITY_MAX_MODES modes: every particle's tau moves to the root tau' of
+ *   tau' + sum_m c_m sin(2 pi (tau' nu_m + phi_t,m)) = tau,   nu_m = 1 / lambda_m, phi_t,m = phi_m / fl(2 pi), c_m = A_m / (fl(2 pi) nu_m),
+ * in fp64 whatever the dtype, rounded once on the store. amplitudes[Ba][K], wavelengths[Bw][K], phases[Bp][K]: fp64 device arrays of 1
+ * or B rows. The phase of mode m at t in turns: w = fl(fl(t nu_m) + phi_t,m), f = w - rint(w), sincospi(2 f). Solver: at most 32
+ * steps from t = tau; the bracket [lo, hi], from tau -+ sum |c_m|, takes t on the side of the sign of g = t + sum c_m sin theta_m - tau
+ * (theta_m the phase of mode m at t), and the step is Newton's t - g / D, D = 1 + sum A_m cos theta_m, where that stays inside the bracket and the bracket's middle otherwise; a particle
+ * is done after a Newton step no longer than 2^-30 / max |nu_m| (the next error is its square: below 10^-16 wavelengths).
+ * Every column but tau keeps its bits; a row whose A_m are all 0 keeps every bit; a non-finite tau stays as it is; in a row with
+ * sum |A_m| >= 1 (or NaN), where the root is not unique, every finite tau becomes NaN. x[Bx][N][7], out[B][N][7] (16-byte aligned).
+ * 1 <= B <= 65535, 1 <= N < 2^32.
+ * chx_density_modulate_bwd: the same arguments and d_out[B][N][7] (dtype) -> dX[B][N][7] and d_rows[B][3][CHX_DENSITY_MAX_MODES] (fp64),
+ * the per-row cotangents of (A_m, nu_m, phi_t,m), 0 for m >= K: the caller chains them to the settings. With G the cotangent of tau'
+ * and theta_m the phase of mode m at tau' (solved again from x): dX = d_out, tau's column G / D; G_A,m = -sum G sin theta_m / (2 pi
+ * nu_m D), G_nu,m = sum G (A_m sin theta_m / (2 pi nu_m^2) - A_m tau' cos theta_m / nu_m) / D, G_phit,m = -sum G A_m cos theta_m /
+ * (nu_m D). The rows' sums are formed in a fixed order (per-workgroup partials in the workspace, then one workgroup per row): bitwise
+ * reproducible, no float atomics. Rows of a broadcast x are NOT reduced — the caller sums. A particle whose tau' is not finite has
+ * zero gradient in the tau column and adds nothing. workspace: chx_density_workspace_bytes(B, N) (0 for a shape out of range). */
+#define CHX_DENSITY_MAX_MODES 8
+size_t chx_density_workspace_bytes(int64_t B, int64_t N);
+int chx_density_modulate(const void* x, const double* amplitudes, const double* wavelengths, const double* phases, int64_t K, int64_t B,
+                         int64_t Bx, int64_t Ba, int64_t Bw, int64_t Bp, int64_t N, int dtype, void* out, void* stream);
+int chx_density_modulate_bwd(const void* x, const double* amplitudes, const double* wavelengths, const double* phases, int64_t K,
+                             int64_t B, int64_t Bx, int64_t Ba, int64_t Bw, int64_t Bp, int64_t N, int dtype, const void* d_out,
+                             void* dX, double* d_rows, void* workspace, size_t workspace_bytes, void* stream);
 /* Backward of chx_moments(y), y_n = R x_n, with respect to the MAP R[BR][7][7] (dtype) when the particles x carry no
  * gradient: mu' = A mu + b, cov' = A C A^T (element.py:180-191 + utils/statistics.py:4-62), so
  * dR[B][7][7] (double) = [2 G A C + g_mu mu^T | g_mu; 0] from d_out[B][29] and the INCOMING beam's chx_moments
