@@ -18,6 +18,7 @@ from .accelerator import (  # noqa: F401
     Drift,
     Element,
     HorizontalCorrector,
+    IBSKick,
     LaserModulator,
     LSCKick,
     Marker,

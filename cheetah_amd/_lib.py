@@ -317,6 +317,12 @@ SIGNATURES = {
                                 c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_size_t, c_void_p]),
     "chx_sr_normals": (c_int, [c_u32, c_u32, c_u64, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
+    "chx_ibs_workspace_bytes": (c_size_t, [c_i64, c_i64, ctypes.c_int32]),
+    "chx_ibs_kick": (c_int, [c_void_p] * 10 + [c_double, c_double, c_u32, c_u32, c_void_p] + [c_i64] * 12
+                     + [ctypes.c_int32, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "chx_ibs_kick_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_u32, c_u32, c_void_p, c_i64, c_i64, c_i64, c_i64, c_i64,
+                                 ctypes.c_int32, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "chx_ibs_normals": (c_int, [c_u32, c_u32, c_u64, c_i64, c_i64, c_void_p, c_void_p, c_void_p]),
     "chx_laser_workspace_bytes": (c_size_t, [c_i64, c_i64]),
     "chx_laser_kick": (c_int, [c_void_p] * 10 + [c_double] + [c_i64] * 12 + [c_int, c_void_p, c_void_p]),
     "chx_laser_kick_bwd": (c_int, [c_void_p] * 10 + [c_double] + [c_i64] * 12 + [c_int, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -1529,7 +1529,7 @@ from ._ops_slices import _slice_moments_bwd_raw, _slice_moments_raw  # noqa: E40
 # ... and the bunching factor (ParticleBeam.bunching_factor) in _ops_bunching.py
 from ._ops_bunching import *  # noqa: E402,F401,F403
 from ._ops_bunching import _bunching_bwd_raw, _bunching_raw  # noqa: E402,F401
-# ... and the kicks from the beam binned on nodes in tau (the Wakefield, CSRKick and LSCKick elements) in _ops_grid1d.py
+# ... and the kicks from the beam binned on nodes in tau (the Wakefield, CSRKick, LSCKick and IBSKick elements) in _ops_grid1d.py
 from ._ops_grid1d import *  # noqa: E402,F401,F403
 # ... and the incoherent synchrotron-radiation kick (the SynchrotronRadiationKick element) in _ops_sr.py
 from ._ops_sr import *  # noqa: E402,F401,F403

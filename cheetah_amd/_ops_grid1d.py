@@ -6,11 +6,13 @@ drift behind a bend (CSRDriftKick: the same sum with the table of the radiation 
 longitudinal space charge (LSCKick: the two-sided Toeplitz sum with the on-axis field of a charged disc). Each is one
 `chx_*_kick` call (four launches, deterministic, no host synchronisation) and an autograd node whose backward is `chx_*_kick_bwd`.
 The CSR and LSC kicks form their per-row factors on the device from the energy and their further settings (length, angle, radius,
-distance); they share one node.
+distance); they share one node. So does the intrabeam-scattering kick (IBSKick), whose node quantity is a variance V_k = K D_k / h:
+every particle gets delta += sqrt(V(u)) xi with a deviate drawn inside the kernel (Philox4x32-10, as `_ops_sr`).
 
 Part of `_ops` (which re-exports every name here). Imported at the END of `_ops`, whose helpers it uses."""
 from __future__ import annotations
 
+import math
 from operator import attrgetter
 from typing import Callable, NamedTuple
 
@@ -20,13 +22,18 @@ from . import _lib
 from ._ops import MAX_GRID_ROWS, aligned, bshapes, check, dtype_code, flat_bcast, numel, ptr, require_device, stream_ptr, workspace
 
 __all__ = ["WAKE_MAX_BINS", "CSR_MAX_BINS", "LSC_MAX_BINS", "WakeKick", "wake_kick", "wake_scale", "csr_kick", "csr_scale", "csr_transient_kick",
-           "csr_transient_x", "csr_drift_kick", "csr_drift_factors", "lsc_kick", "lsc_scale_rho"]
+           "csr_transient_x", "csr_drift_kick", "csr_drift_factors", "lsc_kick", "lsc_scale_rho", "IBS_MAX_BINS", "ibs_kick",
+           "ibs_strength", "ibs_g", "ibs_normals"]
 
 #: CHX_WAKE_MAX_BINS of include/chx.h: the deposit's per-workgroup LDS histograms hold up to 3 channels of M 64-bit nodes; one grid
 #: and one deposit for the three kicks
-WAKE_MAX_BINS = CSR_MAX_BINS = LSC_MAX_BINS = 4096
+WAKE_MAX_BINS = CSR_MAX_BINS = LSC_MAX_BINS = IBS_MAX_BINS = 4096
 #: k_e = 1 / (4 pi eps0), V m / C (chx_grid1d_dev.h)
 _K_E = 8.9875517923e9
+#: r_e (m), m_e c^2 (eV) and e (C), as csrc/chx_ibs.hip
+_R_E = 2.8179403205e-15
+_M_E = 510998.95069
+_E_CHARGE = 1.602176634e-19
 
 
 class _Kick(NamedTuple):
@@ -254,6 +261,38 @@ def csr_drift_factors(energy: torch.Tensor, mass_eV: float, abs_charge_number: f
     return tuple(torch.where(kicks, torch.where(valid, f, nan), zero) for f in factors)
 
 
+def ibs_g(alpha: torch.Tensor) -> torch.Tensor:
+    """Bane's g(alpha) = (2 sqrt(alpha) / pi) int_0^inf du / sqrt((1 + u^2)(alpha^2 + u^2)) in closed form, sqrt(alpha) / AGM(1, alpha),
+    with exactly 8 steps of the arithmetic-geometric mean (a, b) <- ((a + b) / 2, sqrt(a b)), as the kernel forms it."""
+    a, c = torch.ones_like(alpha), alpha
+    for _ in range(8):
+        a, c = 0.5 * (a + c), (a * c).sqrt()
+    return alpha.sqrt() / a
+
+
+def ibs_strength(energy: torch.Tensor, mass_eV: float, abs_z: float, length: torch.Tensor, coulomb_log: torch.Tensor,
+                 sigma_x: torch.Tensor, sigma_y: torch.Tensor, eps_x: torch.Tensor, eps_y: torch.Tensor, h: torch.Tensor) -> torch.Tensor:
+    """K / h in float64, K = sqrt(pi) r_c^2 Lambda L g(alpha) / (4 gamma^3 sqrt(eps_x eps_y sigma_x sigma_y) |Z| e) with alpha =
+    (sigma_x eps_y) / (sigma_y eps_x) and r_c = Z^2 r_e m_e / m, broadcast of the shapes: the factor between the deposits D_k (coulomb)
+    and the node variances of delta that the kernels form on the device, restated here for the chain rule of the backward pass. `h`
+    is the node spacing of the forward's state header, a constant; a row without a grid (h = 0) has the factor 0. A row in which
+    Lambda, a size or an emittance is not > 0 or not finite has NaN."""
+    gamma = energy.to(torch.float64) / mass_eV
+    L, lam, sx, sy, ex, ey = (t.to(torch.float64) for t in (length, coulomb_log, sigma_x, sigma_y, eps_x, eps_y))
+    ok = torch.ones((), dtype=torch.bool, device=h.device)
+    for t in (lam, sx, sy, ex, ey):
+        ok = ok & (t > 0) & torch.isfinite(t)
+    one = torch.ones((), dtype=torch.float64, device=h.device)
+    sx, sy, ex, ey = (torch.where(ok, t, one) for t in (sx, sy, ex, ey))
+    rc = abs_z * abs_z * _R_E * _M_E / mass_eV
+    g = ibs_g((sx * ey) / (sy * ex))
+    K = math.sqrt(math.pi) * (rc * rc) * lam * L * g / (4.0 * (gamma * gamma * gamma) * (ex * ey * sx * sy).sqrt() * abs_z * _E_CHARGE)
+    grid = h > 0
+    Kh = K / torch.where(grid, h, torch.ones_like(h))
+    Kh = torch.where(ok, Kh, torch.full_like(Kh, float("nan")))
+    return torch.where(grid, Kh, torch.zeros_like(Kh))
+
+
 _CSR = _kick("CSRKick", "csr", (8, 1), 1,                                           # CHX_CSR_STATE_DOUBLES
              lambda state, mass_eV, abs_z, e, L, a: (csr_scale(e, mass_eV, abs_z, L, a),))
 _CSR_TRANSIENT = _kick("TransientCSRKick", "csr_transient", (8 + 2, 2), 2,          # CHX_CSR_TRANSIENT_STATE_DOUBLES
@@ -263,31 +302,45 @@ _CSR_DRIFT = _kick("CSRDriftKick", "csr_drift", (8 + 4, 2), 4,                  
                    lambda state, mass_eV, abs_z, e, L, Lb, a, d: csr_drift_factors(e, mass_eV, abs_z, L, Lb, a, d, state[:, 2]))
 _LSC = _kick("LSCKick", "lsc", (8 + 2, 2), 2,                                       # CHX_LSC_STATE_DOUBLES
              lambda state, mass_eV, abs_z, e, L, a: lsc_scale_rho(e, mass_eV, abs_z, L, a, state[:, 2]))
+_IBS = _kick("IBSKick", "ibs", (8, 2), 1,                                           # CHX_IBS_STATE_DOUBLES
+             lambda state, mass_eV, abs_z, e, L, lam, sx, sy, ex, ey: (ibs_strength(e, mass_eV, abs_z, L, lam, sx, sy, ex, ey,
+                                                                                    state[:, 2]),))
 
 
-def _settings_args(settings, mass_eV: float, abs_z: float):
-    return (*map(ptr, settings), mass_eV, abs_z), tuple(t.shape[0] for t in settings)
+def _settings_args(settings, mass_eV: float, abs_z: float, rng=None):
+    """(head, tail) of `_kick_raw`. `rng`: (seed, stream, call index) of a kick that draws, the call index a one-element int64 device
+    tensor that the kernel reads."""
+    key = () if rng is None else (rng[0], rng[1], ptr(rng[2]))
+    return (*map(ptr, settings), mass_eV, abs_z, *key), tuple(t.shape[0] for t in settings)
 
 
 class _SettingsKick(torch.autograd.Function):
-    """out (B, N, 7) = chx_{csr,csr_transient,csr_drift,lsc}_kick(x, q, w, *settings): the energy e, the length L and the kick's further
-    settings (angle, radius, distance), each (1,) or (B,) in the beam dtype; backward = the kick's _bwd call: gradients of the
+    """out (B, N, 7) = chx_{csr,csr_transient,csr_drift,lsc,ibs}_kick(x, q, w, *settings): the energy e, the length L and the kick's further
+    settings (angle, radius, distance, Coulomb logarithm, moments), each (1,) or (B,) in the beam dtype; backward = the kick's _bwd call: gradients of the
     particles, the charges and survival probabilities (through c = |q| w), and of the settings through the per-row cotangents of the
-    kick's factors. The node grid (tau range) is a constant."""
+    kick's factors. The node grid (tau range) is a constant. `rng`: None, or (seed, stream, call index) of a kick that draws (IBS): the
+    backward pass draws the same deviates again from a clone of the call index the forward pass used; the deviates are constants."""
 
     @staticmethod
-    def forward(ctx, kick, mass_eV, abs_z, B, M, x, q, w, *settings):
-        out, state = _kick_raw(kick, x, q, w, *_settings_args(settings, mass_eV, abs_z), B, x.shape[1], M)
-        ctx.save_for_backward(x, q, w, state, *settings)
+    def forward(ctx, kick, mass_eV, abs_z, B, M, rng, x, q, w, *settings):
+        out, state = _kick_raw(kick, x, q, w, *_settings_args(settings, mass_eV, abs_z, rng), B, x.shape[1], M)
+        # the value this call used: the element advances its own buffer in place right after the kick
+        call = () if rng is None else (rng[2].clone(),)
+        ctx.save_for_backward(x, q, w, state, *call, *settings)
         ctx.kick, ctx.B, ctx.M, ctx.mass_eV, ctx.abs_z = kick, B, M, mass_eV, abs_z
+        ctx.key = None if rng is None else rng[:2]
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         x, q, w, state, *given = ctx.saved_tensors
+        head = ()
+        if ctx.key is not None:
+            call, *given = given
+            head = (*ctx.key, ptr(call))
         kick, B, M, N = ctx.kick, ctx.B, ctx.M, x.shape[1]
-        need = ctx.needs_input_grad[5:]
-        dX, dC, d_rows = _kick_bwd_raw(kick, x, q, w, (), state, d_out.contiguous().to(x.dtype), B, N, M, need[1] or need[2])
+        need = ctx.needs_input_grad[6:]
+        dX, dC, d_rows = _kick_bwd_raw(kick, x, q, w, head, state, d_out.contiguous().to(x.dtype), B, N, M, need[1] or need[2])
         settings = [None] * len(given)
         wanted = [i for i in range(len(given)) if need[3 + i]]
         if wanted:
@@ -300,19 +353,20 @@ class _SettingsKick(torch.autograd.Function):
                 grads = torch.autograd.grad([o for o, _ in outs], [leaves[i] for i in wanted], [d for _, d in outs])
             for i, g in zip(wanted, grads):
                 settings[i] = g.to(x.dtype)
-        return None, None, None, None, None, *_beam_grads(dX, dC, x, q, w, B, need), *settings
+        return None, None, None, None, None, None, *_beam_grads(dX, dC, x, q, w, B, need), *settings
 
 
-def _settings_kick(kick: _Kick, particles, charges, survival, mass_eV, abs_charge_number, settings, num_bins):
-    """`settings`: the energy, the length and the kick's further settings, in the order of the C entry point."""
-    x, q, w, batch_shape, B = _beam_rows(kick, particles, charges, survival, *settings)
+def _settings_kick(kick: _Kick, particles, charges, survival, mass_eV, abs_charge_number, settings, num_bins, rng=None):
+    """`settings`: the energy, the length and the kick's further settings, in the order of the C entry point. `rng`: (seed, stream,
+    call index) of a kick that draws."""
+    x, q, w, batch_shape, B = _beam_rows(kick, particles, charges, survival, *settings, others=() if rng is None else (rng[2],))
     N = particles.shape[-2]
     rows = tuple(_rows(t, batch_shape, B, particles.dtype) for t in settings)
     grads = torch.is_grad_enabled() and any(t.requires_grad for t in (x, q, w, *rows))
     if grads:
-        out = _SettingsKick.apply(kick, float(mass_eV), float(abs_charge_number), B, num_bins, x, q, w, *rows)
+        out = _SettingsKick.apply(kick, float(mass_eV), float(abs_charge_number), B, num_bins, rng, x, q, w, *rows)
     else:
-        out, _ = _kick_raw(kick, x, q, w, *_settings_args(rows, float(mass_eV), float(abs_charge_number)), B, N, num_bins)
+        out, _ = _kick_raw(kick, x, q, w, *_settings_args(rows, float(mass_eV), float(abs_charge_number), rng), B, N, num_bins)
     return out.reshape(*batch_shape, N, 7)
 
 
@@ -355,3 +409,30 @@ def lsc_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Ten
     particles (*batch, N, 7). Differentiable with respect to the particles, charges, survival probabilities, energy, length and
     radius."""
     return _settings_kick(_LSC, particles, charges, survival, mass_eV, abs_charge_number, (energy, length, radius), num_bins)
+
+
+def ibs_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Tensor, energy: torch.Tensor, mass_eV: float,
+             abs_charge_number: float, length: torch.Tensor, coulomb_log: torch.Tensor, sigma_x: torch.Tensor, sigma_y: torch.Tensor,
+             eps_x: torch.Tensor, eps_y: torch.Tensor, num_bins: int, seed: int, stream: int, call_index: torch.Tensor) -> torch.Tensor:
+    """The intrabeam-scattering kick of a section of length `length` on a beam of rms sizes `sigma_x`, `sigma_y` and geometric
+    emittances `eps_x`, `eps_y`, with the Coulomb logarithm `coulomb_log`, of any batch shape (broadcast of the particles', charges',
+    survival probabilities', energy's and the six settings' batch shapes) -> particles (*batch, N, 7). `seed`, `stream`: the 32-bit
+    halves of the generator's key; `call_index`: a one-element int64 device tensor, the upper half of its counter, which the kernel
+    reads and the caller advances. Differentiable with respect to the particles, charges, survival probabilities, energy and the six
+    settings; the deviates are constants."""
+    if call_index.dtype != torch.int64 or call_index.numel() != 1:
+        raise TypeError("ibs_kick: call_index must be a one-element int64 tensor")
+    return _settings_kick(_IBS, particles, charges, survival, mass_eV, abs_charge_number,
+                          (energy, length, coulomb_log, sigma_x, sigma_y, eps_x, eps_y), num_bins, (int(seed), int(stream), call_index))
+
+
+def ibs_normals(seed: int, stream: int, call: int, B: int, N: int, device) -> tuple[torch.Tensor, torch.Tensor]:
+    """The kick's draw for call index `call`: (words (B, N, 4) as int64 values 0 ... 2^32 - 1, xi (B, N) float64) — the raw
+    Philox4x32-10 output for the counter (n, b + 2^31, call_lo, call_hi) and the standard normal deviate of every (batch row, particle)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("cheetah_amd draws on the GPU only (HIP kernels, no CPU fallback)")
+    words = torch.empty((B, N, 4), dtype=torch.int32, device=device)
+    xi = torch.empty((B, N), dtype=torch.float64, device=device)
+    check(_lib.lib().chx_ibs_normals(int(seed), int(stream), int(call), B, N, ptr(words), ptr(xi), stream_ptr()), "chx_ibs_normals")
+    return words.to(torch.int64) & 0xFFFFFFFF, xi

@@ -5,6 +5,7 @@ from .custom_transfer_map import CustomTransferMap  # noqa: F401
 from .dipole import Dipole, RBend  # noqa: F401
 from .drift import Drift  # noqa: F401
 from .element import Element, PhysicsWarning  # noqa: F401
+from .ibs import IBSKick  # noqa: F401
 from .laser_modulator import LaserModulator, laser_modulation_amplitude  # noqa: F401
 from .lsc import LSCKick  # noqa: F401
 from .marker import BPM, Aperture, Marker  # noqa: F401

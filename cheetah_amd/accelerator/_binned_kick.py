@@ -1,5 +1,5 @@
 """BinnedKick: the base of the elements whose kick follows the beam's current profile, binned on `num_bins` nodes in tau (`Wakefield`,
-`CSRKick`, `TransientCSRKick`, `CSRDriftKick`, `LSCKick`), and the argument checks they share with the methods that put such kicks into a lattice."""
+`CSRKick`, `TransientCSRKick`, `CSRDriftKick`, `LSCKick`, `IBSKick`), and the argument checks they share with the methods that put such kicks into a lattice."""
 
 from __future__ import annotations
 

@@ -2003,6 +2003,64 @@ class Segment(Element):
             elements += elements_of_e
         return self.__class__(elements=elements, name=self.name, metadata=deepcopy(self.metadata))
 
+    def with_ibs_kicks(self, coulomb_log=10.0, num_bins: int = 200, max_step=None, seed: int = 0, except_for=None,
+                       first_stream: int = 0) -> "Segment":
+        """Every element with a `length` that is anywhere > 0 followed by an `IBSKick(element.length, coulomb_log, num_bins=num_bins,
+        seed=seed, stream=...)` that takes its four moments from the beam, nested Segments included. The placement is
+        `with_lsc_kicks`': the kick's `effect_length` IS the element's `length` tensor, so in-place edits and gradients follow; with
+        `max_step` (metres) an element longer than that is first split with its own `split(resolution=max_step)` and every piece
+        gets its kick; names in `except_for`, the collective kicks already there (`LSCKick`, `CSRKick`, `TransientCSRKick`,
+        `CSRDriftKick`, `Wakefield`, `SpaceChargeKick`) and `IBSKick`s get none. The kicks' `stream` counts `first_stream`,
+        `first_stream` + 1, ... in lattice order, as in `with_radiation_kicks`, so no two kicks of the lattice draw the same
+        deviates. The model has no dispersion term: keep the bends of a chicane in `except_for`, or give them kicks with explicit
+        moments."""
+        from ._binned_kick import check_num_bins
+        from .ibs import check_positive
+        from .synchrotron_radiation import check_key_word
+
+        owner = "Segment.with_ibs_kicks"
+        check_num_bins(num_bins, owner)
+        check_key_word(seed, "seed", owner)
+        check_key_word(first_stream, "first_stream", owner)
+        if coulomb_log is None:
+            raise ValueError(f"{owner}: coulomb_log must be finite and > 0, got None")
+        check_positive(coulomb_log, "coulomb_log", owner)
+        step = None
+        if max_step is not None:
+            step = float(max_step)
+            if not step > 0.0 or step == float("inf"):
+                raise ValueError(f"{owner}: max_step must be a finite length > 0 (metres), got {max_step!r}")
+        return self._with_ibs_kicks(coulomb_log, num_bins, step, seed, except_for or [], first_stream)[0]
+
+    def _with_ibs_kicks(self, coulomb_log, num_bins, step, seed, except_for, stream):
+        """(the segment with the kicks, the first stream not used yet)"""
+        from .csr import CSRDriftKick, CSRKick, TransientCSRKick
+        from .ibs import IBSKick
+        from .lsc import LSCKick
+        from .space_charge_kick import SpaceChargeKick
+        from .wakefield import Wakefield
+
+        elements = []
+        for e in self.elements:
+            if isinstance(e, Segment):
+                e, stream = e._with_ibs_kicks(coulomb_log, num_bins, step, seed, except_for, stream)
+                elements.append(e)
+                continue
+            pieces = [e]
+            if not isinstance(e, (IBSKick, LSCKick, CSRKick, TransientCSRKick, CSRDriftKick, Wakefield, SpaceChargeKick)) \
+                    and e.name not in except_for and bool((e.length > 0).any()):
+                if step is not None and bool((e.length > step).any()):
+                    pieces = e.split(torch.as_tensor(step, device=e.length.device, dtype=e.length.dtype))
+                kw = {"device": e.length.device, "dtype": e.length.dtype}
+                with_kicks = []
+                for piece in pieces:
+                    with_kicks += [piece, IBSKick(piece.length, coulomb_log=coulomb_log, num_bins=num_bins, seed=seed, stream=stream,
+                                                  name=f"{piece.name}_ibs_kick", sanitize_name=False, **kw)]
+                    stream += 1
+                pieces = with_kicks
+            elements += pieces
+        return self.__class__(elements=elements, name=self.name, metadata=deepcopy(self.metadata)), stream
+
     def _no_plot(self, *args, **kwargs):
         raise NotImplementedError("Segment.plot_*: plotting is outside this tracking engine (SURVEY.md section 2); "
                                   "`get_beam_attrs_along_segment` gives the numbers the reference's plots draw")

@@ -6,7 +6,8 @@
 //   g = gamma0 + delta P0,  pi = sqrt(g^2 - 1),  g' = g - a P0^2 pi g - sqrt(b P0^3 g^7 / pi^3) xi
 //   delta' = delta + (g' - g) / P0,  pi' = sqrt(g'^2 - 1),  px' = px pi' / pi,  py' = py pi' / pi
 // xi is one standard normal per (kick, call, batch row, particle): Philox4x32-10 with key (seed, stream) and counter (particle n,
-// flat batch row b, call_lo, call_hi), its four words turned into two uniforms on the 53-bit grid and one Box-Muller cosine branch.
+// flat batch row b, call_lo, call_hi), its four words turned into two uniforms on the 53-bit grid and one Box-Muller cosine branch
+// (chx_philox.h).
 // The call index is read from device memory, so a captured graph follows it. Nothing of xi is stored: the backward pass draws it
 // again from the same counter.
 //   F. sr_kick_kernel      one workgroup per (row tile, batch row): the tile's rows through LDS (coalesced 16-byte transfers of the
@@ -16,6 +17,7 @@
 //                          (gamma0, a, b) (P0 = sqrt(gamma0^2 - 1) folded into gamma0's)
 //   B2. sr_rows_kernel     one workgroup per batch row adds the partials in a fixed order: bitwise reproducible, no float atomics
 #include "chx_apply_tiles.h"
+#include "chx_philox.h"
 
 namespace {
 
@@ -32,33 +34,10 @@ struct SrKey {
     uint32_t seed, stream;
 };
 
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t (&w)[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
-
-// u = ((the 64-bit word >> 11) + 1/2) 2^-53 for both halves, xi = sqrt(-2 ln u1) cospi(2 u2)
-__device__ __forceinline__ double sr_normal_of(const uint32_t (&w)[4]) {
-    const uint64_t k1 = (((uint64_t)w[0] << 32) | w[1]) >> 11, k2 = (((uint64_t)w[2] << 32) | w[3]) >> 11;
-    const double u1 = ((double)k1 + 0.5) * 0x1p-53, u2 = ((double)k2 + 0.5) * 0x1p-53;
-    return sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
-}
-
 __device__ __forceinline__ double sr_normal(SrKey key, uint64_t call, int64_t b, int64_t n) {
     uint32_t w[4];
     philox4x32_10((uint32_t)n, (uint32_t)b, (uint32_t)call, (uint32_t)(call >> 32), key.seed, key.stream, w);
-    return sr_normal_of(w);
+    return philox_normal_of(w);
 }
 
 // The row's factors {gamma0, P0, a, b} in fp64; beta0 as `Beam.p0c` forms it. A negative L gives NaN.
@@ -241,7 +220,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void sr_normals_kernel(SrKey key, uint64
     philox4x32_10((uint32_t)n, (uint32_t)b, (uint32_t)call, (uint32_t)(call >> 32), key.seed, key.stream, w);
     uint4* dst = reinterpret_cast<uint4*>(words) + (b * N + n);
     *dst = make_uint4(w[0], w[1], w[2], w[3]);
-    xi[b * N + n] = sr_normal_of(w);
+    xi[b * N + n] = philox_normal_of(w);
 }
 
 // B rows are grid.y and the particle index is a 32-bit counter word

@@ -468,6 +468,40 @@ int chx_sr_kick_bwd(const void* x, const void* energy, const void* length, const
                     double* d_a, double* d_b, void* workspace, size_t workspace_bytes, void* stream);
 int chx_sr_normals(uint32_t seed, uint32_t rng_stream, uint64_t call, int64_t B, int64_t N, uint32_t* words_out, double* xi_out,
                    void* stream);
+/* ---- intrabeam scattering (IBSKick element): the growth of the slice energy spread along the bunch, Bane's high-energy approximation
+ * of the Bjorken-Mtingwa rate (EPAC 2002) without dispersion and with beta = 1, the bunch average N / sigma_s replaced by the local
+ * line density. Per batch row b, the surviving particles' grid and node-based linear deposit D_k (coulomb) exactly as chx_lsc_kick's
+ * (same tau_lo, node spacing h, u, k, f, clamping, dead particles); in fp64, with gamma = energy / mass_eV, r_c = abs_charge^2 r_e m_e / m:
+ *   alpha = (sigma_x eps_y) / (sigma_y eps_x), g = sqrt(alpha) / AGM(1, alpha) (8 steps of (a, b) <- ((a + b) / 2, sqrt(a b)), result a),
+ *   K = sqrt(pi) r_c^2 Lambda L g / (4 gamma^3 sqrt(eps_x eps_y sigma_x sigma_y) abs_charge e),   V_k = (K / h) D_k
+ * and every particle (dead ones too) gets delta += sqrt(V(u)) xi with V(u) = (1 - f) V_k + f V_(k+1) (fp64, rounded once). Where V(u)
+ * is 0 (both nodes empty, L = 0) delta keeps its bits; every other column always does. A NaN tau gives NaN unless both nodes are
+ * empty. A row in which Lambda, sigma_x, sigma_y, eps_x or eps_y is not > 0 or not finite gets NaN in delta. A row without surviving
+ * particles or with h = 0 is copied bit for bit. xi as chx_sr_kick's, with the counter (n, b + 2^31, call_lo, call_hi): bit 31 of the
+ * second word keeps the draws apart from chx_sr_kick's at the same key and call index. call_index: ONE int64 in device memory, read
+ * by the kernels (a captured graph follows it); the caller advances it. energy[Be], length[Bl], coulomb_log[Bc], sigma_x[Bsx],
+ * sigma_y[Bsy], eps_x[Bex], eps_y[Bey] (geometric emittances, m): device arrays of the beam's dtype, each 1 or B rows.
+ * out[B][N][7], state[B][CHX_IBS_STATE_DOUBLES(M)] (row header as chx_wake_kick's with K / h in its last slot, the M node variances
+ * V_k, the M deposits D_k). 1 <= N < 2^31, 2 <= M <= CHX_WAKE_MAX_BINS. Deterministic (64-bit fixed-point deposit, fixed-order sums).
+ * workspace: chx_ibs_workspace_bytes(B, N, M) (also for the backward pass).
+ * chx_ibs_kick_bwd: given d_out[B][N][7] (dtype), the forward's state and the call index the forward used -> dX[B][N][7] (delta's
+ * cotangent passes through; tau's through V(u) and through the deposit), dC[B][N] (dtype; gradient with respect to c = |q| w, 0 for
+ * particles that do not deposit; may be NULL) and d_scale[B] (fp64, gradient with respect to the row's K / h: the caller chains it to
+ * the seven settings). xi is drawn again. A particle whose V(u) is not > 0 has zero gradient through V. The node grid is a constant.
+ * Bitwise reproducible, no float atomics. Rows of broadcast inputs are NOT reduced — the caller sums.
+ * chx_ibs_normals: the draw itself, words_out[B][N][4] (uint32, 16-byte aligned) and xi_out[B][N] (fp64), `call` by value. */
+#define CHX_IBS_STATE_DOUBLES(M) (CHX_WAKE_STATE_HEADER + 2 * (int64_t)(M))
+size_t chx_ibs_workspace_bytes(int64_t B, int64_t N, int32_t M);
+int chx_ibs_kick(const void* x, const void* q, const void* w, const void* energy, const void* length, const void* coulomb_log,
+                 const void* sigma_x, const void* sigma_y, const void* eps_x, const void* eps_y, double mass_eV, double abs_charge,
+                 uint32_t seed, uint32_t rng_stream, const int64_t* call_index, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                 int64_t Be, int64_t Bl, int64_t Bc, int64_t Bsx, int64_t Bsy, int64_t Bex, int64_t Bey, int64_t N, int32_t M,
+                 int dtype, void* out, double* state, void* workspace, size_t workspace_bytes, void* stream);
+int chx_ibs_kick_bwd(const void* x, const void* q, const void* w, uint32_t seed, uint32_t rng_stream, const int64_t* call_index,
+                     int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M, int dtype, const double* state,
+                     const void* d_out, void* dX, void* dC, double* d_scale, void* workspace, size_t workspace_bytes, void* stream);
+int chx_ibs_normals(uint32_t seed, uint32_t rng_stream, uint64_t call, int64_t B, int64_t N, uint32_t* words_out, double* xi_out,
+                    void* stream);
 /* ---- laser energy modulation in an undulator (LaserModulator element; Huang et al., PRSTAB 7, 074401 (2004), eq. 8), as one
  * zero-length kick. Per batch row b, in fp64, with gamma0 = energy / mass_eV, P0 = beta0 gamma0 (as chx_sr_kick forms them), the
  * amplitude A (eV), the wavelength lambda, the phase phi, the rms size sigma_r of the laser intensity, the laser axis (x0, y0), the rms
