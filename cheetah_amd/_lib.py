@@ -347,6 +347,13 @@ SIGNATURES = {
                                       c_void_p]),
     "chx_build_rmatrix_scalars": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_double, c_double, c_int, c_void_p, c_void_p]),
 }
+# the twins with a cutoff of the binned-beam kicks: cutoff[Bcut] (float64 device array) and Bcut in front of the workspace, and
+# their workspace queries
+for _tag in ("wake", "csr", "csr_transient", "csr_drift", "lsc", "ibs"):
+    for _call in ("kick", "kick_bwd"):
+        _res, _args = SIGNATURES[f"chx_{_tag}_{_call}"]
+        SIGNATURES[f"chx_{_tag}_{_call}_cut"] = (_res, _args[:-3] + [c_void_p, c_i64] + _args[-3:])
+    SIGNATURES[f"chx_{_tag}_workspace_bytes_cut"] = SIGNATURES[f"chx_{_tag}_workspace_bytes"]
 
 _lib = None
 

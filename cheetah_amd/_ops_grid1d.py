@@ -4,7 +4,8 @@ delta, px, py), the steady-state CSR (CSRKick: the anti-causal Toeplitz sum with
 entrance transient (TransientCSRKick: the same sum with the table of the slippage length reached inside the bend), the CSR in the
 drift behind a bend (CSRDriftKick: the same sum with the table of the radiation that left the bend and catches up) and the
 longitudinal space charge (LSCKick: the two-sided Toeplitz sum with the on-axis field of a charged disc). Each is one
-`chx_*_kick` call (four launches, deterministic, no host synchronisation) and an autograd node whose backward is `chx_*_kick_bwd`.
+`chx_*_kick` call (four launches, five with a `cutoff_wavelength`: the Gaussian low-pass filter of the deposit between the deposit
+and the node pass; deterministic, no host synchronisation) and an autograd node whose backward is `chx_*_kick_bwd`.
 The CSR and LSC kicks form their per-row factors on the device from the energy and their further settings (length, angle, radius,
 distance); they share one node. So does the intrabeam-scattering kick (IBSKick), whose node quantity is a variance V_k = K D_k / h:
 every particle gets delta += sqrt(V(u)) xi with a deviate drawn inside the kernel (Philox4x32-10, as `_ops_sr`).
@@ -62,6 +63,17 @@ def _rows(t: torch.Tensor, batch_shape, B: int, dtype):
     return t.expand(batch_shape).reshape(B).contiguous()
 
 
+def _opt(t) -> tuple:
+    """An optional tensor as the arguments it adds to a call: none, or itself."""
+    return () if t is None else (t,)
+
+
+# The low-pass filter every kick of this module takes as `cutoff_wavelength` (metres; None: the raw deposit), as include/chx.h states
+# it. Per batch row, with h the row's node spacing: s = cutoff / (2 pi h), R = max(1, min(ceil(4 s), M - 1)), g_d = exp(-d^2 / 2 s^2)
+# for |d| <= R, normalised to sum 1; D'_j = sum_d g_d D_refl(j - d) with the row mirrored about its ends (numpy's
+# pad(mode="symmetric")). Amplitude response exp(-(cutoff / lambda)^2 / 2); the charge is kept; a constant of the kick (no gradient).
+
+
 def _beam_rows(kick: _Kick, particles, charges, survival, *row_settings, others=()):
     """The beam as flat rows: x (Bx, N, 7) aligned, q (Bq, N), w (Bw, N) in the particles' dtype, and the batch shape (broadcast of
     the particles', charges', survival probabilities' and row settings' batch shapes) with its number of rows B. `others`: further
@@ -78,32 +90,42 @@ def _beam_rows(kick: _Kick, particles, charges, survival, *row_settings, others=
     return aligned(x), q.contiguous(), w.contiguous(), batch_shape, B
 
 
-def _kick_raw(kick: _Kick, x, q, w, head, tail, B: int, N: int, M: int):
-    """The forward entry point on flat inputs x (Bx, N, 7), q (Bq, N), w (Bw, N) -> (out (B, N, 7), state (B, state_doubles)
-    float64), state_doubles = s0 + s1 M. `head`: the kick's own arguments between w and B, `tail`: those between Bw and N."""
+def _cutoff_rows(cutoff, batch_shape, B: int):
+    """The cutoff wavelength as float64 rows, (1,) or (B,), or None. A constant of the kick: detached."""
+    return None if cutoff is None else _rows(cutoff.detach(), batch_shape, B, torch.float64)
+
+
+def _cut_call(kick: _Kick, name: str, cut, B: int, N: int, M: int, device):
+    """(entry point, its arguments in front of the workspace, workspace, its bytes): the call itself without a cutoff, its twin and
+    the twin's workspace with cutoff rows."""
     lib = _lib.lib()
-    ws_bytes = getattr(lib, kick.workspace)(B, N, M)
-    ws = workspace(ws_bytes, x.device)
+    suffix, cut_args = ("", ()) if cut is None else ("_cut", (ptr(cut), cut.shape[0]))
+    ws_bytes = getattr(lib, kick.workspace + suffix)(B, N, M)
+    return getattr(lib, name + suffix), name + suffix, cut_args, workspace(ws_bytes, device), ws_bytes
+
+
+def _kick_raw(kick: _Kick, x, q, w, head, tail, B: int, N: int, M: int, cut=None):
+    """The forward entry point on flat inputs x (Bx, N, 7), q (Bq, N), w (Bw, N) -> (out (B, N, 7), state (B, state_doubles)
+    float64), state_doubles = s0 + s1 M. `head`: the kick's own arguments between w and B, `tail`: those between Bw and N. `cut`:
+    None, or the cutoff wavelengths of the low-pass filter of the deposit as float64 rows (1,) or (B,)."""
+    call, name, cut_args, ws, ws_bytes = _cut_call(kick, kick.forward, cut, B, N, M, x.device)
     out = torch.empty((B, N, 7), dtype=x.dtype, device=x.device)
     state = torch.empty((B, kick.state_doubles[0] + kick.state_doubles[1] * M), dtype=torch.float64, device=x.device)
-    check(getattr(lib, kick.forward)(ptr(x), ptr(q), ptr(w), *head, B, x.shape[0], q.shape[0], w.shape[0], *tail, N, M,
-                                     dtype_code(x.dtype), ptr(out), ptr(state), ptr(ws), ws_bytes, stream_ptr()), kick.forward)
+    check(call(ptr(x), ptr(q), ptr(w), *head, B, x.shape[0], q.shape[0], w.shape[0], *tail, N, M, dtype_code(x.dtype), ptr(out),
+               ptr(state), *cut_args, ptr(ws), ws_bytes, stream_ptr()), name)
     return out, state
 
 
-def _kick_bwd_raw(kick: _Kick, x, q, w, head, state, d_out, B: int, N: int, M: int, need_c: bool, extra=()):
+def _kick_bwd_raw(kick: _Kick, x, q, w, head, state, d_out, B: int, N: int, M: int, need_c: bool, extra=(), cut=None):
     """The backward entry point: (dX (B, N, 7), dC (B, N) | None, the per-row cotangents (B,) float64); rows of broadcast inputs not
-    summed. `extra`: the kick's own gradient outputs (or None) behind the per-row cotangents."""
+    summed. `extra`: the kick's own gradient outputs (or None) behind the per-row cotangents. `cut`: as the forward call's."""
     kw = {"dtype": x.dtype, "device": x.device}
     dX = torch.empty((B, N, 7), **kw)
     dC = torch.empty((B, N), **kw) if need_c else None
     d_rows = [torch.empty((B,), dtype=torch.float64, device=x.device) for _ in range(kick.cotangents)]
-    lib = _lib.lib()
-    ws_bytes = getattr(lib, kick.workspace)(B, N, M)
-    ws = workspace(ws_bytes, x.device)
-    check(getattr(lib, kick.backward)(ptr(x), ptr(q), ptr(w), *head, B, x.shape[0], q.shape[0], w.shape[0], N, M, dtype_code(x.dtype),
-                                      ptr(state), ptr(d_out), ptr(dX), ptr(dC), *map(ptr, d_rows), *map(ptr, extra),
-                                      ptr(ws), ws_bytes, stream_ptr()), kick.backward)
+    call, name, cut_args, ws, ws_bytes = _cut_call(kick, kick.backward, cut, B, N, M, x.device)
+    check(call(ptr(x), ptr(q), ptr(w), *head, B, x.shape[0], q.shape[0], w.shape[0], N, M, dtype_code(x.dtype), ptr(state),
+               ptr(d_out), ptr(dX), ptr(dC), *map(ptr, d_rows), *map(ptr, extra), *cut_args, ptr(ws), ws_bytes, stream_ptr()), name)
     return dX, dC, d_rows
 
 
@@ -148,26 +170,26 @@ def _wake_head(scale, wl, wt, h):
 class WakeKick(torch.autograd.Function):
     """out (B, N, 7) = chx_wake_kick(x, q, w, scale, wl, wt); backward = chx_wake_kick_bwd: gradients of the particles, the charges
     and survival probabilities (through c = |q| w), the per-row scale factor |Z| / p0c and both tables (summed over the rows). The
-    node grid (tau range) and the wake spacing h are constants."""
+    node grid (tau range), the wake spacing h and the cutoff rows `cut` (or None) are constants."""
 
     @staticmethod
-    def forward(ctx, x, q, w, scale, wl, wt, h, B, M):
-        out, state = _kick_raw(_WAKE, x, q, w, _wake_head(scale, wl, wt, h), (), B, x.shape[1], M)
-        ctx.save_for_backward(x, q, w, scale, wl, wt, h, state)
+    def forward(ctx, x, q, w, scale, wl, wt, h, B, M, cut=None):
+        out, state = _kick_raw(_WAKE, x, q, w, _wake_head(scale, wl, wt, h), (), B, x.shape[1], M, cut)
+        ctx.save_for_backward(x, q, w, scale, wl, wt, h, state, cut)
         ctx.B, ctx.M = B, M
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        x, q, w, scale, wl, wt, h, state = ctx.saved_tensors
+        x, q, w, scale, wl, wt, h, state, cut = ctx.saved_tensors
         B, M, N = ctx.B, ctx.M, x.shape[1]
         need = ctx.needs_input_grad
         f64 = {"dtype": torch.float64, "device": x.device}
         d_wl = torch.empty((wl.numel(),), **f64) if need[4] and wl is not None else None
         d_wt = torch.empty((wt.numel(),), **f64) if need[5] and wt is not None else None
         dX, dC, (d_scale,) = _kick_bwd_raw(_WAKE, x, q, w, _wake_head(scale, wl, wt, h), state, d_out.contiguous().to(x.dtype), B, N, M,
-                                           need[1] or need[2], (d_wl, d_wt))
-        return *_beam_grads(dX, dC, x, q, w, B, need), (d_scale if need[3] else None), d_wl, d_wt, None, None, None
+                                           need[1] or need[2], (d_wl, d_wt), cut)
+        return *_beam_grads(dX, dC, x, q, w, B, need), (d_scale if need[3] else None), d_wl, d_wt, None, None, None, None
 
 
 def wake_scale(energy: torch.Tensor, mass_eV: float, abs_charge_number: float, factor: torch.Tensor) -> torch.Tensor:
@@ -177,13 +199,15 @@ def wake_scale(energy: torch.Tensor, mass_eV: float, abs_charge_number: float, f
 
 def wake_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Tensor, energy: torch.Tensor, mass_eV: float,
               abs_charge_number: float, factor: torch.Tensor, longitudinal_wake, transverse_wake, wake_spacing: torch.Tensor,
-              num_bins: int) -> torch.Tensor:
-    """The wake kick of a beam of any batch shape (broadcast of the particles', charges', survival probabilities', energy's and
-    factor's batch shapes) -> particles (*batch, N, 7). `longitudinal_wake` / `transverse_wake`: 1-D tables (V/C, V/(C m)) or
-    None; `wake_spacing`: 0-d tensor h (metres between table entries). Differentiable with respect to the particles, charges,
+              num_bins: int, cutoff_wavelength: torch.Tensor | None = None) -> torch.Tensor:
+    """The wake kick of a beam of any batch shape (broadcast of the particles', charges', survival probabilities', energy's,
+    factor's and cutoff's batch shapes) -> particles (*batch, N, 7). `longitudinal_wake` / `transverse_wake`: 1-D tables (V/C,
+    V/(C m)) or None; `wake_spacing`: 0-d tensor h (metres between table entries); `cutoff_wavelength`: None, or the cutoff (metres)
+    of the Gaussian low-pass filter of the deposits Q, X, Y. Differentiable with respect to the particles, charges,
     survival probabilities, energy, factor and both tables."""
-    x, q, w, batch_shape, B = _beam_rows(_WAKE, particles, charges, survival, energy, factor,
+    x, q, w, batch_shape, B = _beam_rows(_WAKE, particles, charges, survival, energy, factor, *_opt(cutoff_wavelength),
                                          others=(wake_spacing, longitudinal_wake, transverse_wake))
+    cut = _cutoff_rows(cutoff_wavelength, batch_shape, B)
     N = particles.shape[-2]
     scale = wake_scale(energy, mass_eV, abs_charge_number, factor).expand(batch_shape).reshape(B).contiguous()
     wl = None if longitudinal_wake is None else longitudinal_wake.to(torch.float64).contiguous()
@@ -191,9 +215,9 @@ def wake_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Te
     h = wake_spacing.detach().to(torch.float64).reshape(1)
     grads = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, q, w, scale, wl, wt))
     if grads:
-        out = WakeKick.apply(x, q, w, scale, wl, wt, h, B, num_bins)
+        out = WakeKick.apply(x, q, w, scale, wl, wt, h, B, num_bins, *_opt(cut))
     else:
-        out, _ = _kick_raw(_WAKE, x, q, w, _wake_head(scale, wl, wt, h), (), B, N, num_bins)
+        out, _ = _kick_raw(_WAKE, x, q, w, _wake_head(scale, wl, wt, h), (), B, N, num_bins, cut)
     return out.reshape(*batch_shape, N, 7)
 
 
@@ -319,28 +343,29 @@ class _SettingsKick(torch.autograd.Function):
     settings (angle, radius, distance, Coulomb logarithm, moments), each (1,) or (B,) in the beam dtype; backward = the kick's _bwd call: gradients of the
     particles, the charges and survival probabilities (through c = |q| w), and of the settings through the per-row cotangents of the
     kick's factors. The node grid (tau range) is a constant. `rng`: None, or (seed, stream, call index) of a kick that draws (IBS): the
-    backward pass draws the same deviates again from a clone of the call index the forward pass used; the deviates are constants."""
+    backward pass draws the same deviates again from a clone of the call index the forward pass used; the deviates are constants.
+    `cut`: None, or the cutoff rows of the low-pass filter, a constant."""
 
     @staticmethod
-    def forward(ctx, kick, mass_eV, abs_z, B, M, rng, x, q, w, *settings):
-        out, state = _kick_raw(kick, x, q, w, *_settings_args(settings, mass_eV, abs_z, rng), B, x.shape[1], M)
+    def forward(ctx, kick, mass_eV, abs_z, B, M, rng, cut, x, q, w, *settings):
+        out, state = _kick_raw(kick, x, q, w, *_settings_args(settings, mass_eV, abs_z, rng), B, x.shape[1], M, cut)
         # the value this call used: the element advances its own buffer in place right after the kick
         call = () if rng is None else (rng[2].clone(),)
-        ctx.save_for_backward(x, q, w, state, *call, *settings)
+        ctx.save_for_backward(cut, x, q, w, state, *call, *settings)
         ctx.kick, ctx.B, ctx.M, ctx.mass_eV, ctx.abs_z = kick, B, M, mass_eV, abs_z
         ctx.key = None if rng is None else rng[:2]
         return out
 
     @staticmethod
     def backward(ctx, d_out):
-        x, q, w, state, *given = ctx.saved_tensors
+        cut, x, q, w, state, *given = ctx.saved_tensors
         head = ()
         if ctx.key is not None:
             call, *given = given
             head = (*ctx.key, ptr(call))
         kick, B, M, N = ctx.kick, ctx.B, ctx.M, x.shape[1]
-        need = ctx.needs_input_grad[6:]
-        dX, dC, d_rows = _kick_bwd_raw(kick, x, q, w, head, state, d_out.contiguous().to(x.dtype), B, N, M, need[1] or need[2])
+        need = ctx.needs_input_grad[7:]
+        dX, dC, d_rows = _kick_bwd_raw(kick, x, q, w, head, state, d_out.contiguous().to(x.dtype), B, N, M, need[1] or need[2], cut=cut)
         settings = [None] * len(given)
         wanted = [i for i in range(len(given)) if need[3 + i]]
         if wanted:
@@ -353,77 +378,91 @@ class _SettingsKick(torch.autograd.Function):
                 grads = torch.autograd.grad([o for o, _ in outs], [leaves[i] for i in wanted], [d for _, d in outs])
             for i, g in zip(wanted, grads):
                 settings[i] = g.to(x.dtype)
-        return None, None, None, None, None, None, *_beam_grads(dX, dC, x, q, w, B, need), *settings
+        return None, None, None, None, None, None, None, *_beam_grads(dX, dC, x, q, w, B, need), *settings
 
 
-def _settings_kick(kick: _Kick, particles, charges, survival, mass_eV, abs_charge_number, settings, num_bins, rng=None):
+def _settings_kick(kick: _Kick, particles, charges, survival, mass_eV, abs_charge_number, settings, num_bins, rng=None, cutoff=None):
     """`settings`: the energy, the length and the kick's further settings, in the order of the C entry point. `rng`: (seed, stream,
-    call index) of a kick that draws."""
-    x, q, w, batch_shape, B = _beam_rows(kick, particles, charges, survival, *settings, others=() if rng is None else (rng[2],))
+    call index) of a kick that draws. `cutoff`: None, or the cutoff wavelength of the low-pass filter of the deposit."""
+    x, q, w, batch_shape, B = _beam_rows(kick, particles, charges, survival, *settings, *_opt(cutoff),
+                                         others=() if rng is None else (rng[2],))
+    cut = _cutoff_rows(cutoff, batch_shape, B)
     N = particles.shape[-2]
     rows = tuple(_rows(t, batch_shape, B, particles.dtype) for t in settings)
     grads = torch.is_grad_enabled() and any(t.requires_grad for t in (x, q, w, *rows))
     if grads:
-        out = _SettingsKick.apply(kick, float(mass_eV), float(abs_charge_number), B, num_bins, rng, x, q, w, *rows)
+        out = _SettingsKick.apply(kick, float(mass_eV), float(abs_charge_number), B, num_bins, rng, cut, x, q, w, *rows)
     else:
-        out, _ = _kick_raw(kick, x, q, w, *_settings_args(rows, float(mass_eV), float(abs_charge_number), rng), B, N, num_bins)
+        out, _ = _kick_raw(kick, x, q, w, *_settings_args(rows, float(mass_eV), float(abs_charge_number), rng), B, N, num_bins, cut)
     return out.reshape(*batch_shape, N, 7)
 
 
 def csr_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Tensor, energy: torch.Tensor, mass_eV: float,
-             abs_charge_number: float, length: torch.Tensor, angle: torch.Tensor, num_bins: int) -> torch.Tensor:
+             abs_charge_number: float, length: torch.Tensor, angle: torch.Tensor, num_bins: int,
+             cutoff_wavelength: torch.Tensor | None = None) -> torch.Tensor:
     """The steady-state CSR kick of an arc of length `length` and bend angle `angle` on a beam of any batch shape (broadcast of the
     particles', charges', survival probabilities', energy's, length's and angle's batch shapes) -> particles (*batch, N, 7).
-    Differentiable with respect to the particles, charges, survival probabilities, energy, length and angle."""
-    return _settings_kick(_CSR, particles, charges, survival, mass_eV, abs_charge_number, (energy, length, angle), num_bins)
+    Differentiable with respect to the particles, charges, survival probabilities, energy, length and angle.
+    `cutoff_wavelength`: None, or the cutoff (metres) of the Gaussian low-pass
+    filter of the deposit, a constant whose batch shape broadcasts as well."""
+    return _settings_kick(_CSR, particles, charges, survival, mass_eV, abs_charge_number, (energy, length, angle), num_bins,
+                          cutoff=cutoff_wavelength)
 
 
 def csr_transient_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Tensor, energy: torch.Tensor, mass_eV: float,
                        abs_charge_number: float, length: torch.Tensor, angle: torch.Tensor, distance: torch.Tensor,
-                       num_bins: int) -> torch.Tensor:
+                       num_bins: int, cutoff_wavelength: torch.Tensor | None = None) -> torch.Tensor:
     """The CSR kick of an arc of length `length` and bend angle `angle` at the arc length `distance` behind the entrance face of a bend
     that follows a long straight (the entrance transient; the steady state for a large distance), on a beam of any batch shape
     (broadcast of the particles', charges', survival probabilities', energy's, length's, angle's and distance's batch shapes) ->
     particles (*batch, N, 7). Differentiable with respect to the particles, charges, survival probabilities, energy, length, angle
-    and distance."""
+    and distance. `cutoff_wavelength`: None, or the cutoff (metres) of the Gaussian low-pass
+    filter of the deposit, a constant whose batch shape broadcasts as well."""
     return _settings_kick(_CSR_TRANSIENT, particles, charges, survival, mass_eV, abs_charge_number,
-                          (energy, length, angle, distance), num_bins)
+                          (energy, length, angle, distance), num_bins, cutoff=cutoff_wavelength)
 
 
 def csr_drift_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Tensor, energy: torch.Tensor, mass_eV: float,
                    abs_charge_number: float, length: torch.Tensor, bend_length: torch.Tensor, bend_angle: torch.Tensor,
-                   distance: torch.Tensor, num_bins: int) -> torch.Tensor:
+                   distance: torch.Tensor, num_bins: int, cutoff_wavelength: torch.Tensor | None = None) -> torch.Tensor:
     """The CSR kick of a piece of drift of length `length` at the distance `distance` behind the exit face of a bend of arc length
     `bend_length` and angle `bend_angle` (the radiation emitted inside that bend catching up with the bunch), on a beam of any batch
     shape (broadcast of the particles', charges', survival probabilities', energy's and the four settings' batch shapes) ->
     particles (*batch, N, 7). Differentiable with respect to the particles, charges, survival probabilities, energy and the four
-    settings."""
+    settings. `cutoff_wavelength`: None, or the cutoff (metres) of the Gaussian low-pass
+    filter of the deposit, a constant whose batch shape broadcasts as well."""
     return _settings_kick(_CSR_DRIFT, particles, charges, survival, mass_eV, abs_charge_number,
-                          (energy, length, bend_length, bend_angle, distance), num_bins)
+                          (energy, length, bend_length, bend_angle, distance), num_bins, cutoff=cutoff_wavelength)
 
 
 def lsc_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Tensor, energy: torch.Tensor, mass_eV: float,
-             abs_charge_number: float, length: torch.Tensor, radius: torch.Tensor, num_bins: int) -> torch.Tensor:
+             abs_charge_number: float, length: torch.Tensor, radius: torch.Tensor, num_bins: int,
+             cutoff_wavelength: torch.Tensor | None = None) -> torch.Tensor:
     """The longitudinal space-charge kick of a straight section of length `length` on a beam of disc radius `radius` and of any batch
     shape (broadcast of the particles', charges', survival probabilities', energy's, length's and radius' batch shapes) ->
     particles (*batch, N, 7). Differentiable with respect to the particles, charges, survival probabilities, energy, length and
-    radius."""
-    return _settings_kick(_LSC, particles, charges, survival, mass_eV, abs_charge_number, (energy, length, radius), num_bins)
+    radius. `cutoff_wavelength`: None, or the cutoff (metres) of the Gaussian low-pass
+    filter of the deposit, a constant whose batch shape broadcasts as well."""
+    return _settings_kick(_LSC, particles, charges, survival, mass_eV, abs_charge_number, (energy, length, radius), num_bins,
+                          cutoff=cutoff_wavelength)
 
 
 def ibs_kick(particles: torch.Tensor, charges: torch.Tensor, survival: torch.Tensor, energy: torch.Tensor, mass_eV: float,
              abs_charge_number: float, length: torch.Tensor, coulomb_log: torch.Tensor, sigma_x: torch.Tensor, sigma_y: torch.Tensor,
-             eps_x: torch.Tensor, eps_y: torch.Tensor, num_bins: int, seed: int, stream: int, call_index: torch.Tensor) -> torch.Tensor:
+             eps_x: torch.Tensor, eps_y: torch.Tensor, num_bins: int, seed: int, stream: int, call_index: torch.Tensor,
+             cutoff_wavelength: torch.Tensor | None = None) -> torch.Tensor:
     """The intrabeam-scattering kick of a section of length `length` on a beam of rms sizes `sigma_x`, `sigma_y` and geometric
     emittances `eps_x`, `eps_y`, with the Coulomb logarithm `coulomb_log`, of any batch shape (broadcast of the particles', charges',
     survival probabilities', energy's and the six settings' batch shapes) -> particles (*batch, N, 7). `seed`, `stream`: the 32-bit
     halves of the generator's key; `call_index`: a one-element int64 device tensor, the upper half of its counter, which the kernel
     reads and the caller advances. Differentiable with respect to the particles, charges, survival probabilities, energy and the six
-    settings; the deviates are constants."""
+    settings; the deviates are constants. `cutoff_wavelength`: None, or the cutoff (metres) of the Gaussian low-pass
+    filter of the deposit, a constant whose batch shape broadcasts as well."""
     if call_index.dtype != torch.int64 or call_index.numel() != 1:
         raise TypeError("ibs_kick: call_index must be a one-element int64 tensor")
     return _settings_kick(_IBS, particles, charges, survival, mass_eV, abs_charge_number,
-                          (energy, length, coulomb_log, sigma_x, sigma_y, eps_x, eps_y), num_bins, (int(seed), int(stream), call_index))
+                          (energy, length, coulomb_log, sigma_x, sigma_y, eps_x, eps_y), num_bins, (int(seed), int(stream), call_index),
+                          cutoff=cutoff_wavelength)
 
 
 def ibs_normals(seed: int, stream: int, call: int, B: int, N: int, device) -> tuple[torch.Tensor, torch.Tensor]:

@@ -36,11 +36,49 @@ def check_effect_length(effect_length, owner: str) -> None:
         raise ValueError(f"{owner}: effect_length must be finite and >= 0 (metres), got {effect_length!r}")
 
 
+def check_cutoff_wavelength(cutoff_wavelength, owner: str, device=None, dtype=None):
+    """None (no filter), or the cutoff wavelength as a tensor on `device` in `dtype` (a tensor that is there already stays itself):
+    finite and > 0 (metres), and not part of a graph."""
+    if cutoff_wavelength is None:
+        return None
+    if isinstance(cutoff_wavelength, torch.Tensor) and cutoff_wavelength.requires_grad:
+        raise ValueError(f"{owner}: cutoff_wavelength must not require grad: it is a constant of the kick like num_bins (it sets the "
+                         "filter's width in nodes and its weights), so no gradient flows to it; pass a detached tensor")
+    if not isinstance(cutoff_wavelength, torch.Tensor) and dtype is None:
+        dtype = torch.get_default_dtype()
+    cutoff_wavelength = torch.as_tensor(cutoff_wavelength, device=device, dtype=dtype)
+    if not bool(torch.isfinite(cutoff_wavelength).all() & (cutoff_wavelength > 0).all()):
+        raise ValueError(f"{owner}: cutoff_wavelength must be finite and > 0 (metres) or None, got {cutoff_wavelength!r}")
+    return cutoff_wavelength
+
+
 class BinnedKick(Element):
     """A zero-length kick computed from the binned beam. A subclass gives `_follows` (what follows the current profile, for the
-    messages) and `_kick(incoming, species) -> particles`."""
+    messages) and `_kick(incoming, species) -> particles`; it hands `cutoff_wavelength` (checked with `check_cutoff_wavelength`) to
+    `_register_cutoff` and lists its features through `_with_cutoff`.
+
+    `cutoff_wavelength`: `None` (the raw deposit), or the cutoff lambda_c > 0 (m) of a Gaussian low-pass filter of the deposit; may
+    carry a batch shape. Per batch row, with h the node spacing, every deposited channel is smoothed before the node pass:
+
+        s = lambda_c / (2 pi h),   R = max(1, min(ceil(4 s), M - 1)),   g_d = exp(-d^2 / 2 s^2) / sum_{|e| <= R} g_e,
+        D'_j = sum_{|d| <= R} g_d D_refl(j - d),   refl(i) = -1 - i for i < 0, 2 M - 1 - i for i >= M
+
+    (the row mirrored about its ends, numpy's pad(mode="symmetric")). The amplitude response is exp(-(lambda_c / lambda)^2 / 2); the
+    charge is kept and no weight is negative. With a cutoff the kick no longer depends on `num_bins` once h << lambda_c: M sets
+    the resolution, lambda_c the noise. A constant of the kick like `num_bins` (no gradient flows to it); a buffer, so an in-place
+    edit is followed by the next track, also by a captured one."""
 
     _follows: str
+
+    def _register_cutoff(self, cutoff_wavelength) -> None:
+        self.register_buffer("cutoff_wavelength", cutoff_wavelength)
+
+    def _with_cutoff(self, features: list[str]) -> list[str]:
+        """`features` with `cutoff_wavelength` behind `num_bins` if the element has a cutoff."""
+        if self.cutoff_wavelength is None:
+            return features
+        i = features.index("num_bins") + 1
+        return features[:i] + ["cutoff_wavelength"] + features[i:]
 
     @property
     def is_skippable(self) -> bool:

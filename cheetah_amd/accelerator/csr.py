@@ -55,7 +55,7 @@ from __future__ import annotations
 import torch
 
 from .. import _ops
-from ._binned_kick import BinnedKick, _as_tensor, check_effect_length, check_num_bins
+from ._binned_kick import BinnedKick, _as_tensor, check_cutoff_wavelength, check_effect_length, check_num_bins
 
 
 class CSRKick(BinnedKick):
@@ -63,19 +63,22 @@ class CSRKick(BinnedKick):
 
     Limits of the model: steady state only (no exit transient inside the bend; `TransientCSRKick` has the entrance transient and
     `CSRDriftKick` the CSR in the drifts behind a bend); 1-D (a line charge: no transverse forces, no dependence on the transverse size); the arc is taken as long
-    as the formation length (24 sigma_z R^2)^(1/3) or longer, and a shorter arc is overestimated. The deposit is not filtered:
-    at a fixed number of particles N the noise grows with `num_bins` (for a Gaussian bunch of N = 10^6 the pointwise rms error of
-    the kick is about 4 % at M = 200 and 13 % at M = 1000), so choose M for the bunch's structure, not more.
+    as the formation length (24 sigma_z R^2)^(1/3) or longer, and a shorter arc is overestimated. Without a
+    `cutoff_wavelength` the deposit is used raw: at a fixed number of particles N the noise then grows with `num_bins` (for a Gaussian
+    bunch of N = 10^6 the pointwise rms error of the kick is about 4 % at M = 200 and 13 % at M = 1000). With one, `num_bins` sets the
+    resolution and the cutoff the noise, and the kick converges as M grows.
 
     :param effect_length: arc length L >= 0 (m) the kick stands for; may carry a batch shape that broadcasts with the beam's.
     :param angle: bend angle theta (rad) of that arc, L / R; may carry a batch shape. The kick scales as L^(1/3) |theta|^(2/3).
     :param num_bins: number of nodes M of the grid in tau, 2 <= M <= 4096.
+    :param cutoff_wavelength: `None`, or the cutoff wavelength lambda_c > 0 (m) of the Gaussian low-pass filter of the deposit
+        (`BinnedKick`); may carry a batch shape. A constant like `num_bins`: it must not require grad.
     """
 
     _follows = "the CSR kick"
 
     def __init__(self, effect_length, angle, num_bins: int = 200, name=None, sanitize_name=None, metadata=None, device=None,
-                 dtype=None):
+                 dtype=None, *, cutoff_wavelength=None):
         num_bins = check_num_bins(num_bins, "CSRKick")
         effect_length = _as_tensor(effect_length, device, dtype)
         angle = _as_tensor(angle, device, dtype)
@@ -84,19 +87,21 @@ class CSRKick(BinnedKick):
             raise ValueError(f"CSRKick: angle must be finite (rad), got {angle!r}")
         fk = {"device": device if device is not None else effect_length.device,
               "dtype": dtype if dtype is not None else effect_length.dtype}
+        cutoff_wavelength = check_cutoff_wavelength(cutoff_wavelength, type(self).__name__, **fk)
         super().__init__(name=name, sanitize_name=sanitize_name, metadata=metadata, **fk)
         self.num_bins = num_bins
+        self._register_cutoff(cutoff_wavelength)
         self.register_buffer_or_parameter("effect_length", effect_length)
         self.register_buffer_or_parameter("angle", angle)
 
     def _kick(self, incoming, species):
         return _ops.csr_kick(incoming.particles, incoming.particle_charges, incoming.survival_probabilities, incoming.energy,
                              species.mass_eV_float, abs(species.num_elementary_charges_float), self.effect_length, self.angle,
-                             self.num_bins)
+                             self.num_bins, self.cutoff_wavelength)
 
     @property
     def defining_features(self) -> list[str]:
-        return super().defining_features + ["effect_length", "angle", "num_bins"]
+        return self._with_cutoff(super().defining_features + ["effect_length", "angle", "num_bins"])
 
 
 class TransientCSRKick(BinnedKick):
@@ -105,19 +110,21 @@ class TransientCSRKick(BinnedKick):
 
     Limits of the model: ultra-relativistic; 1-D (a line charge: no transverse forces, no dependence on the transverse size); a
     long straight in front of the bend (no radiation of an earlier bend catches up with the bunch); the CSR in the drift behind the
-    bend (exit transient) is `CSRDriftKick`'s. The deposit is not filtered, as in `CSRKick`: choose `num_bins` for the bunch's structure, not more.
+    bend (exit transient) is `CSRDriftKick`'s. The deposit is used raw unless a `cutoff_wavelength` is given, as in `CSRKick`.
 
     :param effect_length: arc length L >= 0 (m) the kick stands for; may carry a batch shape that broadcasts with the beam's.
     :param angle: bend angle theta (rad) of that arc; may carry a batch shape. The bend's radius is R = L / |theta|.
     :param entrance_distance: arc length d >= 0 (m) from the bend's entrance face to the point where the wake is evaluated; may
         carry a batch shape. At d = 0 there is no kick; for d^3 / (24 R^2) beyond the bunch's length the kick is `CSRKick`'s.
     :param num_bins: number of nodes M of the grid in tau, 2 <= M <= 4096.
+    :param cutoff_wavelength: `None`, or the cutoff wavelength lambda_c > 0 (m) of the Gaussian low-pass filter of the deposit
+        (`BinnedKick`); may carry a batch shape. A constant like `num_bins`: it must not require grad.
     """
 
     _follows = "the CSR kick"
 
     def __init__(self, effect_length, angle, entrance_distance, num_bins: int = 200, name=None, sanitize_name=None, metadata=None,
-                 device=None, dtype=None):
+                 device=None, dtype=None, *, cutoff_wavelength=None):
         num_bins = check_num_bins(num_bins, "TransientCSRKick")
         effect_length = _as_tensor(effect_length, device, dtype)
         angle = _as_tensor(angle, device, dtype)
@@ -129,8 +136,10 @@ class TransientCSRKick(BinnedKick):
             raise ValueError(f"TransientCSRKick: entrance_distance must be finite and >= 0 (metres), got {entrance_distance!r}")
         fk = {"device": device if device is not None else effect_length.device,
               "dtype": dtype if dtype is not None else effect_length.dtype}
+        cutoff_wavelength = check_cutoff_wavelength(cutoff_wavelength, type(self).__name__, **fk)
         super().__init__(name=name, sanitize_name=sanitize_name, metadata=metadata, **fk)
         self.num_bins = num_bins
+        self._register_cutoff(cutoff_wavelength)
         self.register_buffer_or_parameter("effect_length", effect_length)
         self.register_buffer_or_parameter("angle", angle)
         self.register_buffer_or_parameter("entrance_distance", entrance_distance)
@@ -138,11 +147,11 @@ class TransientCSRKick(BinnedKick):
     def _kick(self, incoming, species):
         return _ops.csr_transient_kick(incoming.particles, incoming.particle_charges, incoming.survival_probabilities,
                                        incoming.energy, species.mass_eV_float, abs(species.num_elementary_charges_float),
-                                       self.effect_length, self.angle, self.entrance_distance, self.num_bins)
+                                       self.effect_length, self.angle, self.entrance_distance, self.num_bins, self.cutoff_wavelength)
 
     @property
     def defining_features(self) -> list[str]:
-        return super().defining_features + ["effect_length", "angle", "entrance_distance", "num_bins"]
+        return self._with_cutoff(super().defining_features + ["effect_length", "angle", "entrance_distance", "num_bins"])
 
 
 class CSRDriftKick(BinnedKick):
@@ -151,8 +160,7 @@ class CSRDriftKick(BinnedKick):
 
     Limits of the model: ultra-relativistic; 1-D (a line charge: no transverse forces, no dependence on the transverse size); the
     sources are in this one bend only (no radiation of an earlier bend); the straight in front of the bend is ignored (the bend's
-    own entrance transient is not carried into the drift). The deposit is not filtered, as in `CSRKick`: choose `num_bins` for the
-    bunch's structure, not more.
+    own entrance transient is not carried into the drift). The deposit is used raw unless a `cutoff_wavelength` is given, as in `CSRKick`.
 
     :param effect_length: length L >= 0 (m) of the piece of drift the kick stands for; may carry a batch shape that broadcasts with
         the beam's.
@@ -162,12 +170,14 @@ class CSRDriftKick(BinnedKick):
         shape. The kick decays with x; at x = 0 it is `TransientCSRKick`'s at the end of the bend without the term of the straight
         in front of the bend.
     :param num_bins: number of nodes M of the grid in tau, 2 <= M <= 4096.
+    :param cutoff_wavelength: `None`, or the cutoff wavelength lambda_c > 0 (m) of the Gaussian low-pass filter of the deposit
+        (`BinnedKick`); may carry a batch shape. A constant like `num_bins`: it must not require grad.
     """
 
     _follows = "the CSR kick"
 
     def __init__(self, effect_length, bend_length, bend_angle, exit_distance, num_bins: int = 200, name=None, sanitize_name=None,
-                 metadata=None, device=None, dtype=None):
+                 metadata=None, device=None, dtype=None, *, cutoff_wavelength=None):
         num_bins = check_num_bins(num_bins, "CSRDriftKick")
         effect_length = _as_tensor(effect_length, device, dtype)
         bend_length = _as_tensor(bend_length, device, dtype)
@@ -181,8 +191,10 @@ class CSRDriftKick(BinnedKick):
             raise ValueError(f"CSRDriftKick: bend_angle must be finite (rad), got {bend_angle!r}")
         fk = {"device": device if device is not None else effect_length.device,
               "dtype": dtype if dtype is not None else effect_length.dtype}
+        cutoff_wavelength = check_cutoff_wavelength(cutoff_wavelength, type(self).__name__, **fk)
         super().__init__(name=name, sanitize_name=sanitize_name, metadata=metadata, **fk)
         self.num_bins = num_bins
+        self._register_cutoff(cutoff_wavelength)
         self.register_buffer_or_parameter("effect_length", effect_length)
         self.register_buffer_or_parameter("bend_length", bend_length)
         self.register_buffer_or_parameter("bend_angle", bend_angle)
@@ -191,8 +203,10 @@ class CSRDriftKick(BinnedKick):
     def _kick(self, incoming, species):
         return _ops.csr_drift_kick(incoming.particles, incoming.particle_charges, incoming.survival_probabilities, incoming.energy,
                                    species.mass_eV_float, abs(species.num_elementary_charges_float), self.effect_length,
-                                   self.bend_length, self.bend_angle, self.exit_distance, self.num_bins)
+                                   self.bend_length, self.bend_angle, self.exit_distance, self.num_bins,
+                                   self.cutoff_wavelength)
 
     @property
     def defining_features(self) -> list[str]:
-        return super().defining_features + ["effect_length", "bend_length", "bend_angle", "exit_distance", "num_bins"]
+        return self._with_cutoff(super().defining_features
+                                 + ["effect_length", "bend_length", "bend_angle", "exit_distance", "num_bins"])

@@ -84,25 +84,28 @@ class Dipole(Element):
     def is_active(self) -> bool:
         return bool((self.angle != 0).any().item())
 
-    def split_for_csr(self, num_kicks: int, num_bins: int = 200, transient: bool = False) -> list[Element]:
+    def split_for_csr(self, num_kicks: int, num_bins: int = 200, transient: bool = False, cutoff_wavelength=None) -> list[Element]:
         """The bend as `num_kicks` x [Dipole of L / n and theta / n, CSRKick(L / n, theta / n, num_bins)]: steady-state CSR kicks
         spread along the arc. With `transient`, piece i gets `TransientCSRKick(L / n, theta / n, entrance_distance=(i + 1/2) L / n,
         num_bins)` instead: the wake at the piece's midpoint (the midpoint rule) of a bend behind a long straight. Only the first
         piece keeps the entrance face (dipole_e1, fringe_integral, the entrance fringe of `fringe_at`) and only the last keeps the
         exit face; k1, tilt, gap, gap_exit, fringe_type and tracking_method are kept. An RBend becomes Dipole pieces with its
-        effective face angles. A bend of zero angle is returned unchanged, as [self]."""
-        from ._binned_kick import check_num_bins, check_num_kicks
+        effective face angles. A bend of zero angle is returned unchanged, as [self]. Every kick gets `cutoff_wavelength`
+        (`None`, or the cutoff of the low-pass filter of its deposit; a tensor of the bend's device and dtype is shared by the kicks)."""
+        from ._binned_kick import check_cutoff_wavelength, check_num_bins, check_num_kicks
         from .csr import CSRKick, TransientCSRKick
 
         n = check_num_kicks(num_kicks, "Dipole.split_for_csr")
         num_bins = check_num_bins(num_bins, "Dipole.split_for_csr")
+        fk = {"device": self.angle.device, "dtype": self.angle.dtype}
+        cutoff_wavelength = check_cutoff_wavelength(cutoff_wavelength, "Dipole.split_for_csr", **fk)
         if not bool((self.angle != 0).any()):
             return [self]
-        fk = {"device": self.angle.device, "dtype": self.angle.dtype}
         parts = []
         for i, piece in enumerate(self._arc_pieces(n, "csr")):
             parts.append(piece)
-            kk = {"num_bins": num_bins, "name": f"{self.name}_csr_kick_{i}", "sanitize_name": False, **fk}
+            kk = {"num_bins": num_bins, "cutoff_wavelength": cutoff_wavelength, "name": f"{self.name}_csr_kick_{i}",
+                  "sanitize_name": False, **fk}
             parts.append(TransientCSRKick(piece.length, piece.angle, (i + 0.5) * piece.length, **kk) if transient
                          else CSRKick(piece.length, piece.angle, **kk))
         return parts

@@ -35,7 +35,7 @@ import numbers
 import torch
 
 from .. import _ops
-from ._binned_kick import BinnedKick, _as_tensor, check_effect_length, check_num_bins
+from ._binned_kick import BinnedKick, _as_tensor, check_cutoff_wavelength, check_effect_length, check_num_bins
 from .synchrotron_radiation import check_key_word
 
 _MOMENTS = ("sigma_x", "sigma_y", "emittance_x", "emittance_y")
@@ -53,9 +53,9 @@ class IBSKick(BinnedKick):
     Limits of the model: beta = 1 (ultra-relativistic); no dispersion term (the sigma_H of Bane's formula is the dispersion-free
     one), so in a chicane pass the moments explicitly or leave the bends out; Bane's condition sigma_delta sigma_x / (gamma eps_x)
     << 1 (the beam is much colder longitudinally than transversely in its rest frame); only delta is excited, the transverse
-    emittance growth is neglected; the moments, the energy and the current profile are taken constant over `effect_length`. The
-    deposit is not filtered, as in `LSCKick`: at a fixed number of particles the shot noise of the variance grows with `num_bins`,
-    so choose M for the bunch's structure, not more.
+    emittance growth is neglected; the moments, the energy and the current profile are taken constant over `effect_length`. Without a
+    `cutoff_wavelength` the deposit is used raw, as in `LSCKick`: at a fixed number of particles the shot noise of the variance then
+    grows with `num_bins`. The filter's weights are not negative, so a filtered variance is not either.
 
     :param effect_length: length L >= 0 (m) of the section the kick stands for; may carry a batch shape that broadcasts with the
         beam's.
@@ -64,6 +64,8 @@ class IBSKick(BinnedKick):
         the device (differentiable through the beam's moments).
     :param emittance_x, emittance_y: geometric emittances (m) > 0; may carry a batch shape. `None`: the incoming beam's.
     :param num_bins: number of nodes M of the grid in tau, 2 <= M <= 4096.
+    :param cutoff_wavelength: `None`, or the cutoff wavelength lambda_c > 0 (m) of the Gaussian low-pass filter of the deposit
+        (`BinnedKick`); may carry a batch shape. A constant like `num_bins`: it must not require grad.
     :param seed: first half of the generator's key, an integer in 0 ... 2^32 - 1.
     :param stream: second half of the key, an integer in 0 ... 2^32 - 1: the kick's number within its lattice.
 
@@ -76,7 +78,7 @@ class IBSKick(BinnedKick):
 
     def __init__(self, effect_length, coulomb_log=10.0, sigma_x=None, sigma_y=None, emittance_x=None, emittance_y=None,
                  num_bins: int = 200, seed: int = 0, stream: int = 0, name=None, sanitize_name=None, metadata=None, device=None,
-                 dtype=None):
+                 dtype=None, *, cutoff_wavelength=None):
         owner = "IBSKick"
         num_bins = check_num_bins(num_bins, owner)
         seed, stream = check_key_word(seed, "seed", owner), check_key_word(stream, "stream", owner)
@@ -94,8 +96,10 @@ class IBSKick(BinnedKick):
                 v = _as_tensor(v, fk["device"], fk["dtype"])
                 check_positive(v, f"{what} (metres)")
             moments[what] = v
+        cutoff_wavelength = check_cutoff_wavelength(cutoff_wavelength, owner, **fk)
         super().__init__(name=name, sanitize_name=sanitize_name, metadata=metadata, **fk)
         self.num_bins = num_bins
+        self._register_cutoff(cutoff_wavelength)
         self.seed, self.stream = seed, stream
         self.register_buffer_or_parameter("effect_length", effect_length)
         self.register_buffer_or_parameter("coulomb_log", coulomb_log)
@@ -130,10 +134,10 @@ class IBSKick(BinnedKick):
         moments = [getattr(incoming, what) if v is None else v for what, v in zip(_MOMENTS, given)]
         out = _ops.ibs_kick(incoming.particles, incoming.particle_charges, incoming.survival_probabilities, incoming.energy,
                             species.mass_eV_float, abs(species.num_elementary_charges_float), self.effect_length, self.coulomb_log,
-                            *moments, self.num_bins, self.seed, self.stream, self._call_index)
+                            *moments, self.num_bins, self.seed, self.stream, self._call_index, self.cutoff_wavelength)
         self._call_index.add_(1)
         return out
 
     @property
     def defining_features(self) -> list[str]:
-        return super().defining_features + ["effect_length", "coulomb_log", *_MOMENTS, "num_bins", "seed", "stream"]
+        return self._with_cutoff(super().defining_features + ["effect_length", "coulomb_log", *_MOMENTS, "num_bins", "seed", "stream"])

@@ -30,7 +30,7 @@ import math
 import torch
 
 from .. import _ops
-from ._binned_kick import BinnedKick, _as_tensor, check_effect_length, check_num_bins
+from ._binned_kick import BinnedKick, _as_tensor, check_cutoff_wavelength, check_effect_length, check_num_bins
 
 
 def check_radius_factor(radius_factor, owner: str = "LSCKick") -> float:
@@ -53,9 +53,9 @@ class LSCKick(BinnedKick):
     """Longitudinal space charge of a straight section, as one zero-length energy kick.
 
     Limits of the model: 1-D (the on-axis field of a transversely uniform disc for every particle: no transverse forces, no
-    dependence on a particle's own offset); the beam's size and energy are taken constant over `effect_length`. The deposit is not
-    filtered: at a fixed number of particles the shot noise of the kick grows with `num_bins`, so choose M for the bunch's structure,
-    not more.
+    dependence on a particle's own offset); the beam's size and energy are taken constant over `effect_length`. Without a
+    `cutoff_wavelength` the deposit is used raw: at a fixed number of particles the shot noise of the kick then grows with `num_bins`.
+    With one, `num_bins` sets the resolution and the cutoff the noise, and the kick converges as M grows.
 
     :param effect_length: length L >= 0 (m) of the straight section the kick stands for; may carry a batch shape that broadcasts
         with the beam's.
@@ -65,6 +65,8 @@ class LSCKick(BinnedKick):
     :param radius_factor: factor of the beam's mean rms size when `beam_radius` is `None`; 1.7 is elegant's convention for a Gaussian
         beam.
     :param num_bins: number of nodes M of the grid in tau, 2 <= M <= 4096.
+    :param cutoff_wavelength: `None`, or the cutoff wavelength lambda_c > 0 (m) of the Gaussian low-pass filter of the deposit
+        (`BinnedKick`); may carry a batch shape. A constant like `num_bins`: it must not require grad.
     """
 
     #: LatticeJSON: read back as the Python number it was written as, not as a tensor of the file's dtype
@@ -72,7 +74,7 @@ class LSCKick(BinnedKick):
     _follows = "the LSC kick"
 
     def __init__(self, effect_length, beam_radius=None, radius_factor: float = 1.7, num_bins: int = 200, name=None,
-                 sanitize_name=None, metadata=None, device=None, dtype=None):
+                 sanitize_name=None, metadata=None, device=None, dtype=None, *, cutoff_wavelength=None):
         num_bins = check_num_bins(num_bins, "LSCKick")
         radius_factor = check_radius_factor(radius_factor)
         effect_length = _as_tensor(effect_length, device, dtype)
@@ -82,8 +84,10 @@ class LSCKick(BinnedKick):
             check_beam_radius(beam_radius)
         fk = {"device": device if device is not None else effect_length.device,
               "dtype": dtype if dtype is not None else effect_length.dtype}
+        cutoff_wavelength = check_cutoff_wavelength(cutoff_wavelength, "LSCKick", **fk)
         super().__init__(name=name, sanitize_name=sanitize_name, metadata=metadata, **fk)
         self.num_bins = num_bins
+        self._register_cutoff(cutoff_wavelength)
         self.radius_factor = radius_factor
         self.register_buffer_or_parameter("effect_length", effect_length)
         self.register_buffer_or_parameter("beam_radius", beam_radius)
@@ -95,8 +99,8 @@ class LSCKick(BinnedKick):
             radius = (self.radius_factor / 2) * (incoming.sigma_x + incoming.sigma_y)
         return _ops.lsc_kick(incoming.particles, incoming.particle_charges, incoming.survival_probabilities, incoming.energy,
                              species.mass_eV_float, abs(species.num_elementary_charges_float), self.effect_length, radius,
-                             self.num_bins)
+                             self.num_bins, self.cutoff_wavelength)
 
     @property
     def defining_features(self) -> list[str]:
-        return super().defining_features + ["effect_length", "beam_radius", "radius_factor", "num_bins"]
+        return self._with_cutoff(super().defining_features + ["effect_length", "beam_radius", "radius_factor", "num_bins"])

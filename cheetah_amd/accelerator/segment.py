@@ -1866,8 +1866,9 @@ class Segment(Element):
         return self.__class__(elements=merged_elements, name=self.name, metadata=deepcopy(self.metadata))
 
     def with_csr_kicks(self, num_kicks: int, num_bins: int = 200, except_for=None, transient: bool = False, drift_kicks: int = 0,
-                       max_distance=None) -> "Segment":
-        """Every bending Dipole (and RBend) split by `Dipole.split_for_csr(num_kicks, num_bins, transient)` into pieces with
+                       max_distance=None, cutoff_wavelength=None) -> "Segment":
+        """Every bending Dipole (and RBend) split by `Dipole.split_for_csr(num_kicks, num_bins, transient, cutoff_wavelength)` into
+        pieces with
         steady-state CSR kicks between them (with `transient`: kicks with the entrance transient, every bend taken to follow a long
         straight), nested Segments included; other elements, bends of zero angle and names in `except_for` unchanged.
 
@@ -1877,8 +1878,10 @@ class Segment(Element):
         `{drift}_csr_drift_{i}` and `{drift}_csr_drift_kick_{i}`, x0 the distance from the bend's exit face to the drift; any other
         element with a length > 0 is kept whole and followed by one kick for its length at its mid-distance
         (`{element}_csr_drift_kick`); elements of zero length pass unchanged. A bend in `except_for` ends the run without kicks, and
-        so does an element that starts beyond `max_distance` (metres, compared on the largest batch entry)."""
-        from ._binned_kick import check_num_bins, check_num_kicks
+        so does an element that starts beyond `max_distance` (metres, compared on the largest batch entry). Every kick, in the bends
+        and behind them, gets `cutoff_wavelength` (`None`, or the cutoff of the low-pass filter of its deposit; a tensor is handed on
+        as it is)."""
+        from ._binned_kick import check_cutoff_wavelength, check_num_bins, check_num_kicks
 
         owner = "Segment.with_csr_kicks"
         check_num_kicks(num_kicks, owner)
@@ -1888,9 +1891,11 @@ class Segment(Element):
         if max_distance is not None and not float(max_distance) >= 0.0:
             raise ValueError(f"{owner}: max_distance must be a length >= 0 (metres), got {max_distance!r}")
         limit = None if max_distance is None else float(max_distance)
-        return self._with_csr_kicks(num_kicks, num_bins, except_for or [], transient, int(drift_kicks), limit, None)[0]
+        check_cutoff_wavelength(cutoff_wavelength, owner)
+        return self._with_csr_kicks(num_kicks, num_bins, except_for or [], transient, int(drift_kicks), limit, None,
+                                    cutoff_wavelength)[0]
 
-    def _with_csr_kicks(self, num_kicks, num_bins, except_for, transient, drift_kicks, max_distance, behind):
+    def _with_csr_kicks(self, num_kicks, num_bins, except_for, transient, drift_kicks, max_distance, behind, cutoff):
         """(the segment with the kicks, the state of the drift kicks behind it). `behind`: None, or (length, angle, distance) of the
         last split bend: its two tensors and the distance travelled since its exit face."""
         from .csr import CSRDriftKick
@@ -1900,7 +1905,7 @@ class Segment(Element):
         elements = []
         for e in self.elements:
             if isinstance(e, Segment):
-                e, behind = e._with_csr_kicks(num_kicks, num_bins, except_for, transient, drift_kicks, max_distance, behind)
+                e, behind = e._with_csr_kicks(num_kicks, num_bins, except_for, transient, drift_kicks, max_distance, behind, cutoff)
                 elements.append(e)
                 continue
             if isinstance(e, Dipole) and e.is_active:
@@ -1908,7 +1913,7 @@ class Segment(Element):
                     elements.append(e)
                     behind = None
                 else:
-                    elements += e.split_for_csr(num_kicks, num_bins, transient)
+                    elements += e.split_for_csr(num_kicks, num_bins, transient, cutoff)
                     behind = (e.length, e.angle, torch.zeros_like(e.length)) if drift_kicks else None
                 continue
             if behind is not None and max_distance is not None and float(behind[2].detach().max()) > max_distance:
@@ -1917,7 +1922,8 @@ class Segment(Element):
                 elements.append(e)
                 continue
             bend_length, bend_angle, x0 = behind
-            kk = {"num_bins": num_bins, "sanitize_name": False, "device": e.length.device, "dtype": e.length.dtype}
+            kk = {"num_bins": num_bins, "cutoff_wavelength": cutoff, "sanitize_name": False, "device": e.length.device,
+                  "dtype": e.length.dtype}
             if isinstance(e, Drift):
                 piece = e.length / drift_kicks
                 for i in range(drift_kicks):
@@ -1962,15 +1968,16 @@ class Segment(Element):
         return self.__class__(elements=elements, name=self.name, metadata=deepcopy(self.metadata)), stream
 
     def with_lsc_kicks(self, num_bins: int = 200, beam_radius=None, radius_factor: float = 1.7, max_step=None,
-                       except_for=None) -> "Segment":
+                       except_for=None, cutoff_wavelength=None) -> "Segment":
         """Every element with a `length` that is anywhere > 0 followed by an `LSCKick(element.length, beam_radius, radius_factor,
-        num_bins)`, nested Segments included. The kick's `effect_length` IS the element's `length` tensor, so in-place edits and
+        num_bins, cutoff_wavelength=cutoff_wavelength)`, nested Segments included. The kick's `effect_length` IS the element's
+        `length` tensor, so in-place edits and
         gradients follow. With `max_step` (metres) an element longer than that is first split with its own
         `split(resolution=max_step)` and every piece gets its kick. Names in `except_for` and the collective kicks already there
         (`LSCKick`, `CSRKick`, `TransientCSRKick`, `CSRDriftKick`, `Wakefield`, `SpaceChargeKick`) get none. A kick stands behind its element and
         sees the outgoing beam: the kick after a `Cavity` uses the energy the beam leaves the cavity with, not the mean energy inside
         it."""
-        from ._binned_kick import check_num_bins
+        from ._binned_kick import check_cutoff_wavelength, check_num_bins
         from .csr import CSRDriftKick, CSRKick, TransientCSRKick
         from .lsc import LSCKick, check_beam_radius, check_radius_factor
         from .space_charge_kick import SpaceChargeKick
@@ -1979,6 +1986,7 @@ class Segment(Element):
         owner = "Segment.with_lsc_kicks"
         check_num_bins(num_bins, owner)
         check_radius_factor(radius_factor, owner)
+        check_cutoff_wavelength(cutoff_wavelength, owner)
         if beam_radius is not None:
             check_beam_radius(beam_radius if isinstance(beam_radius, torch.Tensor) else torch.as_tensor(beam_radius), owner)
         if max_step is not None:
@@ -1989,7 +1997,7 @@ class Segment(Element):
         elements = []
         for e in self.elements:
             if isinstance(e, Segment):
-                elements.append(e.with_lsc_kicks(num_bins, beam_radius, radius_factor, max_step, except_for))
+                elements.append(e.with_lsc_kicks(num_bins, beam_radius, radius_factor, max_step, except_for, cutoff_wavelength))
                 continue
             elements_of_e = [e]
             if not isinstance(e, (LSCKick, CSRKick, TransientCSRKick, CSRDriftKick, Wakefield, SpaceChargeKick)) and e.name not in except_for \
@@ -1999,14 +2007,15 @@ class Segment(Element):
                 kw = {"device": e.length.device, "dtype": e.length.dtype}
                 elements_of_e = [p for piece in elements_of_e for p in (
                     piece, LSCKick(piece.length, beam_radius=beam_radius, radius_factor=radius_factor, num_bins=num_bins,
-                                   name=f"{piece.name}_lsc_kick", sanitize_name=False, **kw))]
+                                   name=f"{piece.name}_lsc_kick", sanitize_name=False, cutoff_wavelength=cutoff_wavelength, **kw))]
             elements += elements_of_e
         return self.__class__(elements=elements, name=self.name, metadata=deepcopy(self.metadata))
 
     def with_ibs_kicks(self, coulomb_log=10.0, num_bins: int = 200, max_step=None, seed: int = 0, except_for=None,
-                       first_stream: int = 0) -> "Segment":
+                       first_stream: int = 0, cutoff_wavelength=None) -> "Segment":
         """Every element with a `length` that is anywhere > 0 followed by an `IBSKick(element.length, coulomb_log, num_bins=num_bins,
-        seed=seed, stream=...)` that takes its four moments from the beam, nested Segments included. The placement is
+        seed=seed, stream=..., cutoff_wavelength=cutoff_wavelength)` that takes its four moments from the beam, nested Segments
+        included. The placement is
         `with_lsc_kicks`': the kick's `effect_length` IS the element's `length` tensor, so in-place edits and gradients follow; with
         `max_step` (metres) an element longer than that is first split with its own `split(resolution=max_step)` and every piece
         gets its kick; names in `except_for`, the collective kicks already there (`LSCKick`, `CSRKick`, `TransientCSRKick`,
@@ -2014,7 +2023,7 @@ class Segment(Element):
         `first_stream` + 1, ... in lattice order, as in `with_radiation_kicks`, so no two kicks of the lattice draw the same
         deviates. The model has no dispersion term: keep the bends of a chicane in `except_for`, or give them kicks with explicit
         moments."""
-        from ._binned_kick import check_num_bins
+        from ._binned_kick import check_cutoff_wavelength, check_num_bins
         from .ibs import check_positive
         from .synchrotron_radiation import check_key_word
 
@@ -2030,9 +2039,10 @@ class Segment(Element):
             step = float(max_step)
             if not step > 0.0 or step == float("inf"):
                 raise ValueError(f"{owner}: max_step must be a finite length > 0 (metres), got {max_step!r}")
-        return self._with_ibs_kicks(coulomb_log, num_bins, step, seed, except_for or [], first_stream)[0]
+        check_cutoff_wavelength(cutoff_wavelength, owner)
+        return self._with_ibs_kicks(coulomb_log, num_bins, step, seed, except_for or [], first_stream, cutoff_wavelength)[0]
 
-    def _with_ibs_kicks(self, coulomb_log, num_bins, step, seed, except_for, stream):
+    def _with_ibs_kicks(self, coulomb_log, num_bins, step, seed, except_for, stream, cutoff):
         """(the segment with the kicks, the first stream not used yet)"""
         from .csr import CSRDriftKick, CSRKick, TransientCSRKick
         from .ibs import IBSKick
@@ -2043,7 +2053,7 @@ class Segment(Element):
         elements = []
         for e in self.elements:
             if isinstance(e, Segment):
-                e, stream = e._with_ibs_kicks(coulomb_log, num_bins, step, seed, except_for, stream)
+                e, stream = e._with_ibs_kicks(coulomb_log, num_bins, step, seed, except_for, stream, cutoff)
                 elements.append(e)
                 continue
             pieces = [e]
@@ -2055,7 +2065,7 @@ class Segment(Element):
                 with_kicks = []
                 for piece in pieces:
                     with_kicks += [piece, IBSKick(piece.length, coulomb_log=coulomb_log, num_bins=num_bins, seed=seed, stream=stream,
-                                                  name=f"{piece.name}_ibs_kick", sanitize_name=False, **kw)]
+                                                  name=f"{piece.name}_ibs_kick", sanitize_name=False, cutoff_wavelength=cutoff, **kw)]
                     stream += 1
                 pieces = with_kicks
             elements += pieces

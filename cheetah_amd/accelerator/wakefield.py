@@ -17,7 +17,7 @@ from __future__ import annotations
 import torch
 
 from .. import _ops
-from ._binned_kick import BinnedKick, _as_tensor, check_num_bins
+from ._binned_kick import BinnedKick, _as_tensor, check_cutoff_wavelength, check_num_bins
 
 
 class Wakefield(BinnedKick):
@@ -30,12 +30,14 @@ class Wakefield(BinnedKick):
     :param factor: scaling of the wake (structure length, number of cells), default 1; may carry a batch shape that broadcasts
         with the beam's.
     :param num_bins: number of nodes M of the grid in tau, 2 <= M <= 4096.
+    :param cutoff_wavelength: `None`, or the cutoff wavelength lambda_c > 0 (m) of the Gaussian low-pass filter of the deposits Q, X, Y
+        (`BinnedKick`); may carry a batch shape. A constant like `num_bins`: it must not require grad.
     """
 
     _follows = "the wake"
 
     def __init__(self, wake_spacing, longitudinal_wake=None, transverse_wake=None, factor=None, num_bins: int = 200, name=None,
-                 sanitize_name=None, metadata=None, device=None, dtype=None):
+                 sanitize_name=None, metadata=None, device=None, dtype=None, *, cutoff_wavelength=None):
         num_bins = check_num_bins(num_bins, "Wakefield")
         longitudinal_wake = _as_tensor(longitudinal_wake, device, dtype)
         transverse_wake = _as_tensor(transverse_wake, device, dtype)
@@ -51,7 +53,9 @@ class Wakefield(BinnedKick):
         wake_spacing = _as_tensor(wake_spacing, fk["device"], fk["dtype"])
         if wake_spacing is None or wake_spacing.dim() != 0 or not bool(torch.isfinite(wake_spacing.detach()) & (wake_spacing.detach() > 0)):
             raise ValueError(f"Wakefield: wake_spacing must be a positive scalar (metres), got {wake_spacing!r}")
+        cutoff_wavelength = check_cutoff_wavelength(cutoff_wavelength, "Wakefield", **fk)
         super().__init__(name=name, sanitize_name=sanitize_name, metadata=metadata, **fk)
+        self._register_cutoff(cutoff_wavelength)
         empty = lambda t: t if t is not None and t.numel() > 0 else torch.zeros(0, **fk)  # noqa: E731
         self.num_bins = num_bins
         self.register_buffer_or_parameter("wake_spacing", wake_spacing)
@@ -64,8 +68,10 @@ class Wakefield(BinnedKick):
         wl, wt = self.longitudinal_wake, self.transverse_wake
         return _ops.wake_kick(incoming.particles, incoming.particle_charges, incoming.survival_probabilities, incoming.energy,
                               species.mass_eV_float, abs(species.num_elementary_charges_float), self.factor,
-                              wl if wl.numel() > 0 else None, wt if wt.numel() > 0 else None, self.wake_spacing, self.num_bins)
+                              wl if wl.numel() > 0 else None, wt if wt.numel() > 0 else None, self.wake_spacing, self.num_bins,
+                              self.cutoff_wavelength)
 
     @property
     def defining_features(self) -> list[str]:
-        return super().defining_features + ["wake_spacing", "longitudinal_wake", "transverse_wake", "factor", "num_bins"]
+        return self._with_cutoff(super().defining_features
+                                 + ["wake_spacing", "longitudinal_wake", "transverse_wake", "factor", "num_bins"])

@@ -169,8 +169,10 @@ int csr_kick_bwd_t(const T* x, const T* q, const T* w, int64_t B, int64_t Bx, in
     if (st != CHX_OK) return st;
     hipLaunchKernelGGL(csr_bwd_toeplitz_kernel, grid_nodes(M, B), dim3(kWB), toeplitz_lds(M), s, M, state, ws.bhdr, ws.ggrid, ws.adj);
     CHX_CHECK_LAUNCH();
+    st = launch_adj_filter(B, M, 1, csr_state_row(M), state, ws, s);
+    if (st != CHX_OK) return st;
     hipLaunchKernelGGL(node_bwd_particles_kernel<T>, grid_particles(N, B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, M, state,
-                       csr_state_row(M), ws.adj, gout, dX, dC);
+                       csr_state_row(M), ws.adj_last, gout, dX, dC);
     CHX_CHECK_LAUNCH();
     return CHX_OK;
 }
@@ -383,7 +385,9 @@ int csrt_kick_bwd_t(const T* x, const T* q, const T* w, int64_t B, int64_t Bx, i
     hipLaunchKernelGGL(csrt_bwd_toeplitz_kernel, grid_nodes(M, B), dim3(kWB), toeplitz_lds(M), s, M, state, ws.bhdr, ws.ggrid, ws.adj,
                        ws.extra);
     CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(csrt_bwd_particles_kernel<T>, grid_particles(N, B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, M, state, ws.adj,
+    st = launch_adj_filter(B, M, 1, csrt_state_row(M), state, ws, s);
+    if (st != CHX_OK) return st;
+    hipLaunchKernelGGL(csrt_bwd_particles_kernel<T>, grid_particles(N, B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, M, state, ws.adj_last,
                        ws.extra, gout, dX, dC, d_x);
     CHX_CHECK_LAUNCH();
     return CHX_OK;
@@ -717,7 +721,9 @@ int csrd_kick_bwd_t(const T* x, const T* q, const T* w, int64_t B, int64_t Bx, i
     hipLaunchKernelGGL(csrd_bwd_toeplitz_kernel, grid_nodes(M, B), dim3(kWB), toeplitz_lds(M), s, M, state, ws.bhdr, ws.ggrid, ws.adj,
                        ws.extra);
     CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(csrd_bwd_particles_kernel<T>, grid_particles(N, B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, M, state, ws.adj,
+    st = launch_adj_filter(B, M, 1, csrd_state_row(M), state, ws, s);
+    if (st != CHX_OK) return st;
+    hipLaunchKernelGGL(csrd_bwd_particles_kernel<T>, grid_particles(N, B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, M, state, ws.adj_last,
                        ws.extra, gout, dX, dC, d_xh, d_phi, d_kappa);
     CHX_CHECK_LAUNCH();
     return CHX_OK;
@@ -725,19 +731,25 @@ int csrd_kick_bwd_t(const T* x, const T* q, const T* w, int64_t B, int64_t Bx, i
 
 }  // namespace
 
+// Every entry point has a twin that takes cutoff[Bcut] in front of the workspace (the low-pass stage of chx_grid1d_dev.h, launched by
+// launch_deposit and launch_adj_filter); the call without the suffix is the twin with a null cutoff.
 extern "C" size_t chx_csr_workspace_bytes(int64_t B, int64_t N, int32_t M) { return csr_ws(nullptr, B, N, M).bytes; }
+extern "C" size_t chx_csr_workspace_bytes_cut(int64_t B, int64_t N, int32_t M) {
+    return cutoff_ws_bytes(csr_ws(nullptr, B, N, M), B, M, 1);
+}
 
-extern "C" int chx_csr_kick(const void* x, const void* q, const void* w, const void* energy, const void* length, const void* angle,
-                            double mass_eV, double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl,
-                            int64_t Ba, int64_t N, int32_t M, int dtype, void* out, double* state, void* workspace,
-                            size_t workspace_bytes, void* stream) {
+extern "C" int chx_csr_kick_cut(const void* x, const void* q, const void* w, const void* energy, const void* length,
+                                const void* angle, double mass_eV, double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                                int64_t Be, int64_t Bl, int64_t Ba, int64_t N, int32_t M, int dtype, void* out, double* state,
+                                const double* cutoff, int64_t Bcut, void* workspace, size_t workspace_bytes, void* stream) {
     const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!energy || !length || !angle || !(mass_eV > 0.0) || !chx_bcast_ok(Be, B) || !chx_bcast_ok(Bl, B) || !chx_bcast_ok(Ba, B) ||
         !out)
         return CHX_ERR_INVALID_ARG;
     if (!chx_aligned16(out)) return CHX_ERR_MISALIGNED;
-    const Grid1dWs ws = csr_ws(workspace, B, N, M);
+    if (!cutoff_ok(cutoff, Bcut, B)) return CHX_ERR_INVALID_ARG;
+    const Grid1dWs ws = with_cutoff(csr_ws(workspace, B, N, M), workspace, B, M, 1, cutoff, Bcut);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
     return dispatch_dtype(dtype, [&](auto t) {
         using T = decltype(t);
@@ -746,13 +758,23 @@ extern "C" int chx_csr_kick(const void* x, const void* q, const void* w, const v
     });
 }
 
-extern "C" int chx_csr_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
-                                int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
-                                void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int chx_csr_kick(const void* x, const void* q, const void* w, const void* energy, const void* length, const void* angle,
+                            double mass_eV, double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be,
+                            int64_t Bl, int64_t Ba, int64_t N, int32_t M, int dtype, void* out, double* state, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    return chx_csr_kick_cut(x, q, w, energy, length, angle, mass_eV, abs_charge, B, Bx, Bq, Bw, Be, Bl, Ba, N, M, dtype, out, state,
+                            nullptr, 1, workspace, workspace_bytes, stream);
+}
+
+extern "C" int chx_csr_kick_bwd_cut(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                                    int64_t N, int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC,
+                                    double* d_scale, const double* cutoff, int64_t Bcut, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
     const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!d_out || !dX || !d_scale) return CHX_ERR_INVALID_ARG;
-    const Grid1dWs ws = csr_ws(workspace, B, N, M);
+    if (!cutoff_ok(cutoff, Bcut, B)) return CHX_ERR_INVALID_ARG;
+    const Grid1dWs ws = with_cutoff(csr_ws(workspace, B, N, M), workspace, B, M, 1, cutoff, Bcut);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
     return dispatch_dtype(dtype, [&](auto t) {
         using T = decltype(t);
@@ -761,20 +783,31 @@ extern "C" int chx_csr_kick_bwd(const void* x, const void* q, const void* w, int
     });
 }
 
-extern "C" size_t chx_csr_transient_workspace_bytes(int64_t B, int64_t N, int32_t M) { return csrt_ws(nullptr, B, N, M).bytes; }
+extern "C" int chx_csr_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                                int64_t N, int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC,
+                                double* d_scale, void* workspace, size_t workspace_bytes, void* stream) {
+    return chx_csr_kick_bwd_cut(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state, d_out, dX, dC, d_scale, nullptr, 1, workspace,
+                                workspace_bytes, stream);
+}
 
-extern "C" int chx_csr_transient_kick(const void* x, const void* q, const void* w, const void* energy, const void* length,
-                                      const void* angle, const void* distance, double mass_eV, double abs_charge, int64_t B,
-                                      int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Ba, int64_t Bd, int64_t N,
-                                      int32_t M, int dtype, void* out, double* state, void* workspace, size_t workspace_bytes,
-                                      void* stream) {
+extern "C" size_t chx_csr_transient_workspace_bytes(int64_t B, int64_t N, int32_t M) { return csrt_ws(nullptr, B, N, M).bytes; }
+extern "C" size_t chx_csr_transient_workspace_bytes_cut(int64_t B, int64_t N, int32_t M) {
+    return cutoff_ws_bytes(csrt_ws(nullptr, B, N, M), B, M, 1);
+}
+
+extern "C" int chx_csr_transient_kick_cut(const void* x, const void* q, const void* w, const void* energy, const void* length,
+                                          const void* angle, const void* distance, double mass_eV, double abs_charge, int64_t B,
+                                          int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Ba, int64_t Bd,
+                                          int64_t N, int32_t M, int dtype, void* out, double* state, const double* cutoff,
+                                          int64_t Bcut, void* workspace, size_t workspace_bytes, void* stream) {
     const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!energy || !length || !angle || !distance || !(mass_eV > 0.0) || !chx_bcast_ok(Be, B) || !chx_bcast_ok(Bl, B) ||
         !chx_bcast_ok(Ba, B) || !chx_bcast_ok(Bd, B) || !out)
         return CHX_ERR_INVALID_ARG;
     if (!chx_aligned16(out)) return CHX_ERR_MISALIGNED;
-    const Grid1dWs ws = csrt_ws(workspace, B, N, M);
+    if (!cutoff_ok(cutoff, Bcut, B)) return CHX_ERR_INVALID_ARG;
+    const Grid1dWs ws = with_cutoff(csrt_ws(workspace, B, N, M), workspace, B, M, 1, cutoff, Bcut);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
     return dispatch_dtype(dtype, [&](auto t) {
         using T = decltype(t);
@@ -784,13 +817,24 @@ extern "C" int chx_csr_transient_kick(const void* x, const void* q, const void* 
     });
 }
 
-extern "C" int chx_csr_transient_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
-                                          int64_t N, int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC,
-                                          double* d_scale, double* d_x, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int chx_csr_transient_kick(const void* x, const void* q, const void* w, const void* energy, const void* length,
+                                      const void* angle, const void* distance, double mass_eV, double abs_charge, int64_t B,
+                                      int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Ba, int64_t Bd, int64_t N,
+                                      int32_t M, int dtype, void* out, double* state, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    return chx_csr_transient_kick_cut(x, q, w, energy, length, angle, distance, mass_eV, abs_charge, B, Bx, Bq, Bw, Be, Bl, Ba, Bd,
+                                      N, M, dtype, out, state, nullptr, 1, workspace, workspace_bytes, stream);
+}
+
+extern "C" int chx_csr_transient_kick_bwd_cut(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq,
+                                              int64_t Bw, int64_t N, int32_t M, int dtype, const double* state, const void* d_out,
+                                              void* dX, void* dC, double* d_scale, double* d_x, const double* cutoff, int64_t Bcut,
+                                              void* workspace, size_t workspace_bytes, void* stream) {
     const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!d_out || !dX || !d_scale || !d_x) return CHX_ERR_INVALID_ARG;
-    const Grid1dWs ws = csrt_ws(workspace, B, N, M);
+    if (!cutoff_ok(cutoff, Bcut, B)) return CHX_ERR_INVALID_ARG;
+    const Grid1dWs ws = with_cutoff(csrt_ws(workspace, B, N, M), workspace, B, M, 1, cutoff, Bcut);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
     return dispatch_dtype(dtype, [&](auto t) {
         using T = decltype(t);
@@ -799,20 +843,33 @@ extern "C" int chx_csr_transient_kick_bwd(const void* x, const void* q, const vo
     });
 }
 
-extern "C" size_t chx_csr_drift_workspace_bytes(int64_t B, int64_t N, int32_t M) { return csrd_ws(nullptr, B, N, M).bytes; }
+extern "C" int chx_csr_transient_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq,
+                                          int64_t Bw, int64_t N, int32_t M, int dtype, const double* state, const void* d_out,
+                                          void* dX, void* dC, double* d_scale, double* d_x, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
+    return chx_csr_transient_kick_bwd_cut(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state, d_out, dX, dC, d_scale, d_x, nullptr, 1,
+                                          workspace, workspace_bytes, stream);
+}
 
-extern "C" int chx_csr_drift_kick(const void* x, const void* q, const void* w, const void* energy, const void* length,
-                                  const void* bend_length, const void* bend_angle, const void* distance, double mass_eV,
-                                  double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Bbl,
-                                  int64_t Bba, int64_t Bd, int64_t N, int32_t M, int dtype, void* out, double* state, void* workspace,
-                                  size_t workspace_bytes, void* stream) {
+extern "C" size_t chx_csr_drift_workspace_bytes(int64_t B, int64_t N, int32_t M) { return csrd_ws(nullptr, B, N, M).bytes; }
+extern "C" size_t chx_csr_drift_workspace_bytes_cut(int64_t B, int64_t N, int32_t M) {
+    return cutoff_ws_bytes(csrd_ws(nullptr, B, N, M), B, M, 1);
+}
+
+extern "C" int chx_csr_drift_kick_cut(const void* x, const void* q, const void* w, const void* energy, const void* length,
+                                      const void* bend_length, const void* bend_angle, const void* distance, double mass_eV,
+                                      double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl,
+                                      int64_t Bbl, int64_t Bba, int64_t Bd, int64_t N, int32_t M, int dtype, void* out,
+                                      double* state, const double* cutoff, int64_t Bcut, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
     const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!energy || !length || !bend_length || !bend_angle || !distance || !(mass_eV > 0.0) || !chx_bcast_ok(Be, B) ||
         !chx_bcast_ok(Bl, B) || !chx_bcast_ok(Bbl, B) || !chx_bcast_ok(Bba, B) || !chx_bcast_ok(Bd, B) || !out)
         return CHX_ERR_INVALID_ARG;
     if (!chx_aligned16(out)) return CHX_ERR_MISALIGNED;
-    const Grid1dWs ws = csrd_ws(workspace, B, N, M);
+    if (!cutoff_ok(cutoff, Bcut, B)) return CHX_ERR_INVALID_ARG;
+    const Grid1dWs ws = with_cutoff(csrd_ws(workspace, B, N, M), workspace, B, M, 1, cutoff, Bcut);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
     return dispatch_dtype(dtype, [&](auto t) {
         using T = decltype(t);
@@ -822,18 +879,37 @@ extern "C" int chx_csr_drift_kick(const void* x, const void* q, const void* w, c
     });
 }
 
-extern "C" int chx_csr_drift_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
-                                      int64_t N, int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC,
-                                      double* d_scale, double* d_xh, double* d_phi, double* d_kappa, void* workspace,
-                                      size_t workspace_bytes, void* stream) {
+extern "C" int chx_csr_drift_kick(const void* x, const void* q, const void* w, const void* energy, const void* length,
+                                  const void* bend_length, const void* bend_angle, const void* distance, double mass_eV,
+                                  double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl,
+                                  int64_t Bbl, int64_t Bba, int64_t Bd, int64_t N, int32_t M, int dtype, void* out, double* state,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    return chx_csr_drift_kick_cut(x, q, w, energy, length, bend_length, bend_angle, distance, mass_eV, abs_charge, B, Bx, Bq, Bw,
+                                  Be, Bl, Bbl, Bba, Bd, N, M, dtype, out, state, nullptr, 1, workspace, workspace_bytes, stream);
+}
+
+extern "C" int chx_csr_drift_kick_bwd_cut(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq,
+                                          int64_t Bw, int64_t N, int32_t M, int dtype, const double* state, const void* d_out,
+                                          void* dX, void* dC, double* d_scale, double* d_xh, double* d_phi, double* d_kappa,
+                                          const double* cutoff, int64_t Bcut, void* workspace, size_t workspace_bytes,
+                                          void* stream) {
     const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!d_out || !dX || !d_scale || !d_xh || !d_phi || !d_kappa) return CHX_ERR_INVALID_ARG;
-    const Grid1dWs ws = csrd_ws(workspace, B, N, M);
+    if (!cutoff_ok(cutoff, Bcut, B)) return CHX_ERR_INVALID_ARG;
+    const Grid1dWs ws = with_cutoff(csrd_ws(workspace, B, N, M), workspace, B, M, 1, cutoff, Bcut);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
     return dispatch_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return csrd_kick_bwd_t<T>((const T*)x, (const T*)q, (const T*)w, B, Bx, Bq, Bw, N, M, state, (const T*)d_out, (T*)dX, (T*)dC,
                                   d_scale, d_xh, d_phi, d_kappa, ws, (hipStream_t)stream);
     });
+}
+
+extern "C" int chx_csr_drift_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                                      int64_t N, int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC,
+                                      double* d_scale, double* d_xh, double* d_phi, double* d_kappa, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+    return chx_csr_drift_kick_bwd_cut(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state, d_out, dX, dC, d_scale, d_xh, d_phi, d_kappa,
+                                      nullptr, 1, workspace, workspace_bytes, stream);
 }

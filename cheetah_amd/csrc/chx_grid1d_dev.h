@@ -2,8 +2,10 @@
 // chx_csr.hip, chx_lsc.hip): the node coordinate, 64-bit fixed-point deposits, fixed-order reductions, the two particle passes that
 // find the row's tau range (F1, wake_range_kernel) and deposit the line density (F2, wake_deposit_kernel), and the particle passes
 // of the single-channel kicks (CSR, LSC): the gather-kick F4 (node_kick_kernel) and the backward passes B1 (node_bwd_range_kernel),
-// B2 (node_bwd_deposit_kernel) and B4 (node_bwd_particles_kernel), which take the doubles per state row as an argument. Per batch
-// row, every grid quantity in fp64. The host side of the same layer (argument check, workspace, launchers) is chx_grid1d_host.h.
+// B2 (node_bwd_deposit_kernel) and B4 (node_bwd_particles_kernel), which take the doubles per state row as an argument, and the
+// low-pass stage of the calls with a cutoff (grid_filter_kernel) between F2 and a kick's node pass and, backward, in front of its last
+// particle pass. Per batch row, every grid quantity in fp64. The host side of the same layer (argument check, workspace, launchers)
+// is chx_grid1d_host.h.
 #pragma once
 #include "chx_common.h"
 
@@ -222,6 +224,82 @@ __global__ __launch_bounds__(kWB) void wake_deposit_kernel(const T* __restrict__
         const unsigned long long v = hist[i];
         if (v) atomicAdd(&gr[i], v);
     }
+}
+
+// ---- the low-pass stage between F2 and a kick's node pass, and between a kick's adjoint node pass and its last particle pass: one
+// workgroup per (row, channel, tile of kWB nodes) smooths the channel's M values with the Gaussian of rms width s = cutoff / (2 pi h)
+// nodes, from `src` into `dst`,
+//   R = max(1, min(ceil(4 s), M - 1)), g_d = exp(-d^2 / 2 s^2) / sum_{|e| <= R} g_e, D'_j = sum_{|d| <= R} g_d D_refl(j - d),
+// refl(i) = -1 - i for i < 0 and 2 M - 1 - i for i >= M (the row mirrored about its two ends; R <= M - 1, so once is enough). The matrix
+// is symmetric (the adjoint is the same stage), its columns sum to 1 (the charge is kept) and no weight is negative (|D'| <= max |D|:
+// the fixed-point scale still holds). The weights (formed once per workgroup) and the tile's window j0 - R ... j0 + kWB - 1 + R, already
+// mirrored, sit in LDS; D'_j is one thread's sum g_0 D_j + sum_{d = 1 ... R} g_d (D_(j-d) + D_(j+d)) in that order. kFixed: the
+// fixed-point grids (channel c scaled by the header's S[c]), else the float64 cotangents. A row without a grid (no survivor, h = 0),
+// a cutoff that is not > 0 or not finite, a channel whose scale is 0 (non-finite deposits) and weights that are the identity
+// (g_1 = 0) are copied bit for bit.
+constexpr double kTwoPi = 6.283185307179586;
+
+template <bool kFixed>
+__global__ __launch_bounds__(kWB) void grid_filter_kernel(const double* __restrict__ cutoff, int64_t Bc, int M, int channels,
+                                                          const double* __restrict__ state, int64_t state_row,
+                                                          const void* __restrict__ src, void* __restrict__ dst) {
+    extern __shared__ __attribute__((aligned(16))) double flt[];             // g[M], red[kWB / 64], norm, win[nodes of the tile + 2 R]
+    const int64_t b = blockIdx.y;
+    const int c = blockIdx.z, t = threadIdx.x, j0 = blockIdx.x * kWB, j = j0 + t;
+    const int64_t row = (b * channels + c) * M;
+    const unsigned long long* sx = (const unsigned long long*)src + row;
+    const double* sd = (const double*)src + row;
+    unsigned long long* dx = (unsigned long long*)dst + row;
+    double* dd = (double*)dst + row;
+    const double* st = state + b * state_row;
+    const double h = st[2], lc = cutoff[Bc == 1 ? 0 : b], S = kFixed ? st[3 + c] : 1.0;
+    double* g = flt;
+    double* red = flt + M;
+    double* win = flt + M + kWB / 64 + 1;
+    bool copy = st[0] == 0.0 || !(h > 0.0) || !(lc > 0.0) || !isfinite(lc) || S == 0.0;     // the same in every thread
+    int R = 0;
+    if (!copy) {
+        const double s = lc / (kTwoPi * h);
+        R = (int)fmax(1.0, fmin(ceil(4.0 * s), (double)(M - 1)));
+        double part = 0.0;
+        for (int d = t; d <= R; d += kWB) {
+            const double r = (double)d / s, v = d == 0 ? 1.0 : exp(-0.5 * r * r);
+            g[d] = v;
+            part += d == 0 ? v : 2.0 * v;
+        }
+        part = chx_wave_sum(part);
+        if ((t & 63) == 0) red[t >> 6] = part;
+        __syncthreads();
+        if (t == 0) {
+            double n = 0.0;
+            for (int v = 0; v < kWB / 64; ++v) n += red[v];
+            red[kWB / 64] = n;
+        }
+        __syncthreads();
+        copy = g[1] == 0.0;
+    }
+    if (copy) {
+        if (j < M) {
+            if (kFixed) dx[j] = sx[j];
+            else dd[j] = sd[j];
+        }
+        return;
+    }
+    const double norm = red[kWB / 64];
+    const int nodes = M - j0 < kWB ? M - j0 : kWB;
+    for (int i = t; i < nodes + 2 * R; i += kWB) {
+        int m = j0 - R + i;
+        m = m < 0 ? -1 - m : (m >= M ? 2 * M - 1 - m : m);
+        win[i] = kFixed ? from_fixed(sx[m], S) : sd[m];
+    }
+    __syncthreads();
+    if (j >= M) return;
+    const double* w0 = win + t + R;
+    double acc = g[0] * w0[0];
+    for (int d = 1; d <= R; ++d) acc += g[d] * (w0[-d] + w0[d]);
+    acc /= norm;
+    if (kFixed) dx[j] = to_fixed(acc, S);
+    else dd[j] = acc;
 }
 
 // ---- the particle passes of the kicks whose state row is [header | M node kicks | ...] with the row's scale in the header's last

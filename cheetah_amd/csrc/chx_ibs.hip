@@ -329,22 +329,30 @@ int ibs_kick_bwd_t(const T* x, const T* q, const T* w, IbsKey key, const int64_t
     CHX_CHECK_LAUNCH();
     hipLaunchKernelGGL(ibs_bwd_node_kernel, dim3((unsigned)B), dim3(kWB), 0, s, M, state, ws.bhdr, ws.ggrid, ws.adj, d_scale);
     CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(ibs_bwd_particles_kernel<T>, grid_particles(N, B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, M, state, ws.adj,
-                       gout, key, call_index, dX, dC);
+    const int st = launch_adj_filter(B, M, 1, ibs_state_row(M), state, ws, s);
+    if (st != CHX_OK) return st;
+    hipLaunchKernelGGL(ibs_bwd_particles_kernel<T>, grid_particles(N, B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, M, state,
+                       ws.adj_last, gout, key, call_index, dX, dC);
     CHX_CHECK_LAUNCH();
     return CHX_OK;
 }
 
 }  // namespace
 
+// Every entry point has a twin that takes cutoff[Bcut] in front of the workspace (the low-pass stage of chx_grid1d_dev.h, launched by
+// launch_deposit and launch_adj_filter); the call without the suffix is the twin with a null cutoff.
 extern "C" size_t chx_ibs_workspace_bytes(int64_t B, int64_t N, int32_t M) { return ibs_ws(nullptr, B, N, M).bytes; }
+extern "C" size_t chx_ibs_workspace_bytes_cut(int64_t B, int64_t N, int32_t M) {
+    return cutoff_ws_bytes(ibs_ws(nullptr, B, N, M), B, M, 1);
+}
 
-extern "C" int chx_ibs_kick(const void* x, const void* q, const void* w, const void* energy, const void* length,
-                            const void* coulomb_log, const void* sigma_x, const void* sigma_y, const void* eps_x, const void* eps_y,
-                            double mass_eV, double abs_charge, uint32_t seed, uint32_t rng_stream, const int64_t* call_index,
-                            int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Bc, int64_t Bsx,
-                            int64_t Bsy, int64_t Bex, int64_t Bey, int64_t N, int32_t M, int dtype, void* out, double* state,
-                            void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int chx_ibs_kick_cut(const void* x, const void* q, const void* w, const void* energy, const void* length,
+                                const void* coulomb_log, const void* sigma_x, const void* sigma_y, const void* eps_x,
+                                const void* eps_y, double mass_eV, double abs_charge, uint32_t seed, uint32_t rng_stream,
+                                const int64_t* call_index, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl,
+                                int64_t Bc, int64_t Bsx, int64_t Bsy, int64_t Bex, int64_t Bey, int64_t N, int32_t M, int dtype,
+                                void* out, double* state, const double* cutoff, int64_t Bcut, void* workspace,
+                                size_t workspace_bytes, void* stream) {
     const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     const void* ptrs[kSettings] = {energy, length, coulomb_log, sigma_x, sigma_y, eps_x, eps_y};
@@ -353,7 +361,8 @@ extern "C" int chx_ibs_kick(const void* x, const void* q, const void* w, const v
         if (!ptrs[i] || !chx_bcast_ok(rows[i], B)) return CHX_ERR_INVALID_ARG;
     if (!(mass_eV > 0.0) || !call_index || !out) return CHX_ERR_INVALID_ARG;
     if (!chx_aligned16(out)) return CHX_ERR_MISALIGNED;
-    const Grid1dWs ws = ibs_ws(workspace, B, N, M);
+    if (!cutoff_ok(cutoff, Bcut, B)) return CHX_ERR_INVALID_ARG;
+    const Grid1dWs ws = with_cutoff(ibs_ws(workspace, B, N, M), workspace, B, M, 1, cutoff, Bcut);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
     return dispatch_dtype(dtype, [&](auto t) {
         using T = decltype(t);
@@ -367,20 +376,40 @@ extern "C" int chx_ibs_kick(const void* x, const void* q, const void* w, const v
     });
 }
 
-extern "C" int chx_ibs_kick_bwd(const void* x, const void* q, const void* w, uint32_t seed, uint32_t rng_stream,
-                                const int64_t* call_index, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M,
-                                int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
-                                void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int chx_ibs_kick(const void* x, const void* q, const void* w, const void* energy, const void* length,
+                            const void* coulomb_log, const void* sigma_x, const void* sigma_y, const void* eps_x, const void* eps_y,
+                            double mass_eV, double abs_charge, uint32_t seed, uint32_t rng_stream, const int64_t* call_index,
+                            int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Bc, int64_t Bsx,
+                            int64_t Bsy, int64_t Bex, int64_t Bey, int64_t N, int32_t M, int dtype, void* out, double* state,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    return chx_ibs_kick_cut(x, q, w, energy, length, coulomb_log, sigma_x, sigma_y, eps_x, eps_y, mass_eV, abs_charge, seed,
+                            rng_stream, call_index, B, Bx, Bq, Bw, Be, Bl, Bc, Bsx, Bsy, Bex, Bey, N, M, dtype, out, state, nullptr,
+                            1, workspace, workspace_bytes, stream);
+}
+
+extern "C" int chx_ibs_kick_bwd_cut(const void* x, const void* q, const void* w, uint32_t seed, uint32_t rng_stream,
+                                    const int64_t* call_index, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M,
+                                    int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
+                                    const double* cutoff, int64_t Bcut, void* workspace, size_t workspace_bytes, void* stream) {
     const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!call_index || !d_out || !dX || !d_scale) return CHX_ERR_INVALID_ARG;
-    const Grid1dWs ws = ibs_ws(workspace, B, N, M);
+    if (!cutoff_ok(cutoff, Bcut, B)) return CHX_ERR_INVALID_ARG;
+    const Grid1dWs ws = with_cutoff(ibs_ws(workspace, B, N, M), workspace, B, M, 1, cutoff, Bcut);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
     return dispatch_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return ibs_kick_bwd_t<T>((const T*)x, (const T*)q, (const T*)w, IbsKey{seed, rng_stream}, call_index, B, Bx, Bq, Bw, N, M,
                                  state, (const T*)d_out, (T*)dX, (T*)dC, d_scale, ws, (hipStream_t)stream);
     });
+}
+
+extern "C" int chx_ibs_kick_bwd(const void* x, const void* q, const void* w, uint32_t seed, uint32_t rng_stream,
+                                const int64_t* call_index, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M,
+                                int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
+                                void* workspace, size_t workspace_bytes, void* stream) {
+    return chx_ibs_kick_bwd_cut(x, q, w, seed, rng_stream, call_index, B, Bx, Bq, Bw, N, M, dtype, state, d_out, dX, dC, d_scale,
+                                nullptr, 1, workspace, workspace_bytes, stream);
 }
 
 extern "C" int chx_ibs_normals(uint32_t seed, uint32_t rng_stream, uint64_t call, int64_t B, int64_t N, uint32_t* words_out,

@@ -240,7 +240,9 @@ int lsc_kick_bwd_t(const T* x, const T* q, const T* w, int64_t B, int64_t Bx, in
     hipLaunchKernelGGL(lsc_bwd_toeplitz_kernel, grid_nodes(M, B), dim3(kWB), lsc_lds(M, 2), s, M, state, ws.bhdr, ws.ggrid, ws.adj,
                        ws.extra);
     CHX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(lsc_bwd_particles_kernel<T>, grid_particles(N, B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, M, state, ws.adj,
+    st = launch_adj_filter(B, M, 1, lsc_state_row(M), state, ws, s);
+    if (st != CHX_OK) return st;
+    hipLaunchKernelGGL(lsc_bwd_particles_kernel<T>, grid_particles(N, B), dim3(kWB), 0, s, x, q, w, Bx, Bq, Bw, N, M, state, ws.adj_last,
                        ws.extra, gout, dX, dC, d_rho);
     CHX_CHECK_LAUNCH();
     return CHX_OK;
@@ -248,19 +250,26 @@ int lsc_kick_bwd_t(const T* x, const T* q, const T* w, int64_t B, int64_t Bx, in
 
 }  // namespace
 
+// Every entry point has a twin that takes cutoff[Bcut] in front of the workspace (the low-pass stage of chx_grid1d_dev.h, launched by
+// launch_deposit and launch_adj_filter); the call without the suffix is the twin with a null cutoff.
 extern "C" size_t chx_lsc_workspace_bytes(int64_t B, int64_t N, int32_t M) { return lsc_ws(nullptr, B, N, M).bytes; }
+extern "C" size_t chx_lsc_workspace_bytes_cut(int64_t B, int64_t N, int32_t M) {
+    return cutoff_ws_bytes(lsc_ws(nullptr, B, N, M), B, M, 1);
+}
 
-extern "C" int chx_lsc_kick(const void* x, const void* q, const void* w, const void* energy, const void* length, const void* radius,
-                            double mass_eV, double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl,
-                            int64_t Ba, int64_t N, int32_t M, int dtype, void* out, double* state, void* workspace,
-                            size_t workspace_bytes, void* stream) {
+extern "C" int chx_lsc_kick_cut(const void* x, const void* q, const void* w, const void* energy, const void* length,
+                                const void* radius, double mass_eV, double abs_charge, int64_t B, int64_t Bx, int64_t Bq,
+                                int64_t Bw, int64_t Be, int64_t Bl, int64_t Ba, int64_t N, int32_t M, int dtype, void* out,
+                                double* state, const double* cutoff, int64_t Bcut, void* workspace, size_t workspace_bytes,
+                                void* stream) {
     const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!energy || !length || !radius || !(mass_eV > 0.0) || !chx_bcast_ok(Be, B) || !chx_bcast_ok(Bl, B) || !chx_bcast_ok(Ba, B) ||
         !out)
         return CHX_ERR_INVALID_ARG;
     if (!chx_aligned16(out)) return CHX_ERR_MISALIGNED;
-    const Grid1dWs ws = lsc_ws(workspace, B, N, M);
+    if (!cutoff_ok(cutoff, Bcut, B)) return CHX_ERR_INVALID_ARG;
+    const Grid1dWs ws = with_cutoff(lsc_ws(workspace, B, N, M), workspace, B, M, 1, cutoff, Bcut);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
     return dispatch_dtype(dtype, [&](auto t) {
         using T = decltype(t);
@@ -269,17 +278,34 @@ extern "C" int chx_lsc_kick(const void* x, const void* q, const void* w, const v
     });
 }
 
-extern "C" int chx_lsc_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
-                                int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
-                                double* d_rho, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int chx_lsc_kick(const void* x, const void* q, const void* w, const void* energy, const void* length, const void* radius,
+                            double mass_eV, double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be,
+                            int64_t Bl, int64_t Ba, int64_t N, int32_t M, int dtype, void* out, double* state, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    return chx_lsc_kick_cut(x, q, w, energy, length, radius, mass_eV, abs_charge, B, Bx, Bq, Bw, Be, Bl, Ba, N, M, dtype, out,
+                            state, nullptr, 1, workspace, workspace_bytes, stream);
+}
+
+extern "C" int chx_lsc_kick_bwd_cut(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                                    int64_t N, int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC,
+                                    double* d_scale, double* d_rho, const double* cutoff, int64_t Bcut, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
     const int st = check_grid1d(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!d_out || !dX || !d_scale || !d_rho) return CHX_ERR_INVALID_ARG;
-    const Grid1dWs ws = lsc_ws(workspace, B, N, M);
+    if (!cutoff_ok(cutoff, Bcut, B)) return CHX_ERR_INVALID_ARG;
+    const Grid1dWs ws = with_cutoff(lsc_ws(workspace, B, N, M), workspace, B, M, 1, cutoff, Bcut);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
     return dispatch_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return lsc_kick_bwd_t<T>((const T*)x, (const T*)q, (const T*)w, B, Bx, Bq, Bw, N, M, state, (const T*)d_out, (T*)dX, (T*)dC,
                                  d_scale, d_rho, ws, (hipStream_t)stream);
     });
+}
+
+extern "C" int chx_lsc_kick_bwd(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                                int64_t N, int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC,
+                                double* d_scale, double* d_rho, void* workspace, size_t workspace_bytes, void* stream) {
+    return chx_lsc_kick_bwd_cut(x, q, w, B, Bx, Bq, Bw, N, M, dtype, state, d_out, dX, dC, d_scale, d_rho, nullptr, 1, workspace,
+                                workspace_bytes, stream);
 }

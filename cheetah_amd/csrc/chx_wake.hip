@@ -525,24 +525,33 @@ int wake_kick_bwd_t(const T* x, const T* q, const T* w, const double* scale, con
             CHX_CHECK_LAUNCH();
         }
     }
+    const int st = launch_adj_filter(B, M, 3, state_row(M), state, ws, s);
+    if (st != CHX_OK) return st;
     hipLaunchKernelGGL(wake_bwd_particles_kernel<T>, dim3((unsigned)((N + kWB - 1) / kWB), (unsigned)B), dim3(kWB), 0, s, x, q, w, Bx,
-                       Bq, Bw, N, M, has_t, scale, state, ws.adj, gout, dX, dC);
+                       Bq, Bw, N, M, has_t, scale, state, ws.adj_last, gout, dX, dC);
     CHX_CHECK_LAUNCH();
     return CHX_OK;
 }
 
 }  // namespace
 
+// Every entry point has a twin that takes cutoff[Bcut] in front of the workspace (the low-pass stage of chx_grid1d_dev.h, launched by
+// launch_deposit and launch_adj_filter); the call without the suffix is the twin with a null cutoff.
 extern "C" size_t chx_wake_workspace_bytes(int64_t B, int64_t N, int32_t M) { return wake_ws(nullptr, B, N, M).bytes; }
+extern "C" size_t chx_wake_workspace_bytes_cut(int64_t B, int64_t N, int32_t M) {
+    return cutoff_ws_bytes(wake_ws(nullptr, B, N, M), B, M, 3);
+}
 
-extern "C" int chx_wake_kick(const void* x, const void* q, const void* w, const double* scale, const double* wl, int64_t Ll,
-                             const double* wt, int64_t Lt, const double* h, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
-                             int32_t M, int dtype, void* out, double* state, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int chx_wake_kick_cut(const void* x, const void* q, const void* w, const double* scale, const double* wl, int64_t Ll,
+                                 const double* wt, int64_t Lt, const double* h, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                                 int64_t N, int32_t M, int dtype, void* out, double* state, const double* cutoff, int64_t Bcut,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
     const int st = check_wake(x, q, w, scale, wl, Ll, wt, Lt, h, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!out) return CHX_ERR_INVALID_ARG;
     if (!chx_aligned16(out)) return CHX_ERR_MISALIGNED;
-    const Grid1dWs ws = wake_ws(workspace, B, N, M);
+    if (!cutoff_ok(cutoff, Bcut, B)) return CHX_ERR_INVALID_ARG;
+    const Grid1dWs ws = with_cutoff(wake_ws(workspace, B, N, M), workspace, B, M, 3, cutoff, Bcut);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
     return dispatch_dtype(dtype, [&](auto t) {
         using T = decltype(t);
@@ -551,18 +560,37 @@ extern "C" int chx_wake_kick(const void* x, const void* q, const void* w, const 
     });
 }
 
-extern "C" int chx_wake_kick_bwd(const void* x, const void* q, const void* w, const double* scale, const double* wl, int64_t Ll,
-                                 const double* wt, int64_t Lt, const double* h, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
-                                 int64_t N, int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC,
-                                 double* d_scale, double* d_wl, double* d_wt, void* workspace, size_t workspace_bytes, void* stream) {
+extern "C" int chx_wake_kick(const void* x, const void* q, const void* w, const double* scale, const double* wl, int64_t Ll,
+                             const double* wt, int64_t Lt, const double* h, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                             int64_t N, int32_t M, int dtype, void* out, double* state, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+    return chx_wake_kick_cut(x, q, w, scale, wl, Ll, wt, Lt, h, B, Bx, Bq, Bw, N, M, dtype, out, state, nullptr, 1, workspace,
+                             workspace_bytes, stream);
+}
+
+extern "C" int chx_wake_kick_bwd_cut(const void* x, const void* q, const void* w, const double* scale, const double* wl, int64_t Ll,
+                                     const double* wt, int64_t Lt, const double* h, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                                     int64_t N, int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC,
+                                     double* d_scale, double* d_wl, double* d_wt, const double* cutoff, int64_t Bcut,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
     const int st = check_wake(x, q, w, scale, wl, Ll, wt, Lt, h, B, Bx, Bq, Bw, N, M, dtype, state);
     if (st != CHX_OK) return st;
     if (!d_out || !dX || !d_scale) return CHX_ERR_INVALID_ARG;
-    const Grid1dWs ws = wake_ws(workspace, B, N, M);
+    if (!cutoff_ok(cutoff, Bcut, B)) return CHX_ERR_INVALID_ARG;
+    const Grid1dWs ws = with_cutoff(wake_ws(workspace, B, N, M), workspace, B, M, 3, cutoff, Bcut);
     if (!workspace || workspace_bytes < ws.bytes) return CHX_ERR_WORKSPACE;
     return dispatch_dtype(dtype, [&](auto t) {
         using T = decltype(t);
         return wake_kick_bwd_t<T>((const T*)x, (const T*)q, (const T*)w, scale, wl, Ll, wt, Lt, h, B, Bx, Bq, Bw, N, M, state,
                                   (const T*)d_out, (T*)dX, (T*)dC, d_scale, d_wl, d_wt, ws, (hipStream_t)stream);
     });
+}
+
+extern "C" int chx_wake_kick_bwd(const void* x, const void* q, const void* w, const double* scale, const double* wl, int64_t Ll,
+                                 const double* wt, int64_t Lt, const double* h, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                                 int64_t N, int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC,
+                                 double* d_scale, double* d_wl, double* d_wt, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    return chx_wake_kick_bwd_cut(x, q, w, scale, wl, Ll, wt, Lt, h, B, Bx, Bq, Bw, N, M, dtype, state, d_out, dX, dC, d_scale, d_wl,
+                                 d_wt, nullptr, 1, workspace, workspace_bytes, stream);
 }

@@ -502,6 +502,76 @@ int chx_ibs_kick_bwd(const void* x, const void* q, const void* w, uint32_t seed,
                      const void* d_out, void* dX, void* dC, double* d_scale, void* workspace, size_t workspace_bytes, void* stream);
 int chx_ibs_normals(uint32_t seed, uint32_t rng_stream, uint64_t call, int64_t B, int64_t N, uint32_t* words_out, double* xi_out,
                     void* stream);
+/* ---- low-pass filter of the binned-beam kicks (the elements' `cutoff_wavelength`): a twin of each of the twelve calls above that takes
+ * cutoff[Bcut] (fp64 device array of cutoff wavelengths lambda_c in metres, Bcut = 1 or B) in front of the workspace. Per batch row, with h
+ * the row's node spacing, between the deposit and the node pass every deposited channel (Q; Q, X, Y of the wake) is smoothed:
+ *   s = lambda_c / (2 pi h),  R = max(1, min(ceil(4 s), M - 1)),  g_d = exp(-d^2 / 2 s^2) / sum_{|e| <= R} g_e,
+ *   D'_j = sum_{|d| <= R} g_d D_refl(j - d),  refl(i) = -1 - i for i < 0, 2 M - 1 - i for i >= M
+ * (amplitude response exp(-(lambda_c / lambda)^2 / 2); symmetric, columns sum to 1: the charge is kept; no negative weight). The node
+ * pass, the state and the gather see D'; the fixed-point scales are those of the deposit. The backward twins apply the same stage to
+ * the deposits' cotangents before the last particle pass. A row without a grid (no survivor, h = 0) and a cutoff that is not > 0 or not
+ * finite are left unfiltered; weights that are the identity (g_1 = 0) leave every bit. The cutoff is a constant: no gradient.
+ * cutoff = NULL is the call without the suffix, bit for bit (which is how those are implemented), with that call's workspace. One more
+ * launch each way (one workgroup per row, channel and 256 nodes; weights and window in LDS, fixed order, no atomics). The stage
+ * writes a grid of its own, so a call with a cutoff needs chx_*_workspace_bytes_cut(B, N, M) (also for the backward pass): the
+ * call's workspace and one more [B][channels][M] block of 8 bytes. */
+size_t chx_wake_workspace_bytes_cut(int64_t B, int64_t N, int32_t M);
+size_t chx_csr_workspace_bytes_cut(int64_t B, int64_t N, int32_t M);
+size_t chx_csr_transient_workspace_bytes_cut(int64_t B, int64_t N, int32_t M);
+size_t chx_csr_drift_workspace_bytes_cut(int64_t B, int64_t N, int32_t M);
+size_t chx_lsc_workspace_bytes_cut(int64_t B, int64_t N, int32_t M);
+size_t chx_ibs_workspace_bytes_cut(int64_t B, int64_t N, int32_t M);
+int chx_lsc_kick_cut(const void* x, const void* q, const void* w, const void* energy, const void* length, const void* radius,
+                     double mass_eV, double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl,
+                     int64_t Ba, int64_t N, int32_t M, int dtype, void* out, double* state, const double* cutoff, int64_t Bcut,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int chx_lsc_kick_bwd_cut(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
+                         int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
+                         double* d_rho, const double* cutoff, int64_t Bcut, void* workspace, size_t workspace_bytes, void* stream);
+int chx_csr_kick_cut(const void* x, const void* q, const void* w, const void* energy, const void* length, const void* angle,
+                     double mass_eV, double abs_charge, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl,
+                     int64_t Ba, int64_t N, int32_t M, int dtype, void* out, double* state, const double* cutoff, int64_t Bcut,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int chx_csr_kick_bwd_cut(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
+                         int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
+                         const double* cutoff, int64_t Bcut, void* workspace, size_t workspace_bytes, void* stream);
+int chx_csr_transient_kick_cut(const void* x, const void* q, const void* w, const void* energy, const void* length,
+                               const void* angle, const void* distance, double mass_eV, double abs_charge, int64_t B, int64_t Bx,
+                               int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Ba, int64_t Bd, int64_t N, int32_t M,
+                               int dtype, void* out, double* state, const double* cutoff, int64_t Bcut, void* workspace,
+                               size_t workspace_bytes, void* stream);
+int chx_csr_transient_kick_bwd_cut(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                                   int64_t N, int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC,
+                                   double* d_scale, double* d_x, const double* cutoff, int64_t Bcut, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+int chx_csr_drift_kick_cut(const void* x, const void* q, const void* w, const void* energy, const void* length,
+                           const void* bend_length, const void* bend_angle, const void* distance, double mass_eV, double abs_charge,
+                           int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Bbl, int64_t Bba,
+                           int64_t Bd, int64_t N, int32_t M, int dtype, void* out, double* state, const double* cutoff,
+                           int64_t Bcut, void* workspace, size_t workspace_bytes, void* stream);
+int chx_csr_drift_kick_bwd_cut(const void* x, const void* q, const void* w, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw,
+                               int64_t N, int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC,
+                               double* d_scale, double* d_xh, double* d_phi, double* d_kappa, const double* cutoff, int64_t Bcut,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int chx_wake_kick_cut(const void* x, const void* q, const void* w, const double* scale, const double* wl, int64_t Ll,
+                      const double* wt, int64_t Lt, const double* h, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
+                      int32_t M, int dtype, void* out, double* state, const double* cutoff, int64_t Bcut, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int chx_wake_kick_bwd_cut(const void* x, const void* q, const void* w, const double* scale, const double* wl, int64_t Ll,
+                          const double* wt, int64_t Lt, const double* h, int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N,
+                          int32_t M, int dtype, const double* state, const void* d_out, void* dX, void* dC, double* d_scale,
+                          double* d_wl, double* d_wt, const double* cutoff, int64_t Bcut, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int chx_ibs_kick_cut(const void* x, const void* q, const void* w, const void* energy, const void* length, const void* coulomb_log,
+                     const void* sigma_x, const void* sigma_y, const void* eps_x, const void* eps_y, double mass_eV,
+                     double abs_charge, uint32_t seed, uint32_t rng_stream, const int64_t* call_index, int64_t B, int64_t Bx,
+                     int64_t Bq, int64_t Bw, int64_t Be, int64_t Bl, int64_t Bc, int64_t Bsx, int64_t Bsy, int64_t Bex, int64_t Bey,
+                     int64_t N, int32_t M, int dtype, void* out, double* state, const double* cutoff, int64_t Bcut, void* workspace,
+                     size_t workspace_bytes, void* stream);
+int chx_ibs_kick_bwd_cut(const void* x, const void* q, const void* w, uint32_t seed, uint32_t rng_stream, const int64_t* call_index,
+                         int64_t B, int64_t Bx, int64_t Bq, int64_t Bw, int64_t N, int32_t M, int dtype, const double* state,
+                         const void* d_out, void* dX, void* dC, double* d_scale, const double* cutoff, int64_t Bcut,
+                         void* workspace, size_t workspace_bytes, void* stream);
 /* ---- laser energy modulation in an undulator (LaserModulator element; Huang et al., PRSTAB 7, 074401 (2004), eq. 8), as one
  * zero-length kick. Per batch row b, in fp64, with gamma0 = energy / mass_eV, P0 = beta0 gamma0 (as chx_sr_kick forms them), the
  * amplitude A (eV), the wavelength lambda, the phase phi, the rms size sigma_r of the laser intensity, the laser axis (x0, y0), the rms
