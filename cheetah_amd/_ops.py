@@ -1000,6 +1000,32 @@ def second_order_chain(T_maps, lengths, x, s, ptrs=None, linear=None):
     return out, s_out, ptrs
 
 
+def second_order_turns_workspace_bytes(E: int, N: int, records: int, dtype) -> int:
+    """Bytes of the workspace of one `second_order_turns` call that records `records` turns: the folded coefficients and the
+    per-workgroup partial sums."""
+    return _lib.lib().chx_second_order_turns_workspace_bytes(E, N, records, dtype_code(dtype))
+
+
+def second_order_turn_ptrs(T_maps, lengths, linear):
+    """The host argument arrays of `second_order_turns` for these map / length tensors (valid while they are alive)."""
+    arr = ctypes.c_void_p * len(T_maps)
+    flags = (ctypes.c_int32 * len(T_maps))(*linear) if linear is not None and any(linear) else None
+    return arr(*[t.data_ptr() for t in T_maps]), arr(*[t.data_ptr() for t in lengths]), flags
+
+
+def second_order_turns(ptrs, E, x_in, x_out, charges, survival, first_turn, num_turns, record_every, aperture, lost_turn, sums, probe,
+                       ws, s_in=None, s_out=None) -> None:
+    """Turns [first_turn, first_turn + num_turns) of a ring of E second-order / linear items (chx_second_order_turns): x_in (N, 7)
+    -> x_out (the same tensor from the second chunk on), lost_turn (N,) int32 in / out, the records of these turns into their
+    rows of sums (R, 14) float64 and probe (R, K, 7) (None: K = 0). Launches only, no synchronisation."""
+    N = x_in.shape[0]
+    K = 0 if probe is None else probe.shape[1]
+    check(_lib.lib().chx_second_order_turns(ptrs[0], ptrs[2], ptrs[1], E, ptr(x_in), ptr(charges), ptr(survival), N, dtype_code(x_in.dtype),
+                                            first_turn, num_turns, record_every, ptr(aperture), K, ptr(x_out), ptr(lost_turn), ptr(sums),
+                                            ptr(probe), ptr(s_in), ptr(s_out), ptr(ws), ws.numel(), stream_ptr()),
+          "chx_second_order_turns")
+
+
 # ---------------------------------------------------------------------------------------------
 # moments
 #: the batch (vector) index of the reductions and deposits is `blockIdx.y`: at most 65 535 rows per launch

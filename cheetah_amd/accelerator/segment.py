@@ -1149,6 +1149,24 @@ class Segment(Element):
             out, s_out, _ = _ops.second_order_chain(ent["maps"], ent["lengths"], x, s, ent["ptrs"])
             return ParticleBeam(out, energy, particle_charges=incoming.particle_charges,
                                 survival_probabilities=incoming.survival_probabilities, s=s_out, species=species), ent["end"]
+        maps, lengths, linear, tensors, j, last_so = self._second_order_items(plan, i, x, energy, species, grad)
+        if last_so is None or len(maps) < 2:
+            return None
+        out, s_out, ptrs = _ops.second_order_chain(maps, lengths, x, s, linear=linear)
+        if not _ops.CAPTURING[0] and not any(t.requires_grad for t in tensors) and not energy.requires_grad:
+            # (maps of tensors that carry gradients are rebuilt on every track, Element._cached_map: nothing to keep)
+            cache[1][i] = {"epoch": Element._epoch, "energy": energy, "energy_version": energy._version, "dtype": x.dtype,
+                           "device": x.device, "mass": species.mass_eV_float, "nq": species.num_elementary_charges_float,
+                           "tensors": tensors, "versions": [t._version for t in tensors], "maps": maps, "lengths": lengths,
+                           "ptrs": ptrs, "end": j}
+        return ParticleBeam(out, energy, particle_charges=incoming.particle_charges,
+                            survival_probabilities=incoming.survival_probabilities, s=s_out, species=species), j
+
+    def _second_order_items(self, plan, i: int, x: torch.Tensor, energy: torch.Tensor, species: Species, grad: bool):
+        """The items of the stretch that begins at plan[i], as `chx_second_order_chain_mixed` and `chx_second_order_turns` take
+        them: (maps, lengths, linear flags, setting tensors, index behind the stretch, index of the last second-order element or
+        None). Second-order elements give their (7, 7, 7) map, a merged run of linear elements its composed (7, 7) map (a copy)
+        and its summed length; the stretch ends in front of the first item that does not qualify."""
         maps, lengths, linear, tensors = [], [], [], []
         j, last_so = i, None
         while j < len(plan):
@@ -1191,17 +1209,157 @@ class Segment(Element):
             else:
                 break
             j += 1
-        if last_so is None or len(maps) < 2:
-            return None
-        out, s_out, ptrs = _ops.second_order_chain(maps, lengths, x, s, linear=linear)
-        if not _ops.CAPTURING[0] and not any(t.requires_grad for t in tensors) and not energy.requires_grad:
-            # (maps of tensors that carry gradients are rebuilt on every track, Element._cached_map: nothing to keep)
-            cache[1][i] = {"epoch": Element._epoch, "energy": energy, "energy_version": energy._version, "dtype": x.dtype,
-                           "device": x.device, "mass": species.mass_eV_float, "nq": species.num_elementary_charges_float,
-                           "tensors": tensors, "versions": [t._version for t in tensors], "maps": maps, "lengths": lengths,
-                           "ptrs": ptrs, "end": j}
-        return ParticleBeam(out, energy, particle_charges=incoming.particle_charges,
-                            survival_probabilities=incoming.survival_probabilities, s=s_out, species=species), j
+        return maps, lengths, linear, tensors, j, last_so
+
+    # ---- multi-turn tracking ---------------------------------------------------------------------------------
+    def _turn_items(self, incoming: ParticleBeam):
+        """(maps, lengths, linear) when the WHOLE lattice is one stretch the fused turn kernel takes — second-order elements and
+        merged linear runs as in `_second_order_run`, or a single merged linear run — else the reason (a str) why not."""
+        x, energy, s = incoming.particles, incoming.energy, incoming.s
+        if x.dim() != 2 or not x.is_cuda:
+            return "the beam is not one plain (N, 7) beam on the device"
+        if energy.dim() != 0 or s.dim() != 0 or s.dtype != x.dtype or s.device != x.device or energy.dtype != x.dtype:
+            return "the beam's energy and path length are not scalars of the particles' dtype on their device"
+        if energy.device != x.device:
+            return "the beam's energy is not on the particles' device"
+        # the kernel reads the weights as N values of the particles' dtype through their addresses: nothing else may reach it (a
+        # beam with vectorised charges, (B, N) under particles (N, 7), is a vectorised beam: the general path)
+        for name, wt in (("particle_charges", incoming.particle_charges), ("survival_probabilities", incoming.survival_probabilities)):
+            if wt.shape != x.shape[:1] or wt.dtype != x.dtype or wt.device != x.device:
+                return f"the beam's {name} are not one (N,) tensor of the particles' dtype on their device"
+        if type(self).track is not Segment.track or type(self)._track_internal is not Segment._track_internal:
+            return "the segment overrides `track`"
+        plan = self._plan()
+        if not plan:
+            return "the lattice holds nothing to track"
+        # (the caller runs under no_grad, so the `grad` flag is False here and `_second_order_items` skips its own requires_grad
+        # tests: trainable settings are turned away by the sweep over `tensors` below)
+        maps, lengths, linear, tensors, j, _ = self._second_order_items(plan, 0, x, energy, incoming.species, torch.is_grad_enabled())
+        if j < len(plan):
+            kind, item = plan[j]
+            what = "a run of linear elements that does not qualify (vectorised or trainable settings, or the run in front of a cavity)" \
+                if kind == "run" else \
+                f"{type(item).__name__} '{item.name}' (tracking method '{item._tracking_method}')"
+            return f"the lattice is not one stretch of second-order and linear items: {what} ends it"
+        if not 1 <= len(maps) <= 224:
+            return f"the lattice has {len(maps)} items, the fused kernel takes 1 to 224"
+        if any(t.requires_grad for t in tensors):
+            return "a setting of the lattice requires grad"
+        return maps, lengths, linear
+
+    def track_turns(self, incoming: ParticleBeam, num_turns: int, *, record_every: int = 1, aperture=None, record_first: int = 0,
+                    fused=None):
+        """`num_turns` passes of the beam through this lattice taken as a ring, with turn-by-turn records: a `TurnByTurn`
+        (particles/turns.py documents its fields).
+
+        At the end of every turn a live particle is LOST when one of its six coordinates is non-finite or, with `aperture` =
+        a tensor (a_x, a_y) of the beam's dtype on its device, |x| > a_x or |y| > a_y. It keeps the coordinates of that moment,
+        is not tracked further, is absent from every record from that turn on, and its survival probability in the outgoing beam
+        is multiplied by 0. The aperture is read on the device when the turns run: an in-place edit is followed.
+        Every turn t with t % record_every == 0 is recorded (R = num_turns // record_every records): the number and charge of
+        the live particles, their weighted mean and spread per coordinate, and rows 0 .. record_first - 1 of the beam.
+
+        fused=None   the fused path when the lattice qualifies, else the general one
+        fused=True   the fused path; ValueError with the reason when the lattice does not qualify
+        fused=False  the general path
+        The FUSED path takes a lattice whose whole plan is one stretch of second-order elements and merged runs of linear
+        elements (or one merged linear run) of at most 224 items, under the conditions of a second-order run in `track`: one
+        plain (N, 7) beam on the device, scalar settings of the beam's dtype, no gradients, the stock `track`. The particles stay
+        in registers from turn to turn (`chx_second_order_turns`); the turns are split into launches of at most 65 536 item
+        steps. The particles are those of `num_turns` calls of `track`, bit for bit. Drift-kick-drift elements are left out on
+        purpose (their reference energy is recomputed in every element; whether a turn reproduces it bit for bit is open).
+        The GENERAL path takes everything else (cavities, drift-kick-drift elements, collective kicks, vectorised beams, longer
+        lattices): a loop over `track` with the same loss rule and the same record definitions in float64 torch operations;
+        there the outgoing beam carries the energy `track` left it with.
+
+        The path length of the outgoing beam is incoming.s + num_turns * (s after one turn - incoming.s): one multiplication,
+        not bit-identical to adding every element's length num_turns times. The weights of the records are those of the incoming
+        beam. No autograd: the call runs without a graph, and an input that requires grad raises ValueError. Neither path
+        synchronises with the host.
+
+        Second-order maps are TRUNCATED Taylor maps and not symplectic: over many turns amplitudes drift where the true motion
+        is bounded (or the reverse), so dynamic-aperture and long-term stability figures from this tracking carry that caveat."""
+        from ..particles import turns as _turns
+
+        if not isinstance(incoming, ParticleBeam):
+            raise TypeError(f"track_turns takes a ParticleBeam, got {type(incoming)}")
+        num_turns, record_every, record_first = int(num_turns), int(record_every), int(record_first)
+        if num_turns < 1 or record_every < 1:
+            raise ValueError("num_turns and record_every must be at least 1")
+        x = incoming.particles
+        if record_first < 0 or record_first > x.shape[-2]:
+            raise ValueError(f"record_first = {record_first} is not within 0 .. {x.shape[-2]} (the number of particles)")
+        sp = incoming.species
+        if any(t.requires_grad for t in (x, incoming.energy, incoming.s, incoming.particle_charges, incoming.survival_probabilities,
+                                         sp.mass_eV, sp.num_elementary_charges)) or (aperture is not None and aperture.requires_grad):
+            raise ValueError("track_turns has no autograd: an input requires grad")
+        if aperture is not None and (aperture.shape != (2,) or aperture.dtype != x.dtype or aperture.device != x.device):
+            raise ValueError("aperture must be a tensor (a_x, a_y) of the beam's dtype on its device")
+        with torch.no_grad():
+            items = "fused=False" if fused is False else self._turn_items(incoming)
+            if isinstance(items, str):
+                if fused:
+                    raise ValueError(f"track_turns(fused=True): {items}")
+                return self._track_turns_general(incoming, num_turns, record_every, aperture, record_first, _turns)
+            return self._track_turns_fused(incoming, items, num_turns, record_every, aperture, record_first, _turns)
+
+    def _track_turns_fused(self, incoming, items, num_turns, record_every, aperture, record_first, _turns):
+        maps, lengths, linear = items
+        x = _ops.aligned(incoming.particles)
+        N, E, dev = x.shape[0], len(maps), x.device
+        _ops.check_current_device(dev)
+        charges, survival = _ops.aligned(incoming.particle_charges), _ops.aligned(incoming.survival_probabilities)
+        if aperture is not None and not aperture.is_contiguous():
+            raise ValueError("aperture must be contiguous (it is read through its address)")
+        R = num_turns // record_every
+        ws_bytes = _ops.second_order_turns_workspace_bytes
+        per_record = ws_bytes(E, N, 1, x.dtype) - ws_bytes(E, N, 0, x.dtype)
+        chunks = _turns.plan_chunks(num_turns, E, record_every, per_record, _turns._MAX_ITEM_STEPS, _turns._MAX_PARTIAL_BYTES)
+        # the coefficient block and the partials: an allocation of its own, sized for the launch that records most
+        ws = _ops.workspace(ws_bytes(E, N, max(_turns.chunk_records(f, n, record_every) for f, n in chunks), x.dtype), dev)
+        out = torch.empty_like(x)
+        lost = torch.zeros(N, dtype=torch.int32, device=dev)
+        sums = torch.empty((R, _turns.NUM_SUMS), dtype=torch.float64, device=dev)
+        probe = torch.empty((R, record_first, 7), dtype=x.dtype, device=dev) if record_first else None
+        s_one = torch.empty_like(incoming.s)
+        ptrs = _ops.second_order_turn_ptrs(maps, lengths, linear)
+        for first, n in chunks:
+            _ops.second_order_turns(ptrs, E, x if first == 1 else out, out, charges, survival, first, n, record_every, aperture, lost,
+                                    sums, probe, ws, incoming.s if first == 1 else None, s_one if first == 1 else None)
+        s_out = incoming.s + num_turns * (s_one - incoming.s)
+        beam = ParticleBeam(out, incoming.energy, particle_charges=incoming.particle_charges,
+                            survival_probabilities=incoming.survival_probabilities * (lost == 0), s=s_out, species=incoming.species)
+        return _turns.TurnByTurn(beam, lost, _turns.recorded_turns(num_turns, record_every, dev), sums, probe)
+
+    def _track_turns_general(self, incoming, num_turns, record_every, aperture, record_first, _turns):
+        x = incoming.particles
+        dev = x.device
+        w = incoming.particle_charges.to(torch.float64) * incoming.survival_probabilities.to(torch.float64)
+        lost = torch.zeros(x.shape[:-1], dtype=torch.int32, device=dev)     # (batch dimensions of a vectorised beam in front)
+        beam, sums, probe, s_one = incoming, [], [], None
+        for t in range(1, num_turns + 1):
+            before = beam.particles
+            beam = self.track(beam)
+            if t == 1:
+                s_one = beam.s
+            alive_before = lost == 0
+            xt = torch.where(alive_before.unsqueeze(-1), beam.particles, before)     # a lost particle stands where it was lost
+            lost = torch.where(alive_before & _turns.is_lost(xt, aperture), torch.full_like(lost, t), lost)
+            # (survival 0 from the turn of the loss on: a collective kick of the lattice no longer counts the particle's charge)
+            beam = ParticleBeam(xt, beam.energy, particle_charges=beam.particle_charges,
+                                survival_probabilities=beam.survival_probabilities * (lost == 0), s=beam.s, species=beam.species)
+            if t % record_every == 0:
+                sums.append(_turns.record_sums(xt, lost == 0, w))
+                if record_first:
+                    probe.append(xt[..., :record_first, :].clone())
+        beam = ParticleBeam(beam.particles, beam.energy, particle_charges=beam.particle_charges,
+                            survival_probabilities=beam.survival_probabilities, s=incoming.s + num_turns * (s_one - incoming.s),
+                            species=beam.species)
+        lead = tuple(beam.particles.shape[:-2])
+        sums = torch.stack(sums) if sums else torch.empty((0, *lead, _turns.NUM_SUMS), dtype=torch.float64, device=dev)
+        if record_first:
+            probe = torch.stack(probe) if probe else torch.empty((0, *lead, record_first, 7), dtype=x.dtype, device=dev)
+        return _turns.TurnByTurn(beam, lost, _turns.recorded_turns(num_turns, record_every, dev), sums, probe if record_first else None)
 
     @staticmethod
     def _stable_energy(ent: dict, energy: torch.Tensor, mass: float, e_out: torch.Tensor) -> torch.Tensor:

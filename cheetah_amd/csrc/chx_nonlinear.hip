@@ -1370,6 +1370,248 @@ __global__ __launch_bounds__(CHX_BLOCK) void so_chain_kernel_f64(const double* x
     tile_store<double, TP>(x_out + n0 * 7, lds, np * 7, out_vec_ok != 0, true);
 }
 
+// ---- the same chain TURN AFTER TURN (chx_second_order_turns): for turn { for item { ... } } over the one coefficient block, the
+// particles in registers for a whole chunk of turns [first_turn, first_turn + num_turns). A ring at 1e3 - 1e4 particles is
+// launch-bound turn by turn (two launches and a round trip of the beam per turn); here a turn costs its multiply-adds.
+//   alive    lost[h] of a lane's particle h: 0 = alive, else the 1-based turn of loss (seeded from lost_turn[N], written back). At
+//            the end of a turn a live particle is lost when one of its six coordinates is non-finite or |x| > a_x or |y| > a_y
+//            (aperture[2], read through its address). Its coordinates of that moment go to the particle's row of the LDS tile
+//            and stand there until the tile is stored: a lane cannot skip a step its other particle (or its neighbours) take,
+//            so the registers of a lost particle go on being stepped, but nothing reads them again — the record and the probe
+//            SELECT on the flag (no 0 * NaN anywhere), the final write-back leaves the row alone. A wave without a live
+//            particle skips the item loop (wave-uniform branch).
+//   records  on turn t = next_record, next_record + record_every, ...: the 14 float64 sums (count, sum w, sum w x_j, sum w x_j^2,
+//            j < 6; w = (double)charge * (double)survival or 1) over the workgroup's live particles, formed one after the other —
+//            a wave sum each, no accumulator lives across the item loop — and written to partials[record][tile][14]; the first
+//            K rows of the beam to probe[record][K][7] (a lost row: its frozen values). so_turns_reduce_kernel adds the tiles
+//            in a fixed order: no float atomics, bitwise reproducible.
+constexpr int kSoTurnSums = 14;
+template <typename T>
+struct SoTurnsArgs {
+    const T* x_in;                     // may be x_out (a tile is read whole before it is written)
+    T* x_out;
+    const T* charges;                  // [N] or NULL
+    const T* survival;                 // [N] or NULL
+    const T* aperture;                 // [2] or NULL
+    int32_t* lost_turn;                // [N], in / out
+    double* partials;                  // [records of this launch][tiles][14]
+    T* probe;                          // [records][K][7], the row of this launch's first record
+    int64_t N, K, next_record, record_every;
+    int E, first_turn, num_turns, in_vec_ok, out_vec_ok;
+};
+
+// the 14 sums of one recorded turn over the workgroup: PP particles per lane, x as doubles
+template <int PP>
+__device__ __forceinline__ void so_turn_record(const double (&w)[PP], const double (&xd)[PP][6], const bool (&live)[PP],
+                                               double* red /* [4][14] */, double* __restrict__ out /* [14] */) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < kSoTurnSums; ++k) {
+        double v = 0.0;
+#pragma unroll
+        for (int h = 0; h < PP; ++h) {
+            double t;
+            if (k == 0) t = 1.0;
+            else if (k == 1) t = w[h];
+            else if (k < 8) t = w[h] * xd[h][k - 2];
+            else t = (w[h] * xd[h][k - 8]) * xd[h][k - 8];
+            v += live[h] ? t : 0.0;                                // a select: a lost particle's NaN never meets a 0
+        }
+        v = chx_wave_sum(v);
+        if (lane == 0) red[wave * kSoTurnSums + k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < kSoTurnSums) {
+        const int k = threadIdx.x;
+        out[k] = ((red[k] + red[kSoTurnSums + k]) + red[2 * kSoTurnSums + k]) + red[3 * kSoTurnSums + k];
+    }
+    __syncthreads();                                               // red is free for the next recorded turn
+}
+
+template <typename T>
+__device__ __forceinline__ bool so_turn_outside(const T (&c)[6], T ax, T ay) {      // (no aperture: ax = ay = +inf, never exceeded)
+    int bad = 0;                                                   // straight-line: every test is evaluated, none branches
+#pragma unroll
+    for (int j = 0; j < 6; ++j) bad |= (int)!__builtin_isfinite(c[j]);
+    bad |= (int)(__builtin_elementwise_abs(c[0]) > ax) | (int)(__builtin_elementwise_abs(c[2]) > ay);
+    return bad != 0;
+}
+
+// (coef is a kernel argument of its own, __restrict__: only then does the compiler know that the stores of the records cannot
+// touch the coefficients and fetch them through scalar loads as so_chain_kernel does — inside the argument block they came
+// through 130 vector loads per item loop, and the kernel took 1.7 us per item step at 1e6 particles instead of the chain's 1.3)
+__global__ __launch_bounds__(CHX_BLOCK) void so_turns_kernel(const float* __restrict__ coef, SoTurnsArgs<float> a) {
+    constexpr int TP = 2 * CHX_BLOCK;
+    __shared__ __attribute__((aligned(16))) float lds[TP * 7];
+    __shared__ double red[4 * kSoTurnSums];
+    const int64_t n0 = (int64_t)blockIdx.x * TP;
+    const int np = (int)((a.N - n0 < TP) ? (a.N - n0) : TP);
+    tile_load<float, TP>(a.x_in + n0 * 7, lds, np * 7, a.in_vec_ok != 0, true);
+    __syncthreads();
+    const int p[2] = {(int)threadIdx.x, (int)threadIdx.x + CHX_BLOCK};
+    const bool on[2] = {p[0] < np, p[1] < np};
+    chx_v2f x[7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) x[j] = chx_v2f{on[0] ? lds[p[0] * 7 + j] : 0.0f, on[1] ? lds[p[1] * 7 + j] : 0.0f};
+    int lost[2];                                                   // (a lane past the end of the beam: never alive)
+#pragma unroll
+    for (int h = 0; h < 2; ++h) lost[h] = on[h] ? a.lost_turn[n0 + p[h]] : -1;
+    float ax = __builtin_inff(), ay = __builtin_inff();
+    if (a.aperture) { ax = a.aperture[0]; ay = a.aperture[1]; }
+    int64_t next_record = a.next_record;
+    int rec = 0;
+    const int end_turn = a.first_turn + a.num_turns;
+    for (int t = a.first_turn; t < end_turn; ++t) {
+        if (__any(lost[0] == 0 || lost[1] == 0)) {
+            for (int e = 0; e < a.E; ++e) {
+                const float* __restrict__ U = coef + (int64_t)e * kSoCoefStride;
+                const unsigned int scheme = reinterpret_cast<const unsigned int*>(U + 196)[2];
+                chx_v2f probe = chx_v2f{0.0f, 0.0f};                // (so_chain_kernel's rule for a non-finite particle)
+#pragma unroll
+                for (int j = 0; j < 7; ++j) probe = __builtin_elementwise_fma(chx_v2f{0.0f, 0.0f}, x[j], probe);
+                if (scheme == 0u) so_step_pattern<SoPatternQuad>(U, x, probe);
+                else if (scheme == 1u) so_step_pattern<SoPatternBend>(U, x, probe);
+                else if (scheme == 3u) so_step_linear(U, x);
+                else so_step_groups(U, x, probe);
+            }
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                float c[6];
+#pragma unroll
+                for (int j = 0; j < 6; ++j) c[j] = h == 0 ? x[j].x : x[j].y;
+                if (so_turn_outside<float>(c, ax, ay) && lost[h] == 0) {
+                    lost[h] = t;
+#pragma unroll
+                    for (int j = 0; j < 7; ++j) lds[p[h] * 7 + j] = h == 0 ? x[j].x : x[j].y;    // frozen here
+                }
+            }
+        }
+        if (t == next_record) {
+            double w[2], xd[2][6];
+            bool live[2];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                live[h] = lost[h] == 0;
+                const int64_t n = n0 + p[h];
+                w[h] = 1.0;
+                if (on[h] && a.charges) w[h] = (double)a.charges[n];
+                if (on[h] && a.survival) w[h] = w[h] * (double)a.survival[n];
+#pragma unroll
+                for (int j = 0; j < 6; ++j) xd[h][j] = (double)(h == 0 ? x[j].x : x[j].y);
+                if (n < a.K) {
+                    float* dst = a.probe + ((int64_t)rec * a.K + n) * 7;
+#pragma unroll
+                    for (int j = 0; j < 7; ++j) dst[j] = live[h] ? (h == 0 ? x[j].x : x[j].y) : lds[p[h] * 7 + j];
+                }
+            }
+            so_turn_record<2>(w, xd, live, red, a.partials + ((int64_t)rec * gridDim.x + blockIdx.x) * kSoTurnSums);
+            next_record += a.record_every;
+            ++rec;
+        }
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (lost[h] == 0) {
+#pragma unroll
+            for (int j = 0; j < 7; ++j) lds[p[h] * 7 + j] = h == 0 ? x[j].x : x[j].y;
+        }
+        if (on[h]) a.lost_turn[n0 + p[h]] = lost[h];
+    }
+    __syncthreads();
+    tile_store<float, TP>(a.x_out + n0 * 7, lds, np * 7, a.out_vec_ok != 0, true);
+}
+
+__global__ __launch_bounds__(CHX_BLOCK) void so_turns_kernel_f64(const double* __restrict__ coef, SoTurnsArgs<double> a) {
+    constexpr int TP = CHX_BLOCK;
+    __shared__ __attribute__((aligned(16))) double lds[TP * 7];
+    __shared__ double red[4 * kSoTurnSums];
+    const int64_t n0 = (int64_t)blockIdx.x * TP;
+    const int np = (int)((a.N - n0 < TP) ? (a.N - n0) : TP);
+    tile_load<double, TP>(a.x_in + n0 * 7, lds, np * 7, a.in_vec_ok != 0, true);
+    __syncthreads();
+    const int p = threadIdx.x;
+    const bool on = p < np;
+    double x[7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) x[j] = on ? lds[p * 7 + j] : 0.0;
+    int lost = on ? a.lost_turn[n0 + p] : -1;
+    double ax = __builtin_inf(), ay = __builtin_inf();
+    if (a.aperture) { ax = a.aperture[0]; ay = a.aperture[1]; }
+    int64_t next_record = a.next_record;
+    int rec = 0;
+    const int end_turn = a.first_turn + a.num_turns;
+    for (int t = a.first_turn; t < end_turn; ++t) {
+        if (__any(lost == 0)) {
+            for (int e = 0; e < a.E; ++e) {
+                const double* __restrict__ U = coef + (int64_t)e * kSoCoefStride;
+                const unsigned int scheme = reinterpret_cast<const unsigned int*>(U + 196)[2];
+                double probe = 0.0;
+#pragma unroll
+                for (int j = 0; j < 7; ++j) probe = fma(0.0, x[j], probe);
+                if (scheme == 0u) so_step_pattern_f64<SoPatternQuad>(U, x, probe);
+                else if (scheme == 1u) so_step_pattern_f64<SoPatternBend>(U, x, probe);
+                else if (scheme == 3u) so_step_linear_f64(U, x);
+                else so_step_groups_f64(U, x, probe);
+            }
+            double c[6];
+#pragma unroll
+            for (int j = 0; j < 6; ++j) c[j] = x[j];
+            if (so_turn_outside<double>(c, ax, ay) && lost == 0) {
+                lost = t;
+#pragma unroll
+                for (int j = 0; j < 7; ++j) lds[p * 7 + j] = x[j];                                  // frozen here
+            }
+        }
+        if (t == next_record) {
+            double w[1], xd[1][6];
+            const bool live[1] = {lost == 0};
+            const int64_t n = n0 + p;
+            w[0] = 1.0;
+            if (on && a.charges) w[0] = a.charges[n];
+            if (on && a.survival) w[0] = w[0] * a.survival[n];
+#pragma unroll
+            for (int j = 0; j < 6; ++j) xd[0][j] = x[j];
+            if (n < a.K) {
+                double* dst = a.probe + ((int64_t)rec * a.K + n) * 7;
+#pragma unroll
+                for (int j = 0; j < 7; ++j) dst[j] = live[0] ? x[j] : lds[p * 7 + j];
+            }
+            so_turn_record<1>(w, xd, live, red, a.partials + ((int64_t)rec * gridDim.x + blockIdx.x) * kSoTurnSums);
+            next_record += a.record_every;
+            ++rec;
+        }
+    }
+    if (lost == 0) {
+#pragma unroll
+        for (int j = 0; j < 7; ++j) lds[p * 7 + j] = x[j];
+    }
+    if (on) a.lost_turn[n0 + p] = lost;
+    __syncthreads();
+    tile_store<double, TP>(a.x_out + n0 * 7, lds, np * 7, a.out_vec_ok != 0, true);
+}
+
+// sums[record][14] = the tiles of partials[record][tiles][14] added in a fixed order: 16 strided slices of tiles, then the slices
+__global__ __launch_bounds__(CHX_BLOCK) void so_turns_reduce_kernel(const double* __restrict__ partials, int64_t tiles,
+                                                                    double* __restrict__ sums) {
+    constexpr int SLICES = 16;
+    static_assert(SLICES * kSoTurnSums <= CHX_BLOCK, "a lane per (slice, sum)");
+    __shared__ double part[SLICES * kSoTurnSums];
+    const double* __restrict__ src = partials + (int64_t)blockIdx.x * tiles * kSoTurnSums;
+    if (threadIdx.x < SLICES * kSoTurnSums) {
+        const int s = threadIdx.x / kSoTurnSums, k = threadIdx.x - s * kSoTurnSums;
+        double acc = 0.0;
+        for (int64_t t = s; t < tiles; t += SLICES) acc += src[t * kSoTurnSums + k];
+        part[threadIdx.x] = acc;
+    }
+    __syncthreads();
+    if (threadIdx.x < kSoTurnSums) {
+        double acc = 0.0;
+#pragma unroll
+        for (int s = 0; s < SLICES; ++s) acc += part[s * kSoTurnSums + threadIdx.x];
+        sums[(int64_t)blockIdx.x * kSoTurnSums + threadIdx.x] = acc;
+    }
+}
+
 }  // namespace
 
 // A run of elements tracked with their second-order maps (element.py:195-228) on ONE beam. float32: the particles stay in
@@ -1457,6 +1699,106 @@ extern "C" int chx_second_order_chain_mixed(const void* const* T_maps, const int
         CHX_CHECK_LAUNCH();
     }
     return CHX_OK;
+}
+
+// The run above as a RING: turns [first_turn, first_turn + num_turns) of it in one particle launch (so_turns_kernel,
+// so_turns_kernel_f64), with the loss flags, the record sums and the probe rows of the recorded turns (see the kernels).
+namespace {
+int64_t so_turns_tiles(int64_t N, int dtype) {
+    const int per_tile = dtype == CHX_F32 ? 2 * CHX_BLOCK : CHX_BLOCK;
+    return (N + per_tile - 1) / per_tile;
+}
+size_t so_turns_coef_bytes(int64_t E, int dtype) { return (size_t)E * kSoCoefStride * (dtype == CHX_F32 ? 4 : 8); }
+template <typename T>
+int so_turns_launch(const SoChainPtrs& maps, int E, const void* x_in, const void* charges, const void* survival, int64_t N,
+                    int first_turn, int num_turns, int64_t record_every, int64_t records, int64_t rec0, const void* aperture, int64_t K,
+                    void* x_out, int32_t* lost_turn, double* sums, void* probe, const void* s_in, void* s_out, void* workspace,
+                    int64_t tiles, size_t coef_bytes, hipStream_t s) {
+    T* coef = (T*)workspace;
+    hipLaunchKernelGGL(so_chain_coeff_kernel<T>, dim3((unsigned)(E + (s_out ? 1 : 0))), dim3(CHX_BLOCK), 0, s, maps, E, coef, (const T*)s_in,
+                       (T*)s_out);
+    CHX_CHECK_LAUNCH();
+    SoTurnsArgs<T> a;
+    a.x_in = (const T*)x_in;
+    a.x_out = (T*)x_out;
+    a.charges = (const T*)charges;
+    a.survival = (const T*)survival;
+    a.aperture = (const T*)aperture;
+    a.lost_turn = lost_turn;
+    a.partials = (double*)((char*)workspace + coef_bytes);
+    a.probe = K > 0 && records > 0 ? (T*)probe + rec0 * K * 7 : nullptr;
+    a.N = N;
+    a.K = K;
+    a.E = E;
+    a.first_turn = first_turn;
+    a.num_turns = num_turns;
+    a.next_record = (rec0 + 1) * record_every;
+    a.record_every = record_every;
+    a.in_vec_ok = (int)chx_aligned16(x_in);
+    a.out_vec_ok = (int)chx_aligned16(x_out);
+    if constexpr (sizeof(T) == 4) hipLaunchKernelGGL(so_turns_kernel, dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const float*)coef, a);
+    else hipLaunchKernelGGL(so_turns_kernel_f64, dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const double*)coef, a);
+    CHX_CHECK_LAUNCH();
+    if (records > 0) {
+        hipLaunchKernelGGL(so_turns_reduce_kernel, dim3((unsigned)records), dim3(CHX_BLOCK), 0, s, (const double*)a.partials, tiles,
+                           sums + rec0 * kSoTurnSums);
+        CHX_CHECK_LAUNCH();
+    }
+    return CHX_OK;
+}
+}  // namespace
+
+extern "C" size_t chx_second_order_turns_workspace_bytes(int64_t E, int64_t N, int64_t records_in_chunk, int dtype) {
+    if (E < 1 || N < 1 || records_in_chunk < 0 || (dtype != CHX_F32 && dtype != CHX_F64)) return 0;
+    return so_turns_coef_bytes(E, dtype) + (size_t)records_in_chunk * (size_t)so_turns_tiles(N, dtype) * kSoTurnSums * sizeof(double);
+}
+
+extern "C" int chx_second_order_turns(const void* const* T_maps, const int32_t* linear, const void* const* lengths, int64_t E,
+                                      const void* x_in, const void* charges, const void* survival, int64_t N, int dtype,
+                                      int64_t first_turn, int64_t num_turns, int64_t record_every, const void* aperture, int64_t K,
+                                      void* x_out, int32_t* lost_turn, double* sums, void* probe, const void* s_in, void* s_out,
+                                      void* workspace, size_t workspace_bytes, void* stream) {
+    if (dtype != CHX_F32 && dtype != CHX_F64) return CHX_ERR_DTYPE;
+    if (!T_maps || E < 1 || E > kSoChainMax || !x_in || !x_out || !lost_turn || !workspace || N < 1) return CHX_ERR_INVALID_ARG;
+    if (first_turn < 1 || num_turns < 1 || record_every < 1 || K < 0 || K > N) return CHX_ERR_INVALID_ARG;
+    // lost_turn holds turn numbers as int32, and the kernels count to first_turn + num_turns in int: the last turn stays below INT_MAX
+    if (first_turn >= 0x7fffffffLL || num_turns >= 0x7fffffffLL || first_turn + num_turns - 1 >= 0x7fffffffLL || record_every > 0x7fffffffLL)
+        return CHX_ERR_INVALID_ARG;
+    if ((s_in == nullptr) != (s_out == nullptr) || (s_out && !lengths)) return CHX_ERR_INVALID_ARG;
+    const int64_t rec0 = (first_turn - 1) / record_every;                           // records in front of this chunk
+    const int64_t records = (first_turn + num_turns - 1) / record_every - rec0;
+    if (records > 0 && (!sums || (K > 0 && !probe))) return CHX_ERR_INVALID_ARG;
+    if (workspace_bytes < chx_second_order_turns_workspace_bytes(E, N, records, dtype) || !chx_aligned16(workspace)) return CHX_ERR_INVALID_ARG;
+    // aliasing: the first chunk reads a beam it must not write (x_out != x_in), later chunks run in place on x_out; nothing else
+    // may share an address
+    if (first_turn == 1 && x_in == x_out) return CHX_ERR_INVALID_ARG;
+    const void* outs[] = {x_out, lost_turn, sums, probe, workspace, s_out};
+    const void* ins[] = {x_in, charges, survival, aperture, s_in};
+    constexpr size_t n_outs = sizeof(outs) / sizeof(outs[0]), n_ins = sizeof(ins) / sizeof(ins[0]);
+    for (size_t i = 0; i < n_outs; ++i) {
+        if (!outs[i]) continue;
+        for (size_t j = i + 1; j < n_outs; ++j)
+            if (outs[i] == outs[j]) return CHX_ERR_INVALID_ARG;
+        for (size_t j = 0; j < n_ins; ++j)
+            if (outs[i] == ins[j] && !(i == 0 && j == 0)) return CHX_ERR_INVALID_ARG;
+    }
+    const int64_t tiles = so_turns_tiles(N, dtype);
+    if (tiles > 0x7fffffffLL || records > 0x7fffffffLL) return CHX_ERR_INVALID_ARG;
+    SoChainPtrs maps;
+    for (int e = 0; e < kSoChainMax; ++e) {
+        maps.T[e] = e < E ? T_maps[e] : nullptr;
+        maps.length[e] = e < E && lengths ? lengths[e] : nullptr;
+        maps.linear[e] = (e < E && linear && linear[e]) ? 1 : 0;
+        if (e < E && (!maps.T[e] || (s_out && !maps.length[e]))) return CHX_ERR_INVALID_ARG;
+    }
+    const size_t coef_bytes = so_turns_coef_bytes(E, dtype);
+    if (dtype == CHX_F32)
+        return so_turns_launch<float>(maps, (int)E, x_in, charges, survival, N, (int)first_turn, (int)num_turns, record_every, records,
+                                      rec0, aperture, K, x_out, lost_turn, sums, probe, s_in, s_out, workspace, tiles, coef_bytes,
+                                      (hipStream_t)stream);
+    return so_turns_launch<double>(maps, (int)E, x_in, charges, survival, N, (int)first_turn, (int)num_turns, record_every, records,
+                                   rec0, aperture, K, x_out, lost_turn, sums, probe, s_in, s_out, workspace, tiles, coef_bytes,
+                                   (hipStream_t)stream);
 }
 
 namespace {

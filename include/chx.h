@@ -1264,6 +1264,26 @@ int chx_second_order_chain(const void* const* T_maps, const void* const* lengths
 int chx_second_order_chain_mixed(const void* const* T_maps, const int32_t* linear, const void* const* lengths, int64_t E,
                                  const void* x_in, int64_t N, int dtype, void* x_out, void* x_tmp, const void* s_in, void* s_out,
                                  void* stream);
+/* The same run as a RING: turns [first_turn, first_turn + num_turns) (1-based) of the E items in one particle launch, the particles
+ * in registers from turn to turn. T_maps / linear / lengths as above, 1 <= E <= 224.
+ *   lost_turn[N] (int32, in / out): 0 = alive, else the turn the particle was lost on. At the end of every turn a live particle is
+ *     lost when one of its six coordinates is non-finite or, with aperture[2] (device, dtype; NULL: none) given, |x| > aperture[0]
+ *     or |y| > aperture[1]. It keeps the coordinates of that moment and is not tracked further.
+ *   Every turn t with t % record_every == 0 is record t / record_every - 1: sums[record][14] (float64) = count, sum w, sum w x_j,
+ *     sum w x_j^2 (j < 6) over the live particles, w = (double)charges[n] * (double)survival[n] (either may be NULL: 1), added
+ *     in a fixed order (bitwise reproducible); probe[record][K][7] (dtype) = the first K rows of the beam, 0 <= K <= N. The call
+ *     writes the rows of the records that fall into its turns; sums / probe point at record 0.
+ *   x_out must not be x_in when first_turn == 1; a later chunk runs in place (x_in == x_out). No other two buffers may alias.
+ *   s_in / s_out (dtype scalars, both or neither): s_out = (((s_in + l_0) + l_1) + ...), the path length after ONE turn.
+ *   workspace: chx_second_order_turns_workspace_bytes(E, N, records of this call, dtype) bytes (the folded coefficients and the
+ *     per-workgroup partial sums), 16-byte aligned.
+ * CHX_ERR_INVALID_ARG: E < 1, E > 224, num_turns < 1, record_every < 1, K > N, a last turn of 2^31 - 1 or beyond, aliased buffers, a
+ * workspace too small or not 16-byte aligned; CHX_ERR_DTYPE: dtype other than CHX_F32 / CHX_F64. */
+size_t chx_second_order_turns_workspace_bytes(int64_t E, int64_t N, int64_t records_in_chunk, int dtype);
+int chx_second_order_turns(const void* const* T_maps, const int32_t* linear, const void* const* lengths, int64_t E, const void* x_in,
+                           const void* charges, const void* survival, int64_t N, int dtype, int64_t first_turn, int64_t num_turns,
+                           int64_t record_every, const void* aperture, int64_t K, void* x_out, int32_t* lost_turn, double* sums,
+                           void* probe, const void* s_in, void* s_out, void* workspace, size_t workspace_bytes, void* stream);
 /* Derivatives of the two calls above (reference: torch autograd through track_methods.py:80-296 and the einsum).
  * chx_build_ttensor_vjp: dparams[B][P], denergy[B] (dtype) = dT[B][343] . dT/dtheta (dual numbers, one workgroup
  * per (row, input)); rows are NOT reduced when params / energy are broadcast (Bp or Be = 1) — the caller sums.
