@@ -221,6 +221,10 @@ SIGNATURES = {
     "chx_second_order_turns": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_int, c_i64, c_i64,
                                        c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_size_t, c_void_p]),
+    "chx_dkd_turns_workspace_bytes": (c_size_t, [c_i64, c_i64, c_i64, c_i64, c_int]),
+    "chx_dkd_turns": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_i64, c_void_p, c_void_p, c_void_p, c_double, c_double,
+                              c_void_p, c_void_p, c_i64, c_int, c_i64, c_i64, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "chx_dkd_bwd_partials_count": (c_i64, [c_int, c_i64, c_i64]),
     "chx_dkd_track_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, ctypes.c_int32,
                                   ctypes.c_int32, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p]),

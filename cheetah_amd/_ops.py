@@ -1026,6 +1026,32 @@ def second_order_turns(ptrs, E, x_in, x_out, charges, survival, first_turn, num_
           "chx_second_order_turns")
 
 
+def dkd_turns_workspace_bytes(E: int, N: int, turns: int, records: int, dtype) -> int:
+    """Bytes of the workspace of one `dkd_turns` call of `turns` turns that records `records` of them: the turns' start energies,
+    their block indices, one block of element constants per turn (the worst case) and the per-workgroup partial sums."""
+    return _lib.lib().chx_dkd_turns_workspace_bytes(E, N, turns, records, dtype_code(dtype))
+
+
+def dkd_turn_arrays(kinds, params, num_steps, fringe):
+    """The host argument arrays of `dkd_turns` for these (1, P) parameter tensors (valid while they are alive)."""
+    i32, vp = ctypes.c_int32 * len(kinds), ctypes.c_void_p * len(kinds)
+    return i32(*kinds), vp(*[p.data_ptr() for p in params]), i32(*num_steps), i32(*fringe)
+
+
+def dkd_turns(arrays, storage, E, x_in, x_out, energy_in, energy_out, mass_eV, n_charges, charges, survival, first_turn, num_turns,
+              record_every, aperture, lost_turn, sums, probe, ws, s_in=None, s_out=None) -> None:
+    """Turns [first_turn, first_turn + num_turns) of a ring of E drift-kick-drift Drifts, Quadrupoles and Dipoles of one arithmetic
+    mode `storage` (chx_dkd_turns): x_in (N, 7) -> x_out (the same tensor from the second chunk on), energy_in (0-d, in front of
+    first_turn) -> energy_out (0-d, behind the last turn; may be the same tensor), the rest as `second_order_turns`. Launches only,
+    no synchronisation."""
+    N = x_in.shape[0]
+    K = 0 if probe is None else probe.shape[1]
+    check(_lib.lib().chx_dkd_turns(arrays[0], arrays[1], arrays[2], arrays[3], int(storage), E, ptr(x_in), ptr(energy_in), ptr(energy_out),
+                                   mass_eV, n_charges, ptr(charges), ptr(survival), N, dtype_code(x_in.dtype), first_turn, num_turns,
+                                   record_every, ptr(aperture), K, ptr(x_out), ptr(lost_turn), ptr(sums), ptr(probe), ptr(s_in), ptr(s_out),
+                                   ptr(ws), ws.numel(), stream_ptr()), "chx_dkd_turns")
+
+
 # ---------------------------------------------------------------------------------------------
 # moments
 #: the batch (vector) index of the reductions and deposits is `blockIdx.y`: at most 65 535 rows per launch

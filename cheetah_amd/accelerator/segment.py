@@ -25,6 +25,7 @@ are applied back to back by `chx_track_elementwise` / `chx_track_fused` from a s
 
 from __future__ import annotations
 
+import collections
 import ctypes
 import numbers
 import os
@@ -106,6 +107,9 @@ class _ElementList(nn.ModuleList):
 _CHECK_PLANS = os.environ.get("CHX_CHECK_PLANS", "0") == "1"
 #: drift-kick-drift kinds chx_dkd_chain carries through a run in registers
 _DKD_IN_REGISTERS = (_ops.DKD_KIND["drift"], _ops.DKD_KIND["quadrupole"], _ops.DKD_KIND["dipole"])
+#: what `Segment._turn_items` hands `_track_turns_fused` for a ring of drift-kick-drift elements (chx_dkd_turns): per element the
+#: kind, the (1, P) parameter tensor, num_steps and fringe_at; `storage` = the ring's one arithmetic mode
+_DkdRing = collections.namedtuple("_DkdRing", "kinds params num_steps fringe_at storage")
 #: CHX_SC_CHAIN = auto (default) | on | off — how `Segment.track` takes [SpaceChargeKick, linear run, SpaceChargeKick, ...]:
 #: "auto" starts on the tile-ordered chain and lets the asynchronous guard (`_chain_allowed`) send a plan whose beam reshuffles
 #: between kicks back to kick-by-kick tracking. The two paths sum the charge in different orders, so WHEN the guard's header
@@ -1214,7 +1218,8 @@ class Segment(Element):
     # ---- multi-turn tracking ---------------------------------------------------------------------------------
     def _turn_items(self, incoming: ParticleBeam):
         """(maps, lengths, linear) when the WHOLE lattice is one stretch the fused turn kernel takes — second-order elements and
-        merged linear runs as in `_second_order_run`, or a single merged linear run — else the reason (a str) why not."""
+        merged linear runs as in `_second_order_run`, or a single merged linear run —, a `_DkdRing` when it is a ring of
+        drift-kick-drift elements instead (`_turn_items_dkd`), else the reason (a str) why neither."""
         x, energy, s = incoming.particles, incoming.energy, incoming.s
         if x.dim() != 2 or not x.is_cuda:
             return "the beam is not one plain (N, 7) beam on the device"
@@ -1240,12 +1245,56 @@ class Segment(Element):
             what = "a run of linear elements that does not qualify (vectorised or trainable settings, or the run in front of a cavity)" \
                 if kind == "run" else \
                 f"{type(item).__name__} '{item.name}' (tracking method '{item._tracking_method}')"
-            return f"the lattice is not one stretch of second-order and linear items: {what} ends it"
-        if not 1 <= len(maps) <= 224:
-            return f"the lattice has {len(maps)} items, the fused kernel takes 1 to 224"
+            reason = f"the lattice is not one stretch of second-order and linear items: {what} ends it"
+        elif not 1 <= len(maps) <= 224:
+            reason = f"the lattice has {len(maps)} items, the fused kernel takes 1 to 224"
+        elif any(t.requires_grad for t in tensors):
+            reason = "a setting of the lattice requires grad"
+        else:
+            return maps, lengths, linear
+        ring = self._turn_items_dkd(plan, x)
+        if isinstance(ring, str):
+            return f"{reason}; nor is it a ring of drift-kick-drift elements: {ring}"
+        return ring
+
+    def _turn_items_dkd(self, plan, x: torch.Tensor):
+        """A `_DkdRing` when the WHOLE plan is a ring `chx_dkd_turns` takes — drift-kick-drift Drifts, Quadrupoles and Dipoles as
+        `_dkd_run` keeps them in registers, all of one arithmetic class, 1 to 192 of them, Markers in between skipped — else the
+        reason (a str) why not. Nothing is kept between calls: settings and `dkd_precision` are read here every time."""
+        kinds, params, steps, fringes, classes, tensors = [], [], [], [], [], []
+        single = x.dtype == torch.float64                      # (float64 beams are evaluated in fp64 whatever `dkd_precision` says)
+        for kind, e in plan:
+            if kind == "run":
+                if self._identity_run(e):
+                    continue                                   # Markers between two magnets: nothing to apply, s + 0
+                return "a run of linear elements stands in the ring (its map depends on the reference energy in front of it, and an " \
+                       "energy that drifts from turn to turn would need a map per turn: left to the general path on purpose)"
+            cls = type(e)
+            name = f"{cls.__name__} '{e.name}'"
+            if e._tracking_method != "drift_kick_drift" or e._dkd_kind not in _DKD_IN_REGISTERS:
+                return f"{name} (tracking method '{e._tracking_method}') is not a drift-kick-drift Drift, Quadrupole or Dipole"
+            if cls.track is not Element.track or cls._track_drift_kick_drift is not Element._track_drift_kick_drift \
+                    or cls._track_internal is not Element._track_internal:
+                return f"{name} overrides `track`"
+            if e.dkd_precision not in _ops.DKD_PRECISION:
+                return f"{name} has the unknown dkd_precision {e.dkd_precision!r}"
+            p = e._dkd_params_stacked(x.dtype, x.device)
+            if p is None:
+                return f"the settings of {name} are not all scalars of the beam's dtype on its device (vectorised settings take the general path)"
+            n, f = e._dkd_options()
+            kinds.append(e._dkd_kind)
+            params.append(p)
+            steps.append(n)
+            fringes.append(f)
+            classes.append(0 if single else _ops.DKD_PRECISION[e.dkd_precision])
+            tensors += [t for t, _ in e._dkd_scalar_refs()]
+        if not 1 <= len(kinds) <= 192:
+            return f"the ring has {len(kinds)} drift-kick-drift elements, the fused kernel takes 1 to 192"
+        if len(set(classes)) > 1:
+            return "the elements' `dkd_precision` settings put them into more than one arithmetic class (one launch evaluates one)"
         if any(t.requires_grad for t in tensors):
             return "a setting of the lattice requires grad"
-        return maps, lengths, linear
+        return _DkdRing(kinds, params, steps, fringes, classes[0])
 
     def track_turns(self, incoming: ParticleBeam, num_turns: int, *, record_every: int = 1, aperture=None, record_first: int = 0,
                     fused=None):
@@ -1266,9 +1315,20 @@ class Segment(Element):
         elements (or one merged linear run) of at most 224 items, under the conditions of a second-order run in `track`: one
         plain (N, 7) beam on the device, scalar settings of the beam's dtype, no gradients, the stock `track`. The particles stay
         in registers from turn to turn (`chx_second_order_turns`); the turns are split into launches of at most 65 536 item
-        steps. The particles are those of `num_turns` calls of `track`, bit for bit. Drift-kick-drift elements are left out on
-        purpose (their reference energy is recomputed in every element; whether a turn reproduces it bit for bit is open).
-        The GENERAL path takes everything else (cavities, drift-kick-drift elements, collective kicks, vectorised beams, longer
+        steps. The particles are those of `num_turns` calls of `track`, bit for bit.
+        It also takes a ring of DRIFT-KICK-DRIFT elements (`chx_dkd_turns`), the symplectic Bmad-X maps: every item of the plan a
+        Drift, Quadrupole or Dipole with `tracking_method="drift_kick_drift"`, scalar settings of the beam's dtype without
+        gradients and the stock `track`, all of one arithmetic class (`dkd_precision`; a float64 beam forms one class), 1 to 192
+        of them, Markers in between skipped, under the same conditions on the beam. Every such element leaves the reference
+        energy as sqrt(sqrt(E^2 - m^2)^2 + m^2) in the beam's dtype. That round trip is monotone and ends in a fixed point, but
+        not at once: about one energy in five moves, a few per thousand still move after 16 elements, and beside a power of two
+        an energy can move one ulp per element for thousands of elements. So the kernels walk the energy through the turns on
+        the device and give a turn the element constants of the turn before exactly when both start with the same energy bits:
+        particles, reference energy and path length are those of `num_turns` calls of `track` bit for bit at EVERY energy, and
+        the outgoing beam carries the energy behind the last turn. Settings and `dkd_precision` are read at every call. A run
+        of linear elements inside such a ring (a linear Drift or corrector between the magnets) ends the attempt on purpose:
+        its map depends on the energy in front of it, and a drifting energy would need a map per turn — the general path.
+        The GENERAL path takes everything else (cavities, mixed lattices, collective kicks, vectorised beams, longer
         lattices): a loop over `track` with the same loss rule and the same record definitions in float64 torch operations;
         there the outgoing beam carries the energy `track` left it with.
 
@@ -1278,7 +1338,8 @@ class Segment(Element):
         synchronises with the host.
 
         Second-order maps are TRUNCATED Taylor maps and not symplectic: over many turns amplitudes drift where the true motion
-        is bounded (or the reverse), so dynamic-aperture and long-term stability figures from this tracking carry that caveat."""
+        is bounded (or the reverse), so dynamic-aperture and long-term stability figures from that tracking carry that caveat.
+        The drift-kick-drift maps are symplectic: a ring of them is the one to use for such figures."""
         from ..particles import turns as _turns
 
         if not isinstance(incoming, ParticleBeam):
@@ -1304,30 +1365,47 @@ class Segment(Element):
             return self._track_turns_fused(incoming, items, num_turns, record_every, aperture, record_first, _turns)
 
     def _track_turns_fused(self, incoming, items, num_turns, record_every, aperture, record_first, _turns):
-        maps, lengths, linear = items
+        dkd = isinstance(items, _DkdRing)
         x = _ops.aligned(incoming.particles)
-        N, E, dev = x.shape[0], len(maps), x.device
+        N, E, dev = x.shape[0], len(items[0]), x.device
         _ops.check_current_device(dev)
         charges, survival = _ops.aligned(incoming.particle_charges), _ops.aligned(incoming.survival_probabilities)
         if aperture is not None and not aperture.is_contiguous():
             raise ValueError("aperture must be contiguous (it is read through its address)")
         R = num_turns // record_every
-        ws_bytes = _ops.second_order_turns_workspace_bytes
-        per_record = ws_bytes(E, N, 1, x.dtype) - ws_bytes(E, N, 0, x.dtype)
+        if dkd:
+            ws_bytes = lambda records, turns=1: _ops.dkd_turns_workspace_bytes(E, N, turns, records, x.dtype)  # noqa: E731
+        else:
+            ws_bytes = lambda records, turns=1: _ops.second_order_turns_workspace_bytes(E, N, records, x.dtype)  # noqa: E731
+        per_record = ws_bytes(1) - ws_bytes(0)
         chunks = _turns.plan_chunks(num_turns, E, record_every, per_record, _turns._MAX_ITEM_STEPS, _turns._MAX_PARTIAL_BYTES)
-        # the coefficient block and the partials: an allocation of its own, sized for the launch that records most
-        ws = _ops.workspace(ws_bytes(E, N, max(_turns.chunk_records(f, n, record_every) for f, n in chunks), x.dtype), dev)
+        # the coefficient block (a drift-kick-drift ring: a block of constants per turn of a launch, the worst case of a drifting
+        # reference energy) and the partials: an allocation of its own, sized for the longest launch and the one that records most
+        ws = _ops.workspace(ws_bytes(max(_turns.chunk_records(f, n, record_every) for f, n in chunks), max(n for _, n in chunks)), dev)
         out = torch.empty_like(x)
         lost = torch.zeros(N, dtype=torch.int32, device=dev)
         sums = torch.empty((R, _turns.NUM_SUMS), dtype=torch.float64, device=dev)
         probe = torch.empty((R, record_first, 7), dtype=x.dtype, device=dev) if record_first else None
         s_one = torch.empty_like(incoming.s)
-        ptrs = _ops.second_order_turn_ptrs(maps, lengths, linear)
-        for first, n in chunks:
-            _ops.second_order_turns(ptrs, E, x if first == 1 else out, out, charges, survival, first, n, record_every, aperture, lost,
-                                    sums, probe, ws, incoming.s if first == 1 else None, s_one if first == 1 else None)
+        energy = incoming.energy
+        if dkd:
+            # the reference energy travels from launch to launch through one device scalar: behind the call the energy behind
+            # the last turn
+            sp = incoming.species
+            arrays = _ops.dkd_turn_arrays(items.kinds, items.params, items.num_steps, items.fringe_at)
+            energy = torch.empty_like(incoming.energy)
+            for first, n in chunks:
+                _ops.dkd_turns(arrays, items.storage, E, x if first == 1 else out, out, incoming.energy if first == 1 else energy, energy,
+                               sp.mass_eV_float, sp.num_elementary_charges_float, charges, survival, first, n, record_every, aperture,
+                               lost, sums, probe, ws, incoming.s if first == 1 else None, s_one if first == 1 else None)
+        else:
+            maps, lengths, linear = items
+            ptrs = _ops.second_order_turn_ptrs(maps, lengths, linear)
+            for first, n in chunks:
+                _ops.second_order_turns(ptrs, E, x if first == 1 else out, out, charges, survival, first, n, record_every, aperture, lost,
+                                        sums, probe, ws, incoming.s if first == 1 else None, s_one if first == 1 else None)
         s_out = incoming.s + num_turns * (s_one - incoming.s)
-        beam = ParticleBeam(out, incoming.energy, particle_charges=incoming.particle_charges,
+        beam = ParticleBeam(out, energy, particle_charges=incoming.particle_charges,
                             survival_probabilities=incoming.survival_probabilities * (lost == 0), s=s_out, species=incoming.species)
         return _turns.TurnByTurn(beam, lost, _turns.recorded_turns(num_turns, record_every, dev), sums, probe)
 

@@ -725,21 +725,47 @@ __device__ __forceinline__ T dkd_energy_round_trip(T E, T m) {       // ref_ener
     return sqrt(p0 * p0 + m * m);
 }
 
+// the path length behind the run (a workgroup of its own in the kernels that prepare the constants): s = ((s_in + l_0) + l_1) + ...
+// in the beam's dtype like the reference's element-by-element additions (every kind's first parameter is its length; s_out may
+// be s_in)
+template <typename T>
+__device__ __forceinline__ void dkd_chain_path_length(const DkdChainArgs& args, int E, const T* s_in, T* s_out) {
+    __shared__ T len[kDkdChainMax];
+    for (int k = threadIdx.x; k < E; k += blockDim.x) len[k] = args.length[k] ? *(const T*)args.length[k] : ((const T*)args.params[k])[0];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        T sum = *s_in;
+        for (int k = 0; k < E; ++k) sum = sum + len[k];
+        *s_out = sum;
+    }
+}
+
+// what one lane leaves in a drift-kick-drift item's slot of the constants (out[kDkdCstStride]) for the reference energy Ee in
+// front of the item: dkd_constants in fp64 whatever the beam's dtype, the extra constants of the mixed evaluation, and at
+// kDkdMeta the kind and the step count. ONE definition for the chain (dkd_chain_prepare_kernel) and the ring
+// (dkd_turns_constants_kernel): the bits of a turn of the ring are those of a pass of the chain by construction.
+template <typename T>
+__device__ __forceinline__ void dkd_item_constants(int kind, int fringe, int steps, const T* __restrict__ pe, T Ee, double mc2, double nq,
+                                                   double* __restrict__ out) {
+    int32_t* w = reinterpret_cast<int32_t*>(out + kDkdMeta);
+    w[0] = kind;
+    w[1] = steps;
+    const int P = kind == CHX_DKD_DRIFT ? 1 : (kind == CHX_DKD_QUADRUPOLE ? 5 : 9);
+    double par[CHX_MAX_PARAMS];
+    for (int k = 0; k < P; ++k) par[k] = (double)pe[k];
+    double c[C_MIXED_N];
+    for (int k = 0; k < C_MIXED_N; ++k) c[k] = 0.0;
+    dkd_constants<double>(kind, par, (double)Ee, mc2, nq, fringe, c);
+    dkd_mixed_constants(c, mc2);
+    for (int k = 0; k < C_MIXED_N; ++k) out[k] = c[k];
+}
+
 template <typename T>
 __global__ void dkd_chain_prepare_kernel(DkdChainArgs args, int E, const T* __restrict__ energy_in, double mc2, double nq,
                                          double* __restrict__ cst, T* __restrict__ energies, const T* s_in, T* s_out) {
     const int e = blockIdx.x;
-    if (e == E) {
-        // one workgroup more: the path length behind the run, s = ((s_in + l_0) + l_1) + ... in the beam's dtype like the
-        // reference's element-by-element additions (every kind's first parameter is its length; s_out may be s_in)
-        __shared__ T len[kDkdChainMax];
-        for (int k = threadIdx.x; k < E; k += blockDim.x) len[k] = args.length[k] ? *(const T*)args.length[k] : ((const T*)args.params[k])[0];
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            T sum = *s_in;
-            for (int k = 0; k < E; ++k) sum = sum + len[k];
-            *s_out = sum;
-        }
+    if (e == E) {                                             // one workgroup more: the path length behind the run
+        dkd_chain_path_length<T>(args, E, s_in, s_out);
         return;
     }
     const int kind = args.meta[e] & 15, fringe = (args.meta[e] >> 4) & 3, steps = args.meta[e] >> 6;
@@ -756,22 +782,14 @@ __global__ void dkd_chain_prepare_kernel(DkdChainArgs args, int E, const T* __re
         if (En == Ee) break;              // a fixed point: every later round trip returns it again
         Ee = En;
     }
-    int32_t* w = reinterpret_cast<int32_t*>(out + kDkdMeta);
-    w[0] = kind;
-    w[1] = steps;
     if (kind == kDkdLinear) {
+        int32_t* w = reinterpret_cast<int32_t*>(out + kDkdMeta);
+        w[0] = kind;
+        w[1] = steps;
         energies[e] = Ee;
         return;
     }
-    const int P = kind == CHX_DKD_DRIFT ? 1 : (kind == CHX_DKD_QUADRUPOLE ? 5 : 9);
-    double par[CHX_MAX_PARAMS];
-    const T* pe = (const T*)args.params[e];
-    for (int k = 0; k < P; ++k) par[k] = (double)pe[k];
-    double c[C_MIXED_N];
-    for (int k = 0; k < C_MIXED_N; ++k) c[k] = 0.0;
-    dkd_constants<double>(kind, par, (double)Ee, mc2, nq, fringe, c);
-    dkd_mixed_constants(c, mc2);
-    for (int k = 0; k < C_MIXED_N; ++k) out[k] = c[k];
+    dkd_item_constants<T>(kind, fringe, steps, (const T*)args.params[e], Ee, mc2, nq, out);
     energies[e] = dkd_energy_round_trip<T>(Ee, m);
 }
 
@@ -1612,6 +1630,225 @@ __global__ __launch_bounds__(CHX_BLOCK) void so_turns_reduce_kernel(const double
     }
 }
 
+// ---- a ring of Drifts, Quadrupoles and Dipoles tracked drift-kick-drift, TURN AFTER TURN (chx_dkd_turns) -------------------------
+// dkd_chain_kernel with the item loop inside the turn loop of so_turns_kernel. What the second-order ring does not have: every
+// drift-kick-drift element leaves the reference energy as the round trip f(E) = sqrt(sqrt(E^2 - m^2)^2 + m^2) of what it received
+// (dkd_energy_round_trip), and an element's constants depend on the energy in front of it. f is a composition of monotone,
+// correctly rounded operations, so E, f(E), f(f(E)), ... is monotone and ends in a fixed point — but not quickly for every E:
+// beside a power of two it can move one ulp per element for thousands of elements. So no turn is ASSUMED to repeat the one before
+// it. The constants of turn t are those of turn t - 1 exactly when both turns start with the same energy bits (then every later
+// turn does too), and that is what the kernels test:
+//   dkd_turns_energy_kernel     one lane walks the turns of the call from energy_in: start[t] = the energy in front of turn t,
+//                               block_of_turn[t] = the block of constants turn t reads. A turn whose start energy has the bits of
+//                               the turn before shares its block, and so do all turns behind it; any other turn opens a block.
+//                               Blocks are opened one per turn from the first turn on, so block k belongs to turn k of the call.
+//                               block_of_turn[turns] = the number of blocks; energy_out = the energy behind the last turn.
+//   dkd_turns_constants_kernel  a workgroup per (block, item); those of blocks that were not opened return at once. The others
+//                               walk from their block's start energy to the energy in front of their item and leave the item's
+//                               constants (dkd_item_constants, the chain's own). One workgroup more adds up the path length.
+//   dkd_turns_kernel<MODE, BEND>, dkd_turns_kernel_f64<BEND>   a particle per lane; per turn the block's address (a scalar load),
+//                               the items through dkd_chain_step / dkd_map as in the chain, then the loss test, the freezing of a
+//                               lost row in the LDS tile, the record and the probe rows as in so_turns_kernel_f64.
+//   so_turns_reduce_kernel      as it is.
+template <typename T>
+__device__ __forceinline__ bool dkd_same_bits(T a, T b) {
+    if constexpr (sizeof(T) == 4) return __float_as_uint(a) == __float_as_uint(b);
+    else return __double_as_longlong(a) == __double_as_longlong(b);
+}
+
+// the reference energy behind `count` drift-kick-drift items that received Ee
+template <typename T>
+__device__ __forceinline__ T dkd_energy_behind(T Ee, T m, int count) {
+    for (int k = 0; k < count; ++k) {
+        const T En = dkd_energy_round_trip<T>(Ee, m);
+        if (dkd_same_bits<T>(En, Ee)) break;                  // a fixed point: every later round trip returns it again
+        Ee = En;
+    }
+    return Ee;
+}
+
+template <typename T>
+__global__ void dkd_turns_energy_kernel(int E, int turns, const T* energy_in, T* energy_out, double mc2, T* __restrict__ start,
+                                        int32_t* __restrict__ block_of_turn) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const T m = (T)mc2;
+    T Et = *energy_in;                                        // (energy_out may be energy_in: read before anything is written)
+    int block = 0, t = 0;
+    for (; t < turns; ++t) {
+        if (t > 0 && dkd_same_bits<T>(Et, start[t - 1])) break;                  // this turn repeats the last one, and so does every later one
+        start[t] = Et;
+        block_of_turn[t] = block++;
+        Et = dkd_energy_behind<T>(Et, m, E);
+    }
+    for (; t < turns; ++t) {
+        start[t] = Et;
+        block_of_turn[t] = block - 1;
+    }
+    block_of_turn[turns] = block;
+    *energy_out = Et;
+}
+
+template <typename T>
+__global__ void dkd_turns_constants_kernel(DkdChainArgs args, int E, int turns, const T* __restrict__ start,
+                                           const int32_t* __restrict__ block_of_turn, double mc2, double nq, double* __restrict__ cst,
+                                           const T* s_in, T* s_out) {
+    if ((int)blockIdx.x == turns * E) {                       // one workgroup more: the path length after ONE turn
+        dkd_chain_path_length<T>(args, E, s_in, s_out);
+        return;
+    }
+    const int block = blockIdx.x / E, e = blockIdx.x - block * E;
+    if (block >= block_of_turn[turns] || threadIdx.x != 0) return;
+    const int kind = args.meta[e] & 15, fringe = (args.meta[e] >> 4) & 3, steps = args.meta[e] >> 6;
+    const T Ee = dkd_energy_behind<T>(start[block], (T)mc2, e);                  // (block k is turn k's: see above)
+    dkd_item_constants<T>(kind, fringe, steps, (const T*)args.params[e], Ee, mc2, nq, cst + ((int64_t)block * E + e) * kDkdCstStride);
+}
+
+// (cst and block_of_turn are kernel arguments of their own, __restrict__: see so_turns_kernel — the stores of the records must not
+// be taken for stores into the constants, or these stop coming through scalar loads)
+template <int MODE, bool BEND>
+__global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel(const double* __restrict__ cst, const int32_t* __restrict__ block_of_turn,
+                                                              double mc2, SoTurnsArgs<float> a) {
+    constexpr int TP = CHX_BLOCK;
+    __shared__ __attribute__((aligned(16))) float lds[TP * 7];
+    __shared__ double red[4 * kSoTurnSums];
+    const int64_t n0 = (int64_t)blockIdx.x * TP;
+    const int np = (int)((a.N - n0 < TP) ? (a.N - n0) : TP);
+    tile_load<float, TP>(a.x_in + n0 * 7, lds, np * 7, a.in_vec_ok != 0, true);
+    __syncthreads();
+    const int p = threadIdx.x;
+    const bool on = p < np;
+    float v[6], v6 = on ? lds[p * 7 + 6] : 1.0f;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) v[j] = on ? lds[p * 7 + j] : 0.0f;
+    int lost = on ? a.lost_turn[n0 + p] : -1;                  // (a lane past the end of the beam: never alive)
+    float ax = __builtin_inff(), ay = __builtin_inff();
+    if (a.aperture) { ax = a.aperture[0]; ay = a.aperture[1]; }
+    int64_t next_record = a.next_record;
+    int rec = 0;
+    const int end_turn = a.first_turn + a.num_turns;
+    for (int t = a.first_turn; t < end_turn; ++t) {
+        if (__any(lost == 0)) {
+            const double* __restrict__ turn_cst = cst + (int64_t)block_of_turn[t - a.first_turn] * a.E * kDkdCstStride;
+            for (int e = 0; e < a.E; ++e) {
+                const double* __restrict__ c = turn_cst + (int64_t)e * kDkdCstStride;
+                const int32_t* w = reinterpret_cast<const int32_t*>(c + kDkdMeta);
+                const int kind = w[0], steps = w[1];
+                if (kind == CHX_DKD_DRIFT) dkd_chain_step<MODE, CHX_DKD_DRIFT>(c, mc2, steps, v);
+                else if (!BEND || kind == CHX_DKD_QUADRUPOLE) dkd_chain_step<MODE, CHX_DKD_QUADRUPOLE>(c, mc2, steps, v);
+                else dkd_chain_step<MODE, CHX_DKD_DIPOLE>(c, mc2, steps, v);
+            }
+            v6 = 1.0f;                                         // (the drift-kick-drift kernels write 1 into the seventh column)
+            if (so_turn_outside<float>(v, ax, ay) && lost == 0) {
+                lost = t;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) lds[p * 7 + j] = v[j];                                  // frozen here
+                lds[p * 7 + 6] = v6;
+            }
+        }
+        if (t == next_record) {
+            double w[1], xd[1][6];
+            const bool live[1] = {lost == 0};
+            const int64_t n = n0 + p;
+            w[0] = 1.0;
+            if (on && a.charges) w[0] = (double)a.charges[n];
+            if (on && a.survival) w[0] = w[0] * (double)a.survival[n];
+#pragma unroll
+            for (int j = 0; j < 6; ++j) xd[0][j] = (double)v[j];
+            if (n < a.K) {
+                float* dst = a.probe + ((int64_t)rec * a.K + n) * 7;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) dst[j] = live[0] ? v[j] : lds[p * 7 + j];
+                dst[6] = live[0] ? v6 : lds[p * 7 + 6];
+            }
+            so_turn_record<1>(w, xd, live, red, a.partials + ((int64_t)rec * gridDim.x + blockIdx.x) * kSoTurnSums);
+            next_record += a.record_every;
+            ++rec;
+        }
+    }
+    if (lost == 0) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) lds[p * 7 + j] = v[j];
+        lds[p * 7 + 6] = v6;
+    }
+    if (on) a.lost_turn[n0 + p] = lost;
+    __syncthreads();
+    tile_store<float, TP>(a.x_out + n0 * 7, lds, np * 7, a.out_vec_ok != 0, true);
+}
+
+// float64 beams: the map in fp64 like dkd_chain_kernel_f64
+template <bool BEND>
+__global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel_f64(const double* __restrict__ cst, const int32_t* __restrict__ block_of_turn,
+                                                                  double mc2, SoTurnsArgs<double> a) {
+    constexpr int TP = CHX_BLOCK;
+    __shared__ __attribute__((aligned(16))) double lds[TP * 7];
+    __shared__ double red[4 * kSoTurnSums];
+    const int64_t n0 = (int64_t)blockIdx.x * TP;
+    const int np = (int)((a.N - n0 < TP) ? (a.N - n0) : TP);
+    tile_load<double, TP>(a.x_in + n0 * 7, lds, np * 7, a.in_vec_ok != 0, true);
+    __syncthreads();
+    const int p = threadIdx.x;
+    const bool on = p < np;
+    double v[6], v6 = on ? lds[p * 7 + 6] : 1.0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) v[j] = on ? lds[p * 7 + j] : 0.0;
+    int lost = on ? a.lost_turn[n0 + p] : -1;
+    double ax = __builtin_inf(), ay = __builtin_inf();
+    if (a.aperture) { ax = a.aperture[0]; ay = a.aperture[1]; }
+    int64_t next_record = a.next_record;
+    int rec = 0;
+    const int end_turn = a.first_turn + a.num_turns;
+    for (int t = a.first_turn; t < end_turn; ++t) {
+        if (__any(lost == 0)) {
+            const double* __restrict__ turn_cst = cst + (int64_t)block_of_turn[t - a.first_turn] * a.E * kDkdCstStride;
+            for (int e = 0; e < a.E; ++e) {
+                const double* __restrict__ c = turn_cst + (int64_t)e * kDkdCstStride;
+                const int32_t* w = reinterpret_cast<const int32_t*>(c + kDkdMeta);
+                const int kind = w[0], steps = w[1];
+                double out[6];
+                if (kind == CHX_DKD_DRIFT) dkd_map<CHX_DKD_DRIFT, double>(c, v, mc2, steps, out);
+                else if (!BEND || kind == CHX_DKD_QUADRUPOLE) dkd_map<CHX_DKD_QUADRUPOLE, double>(c, v, mc2, steps, out);
+                else dkd_map<CHX_DKD_DIPOLE, double>(c, v, mc2, steps, out);
+#pragma unroll
+                for (int j = 0; j < 6; ++j) v[j] = out[j];
+            }
+            v6 = 1.0;
+            if (so_turn_outside<double>(v, ax, ay) && lost == 0) {
+                lost = t;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) lds[p * 7 + j] = v[j];                                  // frozen here
+                lds[p * 7 + 6] = v6;
+            }
+        }
+        if (t == next_record) {
+            double w[1], xd[1][6];
+            const bool live[1] = {lost == 0};
+            const int64_t n = n0 + p;
+            w[0] = 1.0;
+            if (on && a.charges) w[0] = a.charges[n];
+            if (on && a.survival) w[0] = w[0] * a.survival[n];
+#pragma unroll
+            for (int j = 0; j < 6; ++j) xd[0][j] = v[j];
+            if (n < a.K) {
+                double* dst = a.probe + ((int64_t)rec * a.K + n) * 7;
+#pragma unroll
+                for (int j = 0; j < 6; ++j) dst[j] = live[0] ? v[j] : lds[p * 7 + j];
+                dst[6] = live[0] ? v6 : lds[p * 7 + 6];
+            }
+            so_turn_record<1>(w, xd, live, red, a.partials + ((int64_t)rec * gridDim.x + blockIdx.x) * kSoTurnSums);
+            next_record += a.record_every;
+            ++rec;
+        }
+    }
+    if (lost == 0) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) lds[p * 7 + j] = v[j];
+        lds[p * 7 + 6] = v6;
+    }
+    if (on) a.lost_turn[n0 + p] = lost;
+    __syncthreads();
+    tile_store<double, TP>(a.x_out + n0 * 7, lds, np * 7, a.out_vec_ok != 0, true);
+}
+
 }  // namespace
 
 // A run of elements tracked with their second-order maps (element.py:195-228) on ONE beam. float32: the particles stay in
@@ -1799,6 +2036,145 @@ extern "C" int chx_second_order_turns(const void* const* T_maps, const int32_t* 
     return so_turns_launch<double>(maps, (int)E, x_in, charges, survival, N, (int)first_turn, (int)num_turns, record_every, records,
                                    rec0, aperture, K, x_out, lost_turn, sums, probe, s_in, s_out, workspace, tiles, coef_bytes,
                                    (hipStream_t)stream);
+}
+
+// A ring of Drifts, Quadrupoles and Dipoles tracked drift-kick-drift: turns [first_turn, first_turn + num_turns) in one particle
+// launch (dkd_turns_kernel, dkd_turns_kernel_f64; see the kernels for the energy walk in front of it). The workspace, every part
+// 16-byte aligned: start[turns] (dtype) | block_of_turn[turns + 1] (int32) | constants[turns][E][kDkdCstStride] (double) |
+// partials[records][tiles][14] (double). The host cannot know how many blocks of constants the device will open: room for one per turn.
+namespace {
+struct DkdTurnsLayout {
+    size_t blocks, cst, partials, total;                      // byte offsets of the parts behind start[], and the size
+};
+size_t round_up16(size_t n) { return (n + 15) & ~(size_t)15; }
+DkdTurnsLayout dkd_turns_layout(int64_t E, int64_t N, int64_t turns, int64_t records, int dtype) {
+    DkdTurnsLayout l;
+    l.blocks = round_up16((size_t)turns * (dtype == CHX_F32 ? 4 : 8));
+    l.cst = l.blocks + round_up16((size_t)(turns + 1) * sizeof(int32_t));
+    l.partials = l.cst + (size_t)turns * (size_t)E * kDkdCstStride * sizeof(double);
+    l.total = l.partials + (size_t)records * (size_t)((N + CHX_BLOCK - 1) / CHX_BLOCK) * kSoTurnSums * sizeof(double);
+    return l;
+}
+template <typename T>
+int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, int mode, const void* x_in, const void* energy_in, void* energy_out,
+                     double mass_eV, double n_charges, const void* charges, const void* survival, int64_t N, int first_turn,
+                     int num_turns, int64_t record_every, int64_t records, int64_t rec0, const void* aperture, int64_t K, void* x_out,
+                     int32_t* lost_turn, double* sums, void* probe, const void* s_in, void* s_out, void* workspace,
+                     const DkdTurnsLayout& l, int64_t tiles, hipStream_t s) {
+    T* start = (T*)workspace;
+    int32_t* block_of_turn = (int32_t*)((char*)workspace + l.blocks);
+    double* cst = (double*)((char*)workspace + l.cst);
+    hipLaunchKernelGGL(dkd_turns_energy_kernel<T>, dim3(1), dim3(1), 0, s, E, num_turns, (const T*)energy_in, (T*)energy_out, mass_eV,
+                       start, block_of_turn);
+    CHX_CHECK_LAUNCH();
+    hipLaunchKernelGGL(dkd_turns_constants_kernel<T>, dim3((unsigned)((int64_t)num_turns * E + (s_out ? 1 : 0))), dim3(64), 0, s, items, E,
+                       num_turns, (const T*)start, (const int32_t*)block_of_turn, mass_eV, n_charges, cst, (const T*)s_in, (T*)s_out);
+    CHX_CHECK_LAUNCH();
+    SoTurnsArgs<T> a;
+    a.x_in = (const T*)x_in;
+    a.x_out = (T*)x_out;
+    a.charges = (const T*)charges;
+    a.survival = (const T*)survival;
+    a.aperture = (const T*)aperture;
+    a.lost_turn = lost_turn;
+    a.partials = (double*)((char*)workspace + l.partials);
+    a.probe = K > 0 && records > 0 ? (T*)probe + rec0 * K * 7 : nullptr;
+    a.N = N;
+    a.K = K;
+    a.E = E;
+    a.first_turn = first_turn;
+    a.num_turns = num_turns;
+    a.next_record = (rec0 + 1) * record_every;
+    a.record_every = record_every;
+    a.in_vec_ok = (int)chx_aligned16(x_in);
+    a.out_vec_ok = (int)chx_aligned16(x_out);
+    const dim3 grid((unsigned)tiles), wg(CHX_BLOCK);
+    const double* c = cst;
+    const int32_t* b = block_of_turn;
+    if constexpr (sizeof(T) == 8) {
+        if (bend) hipLaunchKernelGGL(dkd_turns_kernel_f64<true>, grid, wg, 0, s, c, b, mass_eV, a);
+        else hipLaunchKernelGGL(dkd_turns_kernel_f64<false>, grid, wg, 0, s, c, b, mass_eV, a);
+    } else {
+        if (mode == 2 && bend) hipLaunchKernelGGL((dkd_turns_kernel<2, true>), grid, wg, 0, s, c, b, mass_eV, a);
+        else if (mode == 2) hipLaunchKernelGGL((dkd_turns_kernel<2, false>), grid, wg, 0, s, c, b, mass_eV, a);
+        else if (mode == 1 && bend) hipLaunchKernelGGL((dkd_turns_kernel<1, true>), grid, wg, 0, s, c, b, mass_eV, a);
+        else if (mode == 1) hipLaunchKernelGGL((dkd_turns_kernel<1, false>), grid, wg, 0, s, c, b, mass_eV, a);
+        else if (bend) hipLaunchKernelGGL((dkd_turns_kernel<0, true>), grid, wg, 0, s, c, b, mass_eV, a);
+        else hipLaunchKernelGGL((dkd_turns_kernel<0, false>), grid, wg, 0, s, c, b, mass_eV, a);
+    }
+    CHX_CHECK_LAUNCH();
+    if (records > 0) {
+        hipLaunchKernelGGL(so_turns_reduce_kernel, dim3((unsigned)records), dim3(CHX_BLOCK), 0, s, (const double*)a.partials, tiles,
+                           sums + rec0 * kSoTurnSums);
+        CHX_CHECK_LAUNCH();
+    }
+    return CHX_OK;
+}
+}  // namespace
+
+extern "C" size_t chx_dkd_turns_workspace_bytes(int64_t E, int64_t N, int64_t turns_in_chunk, int64_t records_in_chunk, int dtype) {
+    if (E < 1 || E > kDkdChainMax || N < 1 || turns_in_chunk < 1 || turns_in_chunk >= 0x7fffffffLL || records_in_chunk < 0 ||
+        (dtype != CHX_F32 && dtype != CHX_F64))
+        return 0;
+    return dkd_turns_layout(E, N, turns_in_chunk, records_in_chunk, dtype).total;
+}
+
+extern "C" int chx_dkd_turns(const int32_t* kinds, const void* const* params, const int32_t* num_steps, const int32_t* fringe_at,
+                             int storage_precision, int64_t E, const void* x_in, const void* energy_in, void* energy_out,
+                             double mass_eV, double n_charges, const void* charges, const void* survival, int64_t N, int dtype,
+                             int64_t first_turn, int64_t num_turns, int64_t record_every, const void* aperture, int64_t K,
+                             void* x_out, int32_t* lost_turn, double* sums, void* probe, const void* s_in, void* s_out,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    if (dtype != CHX_F32 && dtype != CHX_F64) return CHX_ERR_DTYPE;
+    if (!kinds || !params || !num_steps || !fringe_at || E < 1 || E > kDkdChainMax || !x_in || !energy_in || !energy_out || !x_out ||
+        !lost_turn || !workspace || N < 1)
+        return CHX_ERR_INVALID_ARG;
+    if (storage_precision < 0 || storage_precision > 2) return CHX_ERR_INVALID_ARG;
+    if (first_turn < 1 || num_turns < 1 || record_every < 1 || K < 0 || K > N) return CHX_ERR_INVALID_ARG;
+    // lost_turn holds turn numbers as int32, and the kernels count to first_turn + num_turns in int: the last turn stays below INT_MAX
+    if (first_turn >= 0x7fffffffLL || num_turns >= 0x7fffffffLL || first_turn + num_turns - 1 >= 0x7fffffffLL || record_every > 0x7fffffffLL)
+        return CHX_ERR_INVALID_ARG;
+    if ((s_in == nullptr) != (s_out == nullptr)) return CHX_ERR_INVALID_ARG;
+    bool bend = false;
+    for (int64_t e = 0; e < E; ++e) {
+        if (!params[e] || (kinds[e] != CHX_DKD_DRIFT && kinds[e] != CHX_DKD_QUADRUPOLE && kinds[e] != CHX_DKD_DIPOLE) || num_steps[e] < 1 ||
+            num_steps[e] >= (1 << 25) || fringe_at[e] < 0 || fringe_at[e] > 3)
+            return CHX_ERR_INVALID_ARG;
+        bend = bend || kinds[e] == CHX_DKD_DIPOLE;
+    }
+    const int64_t rec0 = (first_turn - 1) / record_every;                           // records in front of this chunk
+    const int64_t records = (first_turn + num_turns - 1) / record_every - rec0;
+    if (records > 0 && (!sums || (K > 0 && !probe))) return CHX_ERR_INVALID_ARG;
+    const int64_t tiles = (N + CHX_BLOCK - 1) / CHX_BLOCK;
+    if (tiles > 0x7fffffffLL || num_turns * E >= 0x7fffffffLL) return CHX_ERR_INVALID_ARG;             // (grid sizes)
+    const DkdTurnsLayout l = dkd_turns_layout(E, N, num_turns, records, dtype);
+    if (workspace_bytes < l.total || !chx_aligned16(workspace)) return CHX_ERR_INVALID_ARG;
+    // aliasing: the first chunk reads a beam it must not write (x_out != x_in), later chunks run in place on x_out; energy_out may
+    // be energy_in (the chunks of a call hand the energy on through one device scalar); nothing else may share an address
+    if (first_turn == 1 && x_in == x_out) return CHX_ERR_INVALID_ARG;
+    const void* outs[] = {x_out, energy_out, lost_turn, sums, probe, workspace, s_out};
+    const void* ins[] = {x_in, energy_in, charges, survival, aperture, s_in};
+    constexpr size_t n_outs = sizeof(outs) / sizeof(outs[0]), n_ins = sizeof(ins) / sizeof(ins[0]);
+    for (size_t i = 0; i < n_outs; ++i) {
+        if (!outs[i]) continue;
+        for (size_t j = i + 1; j < n_outs; ++j)
+            if (outs[i] == outs[j]) return CHX_ERR_INVALID_ARG;
+        for (size_t j = 0; j < n_ins; ++j)
+            if (outs[i] == ins[j] && !(i == 0 && j == 0) && !(i == 1 && j == 1)) return CHX_ERR_INVALID_ARG;
+    }
+    DkdChainArgs items;
+    for (int e = 0; e < kDkdChainMax; ++e) {
+        items.params[e] = e < E ? params[e] : nullptr;
+        items.length[e] = nullptr;                            // every kind's first parameter is its length
+        items.meta[e] = e < E ? (kinds[e] | (fringe_at[e] << 4) | (num_steps[e] << 6)) : 0;
+    }
+    if (dtype == CHX_F32)
+        return dkd_turns_launch<float>(items, (int)E, bend, storage_precision, x_in, energy_in, energy_out, mass_eV, n_charges, charges,
+                                       survival, N, (int)first_turn, (int)num_turns, record_every, records, rec0, aperture, K, x_out,
+                                       lost_turn, sums, probe, s_in, s_out, workspace, l, tiles, (hipStream_t)stream);
+    return dkd_turns_launch<double>(items, (int)E, bend, 0, x_in, energy_in, energy_out, mass_eV, n_charges, charges, survival, N,
+                                    (int)first_turn, (int)num_turns, record_every, records, rec0, aperture, K, x_out, lost_turn, sums,
+                                    probe, s_in, s_out, workspace, l, tiles, (hipStream_t)stream);
 }
 
 namespace {

@@ -1208,6 +1208,32 @@ int chx_dkd_chain_mixed(const int32_t* kinds, const void* const* params, const v
  * maps of the linear runs needs the energy in front of each of them). kinds_scratch: E int32 of device memory. One or two launches. */
 int chx_dkd_energy_chain(const int32_t* kinds, int64_t E, const void* energy_in, double mass_eV, int dtype, void* energies,
                          void* kinds_scratch, void* stream);
+/* A ring of E drift-kick-drift Drifts, Quadrupoles and Dipoles (the symplectic Bmad-X maps) turn after turn: turns [first_turn,
+ * first_turn + num_turns) in one particle launch, the particles in registers from turn to turn; the bits of num_turns passes of
+ * chx_dkd_chain. HOST arrays kinds[E] (CHX_DKD_DRIFT / _QUADRUPOLE / _DIPOLE), params[E], num_steps[E], fringe_at[E] as in
+ * chx_dkd_chain, 1 <= E <= 192; ONE storage_precision (0 double, 1 storage, 2 mixed) for the ring, ignored by float64 beams.
+ *   energy_in (dtype scalar): the reference energy in front of turn first_turn; energy_out: the energy behind the last turn of the
+ *     call (may be energy_in: the chunks of a call hand it on through one device scalar). Every element leaves the round trip
+ *     sqrt(sqrt(E^2 - m^2)^2 + m^2) of the energy it received, which need not be a fixed point: the call walks the energy through its
+ *     turns on the device and computes one block of element constants per turn until two turns in a row start with the same
+ *     energy bits — from there on the turns share a block. Exact for every energy.
+ *   lost_turn, aperture, charges, survival, record_every, sums[record][14], probe[record][K][7], the aliasing of x_in / x_out and
+ *     s_in / s_out (the path length after ONE turn): as in chx_second_order_turns.
+ *   workspace: chx_dkd_turns_workspace_bytes(E, N, turns of this call, records of this call, dtype) bytes, 16-byte aligned — the
+ *     turns' start energies (dtype), block_of_turn[turns + 1] (int32), turns x E x 56 doubles of constants (the worst case: the
+ *     host cannot know how many blocks the device opens) and records x ceil(N / 256) x 14 doubles of partial sums; the first two
+ *     parts rounded up to 16 bytes. The function is monotone in every argument and returns 0 for arguments out of range.
+ * Four launches (energy walk, constants and path length, particles, reduction of the records), none synchronising.
+ * CHX_ERR_INVALID_ARG, before any launch: E < 1, E > 192, a kind other than the three, storage_precision outside 0..2, num_steps
+ * outside 1 .. 2^25 - 1, fringe_at outside 0..3, num_turns < 1, record_every < 1, K > N, a last turn of 2^31 - 1 or beyond, aliased
+ * buffers, a workspace too small or not 16-byte aligned, a required pointer that is NULL; CHX_ERR_DTYPE: dtype other than CHX_F32
+ * / CHX_F64. */
+size_t chx_dkd_turns_workspace_bytes(int64_t E, int64_t N, int64_t turns_in_chunk, int64_t records_in_chunk, int dtype);
+int chx_dkd_turns(const int32_t* kinds, const void* const* params, const int32_t* num_steps, const int32_t* fringe_at,
+                  int storage_precision, int64_t E, const void* x_in, const void* energy_in, void* energy_out, double mass_eV,
+                  double n_charges, const void* charges, const void* survival, int64_t N, int dtype, int64_t first_turn,
+                  int64_t num_turns, int64_t record_every, const void* aperture, int64_t K, void* x_out, int32_t* lost_turn,
+                  double* sums, void* probe, const void* s_in, void* s_out, void* workspace, size_t workspace_bytes, void* stream);
 /* Backward of chx_dkd_track (the reference gets it from torch autograd through utils/bmadx.py): forward-mode dual
  * numbers on device, one seeded evaluation per input. dx[B][N][7] (dtype, may be NULL) = dY . d x_out / d x_in;
  * partials (may be NULL) = chx_dkd_bwd_partials_count() doubles laid out [B][ceil(N/256)][P + 1]: per workgroup
