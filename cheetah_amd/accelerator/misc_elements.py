@@ -4,6 +4,8 @@ kernel (kinds SOLENOID / UNDULATOR / DRIFT) and are tracked by the same apply ke
 
 from __future__ import annotations
 
+import operator
+
 import torch
 
 from .. import _ops
@@ -125,14 +127,19 @@ class Undulator(Element):
 
 
 class Sextupole(Element):
-    """Sextupole (sextupole.py:45-132): a drift in first order, the k2 kick through the second-order tensor."""
+    """Sextupole (sextupole.py:45-132): a drift in first order, the k2 kick through the second-order tensor. With
+    `tracking_method="drift_kick_drift"` (not in the reference): Bmad's exact drifts around `num_steps` thin kicks of k2 L /
+    num_steps each — drift L / 2n, then n x (kick, drift L / n; L / 2n behind the last kick) inside the misalignment and tilt
+    transformations. Symplectic, unlike the truncated second-order map; k2 = 0 is a drift-kick-drift Drift. `num_steps` is
+    read by this method only."""
 
-    supported_tracking_methods = ["linear", "second_order"]
+    supported_tracking_methods = ["linear", "second_order", "drift_kick_drift"]
     _chx_kind = _ops.KIND["drift"]
+    _dkd_kind = _ops.DKD_KIND["sextupole"]
     _t_kind = _ops.T_KIND["sextupole"]
 
     def __init__(self, length, k2=None, misalignment=None, tilt=None, tracking_method="second_order", name=None,
-                 sanitize_name=None, metadata=None, device=None, dtype=None) -> None:
+                 sanitize_name=None, metadata=None, device=None, dtype=None, num_steps=1) -> None:
         fk = {"device": device, "dtype": dtype}
         super().__init__(name=name, sanitize_name=sanitize_name, metadata=metadata, **fk)
         self.length = length
@@ -140,7 +147,23 @@ class Sextupole(Element):
         self.register_buffer_or_parameter(
             "misalignment", misalignment if misalignment is not None else torch.tensor((0.0, 0.0), **fk))
         self.register_buffer_or_parameter("tilt", tilt if tilt is not None else torch.tensor(0.0, **fk))
+        self.num_steps = num_steps
         self.tracking_method = tracking_method
+
+    @property
+    def num_steps(self) -> int:
+        """Number of thin kicks of the drift-kick-drift method (an int of 1 .. 2^25 - 1, what the chain's packing holds)."""
+        return self._num_steps
+
+    @num_steps.setter
+    def num_steps(self, value) -> None:
+        try:
+            steps = None if isinstance(value, bool) else operator.index(value)
+        except TypeError:
+            steps = None
+        if steps is None or not 1 <= steps < (1 << 25):
+            raise ValueError(f"Sextupole.num_steps must be an int of 1 .. {(1 << 25) - 1}, got {value!r}")
+        self._num_steps = steps
 
     def _builder_params(self):
         return [self.length]
@@ -148,7 +171,23 @@ class Sextupole(Element):
     def _t_params(self):
         return [self.length, self.k2, self.tilt, self.misalignment[..., 0], self.misalignment[..., 1]]
 
+    def _dkd_params(self):
+        return self._t_params()
+
+    def _dkd_scalar_refs(self):
+        length, k2, tilt, m = self._settings("length", "k2", "tilt", "misalignment")
+        return [(length, None), (k2, None), (tilt, None), (m, 0), (m, 1)]
+
+    def _dkd_options(self):
+        return self._num_steps, 3
+
     _merge_equal = ("tracking_method", "k2", "misalignment", "tilt")
+
+    def merge(self, other):
+        merged = super().merge(other)
+        if merged is not None and self._tracking_method == "drift_kick_drift":
+            merged.num_steps = self._num_steps + other._num_steps       # (summed like a Quadrupole's; the other methods never read it)
+        return merged
 
     @property
     def is_active(self) -> bool:
@@ -160,7 +199,23 @@ class Sextupole(Element):
 
     @property
     def defining_features(self) -> list[str]:
+        # (`num_steps` is not among them: the reference's Sextupole has no such feature, and the files the two projects write
+        # for one lattice are compared key by key — `clone` and LatticeJSON carry it on their own)
         return super().defining_features + ["length", "k2", "misalignment", "tilt"]
+
+    def clone(self) -> "Sextupole":
+        clone = super().clone()
+        clone.num_steps = self._num_steps
+        return clone
+
+    def _json_extras(self) -> dict:
+        # only where it is read and is not the default: every other Sextupole writes the reference's keys and nothing else (the
+        # reference's constructor has no such argument, so its loader would refuse the file)
+        return {"num_steps": self._num_steps} if self._tracking_method == "drift_kick_drift" and self._num_steps != 1 else {}
+
+    def __repr__(self) -> str:
+        text = super().__repr__()
+        return text if self._num_steps == 1 else f"{text[:-1]}, num_steps={self._num_steps})"
 
 
 class TransverseDeflectingCavity(Element):

@@ -1,6 +1,6 @@
 // chx_nonlinear.hip — per-particle non-linear tracking for gfx950.
 //
-//  * drift-kick-drift (Bmad-X) tracking of Drift, Quadrupole, Dipole and TransverseDeflectingCavity:
+//  * drift-kick-drift (Bmad-X) tracking of Drift, Quadrupole, Dipole, TransverseDeflectingCavity and Sextupole:
 //    cheetah/accelerator/drift.py:106-154, quadrupole.py:168-251, dipole.py:183-370,
 //    transverse_deflecting_cavity.py:122-209 on top of cheetah/utils/bmadx.py;
 //  * second-order (MAD-convention T tensor) tracking: element.py:195-228 with the tensors of
@@ -171,6 +171,12 @@ __device__ void dkd_constants(int kind, const S* par, S E, double mc2, double nq
         c[C_I] = (fringe & 1) ? -g * m_tan(e1 - 2.0 * fint * hg1 * g * (1.0 + s1 * s1) / m_cos(e1)) : zero;
         c[C_J] = (fringe & 2) ? g * m_tan(e2) : zero;
         c[C_N] = (fringe & 2) ? -g * m_tan(e2 - 2.0 * fintx * hg2 * g * (1.0 + s2 * s2) / m_cos(e2)) : zero;
+    } else if (kind == CHX_DKD_SEXTUPOLE) {
+        const S L = par[0], k2 = par[1], tilt = par[2];
+        c[C_SIN] = m_sin(tilt); c[C_COS] = m_cos(tilt);
+        c[C_XO] = par[3]; c[C_YO] = par[4];
+        c[C_A] = L;
+        c[C_B] = k2 * L;  // the integrated strength: every one of the n kicks applies 1 / n of it
     } else {  // CHX_DKD_TDC
         const S L = par[0], V = par[1], phase = par[2], freq = par[3];
         const S tilt = par[4];
@@ -248,6 +254,19 @@ __device__ __forceinline__ void dkd_particle(const S* c, Bmad<S>& q, double mc2,
         q.px = q.px + q.x * c[C_J];
         q.py = q.py + q.y * c[C_N];
         offset_unset<S>(zero, zero, c[C_SIN], c[C_COS], q);
+    } else if (KIND == CHX_DKD_SEXTUPOLE) {
+        // Bmad's exact drifts around thin kicks (the reference has no drift-kick-drift Sextupole; track_a_drift and the offsets
+        // are its building blocks): n kicks of k2 L / n between n + 1 drifts of L / 2n, L / n, ..., L / n, L / 2n. Every piece
+        // is symplectic and leaves pz alone, so the element does.
+        const S h = c[C_A] / (2.0 * (double)num_steps), kappa = c[C_B] / (double)num_steps;
+        offset_set<S>(c[C_XO], c[C_YO], c[C_SIN], c[C_COS], q);
+        track_a_drift<S>(h, q, p0c, mc2);
+        for (int s = 0; s < num_steps; ++s) {
+            q.px = q.px - 0.5 * kappa * (q.x * q.x - q.y * q.y);
+            q.py = q.py + kappa * q.x * q.y;
+            track_a_drift<S>(s + 1 < num_steps ? 2.0 * h : h, q, p0c, mc2);
+        }
+        offset_unset<S>(c[C_XO], c[C_YO], c[C_SIN], c[C_COS], q);
     } else {  // TDC, transverse_deflecting_cavity.py:147-193
         const S half = c[C_A] / 2.0, volt = c[C_B], k_rf = c[C_C], phase0 = c[C_D], freq = c[C_E2];
         offset_set<S>(c[C_XO], c[C_YO], c[C_SIN], c[C_COS], q);
@@ -338,7 +357,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_kernel(const T* __restrict__ x_
     tile_store<T, TP>(x_out + (b * N + n0) * 7, lds, np * 7, out_vec, true);
 }
 
-// ---- float32 beams, MIXED arithmetic (Drift, Quadrupole): the default of float32 beams --------------------------------------
+// ---- float32 beams, MIXED arithmetic (Drift, Quadrupole, Sextupole): the default of float32 beams ---------------------------
 // Where does a float32 evaluation of the Bmad-X maps lose its digits? Not in the transverse map (x, px, y, py move by parts in
 // 1e3 per element; seven significant digits of each step are what the float32 STORAGE keeps anyway) — in the longitudinal pair:
 // pz = (p - p0c) / p0c and delta = (E - E_ref) / p0c subtract numbers that agree to three or four digits (bmadx.py:7-56), the
@@ -384,11 +403,12 @@ __device__ __forceinline__ void dkd_mixed_particle(const double* __restrict__ cs
     // A quadrupole that is shifted off the axis (quadrupole.py:199-215 subtracts the misalignment before its map): the shifted
     // coordinate may be hundreds of beam sizes, float32 steps on it lose digits of the BEAM's scale and its path-length terms
     // dwarf tau — such an element is evaluated in float64 like dkd_kernel<float, ., double> (workgroup-uniform decision).
-    if (KIND == CHX_DKD_QUADRUPOLE && (cst_[C_XO] != 0.0 || cst_[C_YO] != 0.0)) {
+    // A shifted sextupole likewise: its kick is quadratic in the shifted coordinate.
+    if ((KIND == CHX_DKD_QUADRUPOLE || KIND == CHX_DKD_SEXTUPOLE) && (cst_[C_XO] != 0.0 || cst_[C_YO] != 0.0)) {
         double in[6], out[6];
 #pragma unroll
         for (int j = 0; j < 6; ++j) in[j] = (double)v[j];
-        dkd_map<CHX_DKD_QUADRUPOLE, double>(cst_, in, mc2, num_steps, out);
+        dkd_map<KIND, double>(cst_, in, mc2, num_steps, out);
 #pragma unroll
         for (int j = 0; j < 6; ++j) v[j] = (float)out[j];
         return;
@@ -420,6 +440,40 @@ __device__ __forceinline__ void dkd_mixed_particle(const double* __restrict__ cs
         x = x + L * Px * iPl;
         y = y + L * Py * iPl;
         z = z + (double)(L * (so_a + so_b * iPl));
+    } else if (KIND == CHX_DKD_SEXTUPOLE) {                       // drifts as in the branch above around float32 kicks
+        const double sn = cst_[C_SIN], cs = cst_[C_COS];          // (here xo = yo = 0: the rotations as in the quadrupole's branch)
+        const bool upright = sn == 0.0 && cs == 1.0;
+        if (!upright) {
+            const float xr = (float)((double)x * cs + (double)y * sn), yr = (float)(-(double)x * sn + (double)y * cs);
+            const float pxr = (float)((double)px * cs + (double)py * sn), pyr = (float)(-(double)px * sn + (double)py * cs);
+            x = xr; y = yr; px = pxr; py = pyr;
+        }
+        const float h = (float)cst_[C_A] / (2.0f * (float)num_steps), kappa = (float)cst_[C_B] / (float)num_steps;
+        // pz does not change inside the magnet: 1 / (1 + pz) and the energy term of dz are the same for every drift
+        const float ir = __builtin_amdgcn_rcpf(relp);
+        const float pcf = p0cf * relp, m2 = mc2f * mc2f;
+        const float a = (m2 * (2.0f * pzf + pzf * pzf)) * __builtin_amdgcn_rcpf(pcf * pcf + m2);
+        const float so_a = a * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(1.0f + a) + 1.0f);          // sqrt_one(a)
+        for (int s = 0; s <= num_steps; ++s) {
+            if (s > 0) {
+                px = px - 0.5f * kappa * (x * x - y * y);
+                py = py + kappa * x * y;
+            }
+            const float L = (s == 0 || s == num_steps) ? h : 2.0f * h;
+            const float Px = px * ir, Py = py * ir;
+            const float Pxy2 = Px * Px + Py * Py;
+            const float Pl = __builtin_amdgcn_sqrtf(1.0f - Pxy2);
+            const float iPl = __builtin_amdgcn_rcpf(Pl);
+            const float so_b = -Pxy2 * __builtin_amdgcn_rcpf(Pl + 1.0f);                                // sqrt_one(-Pxy2)
+            x = x + L * Px * iPl;
+            y = y + L * Py * iPl;
+            z = z + (double)(L * (so_a + so_b * iPl));            // every increment of z into the fp64 accumulator
+        }
+        if (!upright) {
+            const double xi = (double)x * cs - (double)y * sn, yi = (double)x * sn + (double)y * cs;
+            const float pxr = (float)((double)px * cs - (double)py * sn), pyr = (float)((double)px * sn + (double)py * cs);
+            x = (float)xi; y = (float)yi; px = pxr; py = pyr;
+        }
     } else {                                                      // quadrupole.py:168-251, bmadx.py:219-252
         const double xo = cst_[C_XO], yo = cst_[C_YO], sn = cst_[C_SIN], cs = cst_[C_COS];
         // (here xo = yo = 0.) An upright quadrupole — sin(tilt) = 0, cos(tilt) = 1 — is rotated by the identity: x * 1 + y * 0 is
@@ -622,6 +676,9 @@ int dispatch_dkd(int kind, const void* x_in, const void* params, const void* ene
         case CHX_DKD_TDC:
             return launch_dkd<T, CHX_DKD_TDC, C>(x_in, params, energy, mc2, nq, num_steps, fringe, P, B, Bx, Bp, Be, N,
                                               x_out, energy_out, s);
+        case CHX_DKD_SEXTUPOLE:
+            return launch_dkd<T, CHX_DKD_SEXTUPOLE, C>(x_in, params, energy, mc2, nq, num_steps, fringe, P, B, Bx, Bp, Be,
+                                                    N, x_out, energy_out, s);
     }
     return CHX_ERR_INVALID_ARG;
 }
@@ -634,6 +691,7 @@ extern "C" int chx_dkd_num_params(int kind) {
         case CHX_DKD_QUADRUPOLE: return 5;
         case CHX_DKD_DIPOLE: return 9;
         case CHX_DKD_TDC: return 7;
+        case CHX_DKD_SEXTUPOLE: return 5;
     }
     return -1;
 }
@@ -656,16 +714,21 @@ extern "C" int chx_dkd_track_p(int kind, const void* x_in, const void* params, c
     if (B == 0 || N == 0) return CHX_OK;
     if (!x_in || !params || !energy || !x_out) return CHX_ERR_INVALID_ARG;
     if (!chx_bcast_ok(Bx, B) || !chx_bcast_ok(Bp, B) || !chx_bcast_ok(Be, B)) return CHX_ERR_INVALID_ARG;
-    if (kind == CHX_DKD_QUADRUPOLE && num_steps < 1) return CHX_ERR_INVALID_ARG;
+    if ((kind == CHX_DKD_QUADRUPOLE || kind == CHX_DKD_SEXTUPOLE) && num_steps < 1) return CHX_ERR_INVALID_ARG;
+    if (kind == CHX_DKD_SEXTUPOLE && num_steps >= (1 << 25)) return CHX_ERR_INVALID_ARG;        // (the chain's and the ring's cap)
     if (fringe_at < 0 || fringe_at > 3) return CHX_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == CHX_F32 && storage_precision == 2 && (kind == CHX_DKD_DRIFT || kind == CHX_DKD_QUADRUPOLE)) {
+    if (dtype == CHX_F32 && storage_precision == 2 && (kind == CHX_DKD_DRIFT || kind == CHX_DKD_QUADRUPOLE || kind == CHX_DKD_SEXTUPOLE)) {
         // mixed arithmetic (see dkd_mixed_kernel); the other kinds keep the fp64 evaluation
         const int64_t tiles = ((N + CHX_BLOCK - 1) / CHX_BLOCK) * B;
         if (tiles > 0x7fffffffLL) return CHX_ERR_INVALID_ARG;
         const int P = chx_dkd_num_params(kind);
         if (kind == CHX_DKD_DRIFT)
             hipLaunchKernelGGL(dkd_mixed_kernel<CHX_DKD_DRIFT>, dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const float*)x_in,
+                               (const float*)params, (const float*)energy, mass_eV, n_charges, num_steps, P, B, Bx, Bp, Be, N,
+                               (float*)x_out, (float*)energy_out, (int)chx_aligned16(x_in), (int)chx_aligned16(x_out));
+        else if (kind == CHX_DKD_SEXTUPOLE)
+            hipLaunchKernelGGL(dkd_mixed_kernel<CHX_DKD_SEXTUPOLE>, dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const float*)x_in,
                                (const float*)params, (const float*)energy, mass_eV, n_charges, num_steps, P, B, Bx, Bp, Be, N,
                                (float*)x_out, (float*)energy_out, (int)chx_aligned16(x_in), (int)chx_aligned16(x_out));
         else
@@ -699,7 +762,7 @@ __global__ void dkd_path_length_kernel(DkdLengthPtrs args, int n, const T* __res
     *s_out = s;
 }
 
-// ---- a RUN of Drifts, Quadrupoles and Dipoles on one beam, particles kept in registers (chx_dkd_chain) ---------------------
+// ---- a RUN of Drifts, Quadrupoles, Dipoles and Sextupoles on one beam, particles kept in registers (chx_dkd_chain) ---------------------
 // The per-element kernels above are bound by their arithmetic (a quadrupole in mixed arithmetic: ~450 instructions per particle),
 // yet every one of them also moves its 56 bytes per particle through HBM and waits for them at both ends. A run of E elements of
 // one arithmetic mode is two launches:
@@ -750,7 +813,7 @@ __device__ __forceinline__ void dkd_item_constants(int kind, int fringe, int ste
     int32_t* w = reinterpret_cast<int32_t*>(out + kDkdMeta);
     w[0] = kind;
     w[1] = steps;
-    const int P = kind == CHX_DKD_DRIFT ? 1 : (kind == CHX_DKD_QUADRUPOLE ? 5 : 9);
+    const int P = kind == CHX_DKD_DRIFT ? 1 : (kind == CHX_DKD_DIPOLE ? 9 : 5);          // (Quadrupole, Sextupole: 5)
     double par[CHX_MAX_PARAMS];
     for (int k = 0; k < P; ++k) par[k] = (double)pe[k];
     double c[C_MIXED_N];
@@ -839,7 +902,8 @@ __device__ __forceinline__ void dkd_chain_step(const double* __restrict__ c, dou
 }
 
 // BEND: the run contains Dipoles (their body — asin, atan2, a dozen square roots — costs registers the other runs keep)
-template <int MODE, bool BEND>
+// SEXT: the run contains Sextupoles (a run without one is the instantiation it was before they existed: the branch is not compiled)
+template <int MODE, bool BEND, bool SEXT>
 __global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel(const float* x_in, const double* __restrict__ cst, int E, double mc2,
                                                               float* x_out, int64_t N, int in_vec_ok, int out_vec_ok) {
     // (x_out may be x_in: a tile is read whole before it is written)
@@ -869,6 +933,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel(const float* x_in,
             continue;
         }
         if (kind == CHX_DKD_DRIFT) dkd_chain_step<MODE, CHX_DKD_DRIFT>(c, mc2, steps, v);
+        else if (SEXT && kind == CHX_DKD_SEXTUPOLE) dkd_chain_step<MODE, CHX_DKD_SEXTUPOLE>(c, mc2, steps, v);
         else if (!BEND || kind == CHX_DKD_QUADRUPOLE) dkd_chain_step<MODE, CHX_DKD_QUADRUPOLE>(c, mc2, steps, v);
         else dkd_chain_step<MODE, CHX_DKD_DIPOLE>(c, mc2, steps, v);
         v6 = 1.0f;
@@ -883,7 +948,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel(const float* x_in,
 }
 
 // float64 beams: the map in fp64 like dkd_kernel<double, ., double>, a particle per lane
-template <bool BEND>
+template <bool BEND, bool SEXT>
 __global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel_f64(const double* x_in, const double* __restrict__ cst, int E, double mc2,
                                                                   double* x_out, int64_t N, int in_vec_ok, int out_vec_ok) {
     constexpr int TP = CHX_BLOCK;              // (x_out may be x_in: a tile is read whole before it is written)
@@ -911,6 +976,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel_f64(const double* 
             continue;
         }
         if (kind == CHX_DKD_DRIFT) dkd_map<CHX_DKD_DRIFT, double>(c, v, mc2, steps, out);
+        else if (SEXT && kind == CHX_DKD_SEXTUPOLE) dkd_map<CHX_DKD_SEXTUPOLE, double>(c, v, mc2, steps, out);
         else if (!BEND || kind == CHX_DKD_QUADRUPOLE) dkd_map<CHX_DKD_QUADRUPOLE, double>(c, v, mc2, steps, out);
         else dkd_map<CHX_DKD_DIPOLE, double>(c, v, mc2, steps, out);
 #pragma unroll
@@ -988,20 +1054,21 @@ extern "C" int chx_dkd_chain_mixed(const int32_t* kinds, const void* const* para
             first = e;
         }
     }
-    // Drifts, Quadrupoles, Dipoles (float32: of one arithmetic mode) and linear runs, the constants (448 bytes per item) in x_tmp:
+    // Drifts, Quadrupoles, Dipoles, Sextupoles (float32: of one arithmetic mode) and linear runs, the constants (448 bytes per item) in x_tmp:
     // the particles stay in registers (dkd_chain_kernel, dkd_chain_kernel_f64), two launches per 192 items, the same bits
     static const bool fused_off = [] { const char* v = getenv("CHX_DKD_CHAIN_FUSED"); return v && v[0] == '0'; }();
     // (a longer run takes several such pairs, the later ones in place on x_out: a workgroup holds its whole tile in registers
     // before it writes)
     const int64_t per_pass = std::min<int64_t>(kDkdChainMax, N * 7 * (int64_t)esz / (kDkdCstStride * (int64_t)sizeof(double)));
     bool fuse = !fused_off && E >= 2 && per_pass >= 2 && chx_aligned16(x_tmp) && first >= 0;
-    bool bend = false;
+    bool bend = false, sext = false;
     for (int64_t e = 0; fuse && e < E; ++e) {      // (float64 beams ignore storage_precision, like chx_dkd_track_p)
         if (kinds[e] == kDkdLinear) continue;
-        fuse = (kinds[e] == CHX_DKD_DRIFT || kinds[e] == CHX_DKD_QUADRUPOLE || kinds[e] == CHX_DKD_DIPOLE) &&
+        fuse = (kinds[e] == CHX_DKD_DRIFT || kinds[e] == CHX_DKD_QUADRUPOLE || kinds[e] == CHX_DKD_DIPOLE || kinds[e] == CHX_DKD_SEXTUPOLE) &&
                (dtype == CHX_F64 || (storage_precision[e] == storage_precision[first] && storage_precision[e] >= 0 && storage_precision[e] <= 2)) &&
                num_steps[e] >= 1 && num_steps[e] < (1 << 25) && fringe_at[e] >= 0 && fringe_at[e] <= 3;
         bend = bend || kinds[e] == CHX_DKD_DIPOLE;
+        sext = sext || kinds[e] == CHX_DKD_SEXTUPOLE;
     }
     if (fuse) {
         hipStream_t s = (hipStream_t)stream;
@@ -1027,27 +1094,34 @@ extern "C" int chx_dkd_chain_mixed(const int32_t* kinds, const void* const* para
                 hipLaunchKernelGGL(dkd_chain_prepare_kernel<double>, dim3(blocks), dim3(64), 0, s, a, n, (const double*)e_from, mass_eV,
                                    n_charges, (double*)x_tmp, (double*)e_to, (const double*)s_from, (double*)s_out);
                 CHX_CHECK_LAUNCH();
-                if (bend)
-                    hipLaunchKernelGGL(dkd_chain_kernel_f64<true>, dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const double*)src,
-                                       (const double*)x_tmp, n, mass_eV, (double*)x_out, N, in_ok, out_ok);
-                else
-                    hipLaunchKernelGGL(dkd_chain_kernel_f64<false>, dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const double*)src,
-                                       (const double*)x_tmp, n, mass_eV, (double*)x_out, N, in_ok, out_ok);
+#define CHX_DKD_CHAIN_LAUNCH_F64(B, S)                                                                                                \
+    hipLaunchKernelGGL((dkd_chain_kernel_f64<B, S>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const double*)src,              \
+                       (const double*)x_tmp, n, mass_eV, (double*)x_out, N, in_ok, out_ok)
+                if (bend && sext) CHX_DKD_CHAIN_LAUNCH_F64(true, true);
+                else if (bend) CHX_DKD_CHAIN_LAUNCH_F64(true, false);
+                else if (sext) CHX_DKD_CHAIN_LAUNCH_F64(false, true);
+                else CHX_DKD_CHAIN_LAUNCH_F64(false, false);
+#undef CHX_DKD_CHAIN_LAUNCH_F64
                 CHX_CHECK_LAUNCH();
                 continue;
             }
             hipLaunchKernelGGL(dkd_chain_prepare_kernel<float>, dim3(blocks), dim3(64), 0, s, a, n, (const float*)e_from, mass_eV,
                                n_charges, (double*)x_tmp, (float*)e_to, (const float*)s_from, (float*)s_out);
             CHX_CHECK_LAUNCH();
-#define CHX_DKD_CHAIN_LAUNCH(M, B)                                                                                                \
-    hipLaunchKernelGGL((dkd_chain_kernel<M, B>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const float*)src, (const double*)x_tmp, \
+#define CHX_DKD_CHAIN_LAUNCH(M, B, S)                                                                                                \
+    hipLaunchKernelGGL((dkd_chain_kernel<M, B, S>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const float*)src, (const double*)x_tmp, \
                        n, mass_eV, (float*)x_out, N, in_ok, out_ok)
-            if (mode == 2 && bend) CHX_DKD_CHAIN_LAUNCH(2, true);
-            else if (mode == 2) CHX_DKD_CHAIN_LAUNCH(2, false);
-            else if (mode == 1 && bend) CHX_DKD_CHAIN_LAUNCH(1, true);
-            else if (mode == 1) CHX_DKD_CHAIN_LAUNCH(1, false);
-            else if (bend) CHX_DKD_CHAIN_LAUNCH(0, true);
-            else CHX_DKD_CHAIN_LAUNCH(0, false);
+#define CHX_DKD_CHAIN_MODE(M)                                                                                                     \
+    do {                                                                                                                          \
+        if (bend && sext) CHX_DKD_CHAIN_LAUNCH(M, true, true);                                                                    \
+        else if (bend) CHX_DKD_CHAIN_LAUNCH(M, true, false);                                                                      \
+        else if (sext) CHX_DKD_CHAIN_LAUNCH(M, false, true);                                                                      \
+        else CHX_DKD_CHAIN_LAUNCH(M, false, false);                                                                               \
+    } while (0)
+            if (mode == 2) CHX_DKD_CHAIN_MODE(2);
+            else if (mode == 1) CHX_DKD_CHAIN_MODE(1);
+            else CHX_DKD_CHAIN_MODE(0);
+#undef CHX_DKD_CHAIN_MODE
 #undef CHX_DKD_CHAIN_LAUNCH
             CHX_CHECK_LAUNCH();
         }
@@ -1630,7 +1704,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void so_turns_reduce_kernel(const double
     }
 }
 
-// ---- a ring of Drifts, Quadrupoles and Dipoles tracked drift-kick-drift, TURN AFTER TURN (chx_dkd_turns) -------------------------
+// ---- a ring of Drifts, Quadrupoles, Dipoles and Sextupoles tracked drift-kick-drift, TURN AFTER TURN (chx_dkd_turns) ------------
 // dkd_chain_kernel with the item loop inside the turn loop of so_turns_kernel. What the second-order ring does not have: every
 // drift-kick-drift element leaves the reference energy as the round trip f(E) = sqrt(sqrt(E^2 - m^2)^2 + m^2) of what it received
 // (dkd_energy_round_trip), and an element's constants depend on the energy in front of it. f is a composition of monotone,
@@ -1646,7 +1720,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void so_turns_reduce_kernel(const double
 //   dkd_turns_constants_kernel  a workgroup per (block, item); those of blocks that were not opened return at once. The others
 //                               walk from their block's start energy to the energy in front of their item and leave the item's
 //                               constants (dkd_item_constants, the chain's own). One workgroup more adds up the path length.
-//   dkd_turns_kernel<MODE, BEND>, dkd_turns_kernel_f64<BEND>   a particle per lane; per turn the block's address (a scalar load),
+//   dkd_turns_kernel<MODE, BEND, SEXT>, dkd_turns_kernel_f64<BEND, SEXT>   a particle per lane; per turn the block's address (a scalar load),
 //                               the items through dkd_chain_step / dkd_map as in the chain, then the loss test, the freezing of a
 //                               lost row in the LDS tile, the record and the probe rows as in so_turns_kernel_f64.
 //   so_turns_reduce_kernel      as it is.
@@ -1705,7 +1779,7 @@ __global__ void dkd_turns_constants_kernel(DkdChainArgs args, int E, int turns, 
 
 // (cst and block_of_turn are kernel arguments of their own, __restrict__: see so_turns_kernel — the stores of the records must not
 // be taken for stores into the constants, or these stop coming through scalar loads)
-template <int MODE, bool BEND>
+template <int MODE, bool BEND, bool SEXT>
 __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel(const double* __restrict__ cst, const int32_t* __restrict__ block_of_turn,
                                                               double mc2, SoTurnsArgs<float> a) {
     constexpr int TP = CHX_BLOCK;
@@ -1734,6 +1808,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel(const double* __re
                 const int32_t* w = reinterpret_cast<const int32_t*>(c + kDkdMeta);
                 const int kind = w[0], steps = w[1];
                 if (kind == CHX_DKD_DRIFT) dkd_chain_step<MODE, CHX_DKD_DRIFT>(c, mc2, steps, v);
+                else if (SEXT && kind == CHX_DKD_SEXTUPOLE) dkd_chain_step<MODE, CHX_DKD_SEXTUPOLE>(c, mc2, steps, v);
                 else if (!BEND || kind == CHX_DKD_QUADRUPOLE) dkd_chain_step<MODE, CHX_DKD_QUADRUPOLE>(c, mc2, steps, v);
                 else dkd_chain_step<MODE, CHX_DKD_DIPOLE>(c, mc2, steps, v);
             }
@@ -1776,7 +1851,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel(const double* __re
 }
 
 // float64 beams: the map in fp64 like dkd_chain_kernel_f64
-template <bool BEND>
+template <bool BEND, bool SEXT>
 __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel_f64(const double* __restrict__ cst, const int32_t* __restrict__ block_of_turn,
                                                                   double mc2, SoTurnsArgs<double> a) {
     constexpr int TP = CHX_BLOCK;
@@ -1806,6 +1881,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel_f64(const double* 
                 const int kind = w[0], steps = w[1];
                 double out[6];
                 if (kind == CHX_DKD_DRIFT) dkd_map<CHX_DKD_DRIFT, double>(c, v, mc2, steps, out);
+                else if (SEXT && kind == CHX_DKD_SEXTUPOLE) dkd_map<CHX_DKD_SEXTUPOLE, double>(c, v, mc2, steps, out);
                 else if (!BEND || kind == CHX_DKD_QUADRUPOLE) dkd_map<CHX_DKD_QUADRUPOLE, double>(c, v, mc2, steps, out);
                 else dkd_map<CHX_DKD_DIPOLE, double>(c, v, mc2, steps, out);
 #pragma unroll
@@ -2038,7 +2114,7 @@ extern "C" int chx_second_order_turns(const void* const* T_maps, const int32_t* 
                                    (hipStream_t)stream);
 }
 
-// A ring of Drifts, Quadrupoles and Dipoles tracked drift-kick-drift: turns [first_turn, first_turn + num_turns) in one particle
+// A ring of Drifts, Quadrupoles, Dipoles and Sextupoles tracked drift-kick-drift: turns [first_turn, first_turn + num_turns) in one particle
 // launch (dkd_turns_kernel, dkd_turns_kernel_f64; see the kernels for the energy walk in front of it). The workspace, every part
 // 16-byte aligned: start[turns] (dtype) | block_of_turn[turns + 1] (int32) | constants[turns][E][kDkdCstStride] (double) |
 // partials[records][tiles][14] (double). The host cannot know how many blocks of constants the device will open: room for one per turn.
@@ -2056,7 +2132,7 @@ DkdTurnsLayout dkd_turns_layout(int64_t E, int64_t N, int64_t turns, int64_t rec
     return l;
 }
 template <typename T>
-int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, int mode, const void* x_in, const void* energy_in, void* energy_out,
+int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, bool sext, int mode, const void* x_in, const void* energy_in, void* energy_out,
                      double mass_eV, double n_charges, const void* charges, const void* survival, int64_t N, int first_turn,
                      int num_turns, int64_t record_every, int64_t records, int64_t rec0, const void* aperture, int64_t K, void* x_out,
                      int32_t* lost_turn, double* sums, void* probe, const void* s_in, void* s_out, void* workspace,
@@ -2091,17 +2167,21 @@ int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, int mode, cons
     const dim3 grid((unsigned)tiles), wg(CHX_BLOCK);
     const double* c = cst;
     const int32_t* b = block_of_turn;
+#define CHX_DKD_TURNS_KINDS(K, ...)                                                                                               \
+    do {                                                                                                                          \
+        if (bend && sext) hipLaunchKernelGGL((K<__VA_ARGS__ true, true>), grid, wg, 0, s, c, b, mass_eV, a);                         \
+        else if (bend) hipLaunchKernelGGL((K<__VA_ARGS__ true, false>), grid, wg, 0, s, c, b, mass_eV, a);                           \
+        else if (sext) hipLaunchKernelGGL((K<__VA_ARGS__ false, true>), grid, wg, 0, s, c, b, mass_eV, a);                           \
+        else hipLaunchKernelGGL((K<__VA_ARGS__ false, false>), grid, wg, 0, s, c, b, mass_eV, a);                                    \
+    } while (0)
     if constexpr (sizeof(T) == 8) {
-        if (bend) hipLaunchKernelGGL(dkd_turns_kernel_f64<true>, grid, wg, 0, s, c, b, mass_eV, a);
-        else hipLaunchKernelGGL(dkd_turns_kernel_f64<false>, grid, wg, 0, s, c, b, mass_eV, a);
+        CHX_DKD_TURNS_KINDS(dkd_turns_kernel_f64, );
     } else {
-        if (mode == 2 && bend) hipLaunchKernelGGL((dkd_turns_kernel<2, true>), grid, wg, 0, s, c, b, mass_eV, a);
-        else if (mode == 2) hipLaunchKernelGGL((dkd_turns_kernel<2, false>), grid, wg, 0, s, c, b, mass_eV, a);
-        else if (mode == 1 && bend) hipLaunchKernelGGL((dkd_turns_kernel<1, true>), grid, wg, 0, s, c, b, mass_eV, a);
-        else if (mode == 1) hipLaunchKernelGGL((dkd_turns_kernel<1, false>), grid, wg, 0, s, c, b, mass_eV, a);
-        else if (bend) hipLaunchKernelGGL((dkd_turns_kernel<0, true>), grid, wg, 0, s, c, b, mass_eV, a);
-        else hipLaunchKernelGGL((dkd_turns_kernel<0, false>), grid, wg, 0, s, c, b, mass_eV, a);
+        if (mode == 2) CHX_DKD_TURNS_KINDS(dkd_turns_kernel, 2, );
+        else if (mode == 1) CHX_DKD_TURNS_KINDS(dkd_turns_kernel, 1, );
+        else CHX_DKD_TURNS_KINDS(dkd_turns_kernel, 0, );
     }
+#undef CHX_DKD_TURNS_KINDS
     CHX_CHECK_LAUNCH();
     if (records > 0) {
         hipLaunchKernelGGL(so_turns_reduce_kernel, dim3((unsigned)records), dim3(CHX_BLOCK), 0, s, (const double*)a.partials, tiles,
@@ -2135,12 +2215,13 @@ extern "C" int chx_dkd_turns(const int32_t* kinds, const void* const* params, co
     if (first_turn >= 0x7fffffffLL || num_turns >= 0x7fffffffLL || first_turn + num_turns - 1 >= 0x7fffffffLL || record_every > 0x7fffffffLL)
         return CHX_ERR_INVALID_ARG;
     if ((s_in == nullptr) != (s_out == nullptr)) return CHX_ERR_INVALID_ARG;
-    bool bend = false;
+    bool bend = false, sext = false;
     for (int64_t e = 0; e < E; ++e) {
-        if (!params[e] || (kinds[e] != CHX_DKD_DRIFT && kinds[e] != CHX_DKD_QUADRUPOLE && kinds[e] != CHX_DKD_DIPOLE) || num_steps[e] < 1 ||
-            num_steps[e] >= (1 << 25) || fringe_at[e] < 0 || fringe_at[e] > 3)
+        if (!params[e] || (kinds[e] != CHX_DKD_DRIFT && kinds[e] != CHX_DKD_QUADRUPOLE && kinds[e] != CHX_DKD_DIPOLE && kinds[e] != CHX_DKD_SEXTUPOLE) ||
+            num_steps[e] < 1 || num_steps[e] >= (1 << 25) || fringe_at[e] < 0 || fringe_at[e] > 3)
             return CHX_ERR_INVALID_ARG;
         bend = bend || kinds[e] == CHX_DKD_DIPOLE;
+        sext = sext || kinds[e] == CHX_DKD_SEXTUPOLE;
     }
     const int64_t rec0 = (first_turn - 1) / record_every;                           // records in front of this chunk
     const int64_t records = (first_turn + num_turns - 1) / record_every - rec0;
@@ -2169,10 +2250,10 @@ extern "C" int chx_dkd_turns(const int32_t* kinds, const void* const* params, co
         items.meta[e] = e < E ? (kinds[e] | (fringe_at[e] << 4) | (num_steps[e] << 6)) : 0;
     }
     if (dtype == CHX_F32)
-        return dkd_turns_launch<float>(items, (int)E, bend, storage_precision, x_in, energy_in, energy_out, mass_eV, n_charges, charges,
+        return dkd_turns_launch<float>(items, (int)E, bend, sext, storage_precision, x_in, energy_in, energy_out, mass_eV, n_charges, charges,
                                        survival, N, (int)first_turn, (int)num_turns, record_every, records, rec0, aperture, K, x_out,
                                        lost_turn, sums, probe, s_in, s_out, workspace, l, tiles, (hipStream_t)stream);
-    return dkd_turns_launch<double>(items, (int)E, bend, 0, x_in, energy_in, energy_out, mass_eV, n_charges, charges, survival, N,
+    return dkd_turns_launch<double>(items, (int)E, bend, sext, 0, x_in, energy_in, energy_out, mass_eV, n_charges, charges, survival, N,
                                     (int)first_turn, (int)num_turns, record_every, records, rec0, aperture, K, x_out, lost_turn, sums,
                                     probe, s_in, s_out, workspace, l, tiles, (hipStream_t)stream);
 }
@@ -2209,6 +2290,9 @@ int dispatch_dkd_bwd(int kind, const void* x_in, const void* params, const void*
         case CHX_DKD_TDC:
             return launch_dkd_bwd<T, CHX_DKD_TDC>(x_in, params, energy, dY, mc2, nq, num_steps, fringe, P, B, Bx, Bp, Be,
                                                   N, dx, partials, s);
+        case CHX_DKD_SEXTUPOLE:
+            return launch_dkd_bwd<T, CHX_DKD_SEXTUPOLE>(x_in, params, energy, dY, mc2, nq, num_steps, fringe, P, B, Bx,
+                                                        Bp, Be, N, dx, partials, s);
     }
     return CHX_ERR_INVALID_ARG;
 }
@@ -2230,7 +2314,8 @@ extern "C" int chx_dkd_track_bwd(int kind, const void* x_in, const void* params,
     if (B == 0 || N == 0) return CHX_OK;
     if (!x_in || !params || !energy || !dY || (!dx && !partials)) return CHX_ERR_INVALID_ARG;
     if (!chx_bcast_ok(Bx, B) || !chx_bcast_ok(Bp, B) || !chx_bcast_ok(Be, B)) return CHX_ERR_INVALID_ARG;
-    if (kind == CHX_DKD_QUADRUPOLE && num_steps < 1) return CHX_ERR_INVALID_ARG;
+    if ((kind == CHX_DKD_QUADRUPOLE || kind == CHX_DKD_SEXTUPOLE) && num_steps < 1) return CHX_ERR_INVALID_ARG;
+    if (kind == CHX_DKD_SEXTUPOLE && num_steps >= (1 << 25)) return CHX_ERR_INVALID_ARG;        // (the chain's and the ring's cap)
     if (fringe_at < 0 || fringe_at > 3) return CHX_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
     return dtype == CHX_F32 ? dispatch_dkd_bwd<float>(kind, x_in, params, energy, dY, mass_eV, n_charges, num_steps,

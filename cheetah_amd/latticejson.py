@@ -40,6 +40,7 @@ def convert_element(element, elements_dict: dict | None = None) -> tuple[str, st
             params[feature] = sub_name
         else:
             params[feature] = _plain(value)
+    params.update(element._json_extras())  # optional keys, e.g. a Sextupole's num_steps when it is not the default
     params["metadata"] = element.metadata  # not a defining feature: it does not affect the simulation
     return element.name, element.__class__.__name__, params
 
