@@ -11,6 +11,7 @@
 // LDS tile staging as chx_apply.hip; the per-particle arithmetic runs in fp64 whatever the storage
 // dtype is (transcendental-heavy but far below the HBM time of the pass on 256 CUs).
 #include <cstdlib>
+#include <initializer_list>
 
 #include "chx_common.h"
 #include "chx_dual.h"
@@ -901,32 +902,53 @@ __device__ __forceinline__ void dkd_chain_step(const double* __restrict__ c, dou
     }
 }
 
+// float64 beams (MODE is not read): the map in fp64 like dkd_kernel<double, ., double>
+template <int MODE, int KIND>
+__device__ __forceinline__ void dkd_chain_step(const double* __restrict__ c, double mc2, int num_steps, double (&v)[6]) {
+    double out[6];
+    dkd_map<KIND, double>(c, v, mc2, num_steps, out);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) v[j] = out[j];
+}
+
+// six coordinates from one register array to another. Which spelling leaves the better register allocation is the compiler's
+// whim, not a property of the arithmetic: with hipcc of ROCm 7.2 the fp64 ring keeps 4 waves per SIMD only with the block copy,
+// the float32 chain with Dipoles keeps its 8 only with the element copy. Nothing in the build guards this: after a ROCm update,
+// regenerate the table of profiles/turn_frame.md and choose again.
+template <typename T>
+__device__ __forceinline__ void dkd_copy6(const T (&from)[6], T (&to)[6]) {
+    if constexpr (sizeof(T) == 8) {
+        __builtin_memcpy(to, from, sizeof(to));
+    } else {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) to[j] = from[j];
+    }
+}
+
+// THE ITEM LOOP of a run of drift-kick-drift items, shared by the chain kernels (LINEAR = true) and the float64 ring (false; the
+// float32 ring, dkd_turns_kernel, has the loop written out and says why): the
+// items' constants at cst[e][kDkdCstStride] are wave-uniform scalar loads; lane and lane6 hold the lane's particle, six coordinates
+// and the seventh column, into which every drift-kick-drift item writes 1.
 // BEND: the run contains Dipoles (their body — asin, atan2, a dozen square roots — costs registers the other runs keep)
 // SEXT: the run contains Sextupoles (a run without one is the instantiation it was before they existed: the branch is not compiled)
-template <int MODE, bool BEND, bool SEXT>
-__global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel(const float* x_in, const double* __restrict__ cst, int E, double mc2,
-                                                              float* x_out, int64_t N, int in_vec_ok, int out_vec_ok) {
-    // (x_out may be x_in: a tile is read whole before it is written)
-    constexpr int TP = CHX_BLOCK;
-    __shared__ __attribute__((aligned(16))) float lds[TP * 7];
-    const int64_t n0 = (int64_t)blockIdx.x * TP;
-    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
-    tile_load<float, TP>(x_in + n0 * 7, lds, np * 7, in_vec_ok != 0, true);
-    __syncthreads();
-    const int p = threadIdx.x;
-    float v[6], v6 = p < np ? lds[p * 7 + 6] : 1.0f;       // (the drift-kick-drift kernels write 1 into the seventh column)
-#pragma unroll
-    for (int j = 0; j < 6; ++j) v[j] = p < np ? lds[p * 7 + j] : 0.0f;
+// LINEAR: items of kind kDkdLinear may stand in the run (a chain; a ring has none, and its code has no such branch)
+// A new element kind is one line of the dispatch below.
+// The loop runs on a copy of x that is the function's own: a function is optimised before it is inlined into its caller, and
+// there the lane's registers are memory behind a reference — a loop over them comes out in another shape than a loop over locals,
+// at 3 to 6 VGPRs more per ring kernel and a wave per SIMD fewer in six of them (profiles/turn_frame.md).
+template <int MODE, bool BEND, bool SEXT, bool LINEAR, typename T>
+__device__ __forceinline__ void dkd_items(const double* __restrict__ cst, int E, double mc2, T (&lane)[6], T& lane6) {
+    T v[6], v6 = lane6;
+    dkd_copy6(lane, v);
     for (int e = 0; e < E; ++e) {
         const double* __restrict__ c = cst + (int64_t)e * kDkdCstStride;
         const int32_t* w = reinterpret_cast<const int32_t*>(c + kDkdMeta);
         const int kind = w[0], steps = w[1];
-        if (kind == kDkdLinear) {
-            // a merged run of linear elements: chx_map7 on all seven coordinates, as chx_apply_affine7 does it
-            const float* __restrict__ R = reinterpret_cast<const float*>(c);
-            const float x[7] = {v[0], v[1], v[2], v[3], v[4], v[5], v6};
-            float y[7];
-            chx_map7<float, float>(R, x, y);
+        if (LINEAR && kind == kDkdLinear) {
+            // a merged run of linear elements: chx_map7 on all seven coordinates, as chx_apply_affine7 does it (R in the beam's dtype)
+            const T in[7] = {v[0], v[1], v[2], v[3], v[4], v[5], v6};
+            T y[7];
+            chx_map7<T, T>(reinterpret_cast<const T*>(c), in, y);
 #pragma unroll
             for (int j = 0; j < 6; ++j) v[j] = y[j];
             v6 = y[6];
@@ -936,60 +958,47 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel(const float* x_in,
         else if (SEXT && kind == CHX_DKD_SEXTUPOLE) dkd_chain_step<MODE, CHX_DKD_SEXTUPOLE>(c, mc2, steps, v);
         else if (!BEND || kind == CHX_DKD_QUADRUPOLE) dkd_chain_step<MODE, CHX_DKD_QUADRUPOLE>(c, mc2, steps, v);
         else dkd_chain_step<MODE, CHX_DKD_DIPOLE>(c, mc2, steps, v);
-        v6 = 1.0f;
+        v6 = (T)1;
     }
+    dkd_copy6(v, lane);
+    lane6 = v6;
+}
+
+// a particle per lane through all items of the run, MODE / BEND / SEXT as in dkd_items (x_out may be x_in: a tile is read whole
+// before it is written)
+template <int MODE, bool BEND, bool SEXT, typename T>
+__device__ __forceinline__ void dkd_chain_tile(const T* x_in, const double* __restrict__ cst, int E, double mc2, T* x_out, int64_t N,
+                                               int in_vec_ok, int out_vec_ok) {
+    constexpr int TP = CHX_BLOCK;
+    __shared__ __attribute__((aligned(16))) T lds[TP * 7];
+    const int64_t n0 = (int64_t)blockIdx.x * TP;
+    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
+    tile_load<T, TP>(x_in + n0 * 7, lds, np * 7, in_vec_ok != 0, true);
+    __syncthreads();
+    const int p = threadIdx.x;
+    T v[6], v6 = p < np ? lds[p * 7 + 6] : (T)1;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) v[j] = p < np ? lds[p * 7 + j] : (T)0;
+    dkd_items<MODE, BEND, SEXT, true, T>(cst, E, mc2, v, v6);
     if (p < np) {
 #pragma unroll
         for (int j = 0; j < 6; ++j) lds[p * 7 + j] = v[j];
         lds[p * 7 + 6] = v6;
     }
     __syncthreads();
-    tile_store<float, TP>(x_out + n0 * 7, lds, np * 7, out_vec_ok != 0, true);
+    tile_store<T, TP>(x_out + n0 * 7, lds, np * 7, out_vec_ok != 0, true);
 }
 
-// float64 beams: the map in fp64 like dkd_kernel<double, ., double>, a particle per lane
+template <int MODE, bool BEND, bool SEXT>
+__global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel(const float* x_in, const double* __restrict__ cst, int E, double mc2,
+                                                              float* x_out, int64_t N, int in_vec_ok, int out_vec_ok) {
+    dkd_chain_tile<MODE, BEND, SEXT, float>(x_in, cst, E, mc2, x_out, N, in_vec_ok, out_vec_ok);
+}
+
 template <bool BEND, bool SEXT>
 __global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel_f64(const double* x_in, const double* __restrict__ cst, int E, double mc2,
                                                                   double* x_out, int64_t N, int in_vec_ok, int out_vec_ok) {
-    constexpr int TP = CHX_BLOCK;              // (x_out may be x_in: a tile is read whole before it is written)
-    __shared__ __attribute__((aligned(16))) double lds[TP * 7];
-    const int64_t n0 = (int64_t)blockIdx.x * TP;
-    const int np = (int)((N - n0 < TP) ? (N - n0) : TP);
-    tile_load<double, TP>(x_in + n0 * 7, lds, np * 7, in_vec_ok != 0, true);
-    __syncthreads();
-    const int p = threadIdx.x;
-    double v[6], v6 = p < np ? lds[p * 7 + 6] : 1.0;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) v[j] = p < np ? lds[p * 7 + j] : 0.0;
-    for (int e = 0; e < E; ++e) {
-        const double* __restrict__ c = cst + (int64_t)e * kDkdCstStride;
-        const int32_t* w = reinterpret_cast<const int32_t*>(c + kDkdMeta);
-        const int kind = w[0], steps = w[1];
-        double out[6];
-        if (kind == kDkdLinear) {
-            const double x[7] = {v[0], v[1], v[2], v[3], v[4], v[5], v6};
-            double y[7];
-            chx_map7<double, double>(c, x, y);
-#pragma unroll
-            for (int j = 0; j < 6; ++j) v[j] = y[j];
-            v6 = y[6];
-            continue;
-        }
-        if (kind == CHX_DKD_DRIFT) dkd_map<CHX_DKD_DRIFT, double>(c, v, mc2, steps, out);
-        else if (SEXT && kind == CHX_DKD_SEXTUPOLE) dkd_map<CHX_DKD_SEXTUPOLE, double>(c, v, mc2, steps, out);
-        else if (!BEND || kind == CHX_DKD_QUADRUPOLE) dkd_map<CHX_DKD_QUADRUPOLE, double>(c, v, mc2, steps, out);
-        else dkd_map<CHX_DKD_DIPOLE, double>(c, v, mc2, steps, out);
-#pragma unroll
-        for (int j = 0; j < 6; ++j) v[j] = out[j];
-        v6 = 1.0;
-    }
-    if (p < np) {
-#pragma unroll
-        for (int j = 0; j < 6; ++j) lds[p * 7 + j] = v[j];
-        lds[p * 7 + 6] = v6;
-    }
-    __syncthreads();
-    tile_store<double, TP>(x_out + n0 * 7, lds, np * 7, out_vec_ok != 0, true);
+    dkd_chain_tile<0, BEND, SEXT, double>(x_in, cst, E, mc2, x_out, N, in_vec_ok, out_vec_ok);
 }
 }  // namespace
 
@@ -1345,6 +1354,82 @@ __device__ __forceinline__ void so_step_groups(const float* __restrict__ U, chx_
     for (int j = 0; j < 7; ++j) x[j] = y[j];
 }
 
+// ---- the same for float64 beams: one particle per lane, fp64 multiply-adds. second_order_kernel<double> sums a row densely
+// (U_i0 q_0, then 27 multiply-adds); leaving out the terms whose coefficient is an exact zero changes no value of a finite beam
+// (fma(0, q, acc) = acc), a non-finite coordinate turns the whole particle into NaN there (0 * inf) and here (the probe).
+template <class P>
+__device__ __forceinline__ void so_step_pattern(const double* __restrict__ U, double (&x)[7], double probe) {
+    constexpr unsigned int cols = P::rows[0] | P::rows[1] | P::rows[2] | P::rows[3] | P::rows[4] | P::rows[5] | P::rows[6];
+    double q[28];
+#pragma unroll
+    for (int c = 0; c < 28; ++c)
+        if ((cols >> c) & 1u) q[c] = x[kSoJ[c]] * x[kSoK[c]];
+    double y[7];
+    int n = 0;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        double acc = probe;
+#pragma unroll
+        for (int c = 0; c < 28; ++c)
+            if ((P::rows[i] >> c) & 1u) acc = fma(U[kSoPacked + n++], q[c], acc);
+        y[i] = acc;
+    }
+#pragma unroll
+    for (int j = 0; j < 7; ++j) x[j] = y[j];
+}
+
+__device__ __forceinline__ void so_step_groups(const double* __restrict__ U, double (&x)[7], double probe) {
+    const unsigned long long g = (unsigned long long)reinterpret_cast<const unsigned int*>(U + 196)[0] |
+                                 ((unsigned long long)reinterpret_cast<const unsigned int*>(U + 196)[1] << 32);
+    double y[7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        double acc = probe;
+#pragma unroll
+        for (int m = 0; m < 7; ++m) {
+            if (!((g >> (i * 7 + m)) & 1ull)) continue;           // wave-uniform
+#pragma unroll
+            for (int q4 = 0; q4 < 4; ++q4) {
+                const int c = 4 * m + q4;
+                acc = fma(U[i * 28 + c], x[kSoJ[c]] * x[kSoK[c]], acc);
+            }
+        }
+        y[i] = acc;
+    }
+#pragma unroll
+    for (int j = 0; j < 7; ++j) x[j] = y[j];
+}
+
+__device__ __forceinline__ void so_step_linear(const double* __restrict__ U, double (&x)[7]) { chx_map7_inplace<double, double>(U + kSoPacked, x); }
+
+// THE ITEM LOOP of a run of second-order items, shared by so_chain_kernel_f64 (X = double, one particle per lane) and the float32
+// ring (X = chx_v2f, two particles; so_chain_kernel and so_turns_kernel_f64 have the loop written out and say why). The coefficients at coef[e][kSoCoefStride] are wave-uniform scalar loads, and so
+// is the scheme that picks the evaluation. A new scheme is one line of the dispatch below. (The loop runs on a copy of the
+// lane's registers that is the function's own: see dkd_items.)
+template <typename T, typename X>
+__device__ __forceinline__ void so_items(const T* __restrict__ coef, int E, X (&lane)[7]) {
+    X x[7];
+    __builtin_memcpy(x, lane, sizeof(x));
+    for (int e = 0; e < E; ++e) {
+        const T* __restrict__ U = coef + (int64_t)e * kSoCoefStride;
+        const unsigned int scheme = reinterpret_cast<const unsigned int*>(U + 196)[2];
+        // 0 * x is NaN exactly for a non-finite x and +0 otherwise: every row's sum STARTS from this value, so a particle that
+        // left the finite range comes out as NaN in all seven coordinates (second_order_pk_kernel's rule) and nothing changes
+        // for the others (+0 + a = a)
+        X probe = X{};
+#pragma unroll
+        for (int j = 0; j < 7; ++j) probe = __builtin_elementwise_fma(X{}, x[j], probe);
+        if (scheme == 0u) so_step_pattern<SoPatternQuad>(U, x, probe);
+        else if (scheme == 1u) so_step_pattern<SoPatternBend>(U, x, probe);
+        else if (scheme == 3u) so_step_linear(U, x);
+        else so_step_groups(U, x, probe);
+    }
+    __builtin_memcpy(lane, x, sizeof(x));
+}
+
+// the float32 chain: so_items' loop written out in the kernel. At its cap of 64 VGPRs (8 waves per SIMD) the kernel takes no
+// other shape without a cost: on so_items it spilled 6 VGPRs (loop on references) or grew by 11 instructions and 1 to 2 % in time
+// (loop on a copy; profiles/turn_frame.md). A new scheme in so_items is added here too.
 __global__ __launch_bounds__(CHX_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void so_chain_kernel(const float* x_in, const float* __restrict__ coef, int E, float* x_out, int64_t N, int in_vec_ok,
                      int out_vec_ok) {                  // (x_out may be x_in: a tile is read whole before it is written)
@@ -1382,55 +1467,6 @@ void so_chain_kernel(const float* x_in, const float* __restrict__ coef, int E, f
     tile_store<float, TP>(x_out + n0 * 7, lds, np * 7, out_vec_ok != 0, true);
 }
 
-
-// ---- the same for float64 beams: one particle per lane, fp64 multiply-adds. second_order_kernel<double> sums a row densely
-// (U_i0 q_0, then 27 multiply-adds); leaving out the terms whose coefficient is an exact zero changes no value of a finite beam
-// (fma(0, q, acc) = acc), a non-finite coordinate turns the whole particle into NaN there (0 * inf) and here (the probe).
-template <class P>
-__device__ __forceinline__ void so_step_pattern_f64(const double* __restrict__ U, double (&x)[7], double probe) {
-    constexpr unsigned int cols = P::rows[0] | P::rows[1] | P::rows[2] | P::rows[3] | P::rows[4] | P::rows[5] | P::rows[6];
-    double q[28];
-#pragma unroll
-    for (int c = 0; c < 28; ++c)
-        if ((cols >> c) & 1u) q[c] = x[kSoJ[c]] * x[kSoK[c]];
-    double y[7];
-    int n = 0;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        double acc = probe;
-#pragma unroll
-        for (int c = 0; c < 28; ++c)
-            if ((P::rows[i] >> c) & 1u) acc = fma(U[kSoPacked + n++], q[c], acc);
-        y[i] = acc;
-    }
-#pragma unroll
-    for (int j = 0; j < 7; ++j) x[j] = y[j];
-}
-
-__device__ __forceinline__ void so_step_groups_f64(const double* __restrict__ U, double (&x)[7], double probe) {
-    const unsigned long long g = (unsigned long long)reinterpret_cast<const unsigned int*>(U + 196)[0] |
-                                 ((unsigned long long)reinterpret_cast<const unsigned int*>(U + 196)[1] << 32);
-    double y[7];
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-        double acc = probe;
-#pragma unroll
-        for (int m = 0; m < 7; ++m) {
-            if (!((g >> (i * 7 + m)) & 1ull)) continue;           // wave-uniform
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const int c = 4 * m + q4;
-                acc = fma(U[i * 28 + c], x[kSoJ[c]] * x[kSoK[c]], acc);
-            }
-        }
-        y[i] = acc;
-    }
-#pragma unroll
-    for (int j = 0; j < 7; ++j) x[j] = y[j];
-}
-
-__device__ __forceinline__ void so_step_linear_f64(const double* __restrict__ U, double (&x)[7]) { chx_map7_inplace<double, double>(U + kSoPacked, x); }
-
 __global__ __launch_bounds__(CHX_BLOCK) void so_chain_kernel_f64(const double* x_in, const double* __restrict__ coef, int E, double* x_out,
                                                                  int64_t N, int in_vec_ok, int out_vec_ok) {
     constexpr int TP = CHX_BLOCK;              // (x_out may be x_in: a tile is read whole before it is written)
@@ -1443,17 +1479,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void so_chain_kernel_f64(const double* x
     double x[7];
 #pragma unroll
     for (int j = 0; j < 7; ++j) x[j] = p < np ? lds[p * 7 + j] : 0.0;
-    for (int e = 0; e < E; ++e) {
-        const double* __restrict__ U = coef + (int64_t)e * kSoCoefStride;
-        const unsigned int scheme = reinterpret_cast<const unsigned int*>(U + 196)[2];
-        double probe = 0.0;
-#pragma unroll
-        for (int j = 0; j < 7; ++j) probe = fma(0.0, x[j], probe);
-        if (scheme == 0u) so_step_pattern_f64<SoPatternQuad>(U, x, probe);
-        else if (scheme == 1u) so_step_pattern_f64<SoPatternBend>(U, x, probe);
-        else if (scheme == 3u) so_step_linear_f64(U, x);
-        else so_step_groups_f64(U, x, probe);
-    }
+    so_items<double, double>(coef, E, x);
     if (p < np) {
 #pragma unroll
         for (int j = 0; j < 7; ++j) lds[p * 7 + j] = x[j];
@@ -1529,90 +1555,117 @@ __device__ __forceinline__ bool so_turn_outside(const T (&c)[6], T ax, T ay) {  
     return bad != 0;
 }
 
-// (coef is a kernel argument of its own, __restrict__: only then does the compiler know that the stores of the records cannot
-// touch the coefficients and fetch them through scalar loads as so_chain_kernel does — inside the argument block they came
-// through 130 vector loads per item loop, and the kernel took 1.7 us per item step at 1e6 particles instead of the chain's 1.3)
-__global__ __launch_bounds__(CHX_BLOCK) void so_turns_kernel(const float* __restrict__ coef, SoTurnsArgs<float> a) {
-    constexpr int TP = 2 * CHX_BLOCK;
-    __shared__ __attribute__((aligned(16))) float lds[TP * 7];
+// THE TURN FRAME of the ring kernels (so_turns_kernel and dkd_turns_kernel_f64 run on it; so_turns_kernel_f64 and dkd_turns_kernel
+// hold the same text written out and say why): the tile load, the loss flags, the aperture, the turn loop with its wave-uniform skip,
+// the loss test and the freezing of a lost row in LDS, the record and the probe rows, the write-back — the rules above, once,
+// for PP particles per lane. What a lane holds and what a turn does to it is the Ring's business:
+//   ring.load(lds, p, on)   the lane's rows p[h] of the LDS tile into its registers (on[h] false: a lane past the end of the beam)
+//   ring.get(h, j)          coordinate j < 7 of the lane's particle h
+//   ring.turn(k)            turn k of the call (0-based) on the registers
+// ring and a are taken by reference: the frame is inlined into its kernel, and the kernel's own arguments stay what the
+// compiler sees (see so_turns_kernel for why that matters).
+template <typename T, int PP, class Ring>
+__device__ __forceinline__ void turns_frame(Ring& ring, const SoTurnsArgs<T>& a) {
+    constexpr int TP = PP * CHX_BLOCK;
+    __shared__ __attribute__((aligned(16))) T lds[TP * 7];
     __shared__ double red[4 * kSoTurnSums];
     const int64_t n0 = (int64_t)blockIdx.x * TP;
     const int np = (int)((a.N - n0 < TP) ? (a.N - n0) : TP);
-    tile_load<float, TP>(a.x_in + n0 * 7, lds, np * 7, a.in_vec_ok != 0, true);
+    tile_load<T, TP>(a.x_in + n0 * 7, lds, np * 7, a.in_vec_ok != 0, true);
     __syncthreads();
-    const int p[2] = {(int)threadIdx.x, (int)threadIdx.x + CHX_BLOCK};
-    const bool on[2] = {p[0] < np, p[1] < np};
-    chx_v2f x[7];
+    int p[PP], lost[PP];
+    bool on[PP];
 #pragma unroll
-    for (int j = 0; j < 7; ++j) x[j] = chx_v2f{on[0] ? lds[p[0] * 7 + j] : 0.0f, on[1] ? lds[p[1] * 7 + j] : 0.0f};
-    int lost[2];                                                   // (a lane past the end of the beam: never alive)
+    for (int h = 0; h < PP; ++h) {
+        p[h] = (int)threadIdx.x + h * CHX_BLOCK;
+        on[h] = p[h] < np;
+    }
+    ring.load(lds, p, on);
 #pragma unroll
-    for (int h = 0; h < 2; ++h) lost[h] = on[h] ? a.lost_turn[n0 + p[h]] : -1;
-    float ax = __builtin_inff(), ay = __builtin_inff();
+    for (int h = 0; h < PP; ++h) lost[h] = on[h] ? a.lost_turn[n0 + p[h]] : -1;      // (a lane past the end of the beam: never alive)
+    T ax = (T)__builtin_inf(), ay = (T)__builtin_inf();
     if (a.aperture) { ax = a.aperture[0]; ay = a.aperture[1]; }
     int64_t next_record = a.next_record;
     int rec = 0;
     const int end_turn = a.first_turn + a.num_turns;
     for (int t = a.first_turn; t < end_turn; ++t) {
-        if (__any(lost[0] == 0 || lost[1] == 0)) {
-            for (int e = 0; e < a.E; ++e) {
-                const float* __restrict__ U = coef + (int64_t)e * kSoCoefStride;
-                const unsigned int scheme = reinterpret_cast<const unsigned int*>(U + 196)[2];
-                chx_v2f probe = chx_v2f{0.0f, 0.0f};                // (so_chain_kernel's rule for a non-finite particle)
+        bool alive = false;
 #pragma unroll
-                for (int j = 0; j < 7; ++j) probe = __builtin_elementwise_fma(chx_v2f{0.0f, 0.0f}, x[j], probe);
-                if (scheme == 0u) so_step_pattern<SoPatternQuad>(U, x, probe);
-                else if (scheme == 1u) so_step_pattern<SoPatternBend>(U, x, probe);
-                else if (scheme == 3u) so_step_linear(U, x);
-                else so_step_groups(U, x, probe);
-            }
+        for (int h = 0; h < PP; ++h) alive = alive || lost[h] == 0;
+        if (__any(alive)) {
+            ring.turn(t - a.first_turn);
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                float c[6];
+            for (int h = 0; h < PP; ++h) {
+                T c[6];
 #pragma unroll
-                for (int j = 0; j < 6; ++j) c[j] = h == 0 ? x[j].x : x[j].y;
-                if (so_turn_outside<float>(c, ax, ay) && lost[h] == 0) {
+                for (int j = 0; j < 6; ++j) c[j] = ring.get(h, j);
+                if (so_turn_outside<T>(c, ax, ay) && lost[h] == 0) {
                     lost[h] = t;
 #pragma unroll
-                    for (int j = 0; j < 7; ++j) lds[p[h] * 7 + j] = h == 0 ? x[j].x : x[j].y;    // frozen here
+                    for (int j = 0; j < 7; ++j) lds[p[h] * 7 + j] = ring.get(h, j);              // frozen here
                 }
             }
         }
         if (t == next_record) {
-            double w[2], xd[2][6];
-            bool live[2];
+            double w[PP], xd[PP][6];
+            bool live[PP];
 #pragma unroll
-            for (int h = 0; h < 2; ++h) {
+            for (int h = 0; h < PP; ++h) {
                 live[h] = lost[h] == 0;
                 const int64_t n = n0 + p[h];
                 w[h] = 1.0;
                 if (on[h] && a.charges) w[h] = (double)a.charges[n];
                 if (on[h] && a.survival) w[h] = w[h] * (double)a.survival[n];
 #pragma unroll
-                for (int j = 0; j < 6; ++j) xd[h][j] = (double)(h == 0 ? x[j].x : x[j].y);
+                for (int j = 0; j < 6; ++j) xd[h][j] = (double)ring.get(h, j);
                 if (n < a.K) {
-                    float* dst = a.probe + ((int64_t)rec * a.K + n) * 7;
+                    T* dst = a.probe + ((int64_t)rec * a.K + n) * 7;
 #pragma unroll
-                    for (int j = 0; j < 7; ++j) dst[j] = live[h] ? (h == 0 ? x[j].x : x[j].y) : lds[p[h] * 7 + j];
+                    for (int j = 0; j < 7; ++j) dst[j] = live[h] ? ring.get(h, j) : lds[p[h] * 7 + j];
                 }
             }
-            so_turn_record<2>(w, xd, live, red, a.partials + ((int64_t)rec * gridDim.x + blockIdx.x) * kSoTurnSums);
+            so_turn_record<PP>(w, xd, live, red, a.partials + ((int64_t)rec * gridDim.x + blockIdx.x) * kSoTurnSums);
             next_record += a.record_every;
             ++rec;
         }
     }
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < PP; ++h) {
         if (lost[h] == 0) {
 #pragma unroll
-            for (int j = 0; j < 7; ++j) lds[p[h] * 7 + j] = h == 0 ? x[j].x : x[j].y;
+            for (int j = 0; j < 7; ++j) lds[p[h] * 7 + j] = ring.get(h, j);
         }
         if (on[h]) a.lost_turn[n0 + p[h]] = lost[h];
     }
     __syncthreads();
-    tile_store<float, TP>(a.x_out + n0 * 7, lds, np * 7, a.out_vec_ok != 0, true);
+    tile_store<T, TP>(a.x_out + n0 * 7, lds, np * 7, a.out_vec_ok != 0, true);
 }
 
+// the float32 second-order ring: two particles per lane, rows p and p + CHX_BLOCK of a tile of 2 * CHX_BLOCK; a turn is so_items
+// over the one coefficient block
+struct SoRing {
+    const float* __restrict__ coef;
+    int E;
+    chx_v2f x[7];
+    __device__ __forceinline__ void load(const float* lds, const int (&p)[2], const bool (&on)[2]) {
+#pragma unroll
+        for (int j = 0; j < 7; ++j) x[j] = chx_v2f{on[0] ? lds[p[0] * 7 + j] : 0.0f, on[1] ? lds[p[1] * 7 + j] : 0.0f};
+    }
+    __device__ __forceinline__ float get(int h, int j) const { return h == 0 ? x[j].x : x[j].y; }
+    __device__ __forceinline__ void turn(int) { so_items<float, chx_v2f>(coef, E, x); }
+};
+
+// (coef is a kernel argument of its own, __restrict__: only then does the compiler know that the stores of the records cannot
+// touch the coefficients and fetch them through scalar loads as so_chain_kernel does — inside the argument block they came
+// through 130 vector loads per item loop, and the kernel took 1.7 us per item step at 1e6 particles instead of the chain's 1.3)
+__global__ __launch_bounds__(CHX_BLOCK) void so_turns_kernel(const float* __restrict__ coef, SoTurnsArgs<float> a) {
+    SoRing ring{coef, a.E};
+    turns_frame<float, 2>(ring, a);
+}
+
+// float64 beams: the frame's text written out, with the item loop in the kernel. On turns_frame this kernel kept its registers and
+// its waves per SIMD, but its item loop compiled to twelve more v_mul_f64 and it ran 1.3 to 1.8 % slower at 1e5 and 1e6 particles
+// (profiles/turn_frame.md). A change to the loss, record or probe rules of turns_frame is made here too.
 __global__ __launch_bounds__(CHX_BLOCK) void so_turns_kernel_f64(const double* __restrict__ coef, SoTurnsArgs<double> a) {
     constexpr int TP = CHX_BLOCK;
     __shared__ __attribute__((aligned(16))) double lds[TP * 7];
@@ -1640,10 +1693,10 @@ __global__ __launch_bounds__(CHX_BLOCK) void so_turns_kernel_f64(const double* _
                 double probe = 0.0;
 #pragma unroll
                 for (int j = 0; j < 7; ++j) probe = fma(0.0, x[j], probe);
-                if (scheme == 0u) so_step_pattern_f64<SoPatternQuad>(U, x, probe);
-                else if (scheme == 1u) so_step_pattern_f64<SoPatternBend>(U, x, probe);
-                else if (scheme == 3u) so_step_linear_f64(U, x);
-                else so_step_groups_f64(U, x, probe);
+                if (scheme == 0u) so_step_pattern<SoPatternQuad>(U, x, probe);
+                else if (scheme == 1u) so_step_pattern<SoPatternBend>(U, x, probe);
+                else if (scheme == 3u) so_step_linear(U, x);
+                else so_step_groups(U, x, probe);
             }
             double c[6];
 #pragma unroll
@@ -1721,8 +1774,8 @@ __global__ __launch_bounds__(CHX_BLOCK) void so_turns_reduce_kernel(const double
 //                               walk from their block's start energy to the energy in front of their item and leave the item's
 //                               constants (dkd_item_constants, the chain's own). One workgroup more adds up the path length.
 //   dkd_turns_kernel<MODE, BEND, SEXT>, dkd_turns_kernel_f64<BEND, SEXT>   a particle per lane; per turn the block's address (a scalar load),
-//                               the items through dkd_chain_step / dkd_map as in the chain, then the loss test, the freezing of a
-//                               lost row in the LDS tile, the record and the probe rows as in so_turns_kernel_f64.
+//                               the chain's item loop (dkd_items); the loss test, the freezing of a lost row in the LDS tile,
+//                               the record and the probe rows are turns_frame's.
 //   so_turns_reduce_kernel      as it is.
 template <typename T>
 __device__ __forceinline__ bool dkd_same_bits(T a, T b) {
@@ -1777,8 +1830,32 @@ __global__ void dkd_turns_constants_kernel(DkdChainArgs args, int E, int turns, 
     dkd_item_constants<T>(kind, fringe, steps, (const T*)args.params[e], Ee, mc2, nq, cst + ((int64_t)block * E + e) * kDkdCstStride);
 }
 
+// the drift-kick-drift ring (as built: float64 beams, MODE is not read): a particle per lane; a turn is dkd_items over the block of
+// constants of that turn (its address: a scalar load), which leaves 1 in the seventh column as every drift-kick-drift kernel does.
+// MODE, BEND, SEXT as in dkd_items
+template <int MODE, bool BEND, bool SEXT, typename T>
+struct DkdRing {
+    const double* __restrict__ cst;
+    const int32_t* __restrict__ block_of_turn;
+    int E;
+    double mc2;
+    T v[6], v6;                        // (six coordinates and the seventh column, kept apart as in dkd_items)
+    __device__ __forceinline__ void load(const T* lds, const int (&p)[1], const bool (&on)[1]) {
+        v6 = on[0] ? lds[p[0] * 7 + 6] : (T)1;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) v[j] = on[0] ? lds[p[0] * 7 + j] : (T)0;
+    }
+    __device__ __forceinline__ T get(int, int j) const { return j < 6 ? v[j] : v6; }
+    __device__ __forceinline__ void turn(int k) {
+        dkd_items<MODE, BEND, SEXT, false, T>(cst + (int64_t)block_of_turn[k] * E * kDkdCstStride, E, mc2, v, v6);
+    }
+};
+
 // (cst and block_of_turn are kernel arguments of their own, __restrict__: see so_turns_kernel — the stores of the records must not
 // be taken for stores into the constants, or these stop coming through scalar loads)
+// float32 beams: the frame's text and the item loop written out. On turns_frame with dkd_items every instantiation kept its waves
+// per SIMD, but the "storage" ring ran 1.7 to 2.4 % slower at 1e3 and 1e5 particles and the "mixed" and "double" rings 0.8 to 1.4 %
+// (profiles/turn_frame.md). A change to the rules of turns_frame or a new kind in dkd_items is made here too.
 template <int MODE, bool BEND, bool SEXT>
 __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel(const double* __restrict__ cst, const int32_t* __restrict__ block_of_turn,
                                                               double mc2, SoTurnsArgs<float> a) {
@@ -1850,79 +1927,12 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel(const double* __re
     tile_store<float, TP>(a.x_out + n0 * 7, lds, np * 7, a.out_vec_ok != 0, true);
 }
 
-// float64 beams: the map in fp64 like dkd_chain_kernel_f64
+// float64 beams: turns_frame with the DkdRing policy
 template <bool BEND, bool SEXT>
 __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel_f64(const double* __restrict__ cst, const int32_t* __restrict__ block_of_turn,
                                                                   double mc2, SoTurnsArgs<double> a) {
-    constexpr int TP = CHX_BLOCK;
-    __shared__ __attribute__((aligned(16))) double lds[TP * 7];
-    __shared__ double red[4 * kSoTurnSums];
-    const int64_t n0 = (int64_t)blockIdx.x * TP;
-    const int np = (int)((a.N - n0 < TP) ? (a.N - n0) : TP);
-    tile_load<double, TP>(a.x_in + n0 * 7, lds, np * 7, a.in_vec_ok != 0, true);
-    __syncthreads();
-    const int p = threadIdx.x;
-    const bool on = p < np;
-    double v[6], v6 = on ? lds[p * 7 + 6] : 1.0;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) v[j] = on ? lds[p * 7 + j] : 0.0;
-    int lost = on ? a.lost_turn[n0 + p] : -1;
-    double ax = __builtin_inf(), ay = __builtin_inf();
-    if (a.aperture) { ax = a.aperture[0]; ay = a.aperture[1]; }
-    int64_t next_record = a.next_record;
-    int rec = 0;
-    const int end_turn = a.first_turn + a.num_turns;
-    for (int t = a.first_turn; t < end_turn; ++t) {
-        if (__any(lost == 0)) {
-            const double* __restrict__ turn_cst = cst + (int64_t)block_of_turn[t - a.first_turn] * a.E * kDkdCstStride;
-            for (int e = 0; e < a.E; ++e) {
-                const double* __restrict__ c = turn_cst + (int64_t)e * kDkdCstStride;
-                const int32_t* w = reinterpret_cast<const int32_t*>(c + kDkdMeta);
-                const int kind = w[0], steps = w[1];
-                double out[6];
-                if (kind == CHX_DKD_DRIFT) dkd_map<CHX_DKD_DRIFT, double>(c, v, mc2, steps, out);
-                else if (SEXT && kind == CHX_DKD_SEXTUPOLE) dkd_map<CHX_DKD_SEXTUPOLE, double>(c, v, mc2, steps, out);
-                else if (!BEND || kind == CHX_DKD_QUADRUPOLE) dkd_map<CHX_DKD_QUADRUPOLE, double>(c, v, mc2, steps, out);
-                else dkd_map<CHX_DKD_DIPOLE, double>(c, v, mc2, steps, out);
-#pragma unroll
-                for (int j = 0; j < 6; ++j) v[j] = out[j];
-            }
-            v6 = 1.0;
-            if (so_turn_outside<double>(v, ax, ay) && lost == 0) {
-                lost = t;
-#pragma unroll
-                for (int j = 0; j < 6; ++j) lds[p * 7 + j] = v[j];                                  // frozen here
-                lds[p * 7 + 6] = v6;
-            }
-        }
-        if (t == next_record) {
-            double w[1], xd[1][6];
-            const bool live[1] = {lost == 0};
-            const int64_t n = n0 + p;
-            w[0] = 1.0;
-            if (on && a.charges) w[0] = a.charges[n];
-            if (on && a.survival) w[0] = w[0] * a.survival[n];
-#pragma unroll
-            for (int j = 0; j < 6; ++j) xd[0][j] = v[j];
-            if (n < a.K) {
-                double* dst = a.probe + ((int64_t)rec * a.K + n) * 7;
-#pragma unroll
-                for (int j = 0; j < 6; ++j) dst[j] = live[0] ? v[j] : lds[p * 7 + j];
-                dst[6] = live[0] ? v6 : lds[p * 7 + 6];
-            }
-            so_turn_record<1>(w, xd, live, red, a.partials + ((int64_t)rec * gridDim.x + blockIdx.x) * kSoTurnSums);
-            next_record += a.record_every;
-            ++rec;
-        }
-    }
-    if (lost == 0) {
-#pragma unroll
-        for (int j = 0; j < 6; ++j) lds[p * 7 + j] = v[j];
-        lds[p * 7 + 6] = v6;
-    }
-    if (on) a.lost_turn[n0 + p] = lost;
-    __syncthreads();
-    tile_store<double, TP>(a.x_out + n0 * 7, lds, np * 7, a.out_vec_ok != 0, true);
+    DkdRing<0, BEND, SEXT, double> ring{cst, block_of_turn, a.E, mc2};
+    turns_frame<double, 1>(ring, a);
 }
 
 }  // namespace
@@ -2014,50 +2024,97 @@ extern "C" int chx_second_order_chain_mixed(const void* const* T_maps, const int
     return CHX_OK;
 }
 
-// The run above as a RING: turns [first_turn, first_turn + num_turns) of it in one particle launch (so_turns_kernel,
-// so_turns_kernel_f64), with the loss flags, the record sums and the probe rows of the recorded turns (see the kernels).
+// ---- the host side of the two ring entry points (chx_second_order_turns, chx_dkd_turns): what both check and launch -------------
 namespace {
+// the arguments the two entry points share, and what turns_call_ok derives from them
+struct TurnsCall {
+    const void *x_in, *charges, *survival, *aperture;
+    void* x_out;
+    int32_t* lost_turn;
+    double* sums;
+    void* probe;
+    int64_t N, K, first_turn, num_turns, record_every;
+    int64_t rec0, records;             // records in front of this chunk, records of this chunk
+};
+
+// the turn and record ranges. lost_turn holds turn numbers as int32, and the kernels count to first_turn + num_turns in int: the
+// last turn stays below INT_MAX. Fills rec0 and records.
+bool turns_call_ok(TurnsCall& c) {
+    if (c.first_turn < 1 || c.num_turns < 1 || c.record_every < 1 || c.K < 0 || c.K > c.N) return false;
+    if (c.first_turn >= 0x7fffffffLL || c.num_turns >= 0x7fffffffLL || c.first_turn + c.num_turns - 1 >= 0x7fffffffLL ||
+        c.record_every > 0x7fffffffLL)
+        return false;
+    c.rec0 = (c.first_turn - 1) / c.record_every;
+    c.records = (c.first_turn + c.num_turns - 1) / c.record_every - c.rec0;             // (at most num_turns: a grid size)
+    return !(c.records > 0 && (!c.sums || (c.K > 0 && !c.probe)));
+}
+
+// aliasing: no output may share an address with another output or with an input, except outs[i] == ins[i] for i < same_ok
+// (null pointers are absent arguments)
+bool turns_no_alias(std::initializer_list<const void*> outs, std::initializer_list<const void*> ins, size_t same_ok) {
+    for (size_t i = 0; i < outs.size(); ++i) {
+        const void* o = outs.begin()[i];
+        if (!o) continue;
+        for (size_t j = i + 1; j < outs.size(); ++j)
+            if (o == outs.begin()[j]) return false;
+        for (size_t j = 0; j < ins.size(); ++j)
+            if (o == ins.begin()[j] && !(i == j && i < same_ok)) return false;
+    }
+    return true;
+}
+
+template <typename T>
+SoTurnsArgs<T> turns_args(const TurnsCall& c, int E, void* partials) {
+    SoTurnsArgs<T> a;
+    a.x_in = (const T*)c.x_in;
+    a.x_out = (T*)c.x_out;
+    a.charges = (const T*)c.charges;
+    a.survival = (const T*)c.survival;
+    a.aperture = (const T*)c.aperture;
+    a.lost_turn = c.lost_turn;
+    a.partials = (double*)partials;
+    a.probe = c.K > 0 && c.records > 0 ? (T*)c.probe + c.rec0 * c.K * 7 : nullptr;
+    a.N = c.N;
+    a.K = c.K;
+    a.E = E;
+    a.first_turn = (int)c.first_turn;
+    a.num_turns = (int)c.num_turns;
+    a.next_record = (c.rec0 + 1) * c.record_every;
+    a.record_every = c.record_every;
+    a.in_vec_ok = (int)chx_aligned16(c.x_in);
+    a.out_vec_ok = (int)chx_aligned16(c.x_out);
+    return a;
+}
+
+// sums[record][14] of this chunk's records from partials[record][tiles][14]
+int turns_reduce(const TurnsCall& c, const double* partials, int64_t tiles, hipStream_t s) {
+    if (c.records > 0) {
+        hipLaunchKernelGGL(so_turns_reduce_kernel, dim3((unsigned)c.records), dim3(CHX_BLOCK), 0, s, partials, tiles,
+                           c.sums + c.rec0 * kSoTurnSums);
+        CHX_CHECK_LAUNCH();
+    }
+    return CHX_OK;
+}
+
+// A run of second-order elements as a RING: turns [first_turn, first_turn + num_turns) of it in one particle launch (so_turns_kernel,
+// so_turns_kernel_f64), with the loss flags, the record sums and the probe rows of the recorded turns (see turns_frame).
 int64_t so_turns_tiles(int64_t N, int dtype) {
     const int per_tile = dtype == CHX_F32 ? 2 * CHX_BLOCK : CHX_BLOCK;
     return (N + per_tile - 1) / per_tile;
 }
 size_t so_turns_coef_bytes(int64_t E, int dtype) { return (size_t)E * kSoCoefStride * (dtype == CHX_F32 ? 4 : 8); }
 template <typename T>
-int so_turns_launch(const SoChainPtrs& maps, int E, const void* x_in, const void* charges, const void* survival, int64_t N,
-                    int first_turn, int num_turns, int64_t record_every, int64_t records, int64_t rec0, const void* aperture, int64_t K,
-                    void* x_out, int32_t* lost_turn, double* sums, void* probe, const void* s_in, void* s_out, void* workspace,
-                    int64_t tiles, size_t coef_bytes, hipStream_t s) {
+int so_turns_launch(const SoChainPtrs& maps, int E, const TurnsCall& c, const void* s_in, void* s_out, void* workspace, int64_t tiles,
+                    size_t coef_bytes, hipStream_t s) {
     T* coef = (T*)workspace;
     hipLaunchKernelGGL(so_chain_coeff_kernel<T>, dim3((unsigned)(E + (s_out ? 1 : 0))), dim3(CHX_BLOCK), 0, s, maps, E, coef, (const T*)s_in,
                        (T*)s_out);
     CHX_CHECK_LAUNCH();
-    SoTurnsArgs<T> a;
-    a.x_in = (const T*)x_in;
-    a.x_out = (T*)x_out;
-    a.charges = (const T*)charges;
-    a.survival = (const T*)survival;
-    a.aperture = (const T*)aperture;
-    a.lost_turn = lost_turn;
-    a.partials = (double*)((char*)workspace + coef_bytes);
-    a.probe = K > 0 && records > 0 ? (T*)probe + rec0 * K * 7 : nullptr;
-    a.N = N;
-    a.K = K;
-    a.E = E;
-    a.first_turn = first_turn;
-    a.num_turns = num_turns;
-    a.next_record = (rec0 + 1) * record_every;
-    a.record_every = record_every;
-    a.in_vec_ok = (int)chx_aligned16(x_in);
-    a.out_vec_ok = (int)chx_aligned16(x_out);
+    const SoTurnsArgs<T> a = turns_args<T>(c, E, (char*)workspace + coef_bytes);
     if constexpr (sizeof(T) == 4) hipLaunchKernelGGL(so_turns_kernel, dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const float*)coef, a);
     else hipLaunchKernelGGL(so_turns_kernel_f64, dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const double*)coef, a);
     CHX_CHECK_LAUNCH();
-    if (records > 0) {
-        hipLaunchKernelGGL(so_turns_reduce_kernel, dim3((unsigned)records), dim3(CHX_BLOCK), 0, s, (const double*)a.partials, tiles,
-                           sums + rec0 * kSoTurnSums);
-        CHX_CHECK_LAUNCH();
-    }
-    return CHX_OK;
+    return turns_reduce(c, a.partials, tiles, s);
 }
 }  // namespace
 
@@ -2073,30 +2130,16 @@ extern "C" int chx_second_order_turns(const void* const* T_maps, const int32_t* 
                                       void* workspace, size_t workspace_bytes, void* stream) {
     if (dtype != CHX_F32 && dtype != CHX_F64) return CHX_ERR_DTYPE;
     if (!T_maps || E < 1 || E > kSoChainMax || !x_in || !x_out || !lost_turn || !workspace || N < 1) return CHX_ERR_INVALID_ARG;
-    if (first_turn < 1 || num_turns < 1 || record_every < 1 || K < 0 || K > N) return CHX_ERR_INVALID_ARG;
-    // lost_turn holds turn numbers as int32, and the kernels count to first_turn + num_turns in int: the last turn stays below INT_MAX
-    if (first_turn >= 0x7fffffffLL || num_turns >= 0x7fffffffLL || first_turn + num_turns - 1 >= 0x7fffffffLL || record_every > 0x7fffffffLL)
-        return CHX_ERR_INVALID_ARG;
+    TurnsCall c{x_in, charges, survival, aperture, x_out, lost_turn, sums, probe, N, K, first_turn, num_turns, record_every, 0, 0};
+    if (!turns_call_ok(c)) return CHX_ERR_INVALID_ARG;
     if ((s_in == nullptr) != (s_out == nullptr) || (s_out && !lengths)) return CHX_ERR_INVALID_ARG;
-    const int64_t rec0 = (first_turn - 1) / record_every;                           // records in front of this chunk
-    const int64_t records = (first_turn + num_turns - 1) / record_every - rec0;
-    if (records > 0 && (!sums || (K > 0 && !probe))) return CHX_ERR_INVALID_ARG;
-    if (workspace_bytes < chx_second_order_turns_workspace_bytes(E, N, records, dtype) || !chx_aligned16(workspace)) return CHX_ERR_INVALID_ARG;
+    if (workspace_bytes < chx_second_order_turns_workspace_bytes(E, N, c.records, dtype) || !chx_aligned16(workspace)) return CHX_ERR_INVALID_ARG;
     // aliasing: the first chunk reads a beam it must not write (x_out != x_in), later chunks run in place on x_out; nothing else
     // may share an address
     if (first_turn == 1 && x_in == x_out) return CHX_ERR_INVALID_ARG;
-    const void* outs[] = {x_out, lost_turn, sums, probe, workspace, s_out};
-    const void* ins[] = {x_in, charges, survival, aperture, s_in};
-    constexpr size_t n_outs = sizeof(outs) / sizeof(outs[0]), n_ins = sizeof(ins) / sizeof(ins[0]);
-    for (size_t i = 0; i < n_outs; ++i) {
-        if (!outs[i]) continue;
-        for (size_t j = i + 1; j < n_outs; ++j)
-            if (outs[i] == outs[j]) return CHX_ERR_INVALID_ARG;
-        for (size_t j = 0; j < n_ins; ++j)
-            if (outs[i] == ins[j] && !(i == 0 && j == 0)) return CHX_ERR_INVALID_ARG;
-    }
+    if (!turns_no_alias({x_out, lost_turn, sums, probe, workspace, s_out}, {x_in, charges, survival, aperture, s_in}, 1)) return CHX_ERR_INVALID_ARG;
     const int64_t tiles = so_turns_tiles(N, dtype);
-    if (tiles > 0x7fffffffLL || records > 0x7fffffffLL) return CHX_ERR_INVALID_ARG;
+    if (tiles > 0x7fffffffLL) return CHX_ERR_INVALID_ARG;
     SoChainPtrs maps;
     for (int e = 0; e < kSoChainMax; ++e) {
         maps.T[e] = e < E ? T_maps[e] : nullptr;
@@ -2105,13 +2148,8 @@ extern "C" int chx_second_order_turns(const void* const* T_maps, const int32_t* 
         if (e < E && (!maps.T[e] || (s_out && !maps.length[e]))) return CHX_ERR_INVALID_ARG;
     }
     const size_t coef_bytes = so_turns_coef_bytes(E, dtype);
-    if (dtype == CHX_F32)
-        return so_turns_launch<float>(maps, (int)E, x_in, charges, survival, N, (int)first_turn, (int)num_turns, record_every, records,
-                                      rec0, aperture, K, x_out, lost_turn, sums, probe, s_in, s_out, workspace, tiles, coef_bytes,
-                                      (hipStream_t)stream);
-    return so_turns_launch<double>(maps, (int)E, x_in, charges, survival, N, (int)first_turn, (int)num_turns, record_every, records,
-                                   rec0, aperture, K, x_out, lost_turn, sums, probe, s_in, s_out, workspace, tiles, coef_bytes,
-                                   (hipStream_t)stream);
+    if (dtype == CHX_F32) return so_turns_launch<float>(maps, (int)E, c, s_in, s_out, workspace, tiles, coef_bytes, (hipStream_t)stream);
+    return so_turns_launch<double>(maps, (int)E, c, s_in, s_out, workspace, tiles, coef_bytes, (hipStream_t)stream);
 }
 
 // A ring of Drifts, Quadrupoles, Dipoles and Sextupoles tracked drift-kick-drift: turns [first_turn, first_turn + num_turns) in one particle
@@ -2132,11 +2170,10 @@ DkdTurnsLayout dkd_turns_layout(int64_t E, int64_t N, int64_t turns, int64_t rec
     return l;
 }
 template <typename T>
-int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, bool sext, int mode, const void* x_in, const void* energy_in, void* energy_out,
-                     double mass_eV, double n_charges, const void* charges, const void* survival, int64_t N, int first_turn,
-                     int num_turns, int64_t record_every, int64_t records, int64_t rec0, const void* aperture, int64_t K, void* x_out,
-                     int32_t* lost_turn, double* sums, void* probe, const void* s_in, void* s_out, void* workspace,
+int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, bool sext, int mode, const TurnsCall& c, const void* energy_in,
+                     void* energy_out, double mass_eV, double n_charges, const void* s_in, void* s_out, void* workspace,
                      const DkdTurnsLayout& l, int64_t tiles, hipStream_t s) {
+    const int num_turns = (int)c.num_turns;
     T* start = (T*)workspace;
     int32_t* block_of_turn = (int32_t*)((char*)workspace + l.blocks);
     double* cst = (double*)((char*)workspace + l.cst);
@@ -2146,33 +2183,16 @@ int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, bool sext, int
     hipLaunchKernelGGL(dkd_turns_constants_kernel<T>, dim3((unsigned)((int64_t)num_turns * E + (s_out ? 1 : 0))), dim3(64), 0, s, items, E,
                        num_turns, (const T*)start, (const int32_t*)block_of_turn, mass_eV, n_charges, cst, (const T*)s_in, (T*)s_out);
     CHX_CHECK_LAUNCH();
-    SoTurnsArgs<T> a;
-    a.x_in = (const T*)x_in;
-    a.x_out = (T*)x_out;
-    a.charges = (const T*)charges;
-    a.survival = (const T*)survival;
-    a.aperture = (const T*)aperture;
-    a.lost_turn = lost_turn;
-    a.partials = (double*)((char*)workspace + l.partials);
-    a.probe = K > 0 && records > 0 ? (T*)probe + rec0 * K * 7 : nullptr;
-    a.N = N;
-    a.K = K;
-    a.E = E;
-    a.first_turn = first_turn;
-    a.num_turns = num_turns;
-    a.next_record = (rec0 + 1) * record_every;
-    a.record_every = record_every;
-    a.in_vec_ok = (int)chx_aligned16(x_in);
-    a.out_vec_ok = (int)chx_aligned16(x_out);
+    const SoTurnsArgs<T> a = turns_args<T>(c, E, (char*)workspace + l.partials);
     const dim3 grid((unsigned)tiles), wg(CHX_BLOCK);
-    const double* c = cst;
+    const double* k = cst;
     const int32_t* b = block_of_turn;
 #define CHX_DKD_TURNS_KINDS(K, ...)                                                                                               \
     do {                                                                                                                          \
-        if (bend && sext) hipLaunchKernelGGL((K<__VA_ARGS__ true, true>), grid, wg, 0, s, c, b, mass_eV, a);                         \
-        else if (bend) hipLaunchKernelGGL((K<__VA_ARGS__ true, false>), grid, wg, 0, s, c, b, mass_eV, a);                           \
-        else if (sext) hipLaunchKernelGGL((K<__VA_ARGS__ false, true>), grid, wg, 0, s, c, b, mass_eV, a);                           \
-        else hipLaunchKernelGGL((K<__VA_ARGS__ false, false>), grid, wg, 0, s, c, b, mass_eV, a);                                    \
+        if (bend && sext) hipLaunchKernelGGL((K<__VA_ARGS__ true, true>), grid, wg, 0, s, k, b, mass_eV, a);                         \
+        else if (bend) hipLaunchKernelGGL((K<__VA_ARGS__ true, false>), grid, wg, 0, s, k, b, mass_eV, a);                           \
+        else if (sext) hipLaunchKernelGGL((K<__VA_ARGS__ false, true>), grid, wg, 0, s, k, b, mass_eV, a);                           \
+        else hipLaunchKernelGGL((K<__VA_ARGS__ false, false>), grid, wg, 0, s, k, b, mass_eV, a);                                    \
     } while (0)
     if constexpr (sizeof(T) == 8) {
         CHX_DKD_TURNS_KINDS(dkd_turns_kernel_f64, );
@@ -2183,12 +2203,7 @@ int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, bool sext, int
     }
 #undef CHX_DKD_TURNS_KINDS
     CHX_CHECK_LAUNCH();
-    if (records > 0) {
-        hipLaunchKernelGGL(so_turns_reduce_kernel, dim3((unsigned)records), dim3(CHX_BLOCK), 0, s, (const double*)a.partials, tiles,
-                           sums + rec0 * kSoTurnSums);
-        CHX_CHECK_LAUNCH();
-    }
-    return CHX_OK;
+    return turns_reduce(c, a.partials, tiles, s);
 }
 }  // namespace
 
@@ -2210,10 +2225,8 @@ extern "C" int chx_dkd_turns(const int32_t* kinds, const void* const* params, co
         !lost_turn || !workspace || N < 1)
         return CHX_ERR_INVALID_ARG;
     if (storage_precision < 0 || storage_precision > 2) return CHX_ERR_INVALID_ARG;
-    if (first_turn < 1 || num_turns < 1 || record_every < 1 || K < 0 || K > N) return CHX_ERR_INVALID_ARG;
-    // lost_turn holds turn numbers as int32, and the kernels count to first_turn + num_turns in int: the last turn stays below INT_MAX
-    if (first_turn >= 0x7fffffffLL || num_turns >= 0x7fffffffLL || first_turn + num_turns - 1 >= 0x7fffffffLL || record_every > 0x7fffffffLL)
-        return CHX_ERR_INVALID_ARG;
+    TurnsCall c{x_in, charges, survival, aperture, x_out, lost_turn, sums, probe, N, K, first_turn, num_turns, record_every, 0, 0};
+    if (!turns_call_ok(c)) return CHX_ERR_INVALID_ARG;
     if ((s_in == nullptr) != (s_out == nullptr)) return CHX_ERR_INVALID_ARG;
     bool bend = false, sext = false;
     for (int64_t e = 0; e < E; ++e) {
@@ -2223,26 +2236,15 @@ extern "C" int chx_dkd_turns(const int32_t* kinds, const void* const* params, co
         bend = bend || kinds[e] == CHX_DKD_DIPOLE;
         sext = sext || kinds[e] == CHX_DKD_SEXTUPOLE;
     }
-    const int64_t rec0 = (first_turn - 1) / record_every;                           // records in front of this chunk
-    const int64_t records = (first_turn + num_turns - 1) / record_every - rec0;
-    if (records > 0 && (!sums || (K > 0 && !probe))) return CHX_ERR_INVALID_ARG;
     const int64_t tiles = (N + CHX_BLOCK - 1) / CHX_BLOCK;
     if (tiles > 0x7fffffffLL || num_turns * E >= 0x7fffffffLL) return CHX_ERR_INVALID_ARG;             // (grid sizes)
-    const DkdTurnsLayout l = dkd_turns_layout(E, N, num_turns, records, dtype);
+    const DkdTurnsLayout l = dkd_turns_layout(E, N, num_turns, c.records, dtype);
     if (workspace_bytes < l.total || !chx_aligned16(workspace)) return CHX_ERR_INVALID_ARG;
     // aliasing: the first chunk reads a beam it must not write (x_out != x_in), later chunks run in place on x_out; energy_out may
     // be energy_in (the chunks of a call hand the energy on through one device scalar); nothing else may share an address
     if (first_turn == 1 && x_in == x_out) return CHX_ERR_INVALID_ARG;
-    const void* outs[] = {x_out, energy_out, lost_turn, sums, probe, workspace, s_out};
-    const void* ins[] = {x_in, energy_in, charges, survival, aperture, s_in};
-    constexpr size_t n_outs = sizeof(outs) / sizeof(outs[0]), n_ins = sizeof(ins) / sizeof(ins[0]);
-    for (size_t i = 0; i < n_outs; ++i) {
-        if (!outs[i]) continue;
-        for (size_t j = i + 1; j < n_outs; ++j)
-            if (outs[i] == outs[j]) return CHX_ERR_INVALID_ARG;
-        for (size_t j = 0; j < n_ins; ++j)
-            if (outs[i] == ins[j] && !(i == 0 && j == 0) && !(i == 1 && j == 1)) return CHX_ERR_INVALID_ARG;
-    }
+    if (!turns_no_alias({x_out, energy_out, lost_turn, sums, probe, workspace, s_out}, {x_in, energy_in, charges, survival, aperture, s_in}, 2))
+        return CHX_ERR_INVALID_ARG;
     DkdChainArgs items;
     for (int e = 0; e < kDkdChainMax; ++e) {
         items.params[e] = e < E ? params[e] : nullptr;
@@ -2250,12 +2252,10 @@ extern "C" int chx_dkd_turns(const int32_t* kinds, const void* const* params, co
         items.meta[e] = e < E ? (kinds[e] | (fringe_at[e] << 4) | (num_steps[e] << 6)) : 0;
     }
     if (dtype == CHX_F32)
-        return dkd_turns_launch<float>(items, (int)E, bend, sext, storage_precision, x_in, energy_in, energy_out, mass_eV, n_charges, charges,
-                                       survival, N, (int)first_turn, (int)num_turns, record_every, records, rec0, aperture, K, x_out,
-                                       lost_turn, sums, probe, s_in, s_out, workspace, l, tiles, (hipStream_t)stream);
-    return dkd_turns_launch<double>(items, (int)E, bend, sext, 0, x_in, energy_in, energy_out, mass_eV, n_charges, charges, survival, N,
-                                    (int)first_turn, (int)num_turns, record_every, records, rec0, aperture, K, x_out, lost_turn, sums,
-                                    probe, s_in, s_out, workspace, l, tiles, (hipStream_t)stream);
+        return dkd_turns_launch<float>(items, (int)E, bend, sext, storage_precision, c, energy_in, energy_out, mass_eV, n_charges, s_in,
+                                       s_out, workspace, l, tiles, (hipStream_t)stream);
+    return dkd_turns_launch<double>(items, (int)E, bend, sext, 0, c, energy_in, energy_out, mass_eV, n_charges, s_in, s_out, workspace, l,
+                                    tiles, (hipStream_t)stream);
 }
 
 namespace {

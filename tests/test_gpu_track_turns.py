@@ -196,6 +196,24 @@ def test_losses(dt, bad_row):
     assert np.array_equal(ring.track_turns(beam, TURNS, aperture=aperture, fused=True).lost_turn.cpu().numpy(), lost_half)
 
 
+@pytest.mark.parametrize("dt", DTYPES, ids=["f32", "f64"])
+def test_probe_rows_beyond_the_first_256_and_of_frozen_particles(dt):
+    """record_first = 600: the probe rows of a float32 lane's second particle (rows 256 - 511 of the first tile), of the second
+    tile, and of the float64 kernel's second and third tile, some of them lost and frozen — the fused ring against the turn-by-turn
+    path, bit for bit."""
+    ring, beam = make_ring(dt), make_beam(dt, BIG)
+    aperture = torch.tensor(APERTURE, **_kw(dt))
+    general = ring.track_turns(beam, TURNS, record_every=5, aperture=aperture, record_first=600, fused=False)
+    fused = ring.track_turns(beam, TURNS, record_every=5, aperture=aperture, record_first=600, fused=True)
+    lost = general.lost_turn.cpu().numpy()
+    recorded = general.turns.cpu().numpy()
+    assert general.particles.shape == (len(recorded), 600, 7) and len(recorded) == TURNS // 5
+    frozen = (lost[:600] > 0) & (lost[:600] <= recorded.max())               # recorded at least once after its loss
+    assert frozen.any() and frozen[256:].any()
+    assert np.array_equal(fused.lost_turn.cpu().numpy(), lost)
+    assert same_bits(fused.particles, general.particles)
+
+
 # ---- 4. chunking, 5. determinism ----------------------------------------------------------------------------------------------------------
 def outputs(tbt):
     return [tbt.outgoing.particles, tbt.outgoing.survival_probabilities, tbt.outgoing.s, tbt.lost_turn, tbt.turns, tbt.sums, tbt.particles]

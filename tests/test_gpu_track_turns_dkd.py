@@ -307,6 +307,23 @@ def test_losses(precision, dt, ring_kind):
         check_records(tbt, ref, lost, 5, 3)                  # (row 1 of the probe: frozen at turn 1)
 
 
+@pytest.mark.parametrize("precision,dt", MODES, ids=MODE_IDS)
+def test_probe_rows_of_the_second_tile_and_of_frozen_particles(precision, dt):
+    """record_first = 300: probe rows of the second tile (rows 256 - 299), some of the 300 lost and frozen — the fused ring against
+    the turn-by-turn path, bit for bit and NaN for NaN, in every arithmetic mode."""
+    aperture = loss_aperture(loop_reference(dt, "A", precision, BIG, BAD_ROWS), dt)
+    ring, beam = make_ring(dt, "A", precision), make_beam(dt, BIG, BAD_ROWS)
+    general = ring.track_turns(beam, TURNS, record_every=5, aperture=aperture, record_first=300, fused=False)
+    fused = ring.track_turns(beam, TURNS, record_every=5, aperture=aperture, record_first=300, fused=True)
+    lost = general.lost_turn.cpu().numpy()
+    recorded = general.turns.cpu().numpy()
+    assert general.particles.shape == (len(recorded), 300, 7) and len(recorded) == TURNS // 5
+    frozen = (lost[:300] > 0) & (lost[:300] <= recorded.max())               # recorded at least once after its loss
+    assert frozen.any() and frozen[256:].any()
+    assert np.array_equal(fused.lost_turn.cpu().numpy(), lost)
+    assert same_bits_nan_for_nan(fused.particles, general.particles.cpu().numpy())
+
+
 # ---- 5. chunking ---------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("precision,dt", DTYPE_MODES, ids=DTYPE_IDS)
 @pytest.mark.parametrize("record_every", [1, 5])
