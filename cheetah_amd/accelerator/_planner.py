@@ -23,6 +23,7 @@ import torch
 
 from .. import _ops
 from ..particles.particle_beam import ParticleBeam
+from . import _stretch
 from .space_charge_kick import SpaceChargeKick
 
 
@@ -69,11 +70,11 @@ def _launch_chain(seg, plan, i, kind, item, incoming, state):
 
 # ---- [run | active Cavity | BPM | Aperture | Screen]+ : the stretch call (chx_lattice_track*) --------------------------------------
 def _wants_stretch(seg, plan, i, kind, item, incoming, state) -> bool:
-    return len(plan) - i >= 2 and (kind == "run" or item._is_cavity or item._is_bpm or item._is_aperture or item._is_screen)
+    return len(plan) - i >= 2 and _stretch.joins(kind, item)
 
 
 def _launch_stretch(seg, plan, i, kind, item, incoming, state):
-    return seg._lattice_stretch(plan, i, incoming)
+    return seg._lattice_stretch(plan, i, incoming)      # (through the method: accelerator/_stretch.py track_particles, or a test's stand-in)
 
 
 # ---- a linear run in front of non-linear elements rides in their pass ------------------------------------------------------------------

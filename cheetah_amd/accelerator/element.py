@@ -79,7 +79,7 @@ class Element(nn.Module):
     #: reference (element.py:63-65) — e.g. a Marker does not "support" the linear method, it has none to choose from
     #: libchx map-builder kind (include/chx.h `chx_kind`); None for elements with explicit maps
     _chx_kind: int | None = None
-    _is_cavity = False            # Cavity: may join a stretch of `chx_lattice_track` (Segment._lattice_stretch)
+    _is_cavity = False            # Cavity: may join a stretch of `chx_lattice_track` (accelerator/_stretch.py)
     _is_bpm = False               # BPM (when active): likewise, as an item that reads the beam and lets it pass
     _is_aperture = False          # Aperture (when active): likewise, as an item that thins the survival probabilities
     _is_screen = False            # Screen (when active): likewise, as an item that records the beam (and its image) and lets it pass

@@ -24,7 +24,7 @@ class Screen(Element):
     _is_screen = True
 
     #: beams of at most this many particles get their cloud-in-cell image deposited by the stretch call that tracks them
-    #: (`Segment._lattice_stretch`: no further launch, and `reading` has nothing left to do); larger beams are recorded only and the
+    #: (`_stretch.track_particles`: no further launch, and `reading` has nothing left to do); larger beams are recorded only and the
     #: image is formed when it is asked for — the deposit's atomics then cost more than the launch they save
     _EAGER_IMAGE_PARTICLES = 262_144
 

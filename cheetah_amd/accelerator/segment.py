@@ -4,7 +4,9 @@
 (`chx_compose_maps`, fp64 accumulation) and applied in one pass over the particles; otherwise the
 element list is partitioned into maximal skippable runs (each composed and applied once) and the
 non-skippable elements (active Cavity / Screen / SpaceChargeKick / BPM / Aperture) are tracked one by
-one.
+one. Here: the container, the planner cache, the per-run map products and the fused launchers. The plan classes live in `_plans.py`,
+the ParticleBeam dispatch table in `_planner.py`, the stretch call ([run | Cavity | BPM | Aperture | Screen]+ as one call of the
+host step) in `_stretch.py`: `Segment._lattice_stretch*` only forward there.
 
 Host-side cost matters here (the merged pass is a ~10 us kernel), so unlike the reference
  * no nn.Module sub-segments are built per call (segment.py:558-569);
@@ -29,7 +31,6 @@ import collections
 import ctypes
 import numbers
 import os
-import weakref
 from copy import deepcopy
 
 import torch
@@ -39,7 +40,7 @@ from .. import _lib, _ops
 from ..particles.parameter_beam import ParameterBeam
 from ..particles.particle_beam import ParticleBeam
 from ..particles.species import Species
-from . import _planner
+from . import _planner, _stretch
 from ._plans import _IDENTITY, _FastRun, _LatticePlan, _Run  # noqa: F401  (the plan classes; tests reach them through this module)
 from .element import Element, tracking_call
 from .space_charge_kick import SpaceChargeKick
@@ -257,32 +258,6 @@ class Segment(Element):
             self.__dict__.pop("_lattice_store", None)
         store[key] = (plan, dynamic)
         return plan
-
-    @staticmethod
-    def _lead_at(lead_in, acc, energy_shape) -> tuple:
-        """Batch shape of a beam at a point of a stretch: what it came in with, spread over the vectorised settings in front of
-        that point (`acc`) and over the beam energies once a map was applied."""
-        # (plain tuples, right-aligned: `torch.broadcast_shapes` costs ~6 us a call, and a lattice has a monitor per cell)
-        out = tuple(lead_in)
-        for other in (acc, tuple(energy_shape)):
-            if not other or other == out:
-                continue
-            a, b = ((1,) * (len(other) - len(out)) + out, tuple(other)) if len(other) > len(out) else (out, (1,) * (len(out) - len(other)) + tuple(other))
-            out = tuple(x if y == 1 else y for x, y in zip(a, b))
-        return out
-
-    def _lattice_cache_for(self, plan):
-        """The stretch plans of `plan` (one table per partition of the lattice that `_plan` keeps)."""
-        store = self.__dict__.get("_lattice_store")
-        if store is None:
-            store = self.__dict__["_lattice_store"] = {}
-        cache = store.get(id(plan))
-        if cache is None or cache[0] is not plan:
-            if len(store) >= 8:
-                store.clear()
-            cache = store[id(plan)] = (plan, {})
-        self.__dict__["_lattice_cache"] = cache
-        return cache
 
     # ---- per-run products ------------------------------------------------------------------------------
     @staticmethod
@@ -723,7 +698,7 @@ class Segment(Element):
             while i < n_items:
                 kind, item = plan[i]
                 i += 1
-                if (kind == "run" or item._is_cavity or item._is_bpm or item._is_screen) and n_items - i >= 1:
+                if n_items - i >= 1 and _stretch.joins(kind, item, apertures=False):      # (an aperture does not start a stretch of moments)
                     done = self._lattice_stretch_parameter(plan, i - 1, incoming)
                     if done is not None:
                         incoming, i = done
@@ -750,375 +725,12 @@ class Segment(Element):
         # chain, the stretch call, runs ahead of / made of non-linear elements, the merged run, kick + run, the element's own track)
         return _planner.walk_particles(self, self._plan(), incoming)
 
+    # the stretch call (accelerator/_stretch.py) behind the two methods every caller goes through: a stand-in for either is honoured
     def _lattice_stretch(self, plan, i: int, incoming: ParticleBeam, allow_screens: bool = True):
-        """plan[i] and the items behind it as ONE `chx_lattice_track` call when they form a stretch [run | active Cavity]+ (at
-        least two items, at least one cavity) of scalar settings and the beam is one plain beam without a graph: (outgoing beam,
-        index behind the stretch), else None. Same numbers, bit for bit, as the walk item by item."""
-        cache = self.__dict__.get("_lattice_cache")
-        if cache is None or cache[0] is not plan:
-            cache = self._lattice_cache_for(plan)
-        p = incoming.particles
-        e = incoming.energy
-        # one energy: active Screens are items of the stretch too (their record and image come from the same two launches) — for one
-        # plain beam and for a vectorised one (B beams under the one lattice setting: every record and image holds B of them). Where
-        # the screens' host step does not apply after all (vectorised settings, charges per beam, ...) the stretch is taken again
-        # without them: it then ends in front of the first screen (`allow_screens` False)
-        with_screens = allow_screens and Segment._STRETCH_SCREENS and p.dim() >= 2 and e.dim() == 0
-        key = (i, p.dtype, p.device, with_screens)
-        entry = cache[1].get(key)
-        if entry is None:
-            j, cavities = i, 0
-            while j < len(plan) and (plan[j][0] == "run" or plan[j][1]._is_cavity or plan[j][1]._is_bpm or plan[j][1]._is_aperture
-                                     or (with_screens and plan[j][1]._is_screen)):
-                cavities += plan[j][0] != "run"          # (cavities, active BPMs, apertures, screens: what makes a stretch worth one call)
-                j += 1
-            entry = cache[1][key] = False if (j - i < 2 or cavities == 0 or not p.is_cuda) else [j, None]
-        if entry is False:
-            return None
-        if p.dim() < 2 or not p.is_cuda or (p.dim() > 2 and not p.is_contiguous()):
-            return None                    # (B beams in one ParticleBeam: blockIdx.y of the particle pass)
-        s_in, sp = incoming.s, incoming.species
-        if e.dtype != p.dtype or e.device != p.device or (e.dim() != 0 and not e.is_contiguous()):
-            return None
-        energy_rows = e.dim() != 0          # a scan of beam energies: row b of the maps is built for energy b
-        lp = entry[1]
-        if lp is None or lp.epoch != Element._epoch:
-            if torch.cuda.is_current_stream_capturing():
-                return None     # (the table's upload is not part of a recording: the walk item by item is capturable as it is)
-            if lp is None:
-                lp = entry[1] = _LatticePlan(plan[i:entry[0]], p.dtype, p.device, allow_vector=True, allow_screens=with_screens)
-            else:
-                lp.refresh()
-        if lp.edge_keys:
-            # a histogram screen's bin edges sit in the table as arrays formed from its pixel size: an in-place edit of that tensor
-            # moves no epoch — re-derive the stretch (the cloud-in-cell extent is derived on the device and follows by itself)
-            for screen, ps, version in lp.edge_keys:
-                if ps._version != version:
-                    if torch.cuda.is_current_stream_capturing():
-                        return None
-                    lp.patch = None
-                    lp.refresh()
-                    break
-        if not lp.ok:
-            return None
-        if _CHECK_PLANS:
-            lp.verify()
-        grad_run = None
-        if torch.is_grad_enabled() and (p.requires_grad or e.requires_grad or sp.mass_eV.requires_grad
-                                        or sp.num_elementary_charges.requires_grad or _any_requires_grad(*lp.tensors)):
-            # gradients: [run of scalar settings | one active Screen] on a beam without a graph is ONE differentiable node
-            # (cheetah_amd._chxtorch RunScreenTrack); anything else takes the general differentiable path
-            grad_run = self._stretch_grad_run(lp, incoming)
-            if grad_run is None:
-                return None
-        x = p if p.is_contiguous() and p.data_ptr() % 16 == 0 else _ops.aligned(p)
-        _ops.check_current_device(lp.device)
-        on_device = s_in.dim() == 0 and s_in.dtype == p.dtype and s_in.device == p.device and not s_in.requires_grad
-        if lp.bpms or lp.screens:
-            from .. import sharding
-
-            if sharding.active_group() is not None:
-                return None            # a particle-sharded beam: the monitors read GLOBAL means (BPM._track_internal exchanges them),
-                #                        a screen sums its image over the ranks
-        w_out = incoming.survival_probabilities
-        lead_x, N = tuple(p.shape[:-2]), p.shape[-2]
-        lead, Bm = lead_x, 1
-        if lp.vshape is not None or energy_rows:
-            # settings vectorised over a scan of the lattice (and / or a scan of beam energies): row b of the outgoing beams = the
-            # beam (ONE shared beam, or its own row b) through row b of the settings at energy b — the preparation launch forms
-            # the maps of every row, the particle pass picks its row's by blockIdx.y
-            try:
-                lead = tuple(torch.broadcast_shapes(lead_x, lp.vshape if lp.vshape is not None else (), e.shape))
-            except RuntimeError:
-                return None
-            if (lp.vshape is not None and tuple(lp.vshape) != lead) or (energy_rows and tuple(e.shape) != lead) \
-                    or (_ops.numel(lead_x) != 1 and lead_x != lead):
-                return None
-            Bm = _ops.numel(lead)
-            if Bm > 1 and not lp.small_runs and Bm > Segment._STRETCH_MAX_ROWS:
-                return None       # (a workgroup per (item, row) prepares a stretch with runs of more than 64 elements: beyond a few hundred rows the walk)
-            if not lp.ensure_rows(Bm):
-                return None
-        B, Bx = _ops.numel(lead), _ops.numel(lead_x)
-        if B < 1 or B > 65535:
-            return None
-        flags = lp.small_runs | (2 if energy_rows else 0) | (4 if lp.e_out_rows else 0)
-        if lp.expanded:
-            Segment._refresh_expanded(lp.expanded)
-        w_lead = tuple(incoming.survival_probabilities.shape[:-1])
-        if lp.screens:
-            # [run | cavity | monitor | aperture | active Screen]+ on one plain beam: the C++ host step (cheetah_amd._chxtorch)
-            # allocates the outgoing beam, every screen's record and image and enqueues the two launches
-            q, w = incoming.particle_charges, incoming.survival_probabilities
-            if Bm != 1 or not on_device or q.shape != (N,) or (w.shape != (N,) and tuple(w.shape) != lead + (N,)) or q.dtype != p.dtype \
-                    or w.dtype != p.dtype or q.device != p.device or w.device != p.device or not q.is_contiguous() or not w.is_contiguous() \
-                    or (torch.is_grad_enabled() and (q.requires_grad or w.requires_grad)) or (lead and grad_run is not None) \
-                    or (lead and any(scr.method != "cloud-in-cell" for scr in lp.screens)):      # (screen.py:292-294: the others refuse vectorised beams)
-                # (settings, charges or weights the screens' host step does not take: the stretch without its screens)
-                return self._lattice_stretch(plan, i, incoming, allow_screens=False)
-            if grad_run is not None:
-                run, fr = grad_run
-                out, rows, C, q_at, w_at, e_at, s_at, sums, maps = _TORCH_HOST.run_screen_track(
-                    lp.capsule_s, x, e, s_in, q, w, fr.distinct, fr.grad_meta, sp.mass_eV_float, sp.num_elementary_charges_float)
-                x1, origin = x.reshape(1, N, 7), _ops._origin(p)
-                # the recorded survival probabilities are the incoming ones (no aperture in a [run | Screen] stretch): tagged as
-                # their copy, so that the incoming beam's memoised moments are found again on the next step of a loop; the one-pass
-                # sums of the recorded rows ride on the rows (a beam property of them: one small launch, _ops.moment_entry)
-                _ops.mark_copy_of(w_at, w)
-                rows._chx_partials = (sums, rows._version, w_at,
-                                      (C, e, fr.distinct, fr.grad_meta, sp.mass_eV_float, sp.num_elementary_charges_float, maps))
-                out._chx_lin = _ops._LinearSource(origin, x1, C, (), out._version)
-                lp.screens[0]._record_stretch((rows, q_at, w_at, e_at, s_at, x1, C, origin), N, sp, None, "particles_grad")
-                return ParticleBeam(out, e, particle_charges=q, survival_probabilities=w, s=self._run_s(run, s_in), species=sp), i + lp.count
-            for ap in lp.apertures:
-                ap._check_limits()
-            n_bpm = len(lp.bpms)
-            readings = ws = None
-            ws_bytes = 0
-            if n_bpm:
-                readings = torch.empty((n_bpm, B, 2), dtype=p.dtype, device=p.device)
-                ws_bytes = _lib.lib().chx_lattice_diag_workspace_bytes(N, B, n_bpm)
-                ws = _ops.workspace(ws_bytes, p.device)
-            if lp.apertures:
-                w_out = torch.empty(lead + (N,), dtype=p.dtype, device=p.device)
-            from .screen import Screen
-
-            # (a vectorised beam goes in as (B, N, 7): the beams of a (2, 3, N, 7) array one behind the other)
-            out, e_out, s_out, records, images = _TORCH_HOST.lattice_track_screens(
-                lp.capsule_s, x.reshape(B, N, 7) if lead else x, e, s_in, q, w, sp.mass_eV_float, sp.num_elementary_charges_float,
-                lp.device.index, Screen._EAGER_IMAGE_PARTICLES, w_out if lp.apertures else None, n_bpm, readings, ws, ws_bytes)
-            for k, bpm in enumerate(lp.bpms):
-                bpm.__dict__["_buffers"]["reading"] = readings[k].reshape(lead + (2,))
-            for screen, record, image in zip(lp.screens, records, images):
-                if lead and image is not None:
-                    image = image.reshape(lead + tuple(image.shape[-2:]))
-                screen._record_stretch(record, N, sp, image, lead=lead)
-            return ParticleBeam(out.reshape(p.shape) if lead else out, e_out, particle_charges=q, survival_probabilities=w_out, s=s_out,
-                                species=sp), i + lp.count
-        if lp.bpms or lp.apertures or lead:
-            # active BPMs / apertures in the stretch (chx_lattice_track_diag): the particle pass leaves the weighted sums of x and
-            # y at every monitor (one more launch forms all readings) and thins the survival probabilities at every aperture —
-            # three launches for the lattice instead of six per monitor and a stop per aperture
-            w = None
-            if lp.bpms or lp.apertures:
-                w = incoming.survival_probabilities
-                if w.dtype != p.dtype or w.device != p.device or (torch.is_grad_enabled() and w.requires_grad) \
-                        or w.shape[-1] != N or w.dim() > len(lead) + 1:
-                    return None
-                Bw = B
-                if w.numel() == N and B > 1:
-                    w, Bw = w.reshape(N), 1             # one row of weights for all beams: read as it is, not spread over the rows
-                elif tuple(w.shape) != lead + (N,):
-                    try:
-                        w = w.expand(*lead, N)
-                    except RuntimeError:
-                        return None
-                if not w.is_contiguous():
-                    w = w.contiguous()
-            for ap in lp.apertures:
-                ap._check_limits()           # (aperture.py:72-73; a host read once per value of the two limits)
-            n_bpm = len(lp.bpms)
-            readings = ws = None
-            ws_bytes = 0
-            if n_bpm:
-                readings = torch.empty((n_bpm, B, 2), dtype=p.dtype, device=p.device)
-                ws_bytes = _lib.lib().chx_lattice_diag_workspace_bytes(N, B, n_bpm)
-                ws = _ops.workspace(ws_bytes, p.device)
-            if lp.apertures:
-                w_out = torch.empty((*lead, N), dtype=p.dtype, device=p.device)
-            out = None if lead == lead_x else torch.empty((*lead, N, 7), dtype=p.dtype, device=p.device)
-            out, e_out, s_out = _HOST.lattice_track(lp.capsule, x, N, e, s_in if on_device else None, sp.mass_eV_float,
-                                                    sp.num_elementary_charges_float, lp.device.index, w,
-                                                    w_out if lp.apertures else None, n_bpm, readings, ws, ws_bytes, B,
-                                                    Bx, Bm, Bw if w is not None else B, flags, out,
-                                                    torch.empty(lead, dtype=p.dtype, device=p.device) if (lp.e_out_rows and not energy_rows) else None)
-            if lp.e_out_rows and not energy_rows:
-                here = self._lead_at(e.shape, lp.e_acc, ())
-                if here != lead:                 # (only some axes of a grid scan reach the cavities' voltages and phases)
-                    from .cavity import _narrow_to
-
-                    e_out = _narrow_to(e_out, here)
-            for k, bpm in enumerate(lp.bpms):
-                r = readings[k].reshape(*lead, 2)
-                if lead != lead_x:
-                    # the beam AT the monitor is spread over the settings in front of it only (and over the energies once a map was
-                    # applied): equal rows beyond that, the reading has the shape the walk's has — (2,) in front of the scan,
-                    # (8, 1, 2) behind the first axis of a grid scan
-                    here = lead if lp.bpm_acc[k] == lead else self._lead_at(lead_x, lp.bpm_acc[k], e.shape if (energy_rows and lp.bpm_after[k]) else ())
-                    if here != lead:
-                        from .cavity import _narrow_to
-
-                        r = _narrow_to(r, (*here, 2))
-                bpm.__dict__["_buffers"]["reading"] = r
-            if lp.apertures and lead != lead_x:
-                here = self._lead_at(torch.broadcast_shapes(lead_x, w_lead), lp.ap_acc[-1], e.shape if (energy_rows and lp.ap_after[-1]) else ())
-                if here != lead:
-                    from .cavity import _narrow_to
-
-                    w_out = _narrow_to(w_out, (*here, N))     # (the beam at the LAST aperture is not spread over the whole scan yet)
-        else:
-            out, e_out, s_out = _HOST.lattice_track(lp.capsule, x, x.shape[0], e, s_in if on_device else None, sp.mass_eV_float,
-                                                    sp.num_elementary_charges_float, lp.device.index)
-        if s_out is None:
-            s_out = s_in
-            for kind, item in lp.items[:lp.count]:
-                if kind == "run" or item._is_cavity:           # (monitors and apertures have no length)
-                    s_out = s_out + (self._run_length(item) if kind == "run" else item.length)
-        return ParticleBeam(out, e_out, particle_charges=incoming.particle_charges,
-                            survival_probabilities=w_out, s=s_out, species=sp), i + lp.count
-
-    @staticmethod
-    def _stretch_grad_run(lp, incoming: ParticleBeam):
-        """(run, its differentiable plan) when the stretch `lp` is [run of scalar settings | one active Screen] and the only
-        things that carry a graph are settings of the run (a beam, an energy, a species or a screen geometry with a graph: None)."""
-        p, e, sp = incoming.particles, incoming.energy, incoming.species
-        if p.requires_grad or e.requires_grad or sp.mass_eV.requires_grad or sp.num_elementary_charges.requires_grad:
-            return None
-        if lp.count != 2 or len(lp.screens) != 1 or lp.bpms or lp.apertures or lp.vshape is not None or lp.items[0][0] != "run" \
-                or lp.items[1][1] is not lp.screens[0] or p.dim() != 2 or e.dim() != 0:
-            return None
-        b = lp.screens[0].__dict__["_buffers"]
-        if b["misalignment"].requires_grad or b["pixel_size"].requires_grad:
-            return None
-        run = lp.items[0][1]
-        fr = run.gfast
-        if fr is None or fr.dtype != p.dtype or fr.device != p.device:
-            fr = run.gfast = _FastRun(run, p.dtype, p.device, allow_grad=True)
-        elif fr.epoch != Element._epoch:
-            fr.refresh()
-        if not fr.ok or fr.grad_meta is None or fr.E != lp.shape[1]:
-            return None
-        if _CHECK_PLANS:
-            fr.verify()
-        return run, fr
+        return _stretch.track_particles(self, plan, i, incoming, allow_screens)
 
     def _lattice_stretch_parameter(self, plan, i: int, incoming: ParameterBeam):
-        """The stretch of `_lattice_stretch` for a ParameterBeam (`chx_parameter_lattice_track`: the same preparation launch, then
-        one wavefront per batch row walks the items): (outgoing beam, index behind the stretch) or None. The walk item by item
-        costs ~80-160 us of host time per cavity / monitor cell for 49 numbers of beam state."""
-        mu, cov = incoming.mu, incoming.cov
-        if not mu.is_cuda or cov.dtype != mu.dtype or cov.device != mu.device:
-            return None
-        cache = self.__dict__.get("_lattice_cache")
-        if cache is None or cache[0] is not plan:
-            cache = self._lattice_cache_for(plan)
-        e = incoming.energy
-        with_screens = Segment._STRETCH_SCREENS and mu.dim() == 1 and cov.dim() == 2 and e.dim() == 0       # (one beam: active Screens are items of the stretch)
-        key = (i, mu.dtype, mu.device, "moments", with_screens)
-        entry = cache[1].get(key)
-        if entry is None:
-            j, special = i, 0
-            while j < len(plan) and (plan[j][0] == "run" or plan[j][1]._is_cavity or plan[j][1]._is_bpm or plan[j][1]._is_aperture
-                                     or (with_screens and plan[j][1]._is_screen)):
-                special += plan[j][0] != "run"
-                j += 1
-            entry = cache[1][key] = False if (j - i < 2 or special == 0) else [j, None]
-        if entry is False:
-            return None
-        s_in, sp = incoming.s, incoming.species
-        if e.dtype != mu.dtype or e.device != mu.device or (e.dim() != 0 and not e.is_contiguous()):
-            return None
-        energy_rows = e.dim() != 0          # a scan of beam energies: row b of the maps is built for energy b
-        lp = entry[1]
-        if lp is None or lp.epoch != Element._epoch:
-            if torch.cuda.is_current_stream_capturing():
-                return None
-            if lp is None:
-                lp = entry[1] = _LatticePlan(plan[i:entry[0]], mu.dtype, mu.device, allow_vector=True, allow_screens=with_screens)
-            else:
-                lp.refresh()
-        if not lp.ok or lp.apertures:                # (an aperture only warns for a ParameterBeam: the walk does that)
-            return None
-        if _CHECK_PLANS:
-            lp.verify()
-        if torch.is_grad_enabled() and (mu.requires_grad or cov.requires_grad or e.requires_grad or sp.mass_eV.requires_grad
-                                        or sp.num_elementary_charges.requires_grad or _any_requires_grad(*lp.tensors)):
-            return None
-        if lp.screens:
-            # one ParameterBeam through [run | cavity | monitor | active Screen]+: the C++ host step allocates the outgoing moments,
-            # every screen's record and its image (the bivariate normal density, screen.py:255-291) and enqueues the launches
-            q = incoming.total_charge
-            on_device = s_in.dim() == 0 and s_in.dtype == mu.dtype and s_in.device == mu.device and not s_in.requires_grad
-            if not on_device or not mu.is_contiguous() or not cov.is_contiguous() or q.dim() != 0 or q.dtype != mu.dtype \
-                    or q.device != mu.device or e.dtype != mu.dtype or e.device != mu.device \
-                    or (torch.is_grad_enabled() and q.requires_grad):
-                return None
-            _ops.check_current_device(lp.device)
-            geoms = []
-            for screen in lp.screens:
-                nx, ny = screen._geometry("sample_counts")
-                geoms.append((screen._geometry("gauss_geom"), screen.__dict__["_buffers"]["misalignment"], nx, ny))
-            n_bpm = len(lp.bpms)
-            readings = torch.empty((n_bpm, 1, 2), dtype=mu.dtype, device=mu.device) if n_bpm else None
-            mu_out, cov_out, e_out, s_out, records, images = _TORCH_HOST.parameter_lattice_track_screens(
-                lp.capsule_s, mu, cov, e, s_in, q, sp.mass_eV_float, sp.num_elementary_charges_float, lp.device.index, tuple(geoms),
-                n_bpm, readings)
-            for k, bpm in enumerate(lp.bpms):
-                bpm.__dict__["_buffers"]["reading"] = readings[k].reshape(2)
-            for screen, record, image in zip(lp.screens, records, images):
-                screen._record_stretch(record, 0, sp, image, "moments")
-            return ParameterBeam(mu_out, cov_out, e_out, total_charge=q, s=s_out, species=sp), i + lp.count
-        try:
-            lead = torch.broadcast_shapes(mu.shape[:-1], cov.shape[:-2], lp.vshape if lp.vshape is not None else (), e.shape)
-        except RuntimeError:
-            return None
-        B = _ops.numel(lead)
-        if (lp.vshape is not None and tuple(lp.vshape) != tuple(lead)) or (energy_rows and tuple(e.shape) != tuple(lead)):
-            return None
-        Bm = B if (lp.vshape is not None or energy_rows) else 1
-        if Bm > 1 and not lp.small_runs and Bm > Segment._STRETCH_MAX_ROWS:
-            return None
-        if Bm > 1 and not lp.ensure_rows(Bm):
-            return None
-        if lp.expanded:
-            Segment._refresh_expanded(lp.expanded)
-        m2 = mu.reshape(-1, 7) if mu.is_contiguous() else mu.reshape(-1, 7).contiguous()
-        c2 = cov.reshape(-1, 49) if cov.is_contiguous() else cov.reshape(-1, 49).contiguous()
-        if m2.shape[0] not in (1, B) or c2.shape[0] not in (1, B):
-            return None
-        _ops.check_current_device(lp.device)
-        on_device = s_in.dim() == 0 and s_in.dtype == mu.dtype and s_in.device == mu.device and not s_in.requires_grad
-        mu_out = torch.empty((*lead, 7), dtype=mu.dtype, device=mu.device)
-        cov_out = torch.empty((*lead, 7, 7), dtype=mu.dtype, device=mu.device)
-        e_out = torch.empty(tuple(lead), dtype=e.dtype, device=e.device) if (lp.e_out_rows and not energy_rows) else torch.empty_like(e)
-        s_out = torch.empty_like(s_in) if on_device else None
-        n_bpm = len(lp.bpms)
-        readings = torch.empty((n_bpm, B, 2), dtype=mu.dtype, device=mu.device) if n_bpm else None
-        n_items, n_elems, n_ptrs = lp.shape
-        _ops.check(_lib.lib().chx_parameter_lattice_track(
-            lp.table.data_ptr(), n_items, n_elems, n_ptrs, e.data_ptr(), sp.mass_eV_float, sp.num_elementary_charges_float, lp.code,
-            lp.state.data_ptr(), lp.state.numel() * 8, m2.data_ptr(), c2.data_ptr(), B, m2.shape[0], c2.shape[0], Bm,
-            lp.small_runs | (2 if energy_rows else 0) | (4 if lp.e_out_rows else 0),
-            mu_out.data_ptr(),
-            cov_out.data_ptr(), e_out.data_ptr(), s_in.data_ptr() if on_device else None, s_out.data_ptr() if on_device else None,
-            n_bpm, readings.data_ptr() if n_bpm else None, _ops.stream_ptr()), "chx_parameter_lattice_track")
-        in_lead = tuple(torch.broadcast_shapes(mu.shape[:-1], cov.shape[:-2])) if (mu.dim() > 1 or cov.dim() > 2) else ()
-        lead_t = tuple(lead)
-        if lp.e_out_rows and not energy_rows:
-            here = self._lead_at(e.shape, lp.e_acc, ())
-            if here != tuple(lead):
-                from .cavity import _narrow_to
-
-                e_out = _narrow_to(e_out, here)
-        for k, bpm in enumerate(lp.bpms):
-            r = readings[k].reshape(*lead, 2)
-            if in_lead == lead_t or lp.bpm_acc[k] == lead_t:
-                bpm.__dict__["_buffers"]["reading"] = r         # (nothing to narrow: the usual case, no shape arithmetic per monitor)
-                continue
-            here = self._lead_at(in_lead, lp.bpm_acc[k], e.shape if (energy_rows and lp.bpm_after[k]) else ())
-            if here != lead_t:
-                # the beam at the monitor is spread over the settings in FRONT of it only: equal rows beyond that, the reading has
-                # the shape the walk's has
-                from .cavity import _narrow_to
-
-                r = _narrow_to(r, (*here, 2))
-            bpm.__dict__["_buffers"]["reading"] = r
-        if s_out is None:
-            s_out = s_in
-            for kind, item in lp.items[:lp.count]:
-                if kind == "run" or item._is_cavity:
-                    s_out = s_out + (self._run_length(item) if kind == "run" else item.length)
-        return ParameterBeam(mu_out, cov_out, e_out, total_charge=incoming.total_charge, s=s_out, species=sp), i + lp.count
+        return _stretch.track_parameter(self, plan, i, incoming)
 
     @staticmethod
     def _identity_run(run) -> bool:
