@@ -1063,10 +1063,14 @@ def _moments_raw(x, w, B, N, entry=None):
     launches) -> (moments, entries)."""
     lib = _lib.lib()
     if B > MAX_GRID_ROWS and N > 2048:     # (short rows: one wave per row, the rows are blockIdx.x)
-        # more vector rows than one launch takes (the batch index is a grid dimension of 65 535): row slices, one call each
+        # more vector rows than one launch takes (the batch index is a grid dimension of 65 535): row slices, one call each.
+        # Slices of EQUAL size (>= 32 768 rows each): every one runs one workgroup per row, so a row's sums are taken in the same
+        # order whichever slice it falls into — a short last slice would spread its rows over several workgroups (other bits)
+        n_slices = -(-B // MAX_GRID_ROWS)
+        step = -(-B // n_slices)
         outs = []
-        for b0 in range(0, B, MAX_GRID_ROWS):
-            b1 = min(B, b0 + MAX_GRID_ROWS)
+        for b0 in range(0, B, step):
+            b1 = min(B, b0 + step)
             outs.append(_moments_raw(x if x.shape[0] == 1 else x[b0:b1], w if w is None or w.shape[0] == 1 else w[b0:b1],
                                      b1 - b0, N, entry))
         if entry is None:

@@ -582,8 +582,8 @@ __global__ void track_moments_finalize_kernel(const double* __restrict__ partial
 }
 
 // ---- one-pass moments (chx_moments): same statistics as the two-pass pair above from ONE sweep over the particles.
-// Second moments are accumulated about c = the first particle of the row (a point of the distribution, so
-// |mean - c| is a few sigma at most and sum w d d^T does not cancel), then re-centred exactly:
+// Second moments are accumulated about c = first_wave_centre below, the weighted mean of the row's first 16 particles (a point
+// inside the distribution, so |mean - c| is a fraction of a sigma and sum w d d^T does not cancel), then re-centred exactly:
 //   mu = c + s / W,  M = m - s s^T / W,  cov = M / (W - W2 / W).
 struct OnePassFn {
     double c[6];
@@ -706,6 +706,11 @@ __global__ __launch_bounds__(CHX_BLOCK) void moments_onepass_kernel(const T* __r
 // moments_reduce_finalize_kernel on lanes 0..28 — in one launch without partial sums. The workgroup form above holds 29
 // accumulators and eight rows per lane (~200 VGPRs: two workgroups per CU) and needs eight rounds of workgroups plus a second
 // launch for 4096 rows: 47 + 6 us against ~10 us here. Same statistics, the fp64 sums in another order.
+// The divisor W - W2 / W is formed WITHOUT its cancellation: W^2 - W2 is twice the sum of w_n w_m over the pairs n < m, all terms
+// positive (one fma per particle on the lane's weights so far, the lanes merged with their cross products), so W - W2 / W =
+// 2 pairs / W to a few ulp. A row of two particles with weights 1 : 100 lost two digits of its covariances in the difference.
+// (Its two registers take the kernel from 124 to 131 VGPRs, three waves per SIMD instead of four: float32 rows 27.5 -> 31.3 us
+// for 4096 x 1000, float64 rows unchanged — profiles/moments_paths.md.)
 constexpr int kRowWaveUnroll = 4;
 template <typename T>
 __global__ __launch_bounds__(CHX_BLOCK) void moments_rows_wave_kernel(const T* __restrict__ x, const T* __restrict__ w, int64_t B,
@@ -721,6 +726,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void moments_rows_wave_kernel(const T* _
     double acc[kTM];
 #pragma unroll
     for (int k = 0; k < kTM; ++k) acc[k] = 0.0;
+    double pairs = 0.0;                                    // sum of w_n w_m over the pairs n < m of this lane's particles
     bool have_c = false;
     for (int64_t nb = 0; nb < N; nb += U * 64) {
         T r[U][7];
@@ -745,8 +751,26 @@ __global__ __launch_bounds__(CHX_BLOCK) void moments_rows_wave_kernel(const T* _
             double xv[7];
 #pragma unroll
             for (int j = 0; j < 7; ++j) xv[j] = (double)r[u][j];
+            pairs = fma(wv[u], acc[0], pairs);             // (acc[0]: the lane's weights before this particle)
             f.accumulate(xv, wv[u], nb + lane + u * 64, acc);
         }
+    }
+    {
+        // two sets of particles merge as pairs = pairs_a + pairs_b + W_a W_b: a butterfly over the 64 lanes, every lane ends with the row's
+        // (the lane pairing of chx_wave_sum: four DPP steps inside a row of 16 lanes, two ds_bpermute steps across the rows; the two
+        // sides of a step compute the same bits, so the lanes of a merged group stay equal, which the mirror steps rely on)
+        double sw = acc[0];
+        auto step = [&](auto get) {
+            const double so = get(sw), po = get(pairs);
+            pairs = fma(sw, so, pairs + po);
+            sw += so;
+        };
+        step([](double v) { return chx_dpp_get<0xB1>(v); });    // quad_perm [1,0,3,2]
+        step([](double v) { return chx_dpp_get<0x4E>(v); });    // quad_perm [2,3,0,1]
+        step([](double v) { return chx_dpp_get<0x141>(v); });   // row_half_mirror
+        step([](double v) { return chx_dpp_get<0x140>(v); });   // row_mirror
+        step([](double v) { return __shfl_xor(v, 16, 64); });
+        step([](double v) { return __shfl_xor(v, 32, 64); });
     }
 #pragma unroll
     for (int k = 0; k < kTM; ++k) acc[k] = chx_wave_sum(acc[k]);
@@ -776,7 +800,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void moments_rows_wave_kernel(const T* _
         else if (k < 8) v = ck + tk / W;
         else {
             const double mi = si / W, mj = sj / W;
-            v = (tk - W * mi * mj) / (W - W2 / W);
+            v = (tk - W * mi * mj) / ((2.0 * pairs) / W);
         }
         out[b * CHX_MOM_NOUT + k] = v;
         if (k == entry) entry_out[b] = (T)(entry_sqrt ? sqrt(v) : v);
@@ -845,7 +869,7 @@ __global__ __launch_bounds__(TH) void moments_reduce_finalize_kernel(const doubl
 // ---- beam sizes for the space-charge grid (chx_sc_beam_geometry): the three variances SpaceChargeKick needs
 // (space_charge_kick.py:531-538: sigma_x, sigma_y, sigma_tau) with 8 accumulators instead of the 29 of chx_moments, and the
 // reduce / finalize step folded into the geometry kernel — two launches per kick instead of three, a third of the registers.
-constexpr int kSG = 8;   // W, W2, s_x, s_y, s_tau, m_xx, m_yy, m_tautau (shifted about the row's first particle)
+constexpr int kSG = 8;   // W, W2, s_x, s_y, s_tau, m_xx, m_yy, m_tautau (shifted about first_wave_centre of the row)
 struct SigmaFn {
     double c[3];
     __device__ __forceinline__ void accumulate(const double (&x)[7], double w, int64_t, double (&a)[kSG]) {
@@ -870,10 +894,13 @@ __global__ __launch_bounds__(CHX_BLOCK) void sc_sigma_kernel(const T* __restrict
     // header.parity ^ header.scatter_now (the flip itself happens in the geometry kernel behind this one)
     if (tile_hdr && ((tile_hdr[0] ^ tile_hdr[1]) & 1)) w += N;
     SigmaFn f;
-    const T* x0 = x + ((Bx == 1) ? 0 : (int64_t)blockIdx.y) * N * 7;
-    f.c[0] = (double)x0[0];
-    f.c[1] = (double)x0[2];
-    f.c[2] = (double)x0[4];
+    // the centre of chx_moments: a particle 0 that is dead and far away must not become the shift point of the sums
+    double c6[6];
+    first_wave_centre<T>(x + ((Bx == 1) ? 0 : (int64_t)blockIdx.y) * N * 7, w ? w + ((Bw == 1) ? 0 : (int64_t)blockIdx.y) * N : nullptr,
+                         N, c6);
+    f.c[0] = c6[0];
+    f.c[1] = c6[2];
+    f.c[2] = c6[4];
     // partials[b][k][blk]
     tiled_reduce<T, kSG, SigmaFn, true>(x, w, Bx, Bw, N, f, partials + (int64_t)blockIdx.y * kSG * gridDim.x + blockIdx.x,
                                         gridDim.x);

@@ -2,7 +2,7 @@
 """Beam statistics of beams that are hard on a ONE-PASS moment sum -> tests/golden/moment_outliers.npz.
 
 The reference's weighted statistics are two-pass (utils/statistics.py:30-48: mean first, then the centred sum); the device sums
-sum w d d^T about a provisional centre in one sweep (chx_moments_fused: the weighted mean of the row's first 64 particles) and
+sum w d d^T about a provisional centre in one sweep (chx_moments: the weighted mean of the row's first 16 particles) and
 re-centres exactly. Cases that would break a careless centre:
   dead_outlier_slot0      particle 0 sits 1e8 sigma away and has survival probability 0
   alive_outlier_slot0     particle 0 sits 1e5 sigma away and counts
