@@ -1595,3 +1595,5 @@ from ._ops_laser import *  # noqa: E402,F401,F403
 from ._ops_quiet import *  # noqa: E402,F401,F403
 # ... and the seeded density modulation (ParticleBeam.with_density_modulation) in _ops_density.py
 from ._ops_density import *  # noqa: E402,F401,F403
+# ... and the tunes from turn-by-turn records (TurnByTurn.tunes) in _ops_tunes.py
+from ._ops_tunes import *  # noqa: E402,F401,F403

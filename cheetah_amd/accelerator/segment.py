@@ -1019,7 +1019,7 @@ class Segment(Element):
         s_out = incoming.s + num_turns * (s_one - incoming.s)
         beam = ParticleBeam(out, energy, particle_charges=incoming.particle_charges,
                             survival_probabilities=incoming.survival_probabilities * (lost == 0), s=s_out, species=incoming.species)
-        return _turns.TurnByTurn(beam, lost, _turns.recorded_turns(num_turns, record_every, dev), sums, probe)
+        return _turns.TurnByTurn(beam, lost, _turns.recorded_turns(num_turns, record_every, dev), sums, probe, record_every=record_every)
 
     def _track_turns_general(self, incoming, num_turns, record_every, aperture, record_first, _turns):
         x = incoming.particles
@@ -1049,7 +1049,8 @@ class Segment(Element):
         sums = torch.stack(sums) if sums else torch.empty((0, *lead, _turns.NUM_SUMS), dtype=torch.float64, device=dev)
         if record_first:
             probe = torch.stack(probe) if probe else torch.empty((0, *lead, record_first, 7), dtype=x.dtype, device=dev)
-        return _turns.TurnByTurn(beam, lost, _turns.recorded_turns(num_turns, record_every, dev), sums, probe if record_first else None)
+        return _turns.TurnByTurn(beam, lost, _turns.recorded_turns(num_turns, record_every, dev), sums, probe if record_first else None,
+                                 record_every=record_every)
 
     @staticmethod
     def _stable_energy(ent: dict, energy: torch.Tensor, mass: float, e_out: torch.Tensor) -> torch.Tensor:

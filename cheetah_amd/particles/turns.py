@@ -2,7 +2,14 @@
 sums and the general path's torch restatement) and the planner that splits the turns into launches."""
 from __future__ import annotations
 
+from collections import namedtuple
+
 import torch
+
+#: what `TurnByTurn.tunes` returns: both (..., record_first, len(planes)) float64
+Tunes = namedtuple("Tunes", ["tune", "amplitude"])
+#: what `TurnByTurn.tune_diffusion` returns: the `Tunes` of the two halves and d (..., record_first) float64
+TuneDiffusion = namedtuple("TuneDiffusion", ["first", "second", "d"])
 
 #: sums of one recorded turn, all float64, over the particles alive at the end of that turn: the count, sum w, sum w x_j (j < 6),
 #: sum w x_j^2 (j < 6); w = float64(charge) * float64(survival probability of the incoming beam)
@@ -34,17 +41,31 @@ class TurnByTurn:
 
     A vectorised beam or lattice (the general path) puts its batch dimensions behind R and in front of N: lost_turn (..., N),
     num_alive (R, ...), mean (R, ..., 6), particles (R, ..., record_first, 7).
-    Every tensor lives on the beam's device; nothing here was synchronised with the host."""
+    Every tensor lives on the beam's device; nothing here was synchronised with the host.
 
-    __slots__ = ("outgoing", "lost_turn", "turns", "sums", "particles")
+    From the recorded rows (record_first > 0):
+    tunes(planes, first_record, num_records)   `Tunes(tune, amplitude)`, both (..., record_first, len(planes)) float64: per row
+                and plane the interpolated peak of the Hann-windowed spectrum of a window of 8 .. 4096 consecutive records (NAFF's
+                first line, converging like T^-3 or better in the window length T where an FFT bin resolves 1 / T) and the
+                amplitude of that line in the units of the coordinate. The tune is in cycles per RECORD step and lies in
+                [0, 1/2]: with record_every = m it is m times the turn tune, folded into [0, 1/2] (q -> |q - round(q)|); it is
+                not unfolded. NaN for a row lost up to the window's last record, for a window with a non-finite sample, and
+                (amplitude 0) for a constant signal
+    tune_diffusion(planes)   `TuneDiffusion(first, second, d)`: the tunes of the first and the second half of the records and
+                d = log10 sqrt(sum over planes (tune_2 - tune_1)^2), the frequency-map measure of chaos (-inf where the halves
+                agree exactly, NaN where either half is NaN)"""
 
-    def __init__(self, outgoing, lost_turn: torch.Tensor, turns: torch.Tensor, sums: torch.Tensor, particles=None) -> None:
+    __slots__ = ("outgoing", "lost_turn", "turns", "sums", "particles", "_record_every")
+
+    def __init__(self, outgoing, lost_turn: torch.Tensor, turns: torch.Tensor, sums: torch.Tensor, particles=None,
+                 record_every=None) -> None:
         assert sums.dim() >= 2 and sums.shape[-1] == NUM_SUMS and sums.dtype == torch.float64 and turns.shape == sums.shape[:1]
         self.outgoing = outgoing
         self.lost_turn = lost_turn
         self.turns = turns
         self.sums = sums
         self.particles = particles
+        self._record_every = record_every      # known to the host by `Segment.track_turns`; else read from `turns` when needed
 
     @property
     def num_alive(self) -> torch.Tensor:
@@ -62,6 +83,48 @@ class TurnByTurn:
     def std(self) -> torch.Tensor:
         mean = self.mean
         return torch.sqrt(torch.clamp(self.sums[..., 8:14] / self.sums[..., 1:2] - mean * mean, min=0.0))
+
+    def tunes(self, planes=("x", "y"), first_record: int = 0, num_records=None) -> Tunes:
+        """Per recorded row and plane ("x", "y", "tau") the tune and the amplitude of the strongest line of the records
+        first_record .. first_record + num_records - 1 (`num_records=None`: every record from `first_record` on); see the class.
+        One HIP call (`chx_tunes`), float64 results, bitwise reproducible, no host synchronisation; not differentiable
+        (`Segment.track_turns` is not)."""
+        from .. import _ops
+
+        if self.particles is None:
+            raise ValueError("tunes need the recorded rows: call Segment.track_turns with record_first > 0")
+        planes = (planes,) if isinstance(planes, str) else tuple(planes)
+        if not planes or any(p not in _ops.TUNES_PLANES for p in planes) or len(set(planes)) != len(planes):
+            raise ValueError(f"planes must be distinct names out of {tuple(_ops.TUNES_PLANES)}, got {planes!r}")
+        R = int(self.particles.shape[0])
+        first_record = int(first_record)
+        num_records = R - first_record if num_records is None else int(num_records)
+        if not _ops.TUNES_T_MIN <= num_records <= _ops.TUNES_T_MAX:
+            raise ValueError(f"a window of {num_records} records: tunes take {_ops.TUNES_T_MIN} to {_ops.TUNES_T_MAX} records. Record "
+                             "more turns, thin a long run with record_every, or take windows of it with first_record / num_records")
+        if first_record < 0 or first_record + num_records > R:
+            raise ValueError(f"records {first_record} .. {first_record + num_records - 1} lie outside the {R} records")
+        if self._record_every is None:
+            self._record_every = int(self.turns[0])
+        K = int(self.particles.shape[-2])
+        lead = tuple(self.particles.shape[1:-2])
+        probe = self.particles.reshape(R, -1, 7)
+        lost = self.lost_turn[..., :K].expand(*lead, K).reshape(-1)
+        columns = sum(1 << _ops.TUNES_PLANES[p] for p in planes)
+        nu, amp = _ops.tunes(probe, lost, first_record, num_records, (first_record + num_records) * self._record_every, columns)
+        order = [sorted(planes, key=_ops.TUNES_PLANES.get).index(p) for p in planes]
+        if order != list(range(len(planes))):                      # (column views: no index tensor crosses from the host)
+            nu, amp = torch.stack([nu[:, i] for i in order], dim=1), torch.stack([amp[:, i] for i in order], dim=1)
+        return Tunes(nu.reshape(*lead, K, len(planes)), amp.reshape(*lead, K, len(planes)))
+
+    def tune_diffusion(self, planes=("x", "y")) -> TuneDiffusion:
+        """The tunes of the records [0, T) and [T, 2 T), T = R // 2, and d = log10 sqrt(sum over planes (tune_2 - tune_1)^2):
+        -inf where the two halves agree exactly, NaN where either is NaN (a particle lost during the run)."""
+        T = (0 if self.particles is None else int(self.particles.shape[0])) // 2
+        first = self.tunes(planes, 0, T)
+        second = self.tunes(planes, T, T)
+        diff = second.tune - first.tune
+        return TuneDiffusion(first, second, torch.log10(torch.sqrt((diff * diff).sum(dim=-1))))
 
     def __repr__(self) -> str:
         return f"TurnByTurn(records={self.turns.shape[0]}, particles={tuple(self.lost_turn.shape)})"

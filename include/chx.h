@@ -313,6 +313,27 @@ int chx_bunching(const void* x, const void* w, const void* q, const double* nu, 
 int chx_bunching_bwd(const void* x, const void* w, const void* q, const double* nu, int64_t B, int64_t Bx, int64_t Bw, int64_t Bq,
                      int64_t Bnu, int64_t N, int64_t K, int dtype, const double* dF, const double* dQ, void* dTau, void* dW,
                      void* dQpart, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- tunes from turn-by-turn records (TurnByTurn.tunes): probe[R][S][7] (dtype) holds S rows at R consecutive records. One
+ * signal is column c = 0 (x), 2 (y) or 4 (tau) of one row over the records r0 .. r0 + T - 1: u_n, n < T, exactly as float64. With
+ * the Hann window w_n = sin^2(pi (n + 1/2) / T), the windowed mean m = sum w u / sum w and v_n = w_n (u_n - m), all in float64:
+ *   F(nu) = sum v_n exp(-2 pi i nu n), G(nu) = sum n v_n exp(-2 pi i nu n), A = |F|^2, dA / dnu = 4 pi g, g = F_r G_i - F_i G_r,
+ * the phase nu n reduced in turns (its fractional part) before sin / cos. Coarse grid nu_k = k / (2 P), k = 0 .. P, with
+ * P = 2 * 2^ceil(log2 T); k* = the lowest k with the largest A(nu_k). If 0 < k* < P and g(nu_{k*-1}) > 0 > g(nu_{k*+1}) the tune
+ * is the root of g in that bracket (safeguarded Newton steps, every iterate inside the bracket, until the bracket or the step is
+ * <= 2^-48; a fixed cap of steps), else nu_{k*}. The amplitude of the line is 2 |F(tune)| / sum w.
+ *   nu[S][C], amp[S][C] (float64): C = the bits set in `columns` (bit 0: x, bit 1: y, bit 2: tau), in that order. The tune is in
+ *   cycles per record step and lies in [0, 1/2].
+ *   A = 0 on the whole grid: nu = NaN, amp = 0. A sample of the window that is not finite: NaN, NaN for that signal.
+ *   lost[S] (int32, may be NULL): a row with 0 < lost <= last_turn (the turn number of the window's last record) is NaN, NaN.
+ * k* comes from a float32 transform of P complex points in LDS, settled against its two neighbours in float64; everything else is
+ * float64 sums in a fixed order (bitwise reproducible). One workgroup per row, no workspace, no host synchronisation.
+ * CHX_ERR_INVALID_ARG before any launch: a NULL probe / nu / amp, R < 1, S < 1, r0 < 0, T outside CHX_TUNES_T_MIN .. CHX_TUNES_T_MAX,
+ * r0 + T > R, columns outside 1 .. 7; CHX_ERR_DTYPE: dtype other than CHX_F32 / CHX_F64.
+ * (An additive export: CHX_ABI_VERSION stays as it is.) */
+#define CHX_TUNES_T_MIN 8
+#define CHX_TUNES_T_MAX 4096
+int chx_tunes(const void* probe, const int32_t* lost, int64_t R, int64_t S, int64_t r0, int64_t T, int64_t last_turn,
+              int columns /* bit 0: x, bit 1: y, bit 2: tau */, int dtype, double* nu, double* amp /* (S, C) */, void* stream);
 /* ---- short-range wakefield (Wakefield element): per batch row b, over the SURVIVING particles (w > 0, finite tau; c = |q| w):
  * tau_lo, tau_hi, node spacing D = (tau_hi - tau_lo) / (M - 1); node coordinate u = clamp((tau - tau_lo) / D, 0, M - 1) (0 when
  * D = 0), k = min(floor u, M - 2), f = u - k; node deposits Q_k += (1 - f) c, Q_k+1 += f c (and X, Y with c x, c y when the
