@@ -25,6 +25,7 @@ from .accelerator import (  # noqa: F401
     PhysicsWarning,
     Quadrupole,
     RBend,
+    RFCavity,
     Screen,
     Segment,
     Sextupole,

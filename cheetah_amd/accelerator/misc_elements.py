@@ -258,3 +258,67 @@ class TransverseDeflectingCavity(Element):
     def defining_features(self) -> list[str]:
         return super().defining_features + ["length", "voltage", "phase", "frequency", "misalignment", "tilt",
                                             "num_steps"]
+
+
+class RFCavity(Element):
+    """RF cavity of a storage ring (not in the reference; Bmad's `rfcavity`, bmad_standard, from the reference's Bmad-X building
+    blocks): half a drift, the energy kick dE = |n_q| V sin(2 pi (phase - frequency t)) at the particle's own time offset
+    t = tau / c, half a drift — tracked per particle by chx_dkd_track (drift_kick_drift only), symplectic, in one chain call with
+    its neighbours (`Segment.track`) and inside the fused ring (`Segment.track_turns`). Unlike the linac `Cavity` it does NOT change
+    the reference energy: the storage-ring convention. `phase` is in units of 2 pi, as for the TransverseDeflectingCavity and
+    Bmad: phase = 0 is the stable zero crossing above transition, phase = 0.5 the stable one below. With sin(2 pi phase) != 0 the
+    synchronous particle gains |n_q| V sin(2 pi phase) per pass while the reference energy stays. A thin cavity (`length = 0`)
+    is allowed; the kick depends on neither x nor y, so there is no tilt and no misalignment. A particle whose total energy
+    falls below its rest mass becomes NaN and is lost by the loss rule of `track_turns`."""
+
+    supported_tracking_methods = ["drift_kick_drift"]
+    _dkd_kind = _ops.DKD_KIND["rfcavity"]
+
+    def __init__(self, length, voltage=None, phase=None, frequency=None, tracking_method="drift_kick_drift", name=None,
+                 sanitize_name=None, metadata=None, device=None, dtype=None) -> None:
+        fk = {"device": device, "dtype": dtype}
+        super().__init__(name=name, sanitize_name=sanitize_name, metadata=metadata, **fk)
+        z = lambda v: v if v is not None else torch.tensor(0.0, **fk)  # noqa: E731
+        if bool((torch.as_tensor(length) < 0).any()):
+            raise ValueError(f"RFCavity.length must not be negative, got {length!r}")
+        self.length = length
+        self.register_buffer_or_parameter("voltage", z(voltage))
+        self.register_buffer_or_parameter("phase", z(phase))
+        self.register_buffer_or_parameter("frequency", z(frequency))
+        self._tracking_method = "drift_kick_drift"
+        self.tracking_method = tracking_method
+
+    def _dkd_params(self):
+        return [self.length, self.voltage, self.phase, self.frequency]
+
+    def _dkd_scalar_refs(self):
+        return [(t, None) for t in self._settings("length", "voltage", "phase", "frequency")]
+
+    def _dkd_options(self):
+        return 1, 0         # (num_steps is not read; no fringe)
+
+    @staticmethod
+    def harmonic_frequency(circumference, harmonic, energy, species=None) -> torch.Tensor:
+        """The RF frequency h beta0 c / C (Hz) of harmonic number `harmonic` in a ring of circumference `circumference` (m) for a
+        beam of reference energy `energy` (eV); `species=None` is an electron."""
+        from ..particles.particle_beam import speed_of_light
+        from ..particles.species import electron_mass_eV
+
+        energy = torch.as_tensor(energy)
+        if not energy.is_floating_point():
+            energy = energy.to(torch.get_default_dtype())
+        mass = electron_mass_eV if species is None else species.mass_eV.to(energy.device)
+        beta0 = torch.sqrt(1 - (mass / energy).square())
+        return harmonic * beta0 * speed_of_light / circumference
+
+    @property
+    def is_active(self) -> bool:
+        return bool((self.voltage != 0).any().item())
+
+    @property
+    def is_skippable(self) -> bool:
+        return False
+
+    @property
+    def defining_features(self) -> list[str]:
+        return super().defining_features + ["length", "voltage", "phase", "frequency"]

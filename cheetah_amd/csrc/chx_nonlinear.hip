@@ -1,6 +1,6 @@
 // chx_nonlinear.hip — per-particle non-linear tracking for gfx950.
 //
-//  * drift-kick-drift (Bmad-X) tracking of Drift, Quadrupole, Dipole, TransverseDeflectingCavity and Sextupole:
+//  * drift-kick-drift (Bmad-X) tracking of Drift, Quadrupole, Dipole, TransverseDeflectingCavity, Sextupole and RFCavity:
 //    cheetah/accelerator/drift.py:106-154, quadrupole.py:168-251, dipole.py:183-370,
 //    transverse_deflecting_cavity.py:122-209 on top of cheetah/utils/bmadx.py;
 //  * second-order (MAD-convention T tensor) tracking: element.py:195-228 with the tensors of
@@ -15,6 +15,19 @@
 
 #include "chx_common.h"
 #include "chx_dual.h"
+
+// parameters per drift-kick-drift kind (include/chx.h), -1 for anything else: what every entry point below counts with
+static int dkd_num_params(int kind) {
+    switch (kind) {
+        case CHX_DKD_DRIFT: return 1;
+        case CHX_DKD_QUADRUPOLE: return 5;
+        case CHX_DKD_DIPOLE: return 9;
+        case CHX_DKD_TDC: return 7;
+        case CHX_DKD_SEXTUPOLE: return 5;
+        case CHX_DKD_RFCAVITY: return 4;
+    }
+    return -1;
+}
 
 namespace {
 
@@ -137,6 +150,23 @@ __device__ __forceinline__ Dual sqrta2minusbdiva(Dual a, Dual b) {
     return mk(1.0 / (2.0 * a.v), -a.d / (2.0 * a.v * a.v) - b.d / (8.0 * a.v * a.v * a.v));
 }
 
+// sin and cos of 2 pi u for a phase u in TURNS: r = u - rint(u) is exact and |r| <= 1/2, sincospi(2 r) has no reduction of its own
+// left to do (as in chx_laser.hip, chx_bunching.hip, chx_density.hip) — and u = 0, 1/4, 1/2 ... give exact zeros and ones.
+__device__ __forceinline__ void turn_sincos(double u, double& s, double& c) {
+    const double r = u - __builtin_rint(u);
+    sincospi(2.0 * r, &s, &c);
+}
+__device__ __forceinline__ void turn_sincos(F32 u, F32& s, F32& c) {
+    const float r = u.v - __builtin_rintf(u.v);
+    sincospif(2.0f * r, &s.v, &c.v);
+}
+__device__ __forceinline__ void turn_sincos(Dual u, Dual& s, Dual& c) {
+    double sv, cv;
+    turn_sincos(u.v, sv, cv);
+    s = mk(sv, 2.0 * kPi * cv * u.d);
+    c = mk(cv, -2.0 * kPi * sv * u.d);
+}
+
 // ---------------------------------------------------------------------------------------------
 // per-batch-row constants (computed once per workgroup by lane 0, shared through LDS)
 // ---------------------------------------------------------------------------------------------
@@ -178,6 +208,12 @@ __device__ void dkd_constants(int kind, const S* par, S E, double mc2, double nq
         c[C_XO] = par[3]; c[C_YO] = par[4];
         c[C_A] = L;
         c[C_B] = k2 * L;  // the integrated strength: every one of the n kicks applies 1 / n of it
+    } else if (kind == CHX_DKD_RFCAVITY) {
+        const S L = par[0], V = par[1], phase = par[2], freq = par[3];
+        c[C_A] = L;
+        c[C_B] = V * fabs(nq);               // the energy a particle gains on the crest, in eV
+        turn_sincos(phase, c[C_C], c[C_D]);  // S0 = sin(2 pi phase), C0 = cos(2 pi phase): phase = 0 and 0.5 are exact zero crossings
+        c[C_E2] = freq;
     } else {  // CHX_DKD_TDC
         const S L = par[0], V = par[1], phase = par[2], freq = par[3];
         const S tilt = par[4];
@@ -268,6 +304,28 @@ __device__ __forceinline__ void dkd_particle(const S* c, Bmad<S>& q, double mc2,
             track_a_drift<S>(s + 1 < num_steps ? 2.0 * h : h, q, p0c, mc2);
         }
         offset_unset<S>(c[C_XO], c[C_YO], c[C_SIN], c[C_COS], q);
+    } else if (KIND == CHX_DKD_RFCAVITY) {
+        // Bmad's rfcavity (bmad_standard) from the building blocks of the TDC branch below: half a drift, the energy kick
+        // dE = |n_q| V sin(2 pi (phase0 - f t)) at the particle's own time offset t, half a drift. The kick depends on z alone and
+        // changes pz alone, so it is symplectic; the reference energy stays (the storage-ring convention). The phase f t is
+        // reduced in turns before any sine is taken; sin(a - b) by the addition theorem from the element's S0, C0.
+        const S half = c[C_A] / 2.0, volt = c[C_B], S0 = c[C_C], C0 = c[C_D], freq = c[C_E2];
+        track_a_drift<S>(half, q, p0c, mc2);
+        const S pc_old = (1.0 + q.pz) * p0c;
+        const S E_old = m_sqrt(pc_old * pc_old + mc2 * mc2);
+        const S beta_old = pc_old / E_old;
+        const S time = -q.z / (beta_old * kC);  // bmadx.py:301-310
+        S sn, cs;
+        turn_sincos(freq * time, sn, cs);
+        const S dE = volt * (S0 * cs - C0 * sn);
+        const S E_new = E_old + dE;
+        const S pc = m_sqrt(E_new * E_new - mc2 * mc2);          // (E_new < m: NaN, and the particle is lost by the loss rule)
+        const S beta = pc / E_new;
+        // pz = (pc - p0c) / p0c as an increment, pc^2 - pc_old^2 = dE (2 E_old + dE): no digits of pz are lost to the size of the
+        // energy (one rounding of the kick, not three of the momentum), and dE = 0 leaves pz as it is
+        q.pz = q.pz + dE * (2.0 * E_old + dE) / ((pc + pc_old) * p0c);
+        q.z = q.z * beta / beta_old;
+        track_a_drift<S>(half, q, p0c, mc2);
     } else {  // TDC, transverse_deflecting_cavity.py:147-193
         const S half = c[C_A] / 2.0, volt = c[C_B], k_rf = c[C_C], phase0 = c[C_D], freq = c[C_E2];
         offset_set<S>(c[C_XO], c[C_YO], c[C_SIN], c[C_COS], q);
@@ -663,7 +721,7 @@ template <typename T, typename C = double>
 int dispatch_dkd(int kind, const void* x_in, const void* params, const void* energy, double mc2, double nq,
                  int num_steps, int fringe, int64_t B, int64_t Bx, int64_t Bp, int64_t Be, int64_t N,
                  void* x_out, void* energy_out, hipStream_t s) {
-    const int P = chx_dkd_num_params(kind);
+    const int P = dkd_num_params(kind);
     switch (kind) {
         case CHX_DKD_DRIFT:
             return launch_dkd<T, CHX_DKD_DRIFT, C>(x_in, params, energy, mc2, nq, num_steps, fringe, P, B, Bx, Bp, Be,
@@ -680,22 +738,18 @@ int dispatch_dkd(int kind, const void* x_in, const void* params, const void* ene
         case CHX_DKD_SEXTUPOLE:
             return launch_dkd<T, CHX_DKD_SEXTUPOLE, C>(x_in, params, energy, mc2, nq, num_steps, fringe, P, B, Bx, Bp, Be,
                                                     N, x_out, energy_out, s);
+        case CHX_DKD_RFCAVITY:
+            return launch_dkd<T, CHX_DKD_RFCAVITY, C>(x_in, params, energy, mc2, nq, num_steps, fringe, P, B, Bx, Bp, Be,
+                                                   N, x_out, energy_out, s);
     }
     return CHX_ERR_INVALID_ARG;
 }
 
 }  // namespace
 
-extern "C" int chx_dkd_num_params(int kind) {
-    switch (kind) {
-        case CHX_DKD_DRIFT: return 1;
-        case CHX_DKD_QUADRUPOLE: return 5;
-        case CHX_DKD_DIPOLE: return 9;
-        case CHX_DKD_TDC: return 7;
-        case CHX_DKD_SEXTUPOLE: return 5;
-    }
-    return -1;
-}
+// The exported query keeps the answers it gave before CHX_DKD_RFCAVITY existed (callers of ABI 9 probe the kinds with it, and 6
+// was "no such kind"); the entry points count the cavity's four parameters through dkd_num_params.
+extern "C" int chx_dkd_num_params(int kind) { return kind == CHX_DKD_RFCAVITY ? -1 : dkd_num_params(kind); }
 
 extern "C" int chx_dkd_track(int kind, const void* x_in, const void* params, const void* energy, double mass_eV,
                              double n_charges, int32_t num_steps, int32_t fringe_at, int64_t B, int64_t Bx,
@@ -709,7 +763,7 @@ extern "C" int chx_dkd_track_p(int kind, const void* x_in, const void* params, c
                                double n_charges, int32_t num_steps, int32_t fringe_at, int64_t B, int64_t Bx, int64_t Bp,
                                int64_t Be, int64_t N, int dtype, int storage_precision, void* x_out, void* energy_out,
                                void* stream) {
-    if (chx_dkd_num_params(kind) < 0) return CHX_ERR_INVALID_ARG;
+    if (dkd_num_params(kind) < 0) return CHX_ERR_INVALID_ARG;
     if (dtype != CHX_F32 && dtype != CHX_F64) return CHX_ERR_DTYPE;
     if (B < 0 || N < 0) return CHX_ERR_INVALID_ARG;
     if (B == 0 || N == 0) return CHX_OK;
@@ -720,10 +774,10 @@ extern "C" int chx_dkd_track_p(int kind, const void* x_in, const void* params, c
     if (fringe_at < 0 || fringe_at > 3) return CHX_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (dtype == CHX_F32 && storage_precision == 2 && (kind == CHX_DKD_DRIFT || kind == CHX_DKD_QUADRUPOLE || kind == CHX_DKD_SEXTUPOLE)) {
-        // mixed arithmetic (see dkd_mixed_kernel); the other kinds keep the fp64 evaluation
+        // mixed arithmetic (see dkd_mixed_kernel); the other kinds — Dipole, TDC, RFCavity — keep the fp64 evaluation
         const int64_t tiles = ((N + CHX_BLOCK - 1) / CHX_BLOCK) * B;
         if (tiles > 0x7fffffffLL) return CHX_ERR_INVALID_ARG;
-        const int P = chx_dkd_num_params(kind);
+        const int P = dkd_num_params(kind);
         if (kind == CHX_DKD_DRIFT)
             hipLaunchKernelGGL(dkd_mixed_kernel<CHX_DKD_DRIFT>, dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const float*)x_in,
                                (const float*)params, (const float*)energy, mass_eV, n_charges, num_steps, P, B, Bx, Bp, Be, N,
@@ -814,7 +868,7 @@ __device__ __forceinline__ void dkd_item_constants(int kind, int fringe, int ste
     int32_t* w = reinterpret_cast<int32_t*>(out + kDkdMeta);
     w[0] = kind;
     w[1] = steps;
-    const int P = kind == CHX_DKD_DRIFT ? 1 : (kind == CHX_DKD_DIPOLE ? 9 : 5);          // (Quadrupole, Sextupole: 5)
+    const int P = kind == CHX_DKD_DRIFT ? 1 : (kind == CHX_DKD_DIPOLE ? 9 : (kind == CHX_DKD_RFCAVITY ? 4 : 5));          // (Quadrupole, Sextupole: 5)
     double par[CHX_MAX_PARAMS];
     for (int k = 0; k < P; ++k) par[k] = (double)pe[k];
     double c[C_MIXED_N];
@@ -881,7 +935,7 @@ __global__ void dkd_energy_chain_kernel(const int32_t* __restrict__ kinds_dev, i
 // MODE: chx_dkd_track_p's storage_precision — 0 fp64 evaluation, 1 float32 evaluation, 2 mixed
 template <int MODE, int KIND>
 __device__ __forceinline__ void dkd_chain_step(const double* __restrict__ c, double mc2, int num_steps, float (&v)[6]) {
-    if (MODE == 2 && KIND != CHX_DKD_DIPOLE) {          // (a Dipole in mixed mode: the fp64 evaluation, as chx_dkd_track_p does)
+    if (MODE == 2 && KIND != CHX_DKD_DIPOLE && KIND != CHX_DKD_RFCAVITY) {          // (a Dipole or an RFCavity in mixed mode: the fp64 evaluation, as chx_dkd_track_p does)
         dkd_mixed_particle<KIND>(c, mc2, num_steps, v);
     } else if (MODE == 0 || MODE == 2) {
         double in[6], out[6];
@@ -931,12 +985,14 @@ __device__ __forceinline__ void dkd_copy6(const T (&from)[6], T (&to)[6]) {
 // and the seventh column, into which every drift-kick-drift item writes 1.
 // BEND: the run contains Dipoles (their body — asin, atan2, a dozen square roots — costs registers the other runs keep)
 // SEXT: the run contains Sextupoles (a run without one is the instantiation it was before they existed: the branch is not compiled)
+// RF: the run contains RFCavities, likewise; such a run always has BEND = SEXT = true as well (one more kernel per arithmetic
+//     mode, not four)
 // LINEAR: items of kind kDkdLinear may stand in the run (a chain; a ring has none, and its code has no such branch)
 // A new element kind is one line of the dispatch below.
 // The loop runs on a copy of x that is the function's own: a function is optimised before it is inlined into its caller, and
 // there the lane's registers are memory behind a reference — a loop over them comes out in another shape than a loop over locals,
 // at 3 to 6 VGPRs more per ring kernel and a wave per SIMD fewer in six of them (profiles/turn_frame.md).
-template <int MODE, bool BEND, bool SEXT, bool LINEAR, typename T>
+template <int MODE, bool BEND, bool SEXT, bool RF, bool LINEAR, typename T>
 __device__ __forceinline__ void dkd_items(const double* __restrict__ cst, int E, double mc2, T (&lane)[6], T& lane6) {
     T v[6], v6 = lane6;
     dkd_copy6(lane, v);
@@ -956,6 +1012,7 @@ __device__ __forceinline__ void dkd_items(const double* __restrict__ cst, int E,
         }
         if (kind == CHX_DKD_DRIFT) dkd_chain_step<MODE, CHX_DKD_DRIFT>(c, mc2, steps, v);
         else if (SEXT && kind == CHX_DKD_SEXTUPOLE) dkd_chain_step<MODE, CHX_DKD_SEXTUPOLE>(c, mc2, steps, v);
+        else if (RF && kind == CHX_DKD_RFCAVITY) dkd_chain_step<MODE, CHX_DKD_RFCAVITY>(c, mc2, steps, v);
         else if (!BEND || kind == CHX_DKD_QUADRUPOLE) dkd_chain_step<MODE, CHX_DKD_QUADRUPOLE>(c, mc2, steps, v);
         else dkd_chain_step<MODE, CHX_DKD_DIPOLE>(c, mc2, steps, v);
         v6 = (T)1;
@@ -964,9 +1021,9 @@ __device__ __forceinline__ void dkd_items(const double* __restrict__ cst, int E,
     lane6 = v6;
 }
 
-// a particle per lane through all items of the run, MODE / BEND / SEXT as in dkd_items (x_out may be x_in: a tile is read whole
+// a particle per lane through all items of the run, MODE / BEND / SEXT / RF as in dkd_items (x_out may be x_in: a tile is read whole
 // before it is written)
-template <int MODE, bool BEND, bool SEXT, typename T>
+template <int MODE, bool BEND, bool SEXT, bool RF, typename T>
 __device__ __forceinline__ void dkd_chain_tile(const T* x_in, const double* __restrict__ cst, int E, double mc2, T* x_out, int64_t N,
                                                int in_vec_ok, int out_vec_ok) {
     constexpr int TP = CHX_BLOCK;
@@ -979,7 +1036,7 @@ __device__ __forceinline__ void dkd_chain_tile(const T* x_in, const double* __re
     T v[6], v6 = p < np ? lds[p * 7 + 6] : (T)1;
 #pragma unroll
     for (int j = 0; j < 6; ++j) v[j] = p < np ? lds[p * 7 + j] : (T)0;
-    dkd_items<MODE, BEND, SEXT, true, T>(cst, E, mc2, v, v6);
+    dkd_items<MODE, BEND, SEXT, RF, true, T>(cst, E, mc2, v, v6);
     if (p < np) {
 #pragma unroll
         for (int j = 0; j < 6; ++j) lds[p * 7 + j] = v[j];
@@ -989,16 +1046,16 @@ __device__ __forceinline__ void dkd_chain_tile(const T* x_in, const double* __re
     tile_store<T, TP>(x_out + n0 * 7, lds, np * 7, out_vec_ok != 0, true);
 }
 
-template <int MODE, bool BEND, bool SEXT>
+template <int MODE, bool BEND, bool SEXT, bool RF>
 __global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel(const float* x_in, const double* __restrict__ cst, int E, double mc2,
                                                               float* x_out, int64_t N, int in_vec_ok, int out_vec_ok) {
-    dkd_chain_tile<MODE, BEND, SEXT, float>(x_in, cst, E, mc2, x_out, N, in_vec_ok, out_vec_ok);
+    dkd_chain_tile<MODE, BEND, SEXT, RF, float>(x_in, cst, E, mc2, x_out, N, in_vec_ok, out_vec_ok);
 }
 
-template <bool BEND, bool SEXT>
+template <bool BEND, bool SEXT, bool RF>
 __global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel_f64(const double* x_in, const double* __restrict__ cst, int E, double mc2,
                                                                   double* x_out, int64_t N, int in_vec_ok, int out_vec_ok) {
-    dkd_chain_tile<0, BEND, SEXT, double>(x_in, cst, E, mc2, x_out, N, in_vec_ok, out_vec_ok);
+    dkd_chain_tile<0, BEND, SEXT, RF, double>(x_in, cst, E, mc2, x_out, N, in_vec_ok, out_vec_ok);
 }
 }  // namespace
 
@@ -1063,21 +1120,23 @@ extern "C" int chx_dkd_chain_mixed(const int32_t* kinds, const void* const* para
             first = e;
         }
     }
-    // Drifts, Quadrupoles, Dipoles, Sextupoles (float32: of one arithmetic mode) and linear runs, the constants (448 bytes per item) in x_tmp:
+    // Drifts, Quadrupoles, Dipoles, Sextupoles, RFCavities (float32: of one arithmetic mode) and linear runs, the constants (448 bytes per item) in x_tmp:
     // the particles stay in registers (dkd_chain_kernel, dkd_chain_kernel_f64), two launches per 192 items, the same bits
     static const bool fused_off = [] { const char* v = getenv("CHX_DKD_CHAIN_FUSED"); return v && v[0] == '0'; }();
     // (a longer run takes several such pairs, the later ones in place on x_out: a workgroup holds its whole tile in registers
     // before it writes)
     const int64_t per_pass = std::min<int64_t>(kDkdChainMax, N * 7 * (int64_t)esz / (kDkdCstStride * (int64_t)sizeof(double)));
     bool fuse = !fused_off && E >= 2 && per_pass >= 2 && chx_aligned16(x_tmp) && first >= 0;
-    bool bend = false, sext = false;
+    bool bend = false, sext = false, rf = false;
     for (int64_t e = 0; fuse && e < E; ++e) {      // (float64 beams ignore storage_precision, like chx_dkd_track_p)
         if (kinds[e] == kDkdLinear) continue;
-        fuse = (kinds[e] == CHX_DKD_DRIFT || kinds[e] == CHX_DKD_QUADRUPOLE || kinds[e] == CHX_DKD_DIPOLE || kinds[e] == CHX_DKD_SEXTUPOLE) &&
+        fuse = (kinds[e] == CHX_DKD_DRIFT || kinds[e] == CHX_DKD_QUADRUPOLE || kinds[e] == CHX_DKD_DIPOLE || kinds[e] == CHX_DKD_SEXTUPOLE ||
+                kinds[e] == CHX_DKD_RFCAVITY) &&
                (dtype == CHX_F64 || (storage_precision[e] == storage_precision[first] && storage_precision[e] >= 0 && storage_precision[e] <= 2)) &&
                num_steps[e] >= 1 && num_steps[e] < (1 << 25) && fringe_at[e] >= 0 && fringe_at[e] <= 3;
         bend = bend || kinds[e] == CHX_DKD_DIPOLE;
         sext = sext || kinds[e] == CHX_DKD_SEXTUPOLE;
+        rf = rf || kinds[e] == CHX_DKD_RFCAVITY;
     }
     if (fuse) {
         hipStream_t s = (hipStream_t)stream;
@@ -1103,13 +1162,14 @@ extern "C" int chx_dkd_chain_mixed(const int32_t* kinds, const void* const* para
                 hipLaunchKernelGGL(dkd_chain_prepare_kernel<double>, dim3(blocks), dim3(64), 0, s, a, n, (const double*)e_from, mass_eV,
                                    n_charges, (double*)x_tmp, (double*)e_to, (const double*)s_from, (double*)s_out);
                 CHX_CHECK_LAUNCH();
-#define CHX_DKD_CHAIN_LAUNCH_F64(B, S)                                                                                                \
-    hipLaunchKernelGGL((dkd_chain_kernel_f64<B, S>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const double*)src,              \
+#define CHX_DKD_CHAIN_LAUNCH_F64(B, S, R)                                                                                             \
+    hipLaunchKernelGGL((dkd_chain_kernel_f64<B, S, R>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const double*)src,              \
                        (const double*)x_tmp, n, mass_eV, (double*)x_out, N, in_ok, out_ok)
-                if (bend && sext) CHX_DKD_CHAIN_LAUNCH_F64(true, true);
-                else if (bend) CHX_DKD_CHAIN_LAUNCH_F64(true, false);
-                else if (sext) CHX_DKD_CHAIN_LAUNCH_F64(false, true);
-                else CHX_DKD_CHAIN_LAUNCH_F64(false, false);
+                if (rf) CHX_DKD_CHAIN_LAUNCH_F64(true, true, true);          // (a run with a cavity: every kind compiled in)
+                else if (bend && sext) CHX_DKD_CHAIN_LAUNCH_F64(true, true, false);
+                else if (bend) CHX_DKD_CHAIN_LAUNCH_F64(true, false, false);
+                else if (sext) CHX_DKD_CHAIN_LAUNCH_F64(false, true, false);
+                else CHX_DKD_CHAIN_LAUNCH_F64(false, false, false);
 #undef CHX_DKD_CHAIN_LAUNCH_F64
                 CHX_CHECK_LAUNCH();
                 continue;
@@ -1117,15 +1177,16 @@ extern "C" int chx_dkd_chain_mixed(const int32_t* kinds, const void* const* para
             hipLaunchKernelGGL(dkd_chain_prepare_kernel<float>, dim3(blocks), dim3(64), 0, s, a, n, (const float*)e_from, mass_eV,
                                n_charges, (double*)x_tmp, (float*)e_to, (const float*)s_from, (float*)s_out);
             CHX_CHECK_LAUNCH();
-#define CHX_DKD_CHAIN_LAUNCH(M, B, S)                                                                                                \
-    hipLaunchKernelGGL((dkd_chain_kernel<M, B, S>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const float*)src, (const double*)x_tmp, \
+#define CHX_DKD_CHAIN_LAUNCH(M, B, S, R)                                                                                             \
+    hipLaunchKernelGGL((dkd_chain_kernel<M, B, S, R>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const float*)src, (const double*)x_tmp, \
                        n, mass_eV, (float*)x_out, N, in_ok, out_ok)
 #define CHX_DKD_CHAIN_MODE(M)                                                                                                     \
     do {                                                                                                                          \
-        if (bend && sext) CHX_DKD_CHAIN_LAUNCH(M, true, true);                                                                    \
-        else if (bend) CHX_DKD_CHAIN_LAUNCH(M, true, false);                                                                      \
-        else if (sext) CHX_DKD_CHAIN_LAUNCH(M, false, true);                                                                      \
-        else CHX_DKD_CHAIN_LAUNCH(M, false, false);                                                                               \
+        if (rf) CHX_DKD_CHAIN_LAUNCH(M, true, true, true);                                                                        \
+        else if (bend && sext) CHX_DKD_CHAIN_LAUNCH(M, true, true, false);                                                        \
+        else if (bend) CHX_DKD_CHAIN_LAUNCH(M, true, false, false);                                                               \
+        else if (sext) CHX_DKD_CHAIN_LAUNCH(M, false, true, false);                                                               \
+        else CHX_DKD_CHAIN_LAUNCH(M, false, false, false);                                                                        \
     } while (0)
             if (mode == 2) CHX_DKD_CHAIN_MODE(2);
             else if (mode == 1) CHX_DKD_CHAIN_MODE(1);
@@ -1757,7 +1818,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void so_turns_reduce_kernel(const double
     }
 }
 
-// ---- a ring of Drifts, Quadrupoles, Dipoles and Sextupoles tracked drift-kick-drift, TURN AFTER TURN (chx_dkd_turns) ------------
+// ---- a ring of Drifts, Quadrupoles, Dipoles, Sextupoles and RFCavities tracked drift-kick-drift, TURN AFTER TURN (chx_dkd_turns) --
 // dkd_chain_kernel with the item loop inside the turn loop of so_turns_kernel. What the second-order ring does not have: every
 // drift-kick-drift element leaves the reference energy as the round trip f(E) = sqrt(sqrt(E^2 - m^2)^2 + m^2) of what it received
 // (dkd_energy_round_trip), and an element's constants depend on the energy in front of it. f is a composition of monotone,
@@ -1773,7 +1834,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void so_turns_reduce_kernel(const double
 //   dkd_turns_constants_kernel  a workgroup per (block, item); those of blocks that were not opened return at once. The others
 //                               walk from their block's start energy to the energy in front of their item and leave the item's
 //                               constants (dkd_item_constants, the chain's own). One workgroup more adds up the path length.
-//   dkd_turns_kernel<MODE, BEND, SEXT>, dkd_turns_kernel_f64<BEND, SEXT>   a particle per lane; per turn the block's address (a scalar load),
+//   dkd_turns_kernel<MODE, BEND, SEXT, RF>, dkd_turns_kernel_f64<BEND, SEXT, RF>   a particle per lane; per turn the block's address (a scalar load),
 //                               the chain's item loop (dkd_items); the loss test, the freezing of a lost row in the LDS tile,
 //                               the record and the probe rows are turns_frame's.
 //   so_turns_reduce_kernel      as it is.
@@ -1832,8 +1893,8 @@ __global__ void dkd_turns_constants_kernel(DkdChainArgs args, int E, int turns, 
 
 // the drift-kick-drift ring (as built: float64 beams, MODE is not read): a particle per lane; a turn is dkd_items over the block of
 // constants of that turn (its address: a scalar load), which leaves 1 in the seventh column as every drift-kick-drift kernel does.
-// MODE, BEND, SEXT as in dkd_items
-template <int MODE, bool BEND, bool SEXT, typename T>
+// MODE, BEND, SEXT, RF as in dkd_items
+template <int MODE, bool BEND, bool SEXT, bool RF, typename T>
 struct DkdRing {
     const double* __restrict__ cst;
     const int32_t* __restrict__ block_of_turn;
@@ -1847,7 +1908,7 @@ struct DkdRing {
     }
     __device__ __forceinline__ T get(int, int j) const { return j < 6 ? v[j] : v6; }
     __device__ __forceinline__ void turn(int k) {
-        dkd_items<MODE, BEND, SEXT, false, T>(cst + (int64_t)block_of_turn[k] * E * kDkdCstStride, E, mc2, v, v6);
+        dkd_items<MODE, BEND, SEXT, RF, false, T>(cst + (int64_t)block_of_turn[k] * E * kDkdCstStride, E, mc2, v, v6);
     }
 };
 
@@ -1856,7 +1917,7 @@ struct DkdRing {
 // float32 beams: the frame's text and the item loop written out. On turns_frame with dkd_items every instantiation kept its waves
 // per SIMD, but the "storage" ring ran 1.7 to 2.4 % slower at 1e3 and 1e5 particles and the "mixed" and "double" rings 0.8 to 1.4 %
 // (profiles/turn_frame.md). A change to the rules of turns_frame or a new kind in dkd_items is made here too.
-template <int MODE, bool BEND, bool SEXT>
+template <int MODE, bool BEND, bool SEXT, bool RF>
 __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel(const double* __restrict__ cst, const int32_t* __restrict__ block_of_turn,
                                                               double mc2, SoTurnsArgs<float> a) {
     constexpr int TP = CHX_BLOCK;
@@ -1886,6 +1947,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel(const double* __re
                 const int kind = w[0], steps = w[1];
                 if (kind == CHX_DKD_DRIFT) dkd_chain_step<MODE, CHX_DKD_DRIFT>(c, mc2, steps, v);
                 else if (SEXT && kind == CHX_DKD_SEXTUPOLE) dkd_chain_step<MODE, CHX_DKD_SEXTUPOLE>(c, mc2, steps, v);
+                else if (RF && kind == CHX_DKD_RFCAVITY) dkd_chain_step<MODE, CHX_DKD_RFCAVITY>(c, mc2, steps, v);
                 else if (!BEND || kind == CHX_DKD_QUADRUPOLE) dkd_chain_step<MODE, CHX_DKD_QUADRUPOLE>(c, mc2, steps, v);
                 else dkd_chain_step<MODE, CHX_DKD_DIPOLE>(c, mc2, steps, v);
             }
@@ -1928,10 +1990,10 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel(const double* __re
 }
 
 // float64 beams: turns_frame with the DkdRing policy
-template <bool BEND, bool SEXT>
+template <bool BEND, bool SEXT, bool RF>
 __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel_f64(const double* __restrict__ cst, const int32_t* __restrict__ block_of_turn,
                                                                   double mc2, SoTurnsArgs<double> a) {
-    DkdRing<0, BEND, SEXT, double> ring{cst, block_of_turn, a.E, mc2};
+    DkdRing<0, BEND, SEXT, RF, double> ring{cst, block_of_turn, a.E, mc2};
     turns_frame<double, 1>(ring, a);
 }
 
@@ -2152,7 +2214,7 @@ extern "C" int chx_second_order_turns(const void* const* T_maps, const int32_t* 
     return so_turns_launch<double>(maps, (int)E, c, s_in, s_out, workspace, tiles, coef_bytes, (hipStream_t)stream);
 }
 
-// A ring of Drifts, Quadrupoles, Dipoles and Sextupoles tracked drift-kick-drift: turns [first_turn, first_turn + num_turns) in one particle
+// A ring of Drifts, Quadrupoles, Dipoles, Sextupoles and RFCavities tracked drift-kick-drift: turns [first_turn, first_turn + num_turns) in one particle
 // launch (dkd_turns_kernel, dkd_turns_kernel_f64; see the kernels for the energy walk in front of it). The workspace, every part
 // 16-byte aligned: start[turns] (dtype) | block_of_turn[turns + 1] (int32) | constants[turns][E][kDkdCstStride] (double) |
 // partials[records][tiles][14] (double). The host cannot know how many blocks of constants the device will open: room for one per turn.
@@ -2170,7 +2232,7 @@ DkdTurnsLayout dkd_turns_layout(int64_t E, int64_t N, int64_t turns, int64_t rec
     return l;
 }
 template <typename T>
-int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, bool sext, int mode, const TurnsCall& c, const void* energy_in,
+int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, bool sext, bool rf, int mode, const TurnsCall& c, const void* energy_in,
                      void* energy_out, double mass_eV, double n_charges, const void* s_in, void* s_out, void* workspace,
                      const DkdTurnsLayout& l, int64_t tiles, hipStream_t s) {
     const int num_turns = (int)c.num_turns;
@@ -2189,10 +2251,11 @@ int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, bool sext, int
     const int32_t* b = block_of_turn;
 #define CHX_DKD_TURNS_KINDS(K, ...)                                                                                               \
     do {                                                                                                                          \
-        if (bend && sext) hipLaunchKernelGGL((K<__VA_ARGS__ true, true>), grid, wg, 0, s, k, b, mass_eV, a);                         \
-        else if (bend) hipLaunchKernelGGL((K<__VA_ARGS__ true, false>), grid, wg, 0, s, k, b, mass_eV, a);                           \
-        else if (sext) hipLaunchKernelGGL((K<__VA_ARGS__ false, true>), grid, wg, 0, s, k, b, mass_eV, a);                           \
-        else hipLaunchKernelGGL((K<__VA_ARGS__ false, false>), grid, wg, 0, s, k, b, mass_eV, a);                                    \
+        if (rf) hipLaunchKernelGGL((K<__VA_ARGS__ true, true, true>), grid, wg, 0, s, k, b, mass_eV, a);                             \
+        else if (bend && sext) hipLaunchKernelGGL((K<__VA_ARGS__ true, true, false>), grid, wg, 0, s, k, b, mass_eV, a);             \
+        else if (bend) hipLaunchKernelGGL((K<__VA_ARGS__ true, false, false>), grid, wg, 0, s, k, b, mass_eV, a);                    \
+        else if (sext) hipLaunchKernelGGL((K<__VA_ARGS__ false, true, false>), grid, wg, 0, s, k, b, mass_eV, a);                    \
+        else hipLaunchKernelGGL((K<__VA_ARGS__ false, false, false>), grid, wg, 0, s, k, b, mass_eV, a);                             \
     } while (0)
     if constexpr (sizeof(T) == 8) {
         CHX_DKD_TURNS_KINDS(dkd_turns_kernel_f64, );
@@ -2228,13 +2291,15 @@ extern "C" int chx_dkd_turns(const int32_t* kinds, const void* const* params, co
     TurnsCall c{x_in, charges, survival, aperture, x_out, lost_turn, sums, probe, N, K, first_turn, num_turns, record_every, 0, 0};
     if (!turns_call_ok(c)) return CHX_ERR_INVALID_ARG;
     if ((s_in == nullptr) != (s_out == nullptr)) return CHX_ERR_INVALID_ARG;
-    bool bend = false, sext = false;
+    bool bend = false, sext = false, rf = false;
     for (int64_t e = 0; e < E; ++e) {
-        if (!params[e] || (kinds[e] != CHX_DKD_DRIFT && kinds[e] != CHX_DKD_QUADRUPOLE && kinds[e] != CHX_DKD_DIPOLE && kinds[e] != CHX_DKD_SEXTUPOLE) ||
+        if (!params[e] || (kinds[e] != CHX_DKD_DRIFT && kinds[e] != CHX_DKD_QUADRUPOLE && kinds[e] != CHX_DKD_DIPOLE && kinds[e] != CHX_DKD_SEXTUPOLE &&
+                           kinds[e] != CHX_DKD_RFCAVITY) ||
             num_steps[e] < 1 || num_steps[e] >= (1 << 25) || fringe_at[e] < 0 || fringe_at[e] > 3)
             return CHX_ERR_INVALID_ARG;
         bend = bend || kinds[e] == CHX_DKD_DIPOLE;
         sext = sext || kinds[e] == CHX_DKD_SEXTUPOLE;
+        rf = rf || kinds[e] == CHX_DKD_RFCAVITY;
     }
     const int64_t tiles = (N + CHX_BLOCK - 1) / CHX_BLOCK;
     if (tiles > 0x7fffffffLL || num_turns * E >= 0x7fffffffLL) return CHX_ERR_INVALID_ARG;             // (grid sizes)
@@ -2252,9 +2317,9 @@ extern "C" int chx_dkd_turns(const int32_t* kinds, const void* const* params, co
         items.meta[e] = e < E ? (kinds[e] | (fringe_at[e] << 4) | (num_steps[e] << 6)) : 0;
     }
     if (dtype == CHX_F32)
-        return dkd_turns_launch<float>(items, (int)E, bend, sext, storage_precision, c, energy_in, energy_out, mass_eV, n_charges, s_in,
+        return dkd_turns_launch<float>(items, (int)E, bend, sext, rf, storage_precision, c, energy_in, energy_out, mass_eV, n_charges, s_in,
                                        s_out, workspace, l, tiles, (hipStream_t)stream);
-    return dkd_turns_launch<double>(items, (int)E, bend, sext, 0, c, energy_in, energy_out, mass_eV, n_charges, s_in, s_out, workspace, l,
+    return dkd_turns_launch<double>(items, (int)E, bend, sext, rf, 0, c, energy_in, energy_out, mass_eV, n_charges, s_in, s_out, workspace, l,
                                     tiles, (hipStream_t)stream);
 }
 
@@ -2276,7 +2341,7 @@ template <typename T>
 int dispatch_dkd_bwd(int kind, const void* x_in, const void* params, const void* energy, const void* dY, double mc2,
                      double nq, int num_steps, int fringe, int64_t B, int64_t Bx, int64_t Bp, int64_t Be, int64_t N,
                      void* dx, double* partials, hipStream_t s) {
-    const int P = chx_dkd_num_params(kind);
+    const int P = dkd_num_params(kind);
     switch (kind) {
         case CHX_DKD_DRIFT:
             return launch_dkd_bwd<T, CHX_DKD_DRIFT>(x_in, params, energy, dY, mc2, nq, num_steps, fringe, P, B, Bx, Bp,
@@ -2293,13 +2358,16 @@ int dispatch_dkd_bwd(int kind, const void* x_in, const void* params, const void*
         case CHX_DKD_SEXTUPOLE:
             return launch_dkd_bwd<T, CHX_DKD_SEXTUPOLE>(x_in, params, energy, dY, mc2, nq, num_steps, fringe, P, B, Bx,
                                                         Bp, Be, N, dx, partials, s);
+        case CHX_DKD_RFCAVITY:
+            return launch_dkd_bwd<T, CHX_DKD_RFCAVITY>(x_in, params, energy, dY, mc2, nq, num_steps, fringe, P, B, Bx,
+                                                       Bp, Be, N, dx, partials, s);
     }
     return CHX_ERR_INVALID_ARG;
 }
 }  // namespace
 
 extern "C" int64_t chx_dkd_bwd_partials_count(int kind, int64_t B, int64_t N) {
-    const int P = chx_dkd_num_params(kind);
+    const int P = dkd_num_params(kind);
     if (P < 0 || B < 0 || N < 0) return 0;
     return B * ((N + CHX_BLOCK - 1) / CHX_BLOCK) * (P + 1);
 }
@@ -2308,7 +2376,7 @@ extern "C" int chx_dkd_track_bwd(int kind, const void* x_in, const void* params,
                                  double mass_eV, double n_charges, int32_t num_steps, int32_t fringe_at, int64_t B,
                                  int64_t Bx, int64_t Bp, int64_t Be, int64_t N, int dtype, void* dx, double* partials,
                                  void* stream) {
-    if (chx_dkd_num_params(kind) < 0) return CHX_ERR_INVALID_ARG;
+    if (dkd_num_params(kind) < 0) return CHX_ERR_INVALID_ARG;
     if (dtype != CHX_F32 && dtype != CHX_F64) return CHX_ERR_DTYPE;
     if (B < 0 || N < 0) return CHX_ERR_INVALID_ARG;
     if (B == 0 || N == 0) return CHX_OK;
