@@ -12,6 +12,7 @@
 // dtype is (transcendental-heavy but far below the HBM time of the pass on 256 CUs).
 #include <cstdlib>
 #include <initializer_list>
+#include <type_traits>
 
 #include "chx_common.h"
 #include "chx_dual.h"
@@ -112,10 +113,39 @@ template <typename S>
 struct QuadCoef {
     S a11, a12, a21, a22, c1, c2, c3;
 };
+// cx = cos(sqrt(w) len) and sx = sin(sqrt(w) len) / sqrt(w) are entire functions of u = w len^2: cx = sum (-u)^n / (2n)!,
+// sx = len sum (-u)^n / (2n + 1)!. The closed forms below keep the VALUES to the last digit down to w == 0, which they treat as
+// a constant — but a tangent through them loses its digits near 0 (d sx / d w = (len cos - sx) / (2 w): a difference of order
+// u over u, 3e-5 off at k1 = 1e-12) and all of itself at 0, where d cx / d w = -len^2 / 2 and d sx / d w = -len^3 / 6. So the
+// dual-number evaluation, and it alone, takes the series inside |u| < 1e-4 (first term left out: u^5 / 10!, below 1e-26; the
+// closed forms' tangents are good to 2^-52 / |u| <= 3e-12 outside). The reference's autograd returns NaN at k1 == 0 (a complex
+// square root at 0); the limit is the definition.
+__device__ __forceinline__ bool quad_cs_series(Dual w, Dual len, Dual& cx, Dual& sx) {
+    const Dual u = w * len * len;
+    if (!(fabs(u.v) < 1e-4)) return false;
+    cx = 1.0 - u * (1.0 / 2.0 - u * (1.0 / 24.0 - u * (1.0 / 720.0 - u * (1.0 / 40320.0))));
+    sx = len * (1.0 - u * (1.0 / 6.0 - u * (1.0 / 120.0 - u * (1.0 / 5040.0 - u * (1.0 / 362880.0)))));
+    return true;
+}
+template <typename S>
+__device__ __forceinline__ QuadCoef<S> quad_from_cs(S k1, S len, S rel_p, S cx, S sx) {
+    QuadCoef<S> q;
+    q.a11 = cx;
+    q.a12 = sx / rel_p;
+    q.a21 = k1 * sx * rel_p;
+    q.a22 = cx;
+    q.c1 = k1 * (-cx * sx + len) / 4.0;
+    q.c2 = -k1 * (sx * sx) / (2.0 * rel_p);
+    q.c3 = -(cx * sx + len) / (4.0 * (rel_p * rel_p));
+    return q;
+}
 template <typename S>
 __device__ __forceinline__ QuadCoef<S> quad_coefficients(S k1, S len, S rel_p) {
     S cx, sx;
     const S w = -k1;
+    if constexpr (std::is_same<S, Dual>::value) {
+        if (quad_cs_series(w, len, cx, sx)) return quad_from_cs<S>(k1, len, rel_p, cx, sx);
+    }
     if (val(w) > 0.0) {
         const S k = m_sqrt(w);
         cx = m_cos(k * len);
@@ -128,15 +158,7 @@ __device__ __forceinline__ QuadCoef<S> quad_coefficients(S k1, S len, S rel_p) {
         cx = cst<S>(1.0);
         sx = len;
     }
-    QuadCoef<S> q;
-    q.a11 = cx;
-    q.a12 = sx / rel_p;
-    q.a21 = k1 * sx * rel_p;
-    q.a22 = cx;
-    q.c1 = k1 * (-cx * sx + len) / 4.0;
-    q.c2 = -k1 * (sx * sx) / (2.0 * rel_p);
-    q.c3 = -(cx * sx + len) / (4.0 * (rel_p * rel_p));
-    return q;
+    return quad_from_cs<S>(k1, len, rel_p, cx, sx);
 }
 // utils/autograd.py:669-670 (value) and :672-700 (derivatives, with the b == 0 limits -1/(2a^2), -1/(8a^3))
 __device__ __forceinline__ double sqrta2minusbdiva(double a, double b) {
