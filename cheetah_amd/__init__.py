@@ -22,6 +22,7 @@ from .accelerator import (  # noqa: F401
     LaserModulator,
     LSCKick,
     Marker,
+    Multipole,
     PhysicsWarning,
     Quadrupole,
     RBend,

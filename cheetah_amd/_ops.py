@@ -724,8 +724,8 @@ def cavity_track(x, R, coeffs, B, N):
 
 # ---------------------------------------------------------------------------------------------
 # non-linear tracking (drift_kick_drift, second_order)
-DKD_KIND = {"drift": 0, "quadrupole": 1, "dipole": 2, "tdc": 3, "sextupole": 5, "rfcavity": 6}    # (4: DKD_LINEAR below)
-DKD_NUM_PARAMS = [1, 5, 9, 7, None, 5, 4]
+DKD_KIND = {"drift": 0, "quadrupole": 1, "dipole": 2, "tdc": 3, "sextupole": 5, "rfcavity": 6, "multipole": 8}    # (4: DKD_LINEAR below; 7: no kind)
+DKD_NUM_PARAMS = [1, 5, 9, 7, None, 5, 4, None, 6]
 T_KIND = {"drift": 0, "quadrupole": 1, "dipole": 2, "sextupole": 3, "general": 4}
 T_NUM_PARAMS = [1, 5, 9, 5, 4]
 FRINGE_AT = {"neither": 0, "entrance": 1, "exit": 2, "both": 3}
@@ -833,7 +833,7 @@ def dkd_track(kind: int, particles, params, param_shape, energy, mass_eV: float,
     """One drift-kick-drift element (chx_dkd_track_p): particles (..., N, 7), params (Bp, P) with vector shape
     `param_shape`, energy (...). Returns (particles_out (*batch, N, 7), ref_energy (*energy/param batch)).
     `storage_precision` (DKD_PRECISION): float32 beams in float64 arithmetic (0), in float32 like the reference's own tensor code
-    (1), or mixed (2: the longitudinal pair in float64, the rest in float32; Drift, Quadrupole and Sextupole); the differentiable path always
+    (1), or mixed (2: the longitudinal pair in float64, the rest in float32; Drift, Quadrupole, Sextupole and Multipole); the differentiable path always
     runs in float64 (dual numbers)."""
     require_device(particles, params, energy)
     N = particles.shape[-2]
@@ -1040,7 +1040,7 @@ def dkd_turn_arrays(kinds, params, num_steps, fringe):
 
 def dkd_turns(arrays, storage, E, x_in, x_out, energy_in, energy_out, mass_eV, n_charges, charges, survival, first_turn, num_turns,
               record_every, aperture, lost_turn, sums, probe, ws, s_in=None, s_out=None) -> None:
-    """Turns [first_turn, first_turn + num_turns) of a ring of E drift-kick-drift Drifts, Quadrupoles, Dipoles, Sextupoles and RFCavities of one
+    """Turns [first_turn, first_turn + num_turns) of a ring of E drift-kick-drift Drifts, Quadrupoles, Dipoles, Sextupoles, RFCavities and Multipoles of one
     arithmetic mode `storage` (chx_dkd_turns): x_in (N, 7) -> x_out (the same tensor from the second chunk on), energy_in (0-d, in front of
     first_turn) -> energy_out (0-d, behind the last turn; may be the same tensor), the rest as `second_order_turns`. Launches only,
     no synchronisation."""

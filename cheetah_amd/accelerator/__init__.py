@@ -9,7 +9,7 @@ from .ibs import IBSKick  # noqa: F401
 from .laser_modulator import LaserModulator, laser_modulation_amplitude  # noqa: F401
 from .lsc import LSCKick  # noqa: F401
 from .marker import BPM, Aperture, Marker  # noqa: F401
-from .misc_elements import RFCavity, Sextupole, Solenoid, TransverseDeflectingCavity, Undulator  # noqa: F401
+from .misc_elements import Multipole, RFCavity, Sextupole, Solenoid, TransverseDeflectingCavity, Undulator  # noqa: F401
 from .quadrupole import Quadrupole  # noqa: F401
 from .screen import Screen  # noqa: F401
 from .segment import Segment  # noqa: F401

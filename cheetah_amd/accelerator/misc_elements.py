@@ -322,3 +322,99 @@ class RFCavity(Element):
     @property
     def defining_features(self) -> list[str]:
         return super().defining_features + ["length", "voltage", "phase", "frequency"]
+
+
+class Multipole(Element):
+    """Thin multipole kicks of ONE order m between Bmad's exact drifts (not in the reference; MAD-X's `MULTIPOLE`, Elegant's `MULT`,
+    from the reference's Bmad-X building blocks): drift L / 2n, then n x (kick, drift L / n; L / 2n behind the last kick) inside
+    the misalignment and tilt transformations, every kick
+
+        d px - i d py = -(knl + i ksl) / n (x + i y)^m / m!
+
+    `order` m is a Python int and a constant of the element: 0 a dipole kick, 1 a quadrupole, 2 a sextupole, 3 an octupole. `knl`
+    and `ksl` are the INTEGRATED normal and skew strengths in m^-m (MAD-X's knl / ksl), so a thin element (`length = 0`) is the
+    common case: the drifts then leave the coordinates alone and `s` stays. `Sextupole(L, k2)` is `Multipole(L, 2, knl=k2 L)`, a
+    horizontal corrector of angle theta is order 0 with knl = -theta, a skew quadrupole order 1 with `ksl`. Tracked per particle by
+    chx_dkd_track (drift_kick_drift only), symplectic, in one chain call with its neighbours (`Segment.track`) and inside the
+    fused ring (`Segment.track_turns`). `num_steps` = n as for the Sextupole."""
+
+    supported_tracking_methods = ["drift_kick_drift"]
+    _dkd_kind = _ops.DKD_KIND["multipole"]
+
+    def __init__(self, length, order, knl=None, ksl=None, misalignment=None, tilt=None, num_steps=1,
+                 tracking_method="drift_kick_drift", name=None, sanitize_name=None, metadata=None, device=None, dtype=None) -> None:
+        fk = {"device": device, "dtype": dtype}
+        super().__init__(name=name, sanitize_name=sanitize_name, metadata=metadata, **fk)
+        z = lambda v: v if v is not None else torch.tensor(0.0, **fk)  # noqa: E731
+        if bool((torch.as_tensor(length) < 0).any()):
+            raise ValueError(f"Multipole.length must not be negative, got {length!r}")
+        self.length = length
+        self.order = order
+        self.register_buffer_or_parameter("knl", z(knl))
+        self.register_buffer_or_parameter("ksl", z(ksl))
+        self.register_buffer_or_parameter(
+            "misalignment", misalignment if misalignment is not None else torch.tensor((0.0, 0.0), **fk))
+        self.register_buffer_or_parameter("tilt", z(tilt))
+        self.num_steps = num_steps
+        self._tracking_method = "drift_kick_drift"
+        self.tracking_method = tracking_method
+
+    @property
+    def order(self) -> int:
+        """The order m of the kick (x + i y)^m: an int of 0 .. 3 (what the two `fringe_at` bits of the kernels' arguments hold)."""
+        return self._order
+
+    @order.setter
+    def order(self, value) -> None:
+        if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value <= 3:
+            raise ValueError(f"Multipole.order must be an int of 0 .. 3 (dipole, quadrupole, sextupole, octupole), got {value!r}")
+        self._order = value
+
+    @property
+    def num_steps(self) -> int:
+        """Number of thin kicks (an int of 1 .. 2^25 - 1, what the chain's packing holds)."""
+        return self._num_steps
+
+    @num_steps.setter
+    def num_steps(self, value) -> None:
+        try:
+            steps = None if isinstance(value, bool) else operator.index(value)
+        except TypeError:
+            steps = None
+        if steps is None or not 1 <= steps < (1 << 25):
+            raise ValueError(f"Multipole.num_steps must be an int of 1 .. {(1 << 25) - 1}, got {value!r}")
+        self._num_steps = steps
+
+    def _dkd_params(self):
+        return [self.length, self.knl, self.ksl, self.tilt, self.misalignment[..., 0], self.misalignment[..., 1]]
+
+    def _dkd_scalar_refs(self):
+        length, knl, ksl, tilt, m = self._settings("length", "knl", "ksl", "tilt", "misalignment")
+        return [(length, None), (knl, None), (ksl, None), (tilt, None), (m, 0), (m, 1)]
+
+    def _dkd_options(self):
+        return self._num_steps, self._order         # (the order travels where a Dipole's fringe bits do: include/chx.h)
+
+    @property
+    def is_active(self) -> bool:
+        return bool(torch.logical_or(self.knl != 0, self.ksl != 0).any().item())
+
+    @property
+    def is_skippable(self) -> bool:
+        return False
+
+    @property
+    def defining_features(self) -> list[str]:
+        return super().defining_features + ["length", "order", "knl", "ksl", "misalignment", "tilt"]
+
+    def clone(self) -> "Multipole":
+        clone = super().clone()
+        clone.num_steps = self._num_steps
+        return clone
+
+    def _json_extras(self) -> dict:
+        return {"num_steps": self._num_steps} if self._num_steps != 1 else {}
+
+    def __repr__(self) -> str:
+        text = super().__repr__()
+        return text if self._num_steps == 1 else f"{text[:-1]}, num_steps={self._num_steps})"

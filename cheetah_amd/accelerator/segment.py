@@ -108,7 +108,7 @@ class _ElementList(nn.ModuleList):
 _CHECK_PLANS = os.environ.get("CHX_CHECK_PLANS", "0") == "1"
 #: drift-kick-drift kinds chx_dkd_chain carries through a run in registers
 _DKD_IN_REGISTERS = (_ops.DKD_KIND["drift"], _ops.DKD_KIND["quadrupole"], _ops.DKD_KIND["dipole"], _ops.DKD_KIND["sextupole"],
-                     _ops.DKD_KIND["rfcavity"])
+                     _ops.DKD_KIND["rfcavity"], _ops.DKD_KIND["multipole"])
 #: what `Segment._turn_items` hands `_track_turns_fused` for a ring of drift-kick-drift elements (chx_dkd_turns): per element the
 #: kind, the (1, P) parameter tensor, num_steps and fringe_at; `storage` = the ring's one arithmetic mode
 _DkdRing = collections.namedtuple("_DkdRing", "kinds params num_steps fringe_at storage")
@@ -871,7 +871,7 @@ class Segment(Element):
         return ring
 
     def _turn_items_dkd(self, plan, x: torch.Tensor):
-        """A `_DkdRing` when the WHOLE plan is a ring `chx_dkd_turns` takes — drift-kick-drift Drifts, Quadrupoles, Dipoles, Sextupoles and RFCavities as
+        """A `_DkdRing` when the WHOLE plan is a ring `chx_dkd_turns` takes — drift-kick-drift Drifts, Quadrupoles, Dipoles, Sextupoles, RFCavities and Multipoles as
         `_dkd_run` keeps them in registers, all of one arithmetic class, 1 to 192 of them, Markers in between skipped — else the
         reason (a str) why not. Nothing is kept between calls: settings and `dkd_precision` are read here every time."""
         kinds, params, steps, fringes, classes, tensors = [], [], [], [], [], []
@@ -885,7 +885,7 @@ class Segment(Element):
             cls = type(e)
             name = f"{cls.__name__} '{e.name}'"
             if e._tracking_method != "drift_kick_drift" or e._dkd_kind not in _DKD_IN_REGISTERS:
-                return f"{name} (tracking method '{e._tracking_method}') is not a drift-kick-drift Drift, Quadrupole, Dipole, Sextupole or RFCavity"
+                return f"{name} (tracking method '{e._tracking_method}') is not a drift-kick-drift Drift, Quadrupole, Dipole, Sextupole, RFCavity or Multipole"
             if cls.track is not Element.track or cls._track_drift_kick_drift is not Element._track_drift_kick_drift \
                     or cls._track_internal is not Element._track_internal:
                 return f"{name} overrides `track`"
@@ -930,7 +930,7 @@ class Segment(Element):
         in registers from turn to turn (`chx_second_order_turns`); the turns are split into launches of at most 65 536 item
         steps. The particles are those of `num_turns` calls of `track`, bit for bit.
         It also takes a ring of DRIFT-KICK-DRIFT elements (`chx_dkd_turns`), the symplectic Bmad-X maps: every item of the plan a
-        Drift, Quadrupole, Dipole, Sextupole or RFCavity with `tracking_method="drift_kick_drift"`, scalar settings of the beam's dtype without
+        Drift, Quadrupole, Dipole, Sextupole, RFCavity or Multipole with `tracking_method="drift_kick_drift"`, scalar settings of the beam's dtype without
         gradients and the stock `track`, all of one arithmetic class (`dkd_precision`; a float64 beam forms one class), 1 to 192
         of them, Markers in between skipped, under the same conditions on the beam. Every such element leaves the reference
         energy as sqrt(sqrt(E^2 - m^2)^2 + m^2) in the beam's dtype. That round trip is monotone and ends in a fixed point, but
@@ -1128,7 +1128,7 @@ class Segment(Element):
                 break
             j += 1
             after.append(j)
-        # the arithmetic class of every item: a linear run goes with any (None); Drifts, Quadrupoles, Dipoles, Sextupoles and RFCavities with their
+        # the arithmetic class of every item: a linear run goes with any (None); Drifts, Quadrupoles, Dipoles, Sextupoles, RFCavities and Multipoles with their
         # `dkd_precision` (float64 beams are evaluated in fp64 whatever it says: one class); anything else has none (-1)
         single = x.dtype == torch.float64
         classes = [None if a is None else ((0 if single else a[4]) if a[0] in _DKD_IN_REGISTERS and x.dtype in (torch.float32, torch.float64)

@@ -1,6 +1,6 @@
 // chx_nonlinear.hip — per-particle non-linear tracking for gfx950.
 //
-//  * drift-kick-drift (Bmad-X) tracking of Drift, Quadrupole, Dipole, TransverseDeflectingCavity, Sextupole and RFCavity:
+//  * drift-kick-drift (Bmad-X) tracking of Drift, Quadrupole, Dipole, TransverseDeflectingCavity, Sextupole, RFCavity and Multipole:
 //    cheetah/accelerator/drift.py:106-154, quadrupole.py:168-251, dipole.py:183-370,
 //    transverse_deflecting_cavity.py:122-209 on top of cheetah/utils/bmadx.py;
 //  * second-order (MAD-convention T tensor) tracking: element.py:195-228 with the tensors of
@@ -26,6 +26,7 @@ static int dkd_num_params(int kind) {
         case CHX_DKD_TDC: return 7;
         case CHX_DKD_SEXTUPOLE: return 5;
         case CHX_DKD_RFCAVITY: return 4;
+        case CHX_DKD_MULTIPOLE: return 6;
     }
     return -1;
 }
@@ -236,6 +237,18 @@ __device__ void dkd_constants(int kind, const S* par, S E, double mc2, double nq
         c[C_B] = V * fabs(nq);               // the energy a particle gains on the crest, in eV
         turn_sincos(phase, c[C_C], c[C_D]);  // S0 = sin(2 pi phase), C0 = cos(2 pi phase): phase = 0 and 0.5 are exact zero crossings
         c[C_E2] = freq;
+    } else if (kind == CHX_DKD_MULTIPOLE) {
+        // `fringe` carries the order m = 0 .. 3 of the kick (include/chx.h). 1 / m! goes into the strengths here, so the kick is
+        // C_B Re (x + i y)^m - C_C Im (x + i y)^m with no factorial left in it; m itself in a slot of its own (wave-uniform)
+        const S L = par[0], knl = par[1], ksl = par[2], tilt = par[3];
+        c[C_SIN] = m_sin(tilt); c[C_COS] = m_cos(tilt);
+        c[C_XO] = par[4]; c[C_YO] = par[5];
+        c[C_A] = L;
+        const int m = fringe & 3;
+        const double inv_fact = m < 2 ? 1.0 : (m == 2 ? 0.5 : 1.0 / 6.0);
+        c[C_B] = knl * inv_fact;  // the integrated strengths: every one of the n kicks applies 1 / n of them
+        c[C_C] = ksl * inv_fact;
+        c[C_D] = cst<S>((double)m);
     } else {  // CHX_DKD_TDC
         const S L = par[0], V = par[1], phase = par[2], freq = par[3];
         const S tilt = par[4];
@@ -323,6 +336,26 @@ __device__ __forceinline__ void dkd_particle(const S* c, Bmad<S>& q, double mc2,
         for (int s = 0; s < num_steps; ++s) {
             q.px = q.px - 0.5 * kappa * (q.x * q.x - q.y * q.y);
             q.py = q.py + kappa * q.x * q.y;
+            track_a_drift<S>(s + 1 < num_steps ? 2.0 * h : h, q, p0c, mc2);
+        }
+        offset_unset<S>(c[C_XO], c[C_YO], c[C_SIN], c[C_COS], q);
+    } else if (KIND == CHX_DKD_MULTIPOLE) {
+        // The Sextupole's frame with the kick of one order m: d px - i d py = -(knl + i ksl) / n (x + i y)^m / m!. The power by m
+        // complex multiplications from 1, no pow and no branch on a value: the dual-number evaluation has the right tangent at
+        // x = y = 0 and at knl = ksl = 0 (m is wave-uniform). length = 0: the drifts add 0 to x, y and z.
+        const S h = c[C_A] / (2.0 * (double)num_steps), bn = c[C_B] / (double)num_steps, an = c[C_C] / (double)num_steps;
+        const int m = (int)val(c[C_D]);
+        offset_set<S>(c[C_XO], c[C_YO], c[C_SIN], c[C_COS], q);
+        track_a_drift<S>(h, q, p0c, mc2);
+        for (int s = 0; s < num_steps; ++s) {
+            S re = cst<S>(1.0), im = cst<S>(0.0);
+            for (int k = 0; k < m; ++k) {
+                const S r = re * q.x - im * q.y;
+                im = re * q.y + im * q.x;
+                re = r;
+            }
+            q.px = q.px - (bn * re - an * im);
+            q.py = q.py + (bn * im + an * re);
             track_a_drift<S>(s + 1 < num_steps ? 2.0 * h : h, q, p0c, mc2);
         }
         offset_unset<S>(c[C_XO], c[C_YO], c[C_SIN], c[C_COS], q);
@@ -484,8 +517,8 @@ __device__ __forceinline__ void dkd_mixed_particle(const double* __restrict__ cs
     // A quadrupole that is shifted off the axis (quadrupole.py:199-215 subtracts the misalignment before its map): the shifted
     // coordinate may be hundreds of beam sizes, float32 steps on it lose digits of the BEAM's scale and its path-length terms
     // dwarf tau — such an element is evaluated in float64 like dkd_kernel<float, ., double> (workgroup-uniform decision).
-    // A shifted sextupole likewise: its kick is quadratic in the shifted coordinate.
-    if ((KIND == CHX_DKD_QUADRUPOLE || KIND == CHX_DKD_SEXTUPOLE) && (cst_[C_XO] != 0.0 || cst_[C_YO] != 0.0)) {
+    // A shifted sextupole likewise: its kick is quadratic in the shifted coordinate. A shifted Multipole as a shifted Sextupole.
+    if ((KIND == CHX_DKD_QUADRUPOLE || KIND == CHX_DKD_SEXTUPOLE || KIND == CHX_DKD_MULTIPOLE) && (cst_[C_XO] != 0.0 || cst_[C_YO] != 0.0)) {
         double in[6], out[6];
 #pragma unroll
         for (int j = 0; j < 6; ++j) in[j] = (double)v[j];
@@ -521,7 +554,7 @@ __device__ __forceinline__ void dkd_mixed_particle(const double* __restrict__ cs
         x = x + L * Px * iPl;
         y = y + L * Py * iPl;
         z = z + (double)(L * (so_a + so_b * iPl));
-    } else if (KIND == CHX_DKD_SEXTUPOLE) {                       // drifts as in the branch above around float32 kicks
+    } else if (KIND == CHX_DKD_SEXTUPOLE || KIND == CHX_DKD_MULTIPOLE) {   // drifts as in the branch above around float32 kicks
         const double sn = cst_[C_SIN], cs = cst_[C_COS];          // (here xo = yo = 0: the rotations as in the quadrupole's branch)
         const bool upright = sn == 0.0 && cs == 1.0;
         if (!upright) {
@@ -530,15 +563,27 @@ __device__ __forceinline__ void dkd_mixed_particle(const double* __restrict__ cs
             x = xr; y = yr; px = pxr; py = pyr;
         }
         const float h = (float)cst_[C_A] / (2.0f * (float)num_steps), kappa = (float)cst_[C_B] / (float)num_steps;
+        // (a Multipole: kappa = knl / (m! n), skew = ksl / (m! n), and the order m — see dkd_particle)
+        const float skew = KIND == CHX_DKD_MULTIPOLE ? (float)cst_[C_C] / (float)num_steps : 0.0f;
+        const int order = KIND == CHX_DKD_MULTIPOLE ? (int)cst_[C_D] : 2;
         // pz does not change inside the magnet: 1 / (1 + pz) and the energy term of dz are the same for every drift
         const float ir = __builtin_amdgcn_rcpf(relp);
         const float pcf = p0cf * relp, m2 = mc2f * mc2f;
         const float a = (m2 * (2.0f * pzf + pzf * pzf)) * __builtin_amdgcn_rcpf(pcf * pcf + m2);
         const float so_a = a * __builtin_amdgcn_rcpf(__builtin_amdgcn_sqrtf(1.0f + a) + 1.0f);          // sqrt_one(a)
         for (int s = 0; s <= num_steps; ++s) {
-            if (s > 0) {
+            if (s > 0 && KIND == CHX_DKD_SEXTUPOLE) {
                 px = px - 0.5f * kappa * (x * x - y * y);
                 py = py + kappa * x * y;
+            } else if (s > 0) {
+                float re = 1.0f, im = 0.0f;
+                for (int k = 0; k < order; ++k) {
+                    const float r = re * x - im * y;
+                    im = re * y + im * x;
+                    re = r;
+                }
+                px = px - (kappa * re - skew * im);
+                py = py + (kappa * im + skew * re);
             }
             const float L = (s == 0 || s == num_steps) ? h : 2.0f * h;
             const float Px = px * ir, Py = py * ir;
@@ -602,12 +647,13 @@ __device__ __forceinline__ void dkd_mixed_particle(const double* __restrict__ cs
     v[5] = (float)((en - ref) * inv_p0c);
 }
 
+// (the kernel's text, shared by dkd_mixed_kernel and dkd_mixed_multipole_kernel; `fringe` is what dkd_constants receives)
 template <int KIND>
-__global__ __launch_bounds__(CHX_BLOCK) void dkd_mixed_kernel(const float* __restrict__ x_in, const float* __restrict__ params,
-                                                              const float* __restrict__ energy, double mc2, double nq, int num_steps,
-                                                              int P, int64_t B, int64_t Bx, int64_t Bp, int64_t Be, int64_t N,
-                                                              float* __restrict__ x_out, float* __restrict__ energy_out,
-                                                              int in_vec_ok, int out_vec_ok) {
+__device__ __forceinline__ void dkd_mixed_tile(const float* __restrict__ x_in, const float* __restrict__ params,
+                                               const float* __restrict__ energy, double mc2, double nq, int num_steps, int fringe,
+                                               int P, int64_t B, int64_t Bx, int64_t Bp, int64_t Be, int64_t N,
+                                               float* __restrict__ x_out, float* __restrict__ energy_out,
+                                               int in_vec_ok, int out_vec_ok) {
     constexpr int TP = CHX_BLOCK;
     __shared__ __attribute__((aligned(16))) float lds[TP * 7];
     __shared__ double cst_[C_MIXED_N];
@@ -621,7 +667,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_mixed_kernel(const float* __res
         const float Eb = energy[(Be == 1) ? 0 : b];
         double par[CHX_MAX_PARAMS];
         for (int k = 0; k < P; ++k) par[k] = (double)params[((Bp == 1) ? 0 : b) * P + k];
-        dkd_constants<double>(KIND, par, (double)Eb, mc2, nq, 3, cst_);
+        dkd_constants<double>(KIND, par, (double)Eb, mc2, nq, fringe, cst_);
         dkd_mixed_constants(cst_, mc2);
         if (t == 0 && energy_out) {
             const float m = (float)mc2;
@@ -642,6 +688,25 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_mixed_kernel(const float* __res
     }
     __syncthreads();
     tile_store<float, TP>(x_out + (b * N + n0) * 7, lds, np * 7, out_vec, true);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(CHX_BLOCK) void dkd_mixed_kernel(const float* __restrict__ x_in, const float* __restrict__ params,
+                                                              const float* __restrict__ energy, double mc2, double nq, int num_steps,
+                                                              int P, int64_t B, int64_t Bx, int64_t Bp, int64_t Be, int64_t N,
+                                                              float* __restrict__ x_out, float* __restrict__ energy_out,
+                                                              int in_vec_ok, int out_vec_ok) {
+    dkd_mixed_tile<KIND>(x_in, params, energy, mc2, nq, num_steps, 3, P, B, Bx, Bp, Be, N, x_out, energy_out, in_vec_ok, out_vec_ok);
+}
+
+// a Multipole in mixed arithmetic: the same with the order as an argument (the kinds above read no fringe bits)
+__global__ __launch_bounds__(CHX_BLOCK) void dkd_mixed_multipole_kernel(const float* __restrict__ x_in, const float* __restrict__ params,
+                                                                        const float* __restrict__ energy, double mc2, double nq,
+                                                                        int num_steps, int order, int P, int64_t B, int64_t Bx, int64_t Bp,
+                                                                        int64_t Be, int64_t N, float* __restrict__ x_out,
+                                                                        float* __restrict__ energy_out, int in_vec_ok, int out_vec_ok) {
+    dkd_mixed_tile<CHX_DKD_MULTIPOLE>(x_in, params, energy, mc2, nq, num_steps, order, P, B, Bx, Bp, Be, N, x_out, energy_out, in_vec_ok,
+                                      out_vec_ok);
 }
 
 // Backward of the above. dx[n][m] = sum_i dY[n][i] d out_i / d in_m (six passes, coordinate m seeded), and per
@@ -763,15 +828,21 @@ int dispatch_dkd(int kind, const void* x_in, const void* params, const void* ene
         case CHX_DKD_RFCAVITY:
             return launch_dkd<T, CHX_DKD_RFCAVITY, C>(x_in, params, energy, mc2, nq, num_steps, fringe, P, B, Bx, Bp, Be,
                                                    N, x_out, energy_out, s);
+        case CHX_DKD_MULTIPOLE:
+            return launch_dkd<T, CHX_DKD_MULTIPOLE, C>(x_in, params, energy, mc2, nq, num_steps, fringe, P, B, Bx, Bp, Be,
+                                                    N, x_out, energy_out, s);
     }
     return CHX_ERR_INVALID_ARG;
 }
 
 }  // namespace
 
-// The exported query keeps the answers it gave before CHX_DKD_RFCAVITY existed (callers of ABI 9 probe the kinds with it, and 6
-// was "no such kind"); the entry points count the cavity's four parameters through dkd_num_params.
-extern "C" int chx_dkd_num_params(int kind) { return kind == CHX_DKD_RFCAVITY ? -1 : dkd_num_params(kind); }
+// The exported query keeps the answers it gave before CHX_DKD_RFCAVITY and CHX_DKD_MULTIPOLE existed (callers of ABI 9 probe the
+// kinds with it, and 6 and 8 were "no such kind"); the entry points count the cavity's four parameters and the multipole's six
+// through dkd_num_params.
+extern "C" int chx_dkd_num_params(int kind) {
+    return kind == CHX_DKD_RFCAVITY || kind == CHX_DKD_MULTIPOLE ? -1 : dkd_num_params(kind);
+}
 
 extern "C" int chx_dkd_track(int kind, const void* x_in, const void* params, const void* energy, double mass_eV,
                              double n_charges, int32_t num_steps, int32_t fringe_at, int64_t B, int64_t Bx,
@@ -791,11 +862,12 @@ extern "C" int chx_dkd_track_p(int kind, const void* x_in, const void* params, c
     if (B == 0 || N == 0) return CHX_OK;
     if (!x_in || !params || !energy || !x_out) return CHX_ERR_INVALID_ARG;
     if (!chx_bcast_ok(Bx, B) || !chx_bcast_ok(Bp, B) || !chx_bcast_ok(Be, B)) return CHX_ERR_INVALID_ARG;
-    if ((kind == CHX_DKD_QUADRUPOLE || kind == CHX_DKD_SEXTUPOLE) && num_steps < 1) return CHX_ERR_INVALID_ARG;
-    if (kind == CHX_DKD_SEXTUPOLE && num_steps >= (1 << 25)) return CHX_ERR_INVALID_ARG;        // (the chain's and the ring's cap)
+    if ((kind == CHX_DKD_QUADRUPOLE || kind == CHX_DKD_SEXTUPOLE || kind == CHX_DKD_MULTIPOLE) && num_steps < 1) return CHX_ERR_INVALID_ARG;
+    if ((kind == CHX_DKD_SEXTUPOLE || kind == CHX_DKD_MULTIPOLE) && num_steps >= (1 << 25)) return CHX_ERR_INVALID_ARG;        // (the chain's and the ring's cap)
     if (fringe_at < 0 || fringe_at > 3) return CHX_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == CHX_F32 && storage_precision == 2 && (kind == CHX_DKD_DRIFT || kind == CHX_DKD_QUADRUPOLE || kind == CHX_DKD_SEXTUPOLE)) {
+    if (dtype == CHX_F32 && storage_precision == 2 &&
+        (kind == CHX_DKD_DRIFT || kind == CHX_DKD_QUADRUPOLE || kind == CHX_DKD_SEXTUPOLE || kind == CHX_DKD_MULTIPOLE)) {
         // mixed arithmetic (see dkd_mixed_kernel); the other kinds — Dipole, TDC, RFCavity — keep the fp64 evaluation
         const int64_t tiles = ((N + CHX_BLOCK - 1) / CHX_BLOCK) * B;
         if (tiles > 0x7fffffffLL) return CHX_ERR_INVALID_ARG;
@@ -803,6 +875,10 @@ extern "C" int chx_dkd_track_p(int kind, const void* x_in, const void* params, c
         if (kind == CHX_DKD_DRIFT)
             hipLaunchKernelGGL(dkd_mixed_kernel<CHX_DKD_DRIFT>, dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const float*)x_in,
                                (const float*)params, (const float*)energy, mass_eV, n_charges, num_steps, P, B, Bx, Bp, Be, N,
+                               (float*)x_out, (float*)energy_out, (int)chx_aligned16(x_in), (int)chx_aligned16(x_out));
+        else if (kind == CHX_DKD_MULTIPOLE)          // (fringe_at: the order)
+            hipLaunchKernelGGL(dkd_mixed_multipole_kernel, dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const float*)x_in,
+                               (const float*)params, (const float*)energy, mass_eV, n_charges, num_steps, fringe_at, P, B, Bx, Bp, Be, N,
                                (float*)x_out, (float*)energy_out, (int)chx_aligned16(x_in), (int)chx_aligned16(x_out));
         else if (kind == CHX_DKD_SEXTUPOLE)
             hipLaunchKernelGGL(dkd_mixed_kernel<CHX_DKD_SEXTUPOLE>, dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const float*)x_in,
@@ -890,7 +966,7 @@ __device__ __forceinline__ void dkd_item_constants(int kind, int fringe, int ste
     int32_t* w = reinterpret_cast<int32_t*>(out + kDkdMeta);
     w[0] = kind;
     w[1] = steps;
-    const int P = kind == CHX_DKD_DRIFT ? 1 : (kind == CHX_DKD_DIPOLE ? 9 : (kind == CHX_DKD_RFCAVITY ? 4 : 5));          // (Quadrupole, Sextupole: 5)
+    const int P = kind == CHX_DKD_DRIFT ? 1 : (kind == CHX_DKD_DIPOLE ? 9 : (kind == CHX_DKD_RFCAVITY ? 4 : (kind == CHX_DKD_MULTIPOLE ? 6 : 5)));          // (Quadrupole, Sextupole: 5)
     double par[CHX_MAX_PARAMS];
     for (int k = 0; k < P; ++k) par[k] = (double)pe[k];
     double c[C_MIXED_N];
@@ -1009,12 +1085,14 @@ __device__ __forceinline__ void dkd_copy6(const T (&from)[6], T (&to)[6]) {
 // SEXT: the run contains Sextupoles (a run without one is the instantiation it was before they existed: the branch is not compiled)
 // RF: the run contains RFCavities, likewise; such a run always has BEND = SEXT = true as well (one more kernel per arithmetic
 //     mode, not four)
+// MP: the run contains Multipoles, likewise; such a run always has BEND = SEXT = RF = true as well (again one more kernel per
+//     arithmetic mode)
 // LINEAR: items of kind kDkdLinear may stand in the run (a chain; a ring has none, and its code has no such branch)
 // A new element kind is one line of the dispatch below.
 // The loop runs on a copy of x that is the function's own: a function is optimised before it is inlined into its caller, and
 // there the lane's registers are memory behind a reference — a loop over them comes out in another shape than a loop over locals,
 // at 3 to 6 VGPRs more per ring kernel and a wave per SIMD fewer in six of them (profiles/turn_frame.md).
-template <int MODE, bool BEND, bool SEXT, bool RF, bool LINEAR, typename T>
+template <int MODE, bool BEND, bool SEXT, bool RF, bool MP, bool LINEAR, typename T>
 __device__ __forceinline__ void dkd_items(const double* __restrict__ cst, int E, double mc2, T (&lane)[6], T& lane6) {
     T v[6], v6 = lane6;
     dkd_copy6(lane, v);
@@ -1035,6 +1113,7 @@ __device__ __forceinline__ void dkd_items(const double* __restrict__ cst, int E,
         if (kind == CHX_DKD_DRIFT) dkd_chain_step<MODE, CHX_DKD_DRIFT>(c, mc2, steps, v);
         else if (SEXT && kind == CHX_DKD_SEXTUPOLE) dkd_chain_step<MODE, CHX_DKD_SEXTUPOLE>(c, mc2, steps, v);
         else if (RF && kind == CHX_DKD_RFCAVITY) dkd_chain_step<MODE, CHX_DKD_RFCAVITY>(c, mc2, steps, v);
+        else if (MP && kind == CHX_DKD_MULTIPOLE) dkd_chain_step<MODE, CHX_DKD_MULTIPOLE>(c, mc2, steps, v);
         else if (!BEND || kind == CHX_DKD_QUADRUPOLE) dkd_chain_step<MODE, CHX_DKD_QUADRUPOLE>(c, mc2, steps, v);
         else dkd_chain_step<MODE, CHX_DKD_DIPOLE>(c, mc2, steps, v);
         v6 = (T)1;
@@ -1043,9 +1122,9 @@ __device__ __forceinline__ void dkd_items(const double* __restrict__ cst, int E,
     lane6 = v6;
 }
 
-// a particle per lane through all items of the run, MODE / BEND / SEXT / RF as in dkd_items (x_out may be x_in: a tile is read whole
+// a particle per lane through all items of the run, MODE / BEND / SEXT / RF / MP as in dkd_items (x_out may be x_in: a tile is read whole
 // before it is written)
-template <int MODE, bool BEND, bool SEXT, bool RF, typename T>
+template <int MODE, bool BEND, bool SEXT, bool RF, bool MP, typename T>
 __device__ __forceinline__ void dkd_chain_tile(const T* x_in, const double* __restrict__ cst, int E, double mc2, T* x_out, int64_t N,
                                                int in_vec_ok, int out_vec_ok) {
     constexpr int TP = CHX_BLOCK;
@@ -1058,7 +1137,7 @@ __device__ __forceinline__ void dkd_chain_tile(const T* x_in, const double* __re
     T v[6], v6 = p < np ? lds[p * 7 + 6] : (T)1;
 #pragma unroll
     for (int j = 0; j < 6; ++j) v[j] = p < np ? lds[p * 7 + j] : (T)0;
-    dkd_items<MODE, BEND, SEXT, RF, true, T>(cst, E, mc2, v, v6);
+    dkd_items<MODE, BEND, SEXT, RF, MP, true, T>(cst, E, mc2, v, v6);
     if (p < np) {
 #pragma unroll
         for (int j = 0; j < 6; ++j) lds[p * 7 + j] = v[j];
@@ -1068,16 +1147,16 @@ __device__ __forceinline__ void dkd_chain_tile(const T* x_in, const double* __re
     tile_store<T, TP>(x_out + n0 * 7, lds, np * 7, out_vec_ok != 0, true);
 }
 
-template <int MODE, bool BEND, bool SEXT, bool RF>
+template <int MODE, bool BEND, bool SEXT, bool RF, bool MP>
 __global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel(const float* x_in, const double* __restrict__ cst, int E, double mc2,
                                                               float* x_out, int64_t N, int in_vec_ok, int out_vec_ok) {
-    dkd_chain_tile<MODE, BEND, SEXT, RF, float>(x_in, cst, E, mc2, x_out, N, in_vec_ok, out_vec_ok);
+    dkd_chain_tile<MODE, BEND, SEXT, RF, MP, float>(x_in, cst, E, mc2, x_out, N, in_vec_ok, out_vec_ok);
 }
 
-template <bool BEND, bool SEXT, bool RF>
+template <bool BEND, bool SEXT, bool RF, bool MP>
 __global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel_f64(const double* x_in, const double* __restrict__ cst, int E, double mc2,
                                                                   double* x_out, int64_t N, int in_vec_ok, int out_vec_ok) {
-    dkd_chain_tile<0, BEND, SEXT, RF, double>(x_in, cst, E, mc2, x_out, N, in_vec_ok, out_vec_ok);
+    dkd_chain_tile<0, BEND, SEXT, RF, MP, double>(x_in, cst, E, mc2, x_out, N, in_vec_ok, out_vec_ok);
 }
 }  // namespace
 
@@ -1142,23 +1221,24 @@ extern "C" int chx_dkd_chain_mixed(const int32_t* kinds, const void* const* para
             first = e;
         }
     }
-    // Drifts, Quadrupoles, Dipoles, Sextupoles, RFCavities (float32: of one arithmetic mode) and linear runs, the constants (448 bytes per item) in x_tmp:
+    // Drifts, Quadrupoles, Dipoles, Sextupoles, RFCavities, Multipoles (float32: of one arithmetic mode) and linear runs, the constants (448 bytes per item) in x_tmp:
     // the particles stay in registers (dkd_chain_kernel, dkd_chain_kernel_f64), two launches per 192 items, the same bits
     static const bool fused_off = [] { const char* v = getenv("CHX_DKD_CHAIN_FUSED"); return v && v[0] == '0'; }();
     // (a longer run takes several such pairs, the later ones in place on x_out: a workgroup holds its whole tile in registers
     // before it writes)
     const int64_t per_pass = std::min<int64_t>(kDkdChainMax, N * 7 * (int64_t)esz / (kDkdCstStride * (int64_t)sizeof(double)));
     bool fuse = !fused_off && E >= 2 && per_pass >= 2 && chx_aligned16(x_tmp) && first >= 0;
-    bool bend = false, sext = false, rf = false;
+    bool bend = false, sext = false, rf = false, mp = false;
     for (int64_t e = 0; fuse && e < E; ++e) {      // (float64 beams ignore storage_precision, like chx_dkd_track_p)
         if (kinds[e] == kDkdLinear) continue;
         fuse = (kinds[e] == CHX_DKD_DRIFT || kinds[e] == CHX_DKD_QUADRUPOLE || kinds[e] == CHX_DKD_DIPOLE || kinds[e] == CHX_DKD_SEXTUPOLE ||
-                kinds[e] == CHX_DKD_RFCAVITY) &&
+                kinds[e] == CHX_DKD_RFCAVITY || kinds[e] == CHX_DKD_MULTIPOLE) &&
                (dtype == CHX_F64 || (storage_precision[e] == storage_precision[first] && storage_precision[e] >= 0 && storage_precision[e] <= 2)) &&
                num_steps[e] >= 1 && num_steps[e] < (1 << 25) && fringe_at[e] >= 0 && fringe_at[e] <= 3;
         bend = bend || kinds[e] == CHX_DKD_DIPOLE;
         sext = sext || kinds[e] == CHX_DKD_SEXTUPOLE;
         rf = rf || kinds[e] == CHX_DKD_RFCAVITY;
+        mp = mp || kinds[e] == CHX_DKD_MULTIPOLE;
     }
     if (fuse) {
         hipStream_t s = (hipStream_t)stream;
@@ -1184,14 +1264,15 @@ extern "C" int chx_dkd_chain_mixed(const int32_t* kinds, const void* const* para
                 hipLaunchKernelGGL(dkd_chain_prepare_kernel<double>, dim3(blocks), dim3(64), 0, s, a, n, (const double*)e_from, mass_eV,
                                    n_charges, (double*)x_tmp, (double*)e_to, (const double*)s_from, (double*)s_out);
                 CHX_CHECK_LAUNCH();
-#define CHX_DKD_CHAIN_LAUNCH_F64(B, S, R)                                                                                             \
-    hipLaunchKernelGGL((dkd_chain_kernel_f64<B, S, R>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const double*)src,              \
+#define CHX_DKD_CHAIN_LAUNCH_F64(B, S, R, M)                                                                                          \
+    hipLaunchKernelGGL((dkd_chain_kernel_f64<B, S, R, M>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const double*)src,              \
                        (const double*)x_tmp, n, mass_eV, (double*)x_out, N, in_ok, out_ok)
-                if (rf) CHX_DKD_CHAIN_LAUNCH_F64(true, true, true);          // (a run with a cavity: every kind compiled in)
-                else if (bend && sext) CHX_DKD_CHAIN_LAUNCH_F64(true, true, false);
-                else if (bend) CHX_DKD_CHAIN_LAUNCH_F64(true, false, false);
-                else if (sext) CHX_DKD_CHAIN_LAUNCH_F64(false, true, false);
-                else CHX_DKD_CHAIN_LAUNCH_F64(false, false, false);
+                if (mp) CHX_DKD_CHAIN_LAUNCH_F64(true, true, true, true);    // (a run with a Multipole: every kind compiled in)
+                else if (rf) CHX_DKD_CHAIN_LAUNCH_F64(true, true, true, false);          // (a run with a cavity: every kind but that)
+                else if (bend && sext) CHX_DKD_CHAIN_LAUNCH_F64(true, true, false, false);
+                else if (bend) CHX_DKD_CHAIN_LAUNCH_F64(true, false, false, false);
+                else if (sext) CHX_DKD_CHAIN_LAUNCH_F64(false, true, false, false);
+                else CHX_DKD_CHAIN_LAUNCH_F64(false, false, false, false);
 #undef CHX_DKD_CHAIN_LAUNCH_F64
                 CHX_CHECK_LAUNCH();
                 continue;
@@ -1199,16 +1280,17 @@ extern "C" int chx_dkd_chain_mixed(const int32_t* kinds, const void* const* para
             hipLaunchKernelGGL(dkd_chain_prepare_kernel<float>, dim3(blocks), dim3(64), 0, s, a, n, (const float*)e_from, mass_eV,
                                n_charges, (double*)x_tmp, (float*)e_to, (const float*)s_from, (float*)s_out);
             CHX_CHECK_LAUNCH();
-#define CHX_DKD_CHAIN_LAUNCH(M, B, S, R)                                                                                             \
-    hipLaunchKernelGGL((dkd_chain_kernel<M, B, S, R>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const float*)src, (const double*)x_tmp, \
+#define CHX_DKD_CHAIN_LAUNCH(M, B, S, R, MP)                                                                                         \
+    hipLaunchKernelGGL((dkd_chain_kernel<M, B, S, R, MP>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const float*)src, (const double*)x_tmp, \
                        n, mass_eV, (float*)x_out, N, in_ok, out_ok)
 #define CHX_DKD_CHAIN_MODE(M)                                                                                                     \
     do {                                                                                                                          \
-        if (rf) CHX_DKD_CHAIN_LAUNCH(M, true, true, true);                                                                        \
-        else if (bend && sext) CHX_DKD_CHAIN_LAUNCH(M, true, true, false);                                                        \
-        else if (bend) CHX_DKD_CHAIN_LAUNCH(M, true, false, false);                                                               \
-        else if (sext) CHX_DKD_CHAIN_LAUNCH(M, false, true, false);                                                               \
-        else CHX_DKD_CHAIN_LAUNCH(M, false, false, false);                                                                        \
+        if (mp) CHX_DKD_CHAIN_LAUNCH(M, true, true, true, true);                                                                  \
+        else if (rf) CHX_DKD_CHAIN_LAUNCH(M, true, true, true, false);                                                            \
+        else if (bend && sext) CHX_DKD_CHAIN_LAUNCH(M, true, true, false, false);                                                 \
+        else if (bend) CHX_DKD_CHAIN_LAUNCH(M, true, false, false, false);                                                        \
+        else if (sext) CHX_DKD_CHAIN_LAUNCH(M, false, true, false, false);                                                        \
+        else CHX_DKD_CHAIN_LAUNCH(M, false, false, false, false);                                                                 \
     } while (0)
             if (mode == 2) CHX_DKD_CHAIN_MODE(2);
             else if (mode == 1) CHX_DKD_CHAIN_MODE(1);
@@ -1840,7 +1922,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void so_turns_reduce_kernel(const double
     }
 }
 
-// ---- a ring of Drifts, Quadrupoles, Dipoles, Sextupoles and RFCavities tracked drift-kick-drift, TURN AFTER TURN (chx_dkd_turns) --
+// ---- a ring of Drifts, Quadrupoles, Dipoles, Sextupoles, RFCavities and Multipoles tracked drift-kick-drift, TURN AFTER TURN (chx_dkd_turns) --
 // dkd_chain_kernel with the item loop inside the turn loop of so_turns_kernel. What the second-order ring does not have: every
 // drift-kick-drift element leaves the reference energy as the round trip f(E) = sqrt(sqrt(E^2 - m^2)^2 + m^2) of what it received
 // (dkd_energy_round_trip), and an element's constants depend on the energy in front of it. f is a composition of monotone,
@@ -1856,7 +1938,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void so_turns_reduce_kernel(const double
 //   dkd_turns_constants_kernel  a workgroup per (block, item); those of blocks that were not opened return at once. The others
 //                               walk from their block's start energy to the energy in front of their item and leave the item's
 //                               constants (dkd_item_constants, the chain's own). One workgroup more adds up the path length.
-//   dkd_turns_kernel<MODE, BEND, SEXT, RF>, dkd_turns_kernel_f64<BEND, SEXT, RF>   a particle per lane; per turn the block's address (a scalar load),
+//   dkd_turns_kernel<MODE, BEND, SEXT, RF, MP>, dkd_turns_kernel_f64<BEND, SEXT, RF, MP>   a particle per lane; per turn the block's address (a scalar load),
 //                               the chain's item loop (dkd_items); the loss test, the freezing of a lost row in the LDS tile,
 //                               the record and the probe rows are turns_frame's.
 //   so_turns_reduce_kernel      as it is.
@@ -1915,8 +1997,8 @@ __global__ void dkd_turns_constants_kernel(DkdChainArgs args, int E, int turns, 
 
 // the drift-kick-drift ring (as built: float64 beams, MODE is not read): a particle per lane; a turn is dkd_items over the block of
 // constants of that turn (its address: a scalar load), which leaves 1 in the seventh column as every drift-kick-drift kernel does.
-// MODE, BEND, SEXT, RF as in dkd_items
-template <int MODE, bool BEND, bool SEXT, bool RF, typename T>
+// MODE, BEND, SEXT, RF, MP as in dkd_items
+template <int MODE, bool BEND, bool SEXT, bool RF, bool MP, typename T>
 struct DkdRing {
     const double* __restrict__ cst;
     const int32_t* __restrict__ block_of_turn;
@@ -1930,7 +2012,7 @@ struct DkdRing {
     }
     __device__ __forceinline__ T get(int, int j) const { return j < 6 ? v[j] : v6; }
     __device__ __forceinline__ void turn(int k) {
-        dkd_items<MODE, BEND, SEXT, RF, false, T>(cst + (int64_t)block_of_turn[k] * E * kDkdCstStride, E, mc2, v, v6);
+        dkd_items<MODE, BEND, SEXT, RF, MP, false, T>(cst + (int64_t)block_of_turn[k] * E * kDkdCstStride, E, mc2, v, v6);
     }
 };
 
@@ -1939,7 +2021,7 @@ struct DkdRing {
 // float32 beams: the frame's text and the item loop written out. On turns_frame with dkd_items every instantiation kept its waves
 // per SIMD, but the "storage" ring ran 1.7 to 2.4 % slower at 1e3 and 1e5 particles and the "mixed" and "double" rings 0.8 to 1.4 %
 // (profiles/turn_frame.md). A change to the rules of turns_frame or a new kind in dkd_items is made here too.
-template <int MODE, bool BEND, bool SEXT, bool RF>
+template <int MODE, bool BEND, bool SEXT, bool RF, bool MP>
 __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel(const double* __restrict__ cst, const int32_t* __restrict__ block_of_turn,
                                                               double mc2, SoTurnsArgs<float> a) {
     constexpr int TP = CHX_BLOCK;
@@ -1970,6 +2052,7 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel(const double* __re
                 if (kind == CHX_DKD_DRIFT) dkd_chain_step<MODE, CHX_DKD_DRIFT>(c, mc2, steps, v);
                 else if (SEXT && kind == CHX_DKD_SEXTUPOLE) dkd_chain_step<MODE, CHX_DKD_SEXTUPOLE>(c, mc2, steps, v);
                 else if (RF && kind == CHX_DKD_RFCAVITY) dkd_chain_step<MODE, CHX_DKD_RFCAVITY>(c, mc2, steps, v);
+                else if (MP && kind == CHX_DKD_MULTIPOLE) dkd_chain_step<MODE, CHX_DKD_MULTIPOLE>(c, mc2, steps, v);
                 else if (!BEND || kind == CHX_DKD_QUADRUPOLE) dkd_chain_step<MODE, CHX_DKD_QUADRUPOLE>(c, mc2, steps, v);
                 else dkd_chain_step<MODE, CHX_DKD_DIPOLE>(c, mc2, steps, v);
             }
@@ -2012,10 +2095,10 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel(const double* __re
 }
 
 // float64 beams: turns_frame with the DkdRing policy
-template <bool BEND, bool SEXT, bool RF>
+template <bool BEND, bool SEXT, bool RF, bool MP>
 __global__ __launch_bounds__(CHX_BLOCK) void dkd_turns_kernel_f64(const double* __restrict__ cst, const int32_t* __restrict__ block_of_turn,
                                                                   double mc2, SoTurnsArgs<double> a) {
-    DkdRing<0, BEND, SEXT, RF, double> ring{cst, block_of_turn, a.E, mc2};
+    DkdRing<0, BEND, SEXT, RF, MP, double> ring{cst, block_of_turn, a.E, mc2};
     turns_frame<double, 1>(ring, a);
 }
 
@@ -2236,7 +2319,7 @@ extern "C" int chx_second_order_turns(const void* const* T_maps, const int32_t* 
     return so_turns_launch<double>(maps, (int)E, c, s_in, s_out, workspace, tiles, coef_bytes, (hipStream_t)stream);
 }
 
-// A ring of Drifts, Quadrupoles, Dipoles, Sextupoles and RFCavities tracked drift-kick-drift: turns [first_turn, first_turn + num_turns) in one particle
+// A ring of Drifts, Quadrupoles, Dipoles, Sextupoles, RFCavities and Multipoles tracked drift-kick-drift: turns [first_turn, first_turn + num_turns) in one particle
 // launch (dkd_turns_kernel, dkd_turns_kernel_f64; see the kernels for the energy walk in front of it). The workspace, every part
 // 16-byte aligned: start[turns] (dtype) | block_of_turn[turns + 1] (int32) | constants[turns][E][kDkdCstStride] (double) |
 // partials[records][tiles][14] (double). The host cannot know how many blocks of constants the device will open: room for one per turn.
@@ -2254,7 +2337,7 @@ DkdTurnsLayout dkd_turns_layout(int64_t E, int64_t N, int64_t turns, int64_t rec
     return l;
 }
 template <typename T>
-int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, bool sext, bool rf, int mode, const TurnsCall& c, const void* energy_in,
+int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, bool sext, bool rf, bool mp, int mode, const TurnsCall& c, const void* energy_in,
                      void* energy_out, double mass_eV, double n_charges, const void* s_in, void* s_out, void* workspace,
                      const DkdTurnsLayout& l, int64_t tiles, hipStream_t s) {
     const int num_turns = (int)c.num_turns;
@@ -2273,11 +2356,12 @@ int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, bool sext, boo
     const int32_t* b = block_of_turn;
 #define CHX_DKD_TURNS_KINDS(K, ...)                                                                                               \
     do {                                                                                                                          \
-        if (rf) hipLaunchKernelGGL((K<__VA_ARGS__ true, true, true>), grid, wg, 0, s, k, b, mass_eV, a);                             \
-        else if (bend && sext) hipLaunchKernelGGL((K<__VA_ARGS__ true, true, false>), grid, wg, 0, s, k, b, mass_eV, a);             \
-        else if (bend) hipLaunchKernelGGL((K<__VA_ARGS__ true, false, false>), grid, wg, 0, s, k, b, mass_eV, a);                    \
-        else if (sext) hipLaunchKernelGGL((K<__VA_ARGS__ false, true, false>), grid, wg, 0, s, k, b, mass_eV, a);                    \
-        else hipLaunchKernelGGL((K<__VA_ARGS__ false, false, false>), grid, wg, 0, s, k, b, mass_eV, a);                             \
+        if (mp) hipLaunchKernelGGL((K<__VA_ARGS__ true, true, true, true>), grid, wg, 0, s, k, b, mass_eV, a);                       \
+        else if (rf) hipLaunchKernelGGL((K<__VA_ARGS__ true, true, true, false>), grid, wg, 0, s, k, b, mass_eV, a);                 \
+        else if (bend && sext) hipLaunchKernelGGL((K<__VA_ARGS__ true, true, false, false>), grid, wg, 0, s, k, b, mass_eV, a);      \
+        else if (bend) hipLaunchKernelGGL((K<__VA_ARGS__ true, false, false, false>), grid, wg, 0, s, k, b, mass_eV, a);             \
+        else if (sext) hipLaunchKernelGGL((K<__VA_ARGS__ false, true, false, false>), grid, wg, 0, s, k, b, mass_eV, a);             \
+        else hipLaunchKernelGGL((K<__VA_ARGS__ false, false, false, false>), grid, wg, 0, s, k, b, mass_eV, a);                      \
     } while (0)
     if constexpr (sizeof(T) == 8) {
         CHX_DKD_TURNS_KINDS(dkd_turns_kernel_f64, );
@@ -2313,15 +2397,16 @@ extern "C" int chx_dkd_turns(const int32_t* kinds, const void* const* params, co
     TurnsCall c{x_in, charges, survival, aperture, x_out, lost_turn, sums, probe, N, K, first_turn, num_turns, record_every, 0, 0};
     if (!turns_call_ok(c)) return CHX_ERR_INVALID_ARG;
     if ((s_in == nullptr) != (s_out == nullptr)) return CHX_ERR_INVALID_ARG;
-    bool bend = false, sext = false, rf = false;
+    bool bend = false, sext = false, rf = false, mp = false;
     for (int64_t e = 0; e < E; ++e) {
         if (!params[e] || (kinds[e] != CHX_DKD_DRIFT && kinds[e] != CHX_DKD_QUADRUPOLE && kinds[e] != CHX_DKD_DIPOLE && kinds[e] != CHX_DKD_SEXTUPOLE &&
-                           kinds[e] != CHX_DKD_RFCAVITY) ||
+                           kinds[e] != CHX_DKD_RFCAVITY && kinds[e] != CHX_DKD_MULTIPOLE) ||
             num_steps[e] < 1 || num_steps[e] >= (1 << 25) || fringe_at[e] < 0 || fringe_at[e] > 3)
             return CHX_ERR_INVALID_ARG;
         bend = bend || kinds[e] == CHX_DKD_DIPOLE;
         sext = sext || kinds[e] == CHX_DKD_SEXTUPOLE;
         rf = rf || kinds[e] == CHX_DKD_RFCAVITY;
+        mp = mp || kinds[e] == CHX_DKD_MULTIPOLE;
     }
     const int64_t tiles = (N + CHX_BLOCK - 1) / CHX_BLOCK;
     if (tiles > 0x7fffffffLL || num_turns * E >= 0x7fffffffLL) return CHX_ERR_INVALID_ARG;             // (grid sizes)
@@ -2339,9 +2424,9 @@ extern "C" int chx_dkd_turns(const int32_t* kinds, const void* const* params, co
         items.meta[e] = e < E ? (kinds[e] | (fringe_at[e] << 4) | (num_steps[e] << 6)) : 0;
     }
     if (dtype == CHX_F32)
-        return dkd_turns_launch<float>(items, (int)E, bend, sext, rf, storage_precision, c, energy_in, energy_out, mass_eV, n_charges, s_in,
+        return dkd_turns_launch<float>(items, (int)E, bend, sext, rf, mp, storage_precision, c, energy_in, energy_out, mass_eV, n_charges, s_in,
                                        s_out, workspace, l, tiles, (hipStream_t)stream);
-    return dkd_turns_launch<double>(items, (int)E, bend, sext, rf, 0, c, energy_in, energy_out, mass_eV, n_charges, s_in, s_out, workspace, l,
+    return dkd_turns_launch<double>(items, (int)E, bend, sext, rf, mp, 0, c, energy_in, energy_out, mass_eV, n_charges, s_in, s_out, workspace, l,
                                     tiles, (hipStream_t)stream);
 }
 
@@ -2383,6 +2468,9 @@ int dispatch_dkd_bwd(int kind, const void* x_in, const void* params, const void*
         case CHX_DKD_RFCAVITY:
             return launch_dkd_bwd<T, CHX_DKD_RFCAVITY>(x_in, params, energy, dY, mc2, nq, num_steps, fringe, P, B, Bx,
                                                        Bp, Be, N, dx, partials, s);
+        case CHX_DKD_MULTIPOLE:
+            return launch_dkd_bwd<T, CHX_DKD_MULTIPOLE>(x_in, params, energy, dY, mc2, nq, num_steps, fringe, P, B, Bx,
+                                                        Bp, Be, N, dx, partials, s);
     }
     return CHX_ERR_INVALID_ARG;
 }
@@ -2404,8 +2492,8 @@ extern "C" int chx_dkd_track_bwd(int kind, const void* x_in, const void* params,
     if (B == 0 || N == 0) return CHX_OK;
     if (!x_in || !params || !energy || !dY || (!dx && !partials)) return CHX_ERR_INVALID_ARG;
     if (!chx_bcast_ok(Bx, B) || !chx_bcast_ok(Bp, B) || !chx_bcast_ok(Be, B)) return CHX_ERR_INVALID_ARG;
-    if ((kind == CHX_DKD_QUADRUPOLE || kind == CHX_DKD_SEXTUPOLE) && num_steps < 1) return CHX_ERR_INVALID_ARG;
-    if (kind == CHX_DKD_SEXTUPOLE && num_steps >= (1 << 25)) return CHX_ERR_INVALID_ARG;        // (the chain's and the ring's cap)
+    if ((kind == CHX_DKD_QUADRUPOLE || kind == CHX_DKD_SEXTUPOLE || kind == CHX_DKD_MULTIPOLE) && num_steps < 1) return CHX_ERR_INVALID_ARG;
+    if ((kind == CHX_DKD_SEXTUPOLE || kind == CHX_DKD_MULTIPOLE) && num_steps >= (1 << 25)) return CHX_ERR_INVALID_ARG;        // (the chain's and the ring's cap)
     if (fringe_at < 0 || fringe_at > 3) return CHX_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
     return dtype == CHX_F32 ? dispatch_dkd_bwd<float>(kind, x_in, params, energy, dY, mass_eV, n_charges, num_steps,

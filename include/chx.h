@@ -1202,13 +1202,22 @@ int chx_screen_gaussian(const void* mu, const void* cov, const void* shift, cons
  *                       before the sine, and sin, cos of 2 pi phase are taken once per element, so phase = 0 and 0.5 are exact zero
  *                       crossings. x, px, y, py see only the drifts: symplectic. The reference energy is NOT changed (the
  *                       storage-ring convention); total energy below the rest mass behind the kick: NaN.
+ *   CHX_DKD_MULTIPOLE   [length, knl, ksl, tilt, misalignment_x, misalignment_y]   (+ num_steps = n, 1 <= n < 2^25; fringe_at = the
+ *                       order m = 0 .. 3 of the kick: 0 dipole, 1 quadrupole, 2 sextupole, 3 octupole; length = 0: a thin element)
+ *                       The Sextupole's frame with the kick of one order: knl, ksl are the INTEGRATED normal and skew strengths
+ *                       in m^-m (MAD-X's knl / ksl). With h = L / (2 n): offset_set, drift(h), n x { d px - i d py =
+ *                       -(knl + i ksl) / n (x + i y)^m / m!, drift(2 h; h after the last kick) }, offset_unset. (x + i y)^m by m
+ *                       complex multiplications from 1, 1 / m! folded into the strengths once per element: the backward pass has
+ *                       the right derivative at x = y = 0 and at knl = ksl = 0. pz unchanged, symplectic; knl = ksl = 0: a drift
+ *                       of length L; m = 2, ksl = 0: CHX_DKD_SEXTUPOLE with k2 = knl / L; m = 0: d px = -knl, d py = +ksl.
+ * fringe_at: the Dipole's fringe bits; for CHX_DKD_MULTIPOLE: the order m. No other kind reads it.
  * energy_out[B] (may be NULL) receives the reference energy recomputed from p0c (bmadx.py:49). */
 enum chx_dkd_kind { CHX_DKD_DRIFT = 0, CHX_DKD_QUADRUPOLE = 1, CHX_DKD_DIPOLE = 2, CHX_DKD_TDC = 3,
                     CHX_DKD_LINEAR = 4 /* only in chx_dkd_chain_mixed / chx_dkd_energy_chain: a merged run of linear elements */,
-                    CHX_DKD_SEXTUPOLE = 5, CHX_DKD_RFCAVITY = 6 };
-/* The parameter count of a kind, -1 for anything else — and, still, for CHX_DKD_RFCAVITY: the kind came without a change of the
- * ABI version, and a caller of ABI 9 that probes the kinds with this function sees the set it knew. Its count is 4 (above);
- * chx_dkd_bwd_partials_count and every entry point that takes a kind count it. */
+                    CHX_DKD_SEXTUPOLE = 5, CHX_DKD_RFCAVITY = 6, CHX_DKD_MULTIPOLE = 8 /* (7 is no kind) */ };
+/* The parameter count of a kind, -1 for anything else — and, still, for CHX_DKD_RFCAVITY and CHX_DKD_MULTIPOLE: the kinds came
+ * without a change of the ABI version, and a caller of ABI 9 that probes the kinds with this function sees the set it knew. Their
+ * counts are 4 and 6 (above); chx_dkd_bwd_partials_count and every entry point that takes a kind count them. */
 int chx_dkd_num_params(int kind);
 int chx_dkd_track(int kind, const void* x_in, const void* params, const void* energy, double mass_eV,
                   double n_charges, int32_t num_steps, int32_t fringe_at, int64_t B, int64_t Bx, int64_t Bp,
@@ -1225,7 +1234,7 @@ int chx_dkd_track_p(int kind, const void* x_in, const void* params, const void* 
  * params[E] (device pointers to each element's parameter array), num_steps[E], fringe_at[E], storage_precision[E]; the
  * reference energy travels from element to element on the device (energies[E] (dtype): what each element leaves; energy_in one
  * scalar). x_tmp[N][7] is scratch (may be NULL for E = 1); x_out receives the last element's particles. Drifts, Quadrupoles,
- * Dipoles, Sextupoles and RFCavities (float32 beams: of one storage_precision): two launches per 320 elements, the particles in registers across the run (x_tmp
+ * Dipoles, Sextupoles, RFCavities and Multipoles (float32 beams: of one storage_precision): two launches per 320 elements, the particles in registers across the run (x_tmp
  * holds the elements' constants); otherwise E launches. Either way one call and the bits of E separate chx_dkd_track_p calls.
  * s_in / s_out (one scalar of dtype each, both or neither): the path length, s_out = (((s_in + l_0) + l_1) + ...) with the
  * lengths added one by one in dtype like the reference's `s=incoming.s + self.length` per element. */
@@ -1246,9 +1255,9 @@ int chx_dkd_chain_mixed(const int32_t* kinds, const void* const* params, const v
  * maps of the linear runs needs the energy in front of each of them). kinds_scratch: E int32 of device memory. One or two launches. */
 int chx_dkd_energy_chain(const int32_t* kinds, int64_t E, const void* energy_in, double mass_eV, int dtype, void* energies,
                          void* kinds_scratch, void* stream);
-/* A ring of E drift-kick-drift Drifts, Quadrupoles, Dipoles, Sextupoles and RFCavities (the symplectic Bmad-X maps) turn after turn: turns [first_turn,
+/* A ring of E drift-kick-drift Drifts, Quadrupoles, Dipoles, Sextupoles, RFCavities and Multipoles (the symplectic Bmad-X maps) turn after turn: turns [first_turn,
  * first_turn + num_turns) in one particle launch, the particles in registers from turn to turn; the bits of num_turns passes of
- * chx_dkd_chain. HOST arrays kinds[E] (CHX_DKD_DRIFT / _QUADRUPOLE / _DIPOLE / _SEXTUPOLE / _RFCAVITY), params[E], num_steps[E], fringe_at[E] as in
+ * chx_dkd_chain. HOST arrays kinds[E] (CHX_DKD_DRIFT / _QUADRUPOLE / _DIPOLE / _SEXTUPOLE / _RFCAVITY / _MULTIPOLE), params[E], num_steps[E], fringe_at[E] as in
  * chx_dkd_chain, 1 <= E <= 192; ONE storage_precision (0 double, 1 storage, 2 mixed) for the ring, ignored by float64 beams.
  *   energy_in (dtype scalar): the reference energy in front of turn first_turn; energy_out: the energy behind the last turn of the
  *     call (may be energy_in: the chunks of a call hand it on through one device scalar). Every element leaves the round trip
@@ -1262,7 +1271,7 @@ int chx_dkd_energy_chain(const int32_t* kinds, int64_t E, const void* energy_in,
  *     host cannot know how many blocks the device opens) and records x ceil(N / 256) x 14 doubles of partial sums; the first two
  *     parts rounded up to 16 bytes. The function is monotone in every argument and returns 0 for arguments out of range.
  * Four launches (energy walk, constants and path length, particles, reduction of the records), none synchronising.
- * CHX_ERR_INVALID_ARG, before any launch: E < 1, E > 192, a kind other than the five, storage_precision outside 0..2, num_steps
+ * CHX_ERR_INVALID_ARG, before any launch: E < 1, E > 192, a kind other than the six, storage_precision outside 0..2, num_steps
  * outside 1 .. 2^25 - 1, fringe_at outside 0..3, num_turns < 1, record_every < 1, K > N, a last turn of 2^31 - 1 or beyond, aliased
  * buffers, a workspace too small or not 16-byte aligned, a required pointer that is NULL; CHX_ERR_DTYPE: dtype other than CHX_F32
  * / CHX_F64. */
