@@ -1597,3 +1597,5 @@ from ._ops_quiet import *  # noqa: E402,F401,F403
 from ._ops_density import *  # noqa: E402,F401,F403
 # ... and the tunes from turn-by-turn records (TurnByTurn.tunes) in _ops_tunes.py
 from ._ops_tunes import *  # noqa: E402,F401,F403
+# ... and the one-turn map, closed orbit and Jacobian of a drift-kick-drift ring (Segment.ring_optics) in _ops_optics.py
+from ._ops_optics import *  # noqa: E402,F401,F403

@@ -29,6 +29,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import math
 import numbers
 import os
 from copy import deepcopy
@@ -112,6 +113,8 @@ _DKD_IN_REGISTERS = (_ops.DKD_KIND["drift"], _ops.DKD_KIND["quadrupole"], _ops.D
 #: what `Segment._turn_items` hands `_track_turns_fused` for a ring of drift-kick-drift elements (chx_dkd_turns): per element the
 #: kind, the (1, P) parameter tensor, num_steps and fringe_at; `storage` = the ring's one arithmetic mode
 _DkdRing = collections.namedtuple("_DkdRing", "kinds params num_steps fringe_at storage")
+#: the electrons `one_turn_map`, `closed_orbit` and `ring_optics` take for `species=None`, by (dtype, device)
+_DEFAULT_SPECIES = {}
 #: CHX_SC_CHAIN = auto (default) | on | off — how `Segment.track` takes [SpaceChargeKick, linear run, SpaceChargeKick, ...]:
 #: "auto" starts on the tile-ordered chain and lets the asynchronous guard (`_chain_allowed`) send a plan whose beam reshuffles
 #: between kicks back to kick-by-kick tracking. The two paths sum the charge in different orders, so WHEN the guard's header
@@ -1052,6 +1055,135 @@ class Segment(Element):
             probe = torch.stack(probe) if probe else torch.empty((0, *lead, record_first, 7), dtype=x.dtype, device=dev)
         return _turns.TurnByTurn(beam, lost, _turns.recorded_turns(num_turns, record_every, dev), sums, probe if record_first else None,
                                  record_every=record_every)
+
+    # ---- linear optics of a ring --------------------------------------------------------------------------------
+    def _ring_jacobian(self, what: str, energy, species, start: torch.Tensor, mode: int, num_iterations: int, along: bool):
+        """`_ops.dkd_ring_jacobian` for this lattice taken as a ring: the conditions of `_turn_items_dkd` (whose reason a lattice
+        that does not qualify is refused with), the energy as a 0-d tensor of the settings' dtype on the seeds' device."""
+        if not isinstance(energy, torch.Tensor):
+            lengths = [e.length for e in self._leaves() if isinstance(getattr(e, "length", None), torch.Tensor)]
+            energy = torch.as_tensor(float(energy), dtype=lengths[0].dtype if lengths else torch.float64, device=start.device)
+        if energy.dim() != 0 or not energy.is_floating_point():
+            raise ValueError(f"{what}: the energy must be one scalar")
+        if species is None:
+            # one electron per dtype and device, kept: its tensors are made (and read back once) outside any graph capture
+            key = (energy.dtype, energy.device)
+            species = _DEFAULT_SPECIES.get(key)
+            if species is None:
+                species = _DEFAULT_SPECIES[key] = Species("electron", dtype=energy.dtype, device=energy.device)
+                species.mass_eV_float
+        if any(t.requires_grad for t in (start, energy, species.mass_eV, species.num_elementary_charges)):
+            raise ValueError(f"{what} has no autograd: an input requires grad")
+        if type(self).track is not Segment.track or type(self)._track_internal is not Segment._track_internal:
+            raise ValueError(f"{what}: the segment overrides `track`")
+        with torch.no_grad():
+            plan = self._plan()
+            ring = self._turn_items_dkd(plan, torch.empty((0, 7), dtype=energy.dtype, device=energy.device)) if plan else \
+                "the lattice holds nothing to track"
+            if isinstance(ring, str):
+                raise ValueError(f"{what}: {ring}")
+            arrays = _ops.dkd_turn_arrays(ring.kinds, ring.params, ring.num_steps, ring.fringe_at)
+            return _ops.dkd_ring_jacobian(arrays, len(ring.kinds), energy, species.mass_eV_float, species.num_elementary_charges_float,
+                                          start, mode, num_iterations, along)
+
+    @staticmethod
+    def _seeds(start: torch.Tensor) -> torch.Tensor:
+        """(B, 6) float64 from (B, 6), (B, 7) or one such row."""
+        if start.dim() == 1:
+            start = start.unsqueeze(0)
+        if start.dim() != 2 or start.shape[1] not in (6, 7):
+            raise ValueError(f"the seeds must have the shape (B, 6) or (B, 7) or be one such row, got {tuple(start.shape)}")
+        return start[:, :6].to(torch.float64).contiguous()
+
+    @staticmethod
+    def _rows7(x6: torch.Tensor) -> torch.Tensor:
+        return torch.cat([x6, torch.ones_like(x6[..., :1])], dim=-1)
+
+    def one_turn_map(self, start: torch.Tensor, energy, species=None, along: bool = False):
+        """One turn of this lattice, taken as a ring of drift-kick-drift elements, for the seeds `start` — (B, 6), (B, 7) or one
+        such row, on the device — together with the 6 x 6 Jacobian of the turn at every seed: an `OneTurnMap` (particles/optics.py)
+        with `start`, `end` (B, 7) and `matrix` (B, 6, 6), and with `along` the orbit and the cumulative matrix behind every item
+        and the path length `s`. float64 whatever the settings' dtype: the maps are evaluated through their dual-number form in one
+        launch (`chx_dkd_ring_jacobian`), the values are those `track` gives a float64 beam.
+
+        `energy`: the reference energy in eV, a 0-d tensor of the settings' dtype on their device (a Python number is made one);
+        `species=None`: electrons. The lattice must be a ring `track_turns` fuses — every item a Drift, Quadrupole, Dipole,
+        Sextupole, RFCavity or Multipole with `tracking_method="drift_kick_drift"`, scalar settings without gradients, the stock
+        `track`, 1 to 192 of them, Markers skipped; `dkd_precision` does not matter — else ValueError with the reason. There is no
+        general fallback. No autograd (an input that requires grad raises ValueError); the call does not synchronise.
+        Out of scope: vectorised settings, gradients with respect to settings, second-order and linear rings."""
+        from ..particles.optics import OneTurnMap
+
+        x = self._seeds(start)
+        out = self._ring_jacobian("one_turn_map", energy, species, x, 0, 1, along)
+        if not along:
+            return OneTurnMap(self._rows7(out["orbit"]), self._rows7(out["image"]), out["matrix"])
+        return OneTurnMap(self._rows7(out["orbit"]), self._rows7(out["image"]), out["matrix"], self._rows7(out["orbit_along"]),
+                          out["matrix_along"], out["s_along"])
+
+    def _closed_orbit(self, what, energy, species, delta, guess, longitudinal, num_iterations, along):
+        num_iterations = int(num_iterations)
+        if num_iterations < 1:
+            raise ValueError(f"{what}: num_iterations must be at least 1")
+        if guess is not None:
+            x = self._seeds(guess).clone()
+        else:
+            dev = delta.device if isinstance(delta, torch.Tensor) else (energy.device if isinstance(energy, torch.Tensor) else "cuda")
+            n = delta.numel() if isinstance(delta, torch.Tensor) else 1
+            x = torch.zeros((n, 6), dtype=torch.float64, device=dev)
+        if delta is not None:
+            d = delta.to(torch.float64).reshape(-1) if isinstance(delta, torch.Tensor) else torch.full((1,), float(delta), dtype=torch.float64, device=x.device)
+            if d.requires_grad:
+                raise ValueError(f"{what} has no autograd: an input requires grad")
+            if d.shape[0] != x.shape[0]:
+                if x.shape[0] != 1 and d.shape[0] != 1:
+                    raise ValueError(f"{what}: {d.shape[0]} values of delta for {x.shape[0]} guesses")
+                x = x.expand(max(d.shape[0], x.shape[0]), 6).clone()
+            x[:, 5] = d
+        return self._ring_jacobian(what, energy, species, x, 2 if longitudinal else 1, num_iterations, along)
+
+    def closed_orbit(self, energy, species=None, delta=None, guess=None, longitudinal: bool = False, num_iterations: int = 10):
+        """The closed orbit of this lattice taken as a ring (the conditions of `one_turn_map`): a `ClosedOrbit` with `orbit` (B, 7),
+        `residual` (B,), `matrix` (B, 6, 6) and `dispersion` (B, 4), float64.
+
+        The 4-D search (default) closes x, px, y, py and HOLDS tau and delta: `delta`, a scalar or a (B,) tensor, gives the momentum
+        offsets — one orbit each. With `longitudinal=True` all six coordinates are closed (meaningful with an RFCavity on a
+        harmonic of the revolution frequency) and `delta` is only the initial guess. `guess`, (B, 6) / (B, 7) or one row, starts
+        the search elsewhere than on the axis. `num_iterations` Newton steps, a fixed count, run inside one kernel launch: the
+        call never synchronises, and `residual` = max |turn(orbit) - orbit| over the closed coordinates tells whether each search
+        arrived. A seed that fails (beyond the dynamic aperture, a singular system) is NaN in its own rows.
+        Out of scope: the synchrotron tune of a 6-D search — `matrix` is returned, take its eigenvalues."""
+        from ..particles.optics import ClosedOrbit
+
+        out = self._closed_orbit("closed_orbit", energy, species, delta, guess, longitudinal, num_iterations, False)
+        return ClosedOrbit(self._rows7(out["orbit"]), out["residual"], out["matrix"], out["dispersion"])
+
+    def ring_optics(self, energy, species=None, delta=None, guess=None, longitudinal: bool = False, num_iterations: int = 10,
+                    along: bool = True):
+        """The linear optics of this lattice taken as a ring: the closed-orbit search of `closed_orbit` (same arguments), then the
+        tunes, beta, alpha, phase advance, dispersion and slip factor from the one-turn matrix on that orbit — a `RingOptics`
+        (particles/optics.py lists the fields); with `along` (default) the functions behind every item, index 0 the start.
+        beta, alpha and the phase are the uncoupled (projected) functions: `coupling` tells when to distrust them. One kernel
+        launch and a few float64 torch operations, no synchronisation. Out of scope: Edwards-Teng or other coupled
+        parametrisations, vectorised settings, gradients of the optics with respect to settings."""
+        from ..particles.optics import ClosedOrbit, ring_optics_from
+
+        out = self._closed_orbit("ring_optics", energy, species, delta, guess, longitudinal, num_iterations, along)
+        closed = ClosedOrbit(self._rows7(out["orbit"]), out["residual"], out["matrix"], out["dispersion"])
+        if not along:
+            return ring_optics_from(closed)
+        return ring_optics_from(closed, self._rows7(out["orbit_along"]), out["matrix_along"], out["s_along"])
+
+    def chromaticity(self, energy, species=None, h: float = 1e-4) -> torch.Tensor:
+        """(dQx / d delta, dQy / d delta), shape (2,): the central difference of the FULL tunes (the integer part from the phase
+        advance along the ring) of one `ring_optics` call at delta = (-h, 0, +h). No synchronisation."""
+        h = float(h)
+        if not h > 0:
+            raise ValueError("chromaticity: h must be positive")
+        dev = energy.device if isinstance(energy, torch.Tensor) else "cuda"
+        opt = self.ring_optics(energy, species, delta=torch.tensor([-h, 0.0, h], dtype=torch.float64, device=dev))
+        q = opt.phase_advance[:, -1, :] / (2.0 * math.pi)
+        return (q[2] - q[0]) / (2.0 * h)
 
     @staticmethod
     def _stable_energy(ent: dict, energy: torch.Tensor, mass: float, e_out: torch.Tensor) -> torch.Tensor:

@@ -16,6 +16,7 @@
 
 #include "chx_common.h"
 #include "chx_dual.h"
+#include "chx_optics_dev.h"
 
 // parameters per drift-kick-drift kind (include/chx.h), -1 for anything else: what every entry point below counts with
 static int dkd_num_params(int kind) {
@@ -788,6 +789,152 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_bwd_kernel(const T* __restrict_
             }
             __syncthreads();
         }
+    }
+}
+
+// ---- the one-turn map of a ring of drift-kick-drift items with its 6 x 6 Jacobian, and the closed orbit (chx_dkd_ring_jacobian) -----
+// One lane per (seed, tangent direction): the lane carries the phase-space point and ONE tangent through all E items as six Dual
+// numbers in registers, dkd_map<KIND, Dual> item after item — the instantiations dkd_bwd_kernel compiles, in float64 whatever the
+// settings' dtype. A seed is a group of chx_optics::kGroup = 8 consecutive lanes (tangents e_0 .. e_5, two lanes without one),
+// eight seeds are the one wave of a workgroup: nothing of a seed leaves its wave, the only barrier is the wave's own.
+// The item's constants come from the 56-double block dkd_chain_prepare_kernel leaves (what a turn of chx_dkd_turns reads) through
+// wave-uniform scalar loads and become Dual with a zero tangent per lane as the item is reached: their values stay in scalar
+// registers, no LDS round trip and no barrier per item (DESIGN.md has the register figures).
+// After a pass the group gathers M (lane m holds column m) in LDS; lane 0 of the group takes the Newton step of the closed orbit on
+// the closed coordinates (chx_optics_dev.h), every lane of the group adds it. `passes` is the same for every seed: a seed that
+// has converged keeps stepping (by rounding-size steps), a seed that cannot converge is NaN in its own rows, and two calls give
+// the same bits. The last pass starts from the final point and is the one whose image, matrix and per-item records are stored.
+constexpr int kRingCstStride = 56, kRingMeta = 54;          // kDkdCstStride, kDkdMeta below (asserted equal at the entry point)
+struct RingJacobianOut {
+    double* orbit;          // [B][6]
+    double* image;          // [B][6]
+    double* matrix;         // [B][6][6]
+    double* residual;       // [B]
+    double* dispersion;     // [B][4]
+    double* orbit_along;    // [B][E + 1][6] or null
+    double* matrix_along;   // [B][E + 1][6][6] or null
+    void* s_along;          // [E + 1] in the settings' dtype or null
+};
+
+__global__ __launch_bounds__(chx_optics::kLanes) void dkd_ring_jacobian_kernel(const double* __restrict__ cst, int E, double mc2,
+                                                                              const double* __restrict__ start, int64_t B, int mode,
+                                                                              int passes, int s_is_f32, RingJacobianOut o) {
+    using namespace chx_optics;
+    __shared__ double sM[kSeeds][36];
+    __shared__ double sA[kSeeds][36];
+    __shared__ double sF[kSeeds][6];
+    __shared__ double sStep[kSeeds][6];
+    const int lane = threadIdx.x, g = group_of_lane(lane), m = tangent_of_lane(lane);
+    bool live;
+    const int64_t seed = seed_of_group(blockIdx.x, g, B, live);
+    const bool column = live && m < 6;                        // the lane stores column m of its seed's matrices
+    const int n = closed_count(mode);
+
+    if (blockIdx.x == 0 && lane == 0 && o.s_along) {          // the path length behind every item, added in the settings' dtype
+        if (s_is_f32) {
+            float* s_out = (float*)o.s_along;
+            float s = 0.0f;
+            s_out[0] = s;
+            for (int e = 0; e < E; ++e) s_out[e + 1] = s = s + (float)cst[(int64_t)e * kRingCstStride + C_A];
+        } else {
+            double* s_out = (double*)o.s_along;
+            double s = 0.0;
+            s_out[0] = s;
+            for (int e = 0; e < E; ++e) s_out[e + 1] = s = s + cst[(int64_t)e * kRingCstStride + C_A];
+        }
+    }
+
+    double x[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) x[j] = start[seed * 6 + j];
+
+#pragma unroll 1
+    for (int pass = 0; pass < passes; ++pass) {
+        const bool last = pass == passes - 1;
+        const bool along = last && o.matrix_along != nullptr;
+        Dual v[6];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) v[j] = mk(x[j], j == m ? 1.0 : 0.0);
+        if (along && column) {
+            double* Ma = o.matrix_along + seed * (int64_t)(E + 1) * 36;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) Ma[i * 6 + m] = v[i].d;
+            if (m == 0) {
+                double* xa = o.orbit_along + seed * (int64_t)(E + 1) * 6;
+#pragma unroll
+                for (int i = 0; i < 6; ++i) xa[i] = v[i].v;
+            }
+        }
+#pragma unroll 1
+        for (int e = 0; e < E; ++e) {
+            const double* __restrict__ c = cst + (int64_t)e * kRingCstStride;
+            const int32_t* w = reinterpret_cast<const int32_t*>(c + kRingMeta);
+            const int kind = w[0], steps = w[1];
+            Dual cd[C_N + 1], out[6];
+#pragma unroll
+            for (int k = 0; k <= C_N; ++k) cd[k] = mk(c[k], 0.0);
+            if (kind == CHX_DKD_DRIFT) dkd_map<CHX_DKD_DRIFT, Dual>(cd, v, mc2, steps, out);
+            else if (kind == CHX_DKD_QUADRUPOLE) dkd_map<CHX_DKD_QUADRUPOLE, Dual>(cd, v, mc2, steps, out);
+            else if (kind == CHX_DKD_DIPOLE) dkd_map<CHX_DKD_DIPOLE, Dual>(cd, v, mc2, steps, out);
+            else if (kind == CHX_DKD_SEXTUPOLE) dkd_map<CHX_DKD_SEXTUPOLE, Dual>(cd, v, mc2, steps, out);
+            else if (kind == CHX_DKD_RFCAVITY) dkd_map<CHX_DKD_RFCAVITY, Dual>(cd, v, mc2, steps, out);
+            else dkd_map<CHX_DKD_MULTIPOLE, Dual>(cd, v, mc2, steps, out);
+#pragma unroll
+            for (int j = 0; j < 6; ++j) v[j] = out[j];
+            if (along && column) {
+                double* Ma = o.matrix_along + (seed * (int64_t)(E + 1) + e + 1) * 36;
+#pragma unroll
+                for (int i = 0; i < 6; ++i) Ma[i * 6 + m] = v[i].d;
+                if (m == 0) {
+                    double* xa = o.orbit_along + (seed * (int64_t)(E + 1) + e + 1) * 6;
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) xa[i] = v[i].v;
+                }
+            }
+        }
+        // the group's matrix and image in LDS: lane m < 6 holds column m
+        if (m < 6) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) sM[g][i * 6 + m] = v[i].d;
+        }
+        if (m == 0) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) sF[g][i] = v[i].v;
+        }
+        __syncthreads();
+        if (!last) {
+            if (m == 0) newton_step(n, sM[g], sF[g], x, sA[g], sStep[g]);
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < 6; ++j)
+                if (j < n) x[j] = x[j] + sStep[g][j];
+            __syncthreads();
+            continue;
+        }
+        // a seed whose image is not finite (beyond the dynamic aperture, a search that ran away) is NaN in ALL its rows — the
+        // coordinates a lost particle happens to keep (delta, say) and their unit derivatives would read as results. Every lane
+        // of the group sees the same values. (The seed of a plain map, mode 0, is handed back as it came.)
+        bool lost = false;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) lost = lost || !(fabs(v[i].v) <= 1.79769313486231570815e308);
+        if (column) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) o.matrix[seed * 36 + i * 6 + m] = lost ? NAN : v[i].d;
+            double xm = x[0];
+#pragma unroll
+            for (int j = 1; j < 6; ++j) xm = m == j ? x[j] : xm;
+            o.orbit[seed * 6 + m] = (lost && mode != 0) ? NAN : xm;
+            o.image[seed * 6 + m] = lost ? NAN : sF[g][m];
+        }
+        if (live && m == 0) {
+            o.residual[seed] = lost ? NAN : closing_error(n, sF[g], x);
+            dispersion(sM[g], sA[g], sStep[g]);
+            if (lost) {
+                for (int i = 0; i < 4; ++i) sStep[g][i] = NAN;
+            }
+        }
+        __syncthreads();
+        if (live && m < 4) o.dispersion[seed * 4 + m] = sStep[g][m];
     }
 }
 
@@ -2428,6 +2575,60 @@ extern "C" int chx_dkd_turns(const int32_t* kinds, const void* const* params, co
                                        s_out, workspace, l, tiles, (hipStream_t)stream);
     return dkd_turns_launch<double>(items, (int)E, bend, sext, rf, mp, 0, c, energy_in, energy_out, mass_eV, n_charges, s_in, s_out, workspace, l,
                                     tiles, (hipStream_t)stream);
+}
+
+// The one-turn map of such a ring with its Jacobian, and the closed orbit (include/chx.h). Two launches: the constants of ONE turn
+// (dkd_chain_prepare_kernel: the walk of the reference energy a first turn of chx_dkd_turns makes), then dkd_ring_jacobian_kernel.
+extern "C" size_t chx_dkd_ring_jacobian_workspace_bytes(int64_t E) {
+    if (E < 1 || E > kDkdChainMax) return 0;
+    return (size_t)E * kDkdCstStride * sizeof(double) + (((size_t)E * sizeof(double) + 15) / 16) * 16;
+}
+
+extern "C" int chx_dkd_ring_jacobian(const int32_t* kinds, const void* const* params, const int32_t* num_steps, const int32_t* fringe_at,
+                                     int64_t E, const void* energy_in, double mass_eV, double n_charges, int dtype, const double* start,
+                                     int64_t B, int mode, int64_t num_iterations, int record_along, double* orbit, double* image,
+                                     double* matrix, double* residual, double* dispersion, double* orbit_along, double* matrix_along,
+                                     void* s_along, void* workspace, size_t workspace_bytes, void* stream) {
+    static_assert(kRingCstStride == kDkdCstStride && kRingMeta == kDkdMeta, "dkd_ring_jacobian_kernel reads the chain's blocks");
+    if (dtype != CHX_F32 && dtype != CHX_F64) return CHX_ERR_DTYPE;
+    if (!kinds || !params || !num_steps || !fringe_at || E < 1 || E > kDkdChainMax || !energy_in || !start || B < 1 || !orbit || !image ||
+        !matrix || !residual || !dispersion || !workspace)
+        return CHX_ERR_INVALID_ARG;
+    if (mode < 0 || mode > 2 || (mode != 0 && (num_iterations < 1 || num_iterations >= 0x7fffffffLL))) return CHX_ERR_INVALID_ARG;
+    if (record_along != 0 && record_along != 1) return CHX_ERR_INVALID_ARG;
+    if (record_along && (!orbit_along || !matrix_along || !s_along)) return CHX_ERR_INVALID_ARG;
+    for (int64_t e = 0; e < E; ++e) {
+        if (!params[e] || (kinds[e] != CHX_DKD_DRIFT && kinds[e] != CHX_DKD_QUADRUPOLE && kinds[e] != CHX_DKD_DIPOLE && kinds[e] != CHX_DKD_SEXTUPOLE &&
+                           kinds[e] != CHX_DKD_RFCAVITY && kinds[e] != CHX_DKD_MULTIPOLE) ||
+            num_steps[e] < 1 || num_steps[e] >= (1 << 25) || fringe_at[e] < 0 || fringe_at[e] > 3)
+            return CHX_ERR_INVALID_ARG;
+    }
+    const int64_t groups = chx_optics::workgroups(B);
+    if (groups > 0x7fffffffLL) return CHX_ERR_INVALID_ARG;
+    if (workspace_bytes < chx_dkd_ring_jacobian_workspace_bytes(E) || !chx_aligned16(workspace)) return CHX_ERR_INVALID_ARG;
+    DkdChainArgs items;
+    for (int e = 0; e < kDkdChainMax; ++e) {
+        items.params[e] = e < E ? params[e] : nullptr;
+        items.length[e] = nullptr;                            // every kind's first parameter is its length
+        items.meta[e] = e < E ? (kinds[e] | (fringe_at[e] << 4) | (num_steps[e] << 6)) : 0;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    double* cst = (double*)workspace;
+    void* energies = (char*)workspace + (size_t)E * kDkdCstStride * sizeof(double);
+    if (dtype == CHX_F32)
+        hipLaunchKernelGGL(dkd_chain_prepare_kernel<float>, dim3((unsigned)E), dim3(64), 0, s, items, (int)E, (const float*)energy_in, mass_eV,
+                           n_charges, cst, (float*)energies, (const float*)nullptr, (float*)nullptr);
+    else
+        hipLaunchKernelGGL(dkd_chain_prepare_kernel<double>, dim3((unsigned)E), dim3(64), 0, s, items, (int)E, (const double*)energy_in, mass_eV,
+                           n_charges, cst, (double*)energies, (const double*)nullptr, (double*)nullptr);
+    CHX_CHECK_LAUNCH();
+    const RingJacobianOut o{orbit, image, matrix, residual, dispersion, record_along ? orbit_along : nullptr,
+                            record_along ? matrix_along : nullptr, record_along ? s_along : nullptr};
+    const int passes = mode == 0 ? 1 : (int)num_iterations + 1;
+    hipLaunchKernelGGL(dkd_ring_jacobian_kernel, dim3((unsigned)groups), dim3(chx_optics::kLanes), 0, s, (const double*)cst, (int)E, mass_eV, start,
+                       B, mode, passes, dtype == CHX_F32 ? 1 : 0, o);
+    CHX_CHECK_LAUNCH();
+    return CHX_OK;
 }
 
 namespace {

@@ -1,0 +1,185 @@
+"""Linear optics of a ring from its one-turn matrix: what `Segment.one_turn_map`, `Segment.closed_orbit` and `Segment.ring_optics`
+return, and the algebra between them.
+
+`twiss_from_matrix`, `propagate_twiss` and `eigen_tunes` are plain float64 torch on whatever device their inputs are on (no
+kernel, no synchronisation): they also run on CPU tensors. The matrices come from `chx_dkd_ring_jacobian` (include/chx.h), which
+carries a phase-space point and its six tangents through a ring of drift-kick-drift elements in one launch.
+
+Coordinates: (x, px, y, py, tau, delta). A one-turn matrix M is symplectic with S = diag(J2, J2, -J2) (tau and delta form a pair
+of the opposite sign), which is why the off-momentum quantities below read column 5 and row 4.
+
+beta, alpha and the phase advance are the UNCOUPLED (projected) functions of the two diagonal 2 x 2 blocks. In a ring with
+coupling (tilted quadrupoles, skew multipoles, an orbit off the axis of a sextupole) they are not the functions of the normal
+modes; `RingOptics.coupling` — the largest absolute entry of the two off-diagonal 2 x 2 blocks of M_4 — says when to distrust
+them. The tunes are eigen-tunes of the full 4 x 4 block and stay right with coupling.
+
+Out of scope here: vectorised lattice settings, gradients of the optics with respect to settings, Edwards-Teng or other coupled
+parametrisations, the synchrotron tune of a 6-D search (`matrix` is returned: take its eigenvalues), second-order and linear rings."""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+__all__ = ["OneTurnMap", "ClosedOrbit", "RingOptics", "twiss_from_matrix", "propagate_twiss", "eigen_tunes"]
+
+_TWO_PI = 2.0 * math.pi
+
+
+def _block(M: torch.Tensor, plane: int) -> torch.Tensor:
+    return M[..., 2 * plane:2 * plane + 2, 2 * plane:2 * plane + 2]
+
+
+def twiss_from_matrix(M: torch.Tensor):
+    """(beta, alpha, mu) of a periodic 2 x 2 block M (..., 2, 2): cos mu = tr / 2, beta = M12 / sin mu, alpha = (M11 - M22) / (2 sin mu)
+    with the sign of sin mu taken from M12, so beta > 0 and mu lies in (0, 2 pi): a fractional tune above one half comes back above
+    one half. NaN where |tr| >= 2 (no periodic solution)."""
+    M = M.to(torch.float64)
+    m11, m12, m22 = M[..., 0, 0], M[..., 0, 1], M[..., 1, 1]
+    cos_mu = 0.5 * (m11 + m22)
+    # sin^2 = 1 - cos^2 loses digits beside cos = +-1; det M = 1 gives the same number as -(M12 M21) - ((M11 - M22) / 2)^2
+    half = 0.5 * (m11 - m22)
+    sin2 = -(m12 * M[..., 1, 0]) - half * half
+    stable = (cos_mu.abs() < 1.0) & (sin2 > 0)
+    nan = torch.full_like(cos_mu, float("nan"))
+    sin_mu = torch.where(stable, torch.sqrt(torch.where(stable, sin2, torch.ones_like(sin2))) * torch.sign(m12), nan)
+    beta = m12 / sin_mu
+    alpha = half / sin_mu
+    mu = torch.remainder(torch.atan2(sin_mu, cos_mu), _TWO_PI)
+    return beta, alpha, mu
+
+
+def propagate_twiss(A: torch.Tensor, beta0: torch.Tensor, alpha0: torch.Tensor):
+    """(beta, alpha, phase) behind a 2 x 2 transfer block A (..., 2, 2) for the functions beta0, alpha0 in front of it:
+    beta = ((A11 beta0 - A12 alpha0)^2 + A12^2) / beta0, alpha = -((A11 beta0 - A12 alpha0)(A21 beta0 - A22 alpha0) + A12 A22) / beta0,
+    phase = atan2(A12, A11 beta0 - A12 alpha0) in [0, 2 pi)."""
+    A = A.to(torch.float64)
+    a11, a12, a21, a22 = A[..., 0, 0], A[..., 0, 1], A[..., 1, 0], A[..., 1, 1]
+    u = a11 * beta0 - a12 * alpha0
+    w = a21 * beta0 - a22 * alpha0
+    beta = (u * u + a12 * a12) / beta0
+    alpha = -(u * w + a12 * a22) / beta0
+    phase = torch.remainder(torch.atan2(a12, u), _TWO_PI)
+    return beta, alpha, phase
+
+
+def eigen_tunes(M4: torch.Tensor):
+    """(tunes, stable) of a symplectic 4 x 4 one-turn block (..., 4, 4), both (..., 2): the eigenvalues come in pairs exp(+-i mu), and
+    u = 2 cos mu solves u^2 - a u + (b - 2) = 0 with a = tr M and b = (a^2 - tr M^2) / 2 — closed form, no eigen-solver. The two roots
+    go to x and y by the nearer trace of a diagonal block; the fractional tune lies in [0, 1) with the sign of sin mu from M12 (M34).
+    NaN and stable = False where a root is complex or |u| > 2."""
+    M4 = M4.to(torch.float64)
+    a = M4.diagonal(dim1=-2, dim2=-1).sum(-1)
+    tr2 = (M4 * M4.transpose(-1, -2)).sum((-2, -1))
+    b = 0.5 * (a * a - tr2)
+    # the roots of u^2 - a u + (b - 2): discriminant a^2 - 4 b + 8 = 2 tr M^2 - a^2 + 8
+    disc = a * a - 4.0 * (b - 2.0)
+    real = disc >= 0
+    root = torch.sqrt(torch.where(real, disc, torch.zeros_like(disc)))
+    u_hi, u_lo = 0.5 * (a + root), 0.5 * (a - root)
+    tx = M4[..., 0, 0] + M4[..., 1, 1]
+    ty = M4[..., 2, 2] + M4[..., 3, 3]
+    x_high = tx >= ty                                           # the larger root to the plane with the larger block trace
+    u = torch.stack([torch.where(x_high, u_hi, u_lo), torch.where(x_high, u_lo, u_hi)], dim=-1)
+    sign = torch.sign(torch.stack([M4[..., 0, 1], M4[..., 2, 3]], dim=-1))
+    stable = real.unsqueeze(-1) & (u.abs() <= 2.0)
+    cos_mu = torch.where(stable, 0.5 * u, torch.zeros_like(u))
+    mu = torch.acos(cos_mu)                                     # in [0, pi]
+    mu = torch.where(sign < 0, _TWO_PI - mu, mu)
+    tunes = torch.remainder(mu / _TWO_PI, 1.0)
+    return torch.where(stable, tunes, torch.full_like(tunes, float("nan"))), stable
+
+
+def _along(matrix_along: torch.Tensor, beta0: torch.Tensor, alpha0: torch.Tensor):
+    """beta, alpha and the accumulated phase (B, E + 1, 2) from the cumulative matrices (B, E + 1, 6, 6) and the start values (B, 2)."""
+    betas, alphas, phases = [], [], []
+    for plane in range(2):
+        A = _block(matrix_along, plane)                                        # (B, E + 1, 2, 2)
+        b0, a0 = beta0[:, None, plane], alpha0[:, None, plane]
+        beta, alpha, phi = propagate_twiss(A, b0, a0)
+        # item by item: each increment in [0, 2 pi) (an item advances the phase by less than a turn) — so the accumulated phase is
+        # phi_k plus 2 pi for every item at which phi fell. Counted in integers: no sum of rounded increments, and the same bits
+        # for a seed whatever the batch it stands in. (A fall of rounding size — a thin kick between the two rotations of a tilt —
+        # is no advance of a whole turn.)
+        wraps = torch.cumsum(((phi[:, 1:] - phi[:, :-1]) < -1e-9).to(torch.int64), dim=1)
+        total = phi + _TWO_PI * torch.cat([torch.zeros_like(wraps[:, :1]), wraps], dim=1).to(torch.float64)       # (NaN stays NaN)
+        betas.append(beta)
+        alphas.append(alpha)
+        phases.append(total)
+    return torch.stack(betas, -1), torch.stack(alphas, -1), torch.stack(phases, -1)
+
+
+@dataclass
+class OneTurnMap:
+    """`Segment.one_turn_map`: `start` (B, 7) the seeds, `end` (B, 7) their images after one turn, `matrix` (B, 6, 6) with
+    matrix[b, i, m] = d end_i / d start_m, all float64. With `along`: `orbit_along` (B, E + 1, 7), `matrix_along` (B, E + 1, 6, 6) —
+    index 0 the start (the identity), index k behind item k of the ring, the cumulative map — and `s` (E + 1,) in the settings' dtype."""
+    start: torch.Tensor
+    end: torch.Tensor
+    matrix: torch.Tensor
+    orbit_along: Optional[torch.Tensor] = None
+    matrix_along: Optional[torch.Tensor] = None
+    s: Optional[torch.Tensor] = None
+
+
+@dataclass
+class ClosedOrbit:
+    """`Segment.closed_orbit`: `orbit` (B, 7) the closed orbit at the start of the ring, `residual` (B,) = max |one turn of it - it| over
+    the closed coordinates (x, px, y, py; with `longitudinal` all six), `matrix` (B, 6, 6) the one-turn matrix on it, `dispersion`
+    (B, 4) = (I - M_4)^-1 M[:4, 5], d(x, px, y, py) / d delta of the 4-D closed orbit. float64. A seed whose search failed (beyond the
+    dynamic aperture, a singular Newton system) is NaN in its own rows."""
+    orbit: torch.Tensor
+    residual: torch.Tensor
+    matrix: torch.Tensor
+    dispersion: torch.Tensor
+
+
+@dataclass
+class RingOptics(ClosedOrbit):
+    """`Segment.ring_optics`: the `ClosedOrbit` fields and
+    tunes (B, 2)          the fractional eigen-tunes of the 4 x 4 block in [0, 1) (`eigen_tunes`), NaN where unstable
+    stable (B, 2)         bool
+    coupling (B,)         the largest absolute entry of the two off-diagonal 2 x 2 blocks of M_4
+    beta, alpha, phase_advance   (B, E + 1, 2) with `along` — index 0 the start, index k behind item k — else the start values (B, 2)
+                          (phase_advance: zeros). The UNCOUPLED (projected) functions of the diagonal blocks: `coupling` tells
+                          when to distrust them. phase_advance[:, -1] / 2 pi is the full tune with its integer part.
+    dispersion_along (B, E + 1, 4)   eta_k = A_k[:4, :4] eta_0 + A_k[:4, 5] (None without `along`)
+    orbit_along (B, E + 1, 7)        the closed orbit behind every item (None without `along`)
+    slip (B,)             M[4, 5] + M[4, :4] . eta_0: d tau / d delta per turn on the dispersive orbit
+    s (E + 1,)            the path length behind every item, in the settings' dtype (None without `along`)"""
+    tunes: torch.Tensor = None
+    stable: torch.Tensor = None
+    coupling: torch.Tensor = None
+    beta: torch.Tensor = None
+    alpha: torch.Tensor = None
+    phase_advance: torch.Tensor = None
+    slip: torch.Tensor = None
+    dispersion_along: Optional[torch.Tensor] = None
+    orbit_along: Optional[torch.Tensor] = None
+    s: Optional[torch.Tensor] = None
+
+
+def ring_optics_from(closed: ClosedOrbit, orbit_along=None, matrix_along=None, s=None) -> RingOptics:
+    """The optics of a closed orbit and (optionally) the cumulative matrices along the ring: torch algebra only."""
+    M = closed.matrix
+    M4 = M[:, :4, :4]
+    tunes, stable_eig = eigen_tunes(M4)
+    coupling = torch.maximum(M4[:, :2, 2:].abs().amax((-2, -1)), M4[:, 2:, :2].abs().amax((-2, -1)))
+    b0, a0 = [], []
+    for plane in range(2):
+        beta, alpha, _ = twiss_from_matrix(_block(M, plane))
+        b0.append(beta)
+        a0.append(alpha)
+    beta0, alpha0 = torch.stack(b0, -1), torch.stack(a0, -1)
+    stable = stable_eig
+    eta0 = closed.dispersion
+    slip = M[:, 4, 5] + (M[:, 4, :4] * eta0).sum(-1)
+    if matrix_along is None:
+        return RingOptics(closed.orbit, closed.residual, M, eta0, tunes=tunes, stable=stable, coupling=coupling, beta=beta0, alpha=alpha0,
+                          phase_advance=torch.zeros_like(beta0), slip=slip)
+    beta, alpha, phase = _along(matrix_along, beta0, alpha0)
+    eta = (matrix_along[:, :, :4, :4] @ eta0[:, None, :, None]).squeeze(-1) + matrix_along[:, :, :4, 5]
+    return RingOptics(closed.orbit, closed.residual, M, eta0, tunes=tunes, stable=stable, coupling=coupling, beta=beta, alpha=alpha,
+                      phase_advance=phase, slip=slip, dispersion_along=eta, orbit_along=orbit_along, s=s)

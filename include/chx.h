@@ -1281,6 +1281,40 @@ int chx_dkd_turns(const int32_t* kinds, const void* const* params, const int32_t
                   double n_charges, const void* charges, const void* survival, int64_t N, int dtype, int64_t first_turn,
                   int64_t num_turns, int64_t record_every, const void* aperture, int64_t K, void* x_out, int32_t* lost_turn,
                   double* sums, void* probe, const void* s_in, void* s_out, void* workspace, size_t workspace_bytes, void* stream);
+/* The one-turn map of such a ring with its 6 x 6 Jacobian, and the closed orbit (Segment.one_turn_map, closed_orbit, ring_optics).
+ * HOST arrays kinds[E], params[E], num_steps[E], fringe_at[E] as in chx_dkd_turns, 1 <= E <= 192, scalar settings of `dtype`;
+ * energy_in (dtype scalar) is the reference energy in front of the turn, walked through ONE turn as the first turn of
+ * chx_dkd_turns walks it (the same kernel prepares the same 56 doubles per item). The maps are evaluated in float64 through their
+ * dual-number instantiation whatever dtype is: the values are those of storage_precision = 0, every output is float64.
+ *   start[B][6]: the seeds (x, px, y, py, tau, delta).
+ *   mode 0: the map at the seeds. mode 1: the 4-D closed orbit, x, px, y, py closed while tau and delta keep the seed's values.
+ *     mode 2: the 6-D closed orbit (all six closed; meaningful with an RFCavity on a harmonic of the revolution frequency).
+ *   num_iterations (modes 1, 2; not read in mode 0): Newton steps x_c += solve((M_c - I) step = -(f(x) - x)_c) on the closed
+ *     coordinates c, by Gaussian elimination with partial pivoting in float64 on the device, followed by one more pass from the
+ *     final point. A FIXED count for every seed: no early exit, two calls give the same bits. A singular or non-finite system
+ *     leaves NaN in that seed's outputs and in no other's, and so does an image that is not finite (a seed beyond the dynamic
+ *     aperture): orbit, image, matrix, residual and dispersion of that seed are then NaN throughout (mode 0 hands the seed back
+ *     in orbit), the records along the ring stay what the last pass met.
+ *   orbit[B][6]: the point the last pass started from (mode 0: the seed); image[B][6]: where it went; matrix[B][6][6], matrix[i][m] =
+ *     d image_i / d orbit_m; residual[B] = max |image - orbit| over c (mode 0: over x, px, y, py); dispersion[B][4] = the solution of
+ *     (I - M_4) eta = matrix[:4][5] from the same solver, in every mode (NaN when I - M_4 is singular).
+ *   record_along = 1: orbit_along[B][E + 1][6] and matrix_along[B][E + 1][6][6] of the last pass — index 0 the start (the identity),
+ *     index k behind item k, the cumulative map from the start — and s_along[E + 1] (dtype): 0 and the lengths added item by item
+ *     in dtype as chx_dkd_chain adds them. With record_along = 0 the three pointers are not read.
+ *   workspace: chx_dkd_ring_jacobian_workspace_bytes(E) bytes, 16-byte aligned (the constants and the energies behind the items);
+ *     0 for E out of range.
+ * One lane per (seed, tangent direction), eight lanes per seed, eight seeds per single-wave workgroup. Two launches, none
+ * synchronising; the results of a seed do not depend on B.
+ * CHX_ERR_INVALID_ARG, before any launch: E < 1, E > 192, a kind other than the six, num_steps outside 1 .. 2^25 - 1, fringe_at
+ * outside 0..3, B < 1, mode outside 0..2, num_iterations < 1 in modes 1 and 2, record_along outside 0..1, a required pointer that is
+ * NULL, a workspace too small or not 16-byte aligned; CHX_ERR_DTYPE: dtype other than CHX_F32 / CHX_F64.
+ * (An additive export: CHX_ABI_VERSION stays as it is.) */
+size_t chx_dkd_ring_jacobian_workspace_bytes(int64_t E);
+int chx_dkd_ring_jacobian(const int32_t* kinds, const void* const* params, const int32_t* num_steps, const int32_t* fringe_at,
+                          int64_t E, const void* energy_in, double mass_eV, double n_charges, int dtype, const double* start,
+                          int64_t B, int mode, int64_t num_iterations, int record_along, double* orbit, double* image,
+                          double* matrix, double* residual, double* dispersion, double* orbit_along, double* matrix_along,
+                          void* s_along, void* workspace, size_t workspace_bytes, void* stream);
 /* Backward of chx_dkd_track (the reference gets it from torch autograd through utils/bmadx.py): forward-mode dual
  * numbers on device, one seeded evaluation per input. dx[B][N][7] (dtype, may be NULL) = dY . d x_out / d x_in;
  * partials (may be NULL) = chx_dkd_bwd_partials_count() doubles laid out [B][ceil(N/256)][P + 1]: per workgroup
