@@ -1,7 +1,9 @@
 """The one-turn map of a ring of drift-kick-drift elements, its 6 x 6 Jacobian and the closed orbit (Segment.one_turn_map,
 closed_orbit, ring_optics) in one call of `chx_dkd_ring_jacobian`: a lane per (seed, tangent direction) carries the point and one
 tangent through all items in registers, the Newton steps of the closed orbit run inside the kernel. Two launches, no workspace
-beyond the items' constants, no host synchronisation, deterministic. The definition: include/chx.h, DESIGN.md.
+beyond the items' constants, no host synchronisation, deterministic. `chx_dkd_ring_sensitivity` gives the derivatives of those
+results with respect to knobs on the ring's settings (Segment.ring_sensitivity, the `wrt` argument): a group of lanes per (seed,
+knob) carries second-order dual numbers through the same maps. The definitions: include/chx.h, DESIGN.md.
 
 Part of `_ops` (which re-exports every name here). Imported at the END of `_ops`, whose helpers it uses."""
 from __future__ import annotations
@@ -14,7 +16,7 @@ from . import _lib
 from ._lib import c_i64, c_int, c_void_p
 from ._ops import check, dtype_code, ptr, require_device, stream_ptr, workspace
 
-__all__ = ["RING_MAX_ITEMS", "RING_MODES", "dkd_ring_jacobian"]
+__all__ = ["RING_MAX_ITEMS", "RING_MODES", "dkd_ring_jacobian", "dkd_ring_sensitivity"]
 
 #: the most items one ring may have (kDkdChainMax of csrc/chx_nonlinear.hip, the limit of chx_dkd_turns)
 RING_MAX_ITEMS = 192
@@ -25,8 +27,13 @@ _lib.SIGNATURES["chx_dkd_ring_jacobian_workspace_bytes"] = (ctypes.c_size_t, [c_
 _lib.SIGNATURES["chx_dkd_ring_jacobian"] = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, ctypes.c_double, ctypes.c_double,
                                                     c_int, c_void_p, c_i64, c_int, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p])
+_lib.SIGNATURES["chx_dkd_ring_sensitivity_workspace_bytes"] = (ctypes.c_size_t, [c_i64, c_i64])
+_lib.SIGNATURES["chx_dkd_ring_sensitivity"] = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, ctypes.c_double, ctypes.c_double,
+                                                       c_int, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p,
+                                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p])
 if _lib._lib is not None:                       # the library was loaded before this module: bind the symbols now
-    for _name in ("chx_dkd_ring_jacobian_workspace_bytes", "chx_dkd_ring_jacobian"):
+    for _name in ("chx_dkd_ring_jacobian_workspace_bytes", "chx_dkd_ring_jacobian", "chx_dkd_ring_sensitivity_workspace_bytes",
+                  "chx_dkd_ring_sensitivity"):
         _fn = getattr(_lib._lib, _name)
         _fn.restype, _fn.argtypes = _lib.SIGNATURES[_name]
 
@@ -56,4 +63,33 @@ def dkd_ring_jacobian(arrays, E: int, energy: torch.Tensor, mass_eV: float, n_ch
                                     ptr(out["matrix"]), ptr(out["residual"]), ptr(out["dispersion"]), ptr(out.get("orbit_along")),
                                     ptr(out.get("matrix_along")), ptr(out.get("s_along")), ptr(ws), ws.numel(), stream_ptr()),
           "chx_dkd_ring_jacobian")
+    return out
+
+
+def dkd_ring_sensitivity(arrays, E: int, energy: torch.Tensor, mass_eV: float, n_charges: float, orbit: torch.Tensor, mode: int, components,
+                         K: int, along: bool):
+    """chx_dkd_ring_sensitivity for the host arrays of `dkd_turn_arrays` (E items), the converged orbits (B, 6) float64 of a
+    `dkd_ring_jacobian` call of the same mode and K knobs given by `components`, a sequence of (knob, item, slot): a dict of float64
+    tensors d_orbit (B, K, 6), d_image (B, K, 6), d_matrix (B, K, 6, 6), d_dispersion (B, K, 4) and, with `along`, d_orbit_along (B, K, E + 1, 6) and
+    d_matrix_along (B, K, E + 1, 6, 6). Launches only."""
+    if orbit.dim() != 2 or orbit.shape[1] != 6 or orbit.dtype != torch.float64:
+        raise ValueError(f"the orbits must be a float64 tensor of the shape (B, 6), got {orbit.dtype} {tuple(orbit.shape)}")
+    require_device(orbit, energy)
+    orbit = orbit.contiguous()
+    B, K, dev = int(orbit.shape[0]), int(K), orbit.device
+    f64 = {"dtype": torch.float64, "device": dev}
+    out = {"d_orbit": torch.empty((B, K, 6), **f64), "d_image": torch.empty((B, K, 6), **f64), "d_matrix": torch.empty((B, K, 6, 6), **f64),
+           "d_dispersion": torch.empty((B, K, 4), **f64)}
+    if along:
+        out["d_orbit_along"] = torch.empty((B, K, E + 1, 6), **f64)
+        out["d_matrix_along"] = torch.empty((B, K, E + 1, 6, 6), **f64)
+    components = list(components)
+    i32 = ctypes.c_int32 * max(len(components), 1)
+    knob_of, item_of, slot_of = (i32(*[int(c[j]) for c in components]) for j in range(3))
+    lib = _lib.lib()
+    ws = workspace(lib.chx_dkd_ring_sensitivity_workspace_bytes(E, K), dev)
+    check(lib.chx_dkd_ring_sensitivity(arrays[0], arrays[1], arrays[2], arrays[3], E, ptr(energy), mass_eV, n_charges, dtype_code(energy.dtype),
+                                       ptr(orbit), B, int(mode), knob_of, item_of, slot_of, len(components), K, int(bool(along)),
+                                       ptr(out["d_orbit"]), ptr(out["d_image"]), ptr(out["d_matrix"]), ptr(out["d_dispersion"]), ptr(out.get("d_orbit_along")),
+                                       ptr(out.get("d_matrix_along")), ptr(ws), ws.numel(), stream_ptr()), "chx_dkd_ring_sensitivity")
     return out

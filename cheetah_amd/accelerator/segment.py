@@ -873,10 +873,12 @@ class Segment(Element):
             return f"{reason}; nor is it a ring of drift-kick-drift elements: {ring}"
         return ring
 
-    def _turn_items_dkd(self, plan, x: torch.Tensor):
+    def _turn_items_dkd(self, plan, x: torch.Tensor, trainable=()):
         """A `_DkdRing` when the WHOLE plan is a ring `chx_dkd_turns` takes — drift-kick-drift Drifts, Quadrupoles, Dipoles, Sextupoles, RFCavities and Multipoles as
         `_dkd_run` keeps them in registers, all of one arithmetic class, 1 to 192 of them, Markers in between skipped — else the
-        reason (a str) why not. Nothing is kept between calls: settings and `dkd_precision` are read here every time."""
+        reason (a str) why not. Nothing is kept between calls: settings and `dkd_precision` are read here every time.
+        `trainable`: the ids of the settings that may require grad (the `wrt` of the ring optics; `track_turns` has none), or
+        "all"."""
         kinds, params, steps, fringes, classes, tensors = [], [], [], [], [], []
         single = x.dtype == torch.float64                      # (float64 beams are evaluated in fp64 whatever `dkd_precision` says)
         for kind, e in plan:
@@ -908,7 +910,7 @@ class Segment(Element):
             return f"the ring has {len(kinds)} drift-kick-drift elements, the fused kernel takes 1 to 192"
         if len(set(classes)) > 1:
             return "the elements' `dkd_precision` settings put them into more than one arithmetic class (one launch evaluates one)"
-        if any(t.requires_grad for t in tensors):
+        if trainable != "all" and any(t.requires_grad and id(t) not in trainable for t in tensors):
             return "a setting of the lattice requires grad"
         return _DkdRing(kinds, params, steps, fringes, classes[0])
 
@@ -1057,9 +1059,51 @@ class Segment(Element):
                                  record_every=record_every)
 
     # ---- linear optics of a ring --------------------------------------------------------------------------------
-    def _ring_jacobian(self, what: str, energy, species, start: torch.Tensor, mode: int, num_iterations: int, along: bool):
+    @staticmethod
+    def _ring_knobs(what: str, plan, wrt):
+        """The knobs of `wrt` — a sequence of tensors, each by identity a setting `_dkd_scalar_refs()` lists for an element of the
+        ring, or "all": every such setting that requires grad — as (tensors, per tensor (first knob, count, 0-d?), components
+        [(knob, item, slot)], K). A 0-d setting is one knob, an (n,) setting n knobs; a tensor many elements share is one knob
+        with a component per element."""
+        refs = []                                              # (item, slot, tensor, index) in the ring's order
+        item = 0
+        for kind, e in plan:
+            if kind == "run":
+                continue                                       # (Markers: `_turn_items_dkd` has refused every other run)
+            for slot, (t, index) in enumerate(e._dkd_scalar_refs()):
+                refs.append((item, slot, t, index))
+            item += 1
+        if isinstance(wrt, str):
+            if wrt != "all":
+                raise ValueError(f"{what}: wrt must be a sequence of tensors or 'all', got {wrt!r}")
+            seen, wrt = set(), []
+            for _, _, t, _ in refs:
+                if t.requires_grad and id(t) not in seen:
+                    seen.add(id(t))
+                    wrt.append(t)
+        wrt = list(wrt)
+        first, layout, components = {}, [], []
+        K = 0
+        for pos, t in enumerate(wrt):
+            if not isinstance(t, torch.Tensor) or not any(r[2] is t for r in refs):
+                raise ValueError(f"{what}: wrt[{pos}] is not a setting of a drift-kick-drift element of this ring (settings are found by "
+                                 "identity: pass the tensor the element holds)")
+            if id(t) in first:
+                raise ValueError(f"{what}: wrt[{pos}] is the tensor of wrt[{[id(u) for u in wrt].index(id(t))}] again")
+            first[id(t)] = K
+            layout.append((K, max(t.numel(), 1), t.dim() == 0))
+            K += max(t.numel(), 1)
+        for item, slot, t, index in refs:
+            if id(t) in first:
+                components.append((first[id(t)] + (0 if index is None else int(index)), item, slot))
+        return wrt, layout, components, K
+
+    def _ring_jacobian(self, what: str, energy, species, start: torch.Tensor, mode: int, num_iterations: int, along: bool, wrt=None,
+                       raw: bool = False):
         """`_ops.dkd_ring_jacobian` for this lattice taken as a ring: the conditions of `_turn_items_dkd` (whose reason a lattice
-        that does not qualify is refused with), the energy as a 0-d tensor of the settings' dtype on the seeds' device."""
+        that does not qualify is refused with), the energy as a 0-d tensor of the settings' dtype on the seeds' device.
+        With `wrt` (`_ring_knobs`) also `_ops.dkd_ring_sensitivity` on the orbits found: the same dict with an autograd graph to
+        those settings (`particles.optics.attach_gradients`) or, with `raw`, the pair (values, tangents) as the kernels left them."""
         if not isinstance(energy, torch.Tensor):
             lengths = [e.length for e in self._leaves() if isinstance(getattr(e, "length", None), torch.Tensor)]
             energy = torch.as_tensor(float(energy), dtype=lengths[0].dtype if lengths else torch.float64, device=start.device)
@@ -1076,15 +1120,32 @@ class Segment(Element):
             raise ValueError(f"{what} has no autograd: an input requires grad")
         if type(self).track is not Segment.track or type(self)._track_internal is not Segment._track_internal:
             raise ValueError(f"{what}: the segment overrides `track`")
+        if wrt is not None and not isinstance(wrt, str):
+            try:
+                wrt = list(wrt)                               # once: a generator is read here and nowhere else
+            except TypeError:
+                raise ValueError(f"{what}: wrt must be a sequence of tensors or 'all', got {type(wrt).__name__}") from None
         with torch.no_grad():
             plan = self._plan()
-            ring = self._turn_items_dkd(plan, torch.empty((0, 7), dtype=energy.dtype, device=energy.device)) if plan else \
+            trainable = () if wrt is None else ("all" if isinstance(wrt, str) else {id(t) for t in wrt})
+            ring = self._turn_items_dkd(plan, torch.empty((0, 7), dtype=energy.dtype, device=energy.device), trainable) if plan else \
                 "the lattice holds nothing to track"
             if isinstance(ring, str):
                 raise ValueError(f"{what}: {ring}")
+            if wrt is not None:
+                wrt, layout, components, K = self._ring_knobs(what, plan, wrt)
             arrays = _ops.dkd_turn_arrays(ring.kinds, ring.params, ring.num_steps, ring.fringe_at)
-            return _ops.dkd_ring_jacobian(arrays, len(ring.kinds), energy, species.mass_eV_float, species.num_elementary_charges_float,
-                                          start, mode, num_iterations, along)
+            out = _ops.dkd_ring_jacobian(arrays, len(ring.kinds), energy, species.mass_eV_float, species.num_elementary_charges_float,
+                                         start, mode, num_iterations, along)
+            if wrt is None or (K == 0 and not raw):
+                return out
+            sens = _ops.dkd_ring_sensitivity(arrays, len(ring.kinds), energy, species.mass_eV_float, species.num_elementary_charges_float,
+                                             out["orbit"], mode, components, K, along)
+        if raw:
+            return out, sens
+        from ..particles.optics import attach_gradients
+
+        return attach_gradients(out, sens, layout, wrt, 6 if mode == 2 else 4)
 
     @staticmethod
     def _seeds(start: torch.Tensor) -> torch.Tensor:
@@ -1099,7 +1160,7 @@ class Segment(Element):
     def _rows7(x6: torch.Tensor) -> torch.Tensor:
         return torch.cat([x6, torch.ones_like(x6[..., :1])], dim=-1)
 
-    def one_turn_map(self, start: torch.Tensor, energy, species=None, along: bool = False):
+    def one_turn_map(self, start: torch.Tensor, energy, species=None, along: bool = False, wrt=None):
         """One turn of this lattice, taken as a ring of drift-kick-drift elements, for the seeds `start` — (B, 6), (B, 7) or one
         such row, on the device — together with the 6 x 6 Jacobian of the turn at every seed: an `OneTurnMap` (particles/optics.py)
         with `start`, `end` (B, 7) and `matrix` (B, 6, 6), and with `along` the orbit and the cumulative matrix behind every item
@@ -1110,18 +1171,24 @@ class Segment(Element):
         `species=None`: electrons. The lattice must be a ring `track_turns` fuses — every item a Drift, Quadrupole, Dipole,
         Sextupole, RFCavity or Multipole with `tracking_method="drift_kick_drift"`, scalar settings without gradients, the stock
         `track`, 1 to 192 of them, Markers skipped; `dkd_precision` does not matter — else ValueError with the reason. There is no
-        general fallback. No autograd (an input that requires grad raises ValueError); the call does not synchronise.
-        Out of scope: vectorised settings, gradients with respect to settings, second-order and linear rings."""
+        general fallback. The call does not synchronise.
+
+        `wrt=None`: no autograd (an input that requires grad raises ValueError). `wrt` = a sequence of settings of the ring's
+        elements (the tensors the elements hold, found by identity) or "all" (every setting that requires grad): `end`, `matrix`
+        and the records along the ring carry an autograd graph to those settings, with the same bits as without `wrt`; the
+        derivatives come from `chx_dkd_ring_sensitivity` (`ring_sensitivity` returns them raw). A setting that requires grad and
+        is not in `wrt` is still refused; `start`, `energy` and the species stay without gradient.
+        Out of scope: vectorised settings, second-order and linear rings."""
         from ..particles.optics import OneTurnMap
 
         x = self._seeds(start)
-        out = self._ring_jacobian("one_turn_map", energy, species, x, 0, 1, along)
+        out = self._ring_jacobian("one_turn_map", energy, species, x, 0, 1, along, wrt)
         if not along:
             return OneTurnMap(self._rows7(out["orbit"]), self._rows7(out["image"]), out["matrix"])
         return OneTurnMap(self._rows7(out["orbit"]), self._rows7(out["image"]), out["matrix"], self._rows7(out["orbit_along"]),
                           out["matrix_along"], out["s_along"])
 
-    def _closed_orbit(self, what, energy, species, delta, guess, longitudinal, num_iterations, along):
+    def _closed_orbit(self, what, energy, species, delta, guess, longitudinal, num_iterations, along, wrt=None, raw=False):
         num_iterations = int(num_iterations)
         if num_iterations < 1:
             raise ValueError(f"{what}: num_iterations must be at least 1")
@@ -1140,9 +1207,9 @@ class Segment(Element):
                     raise ValueError(f"{what}: {d.shape[0]} values of delta for {x.shape[0]} guesses")
                 x = x.expand(max(d.shape[0], x.shape[0]), 6).clone()
             x[:, 5] = d
-        return self._ring_jacobian(what, energy, species, x, 2 if longitudinal else 1, num_iterations, along)
+        return self._ring_jacobian(what, energy, species, x, 2 if longitudinal else 1, num_iterations, along, wrt, raw)
 
-    def closed_orbit(self, energy, species=None, delta=None, guess=None, longitudinal: bool = False, num_iterations: int = 10):
+    def closed_orbit(self, energy, species=None, delta=None, guess=None, longitudinal: bool = False, num_iterations: int = 10, wrt=None):
         """The closed orbit of this lattice taken as a ring (the conditions of `one_turn_map`): a `ClosedOrbit` with `orbit` (B, 7),
         `residual` (B,), `matrix` (B, 6, 6) and `dispersion` (B, 4), float64.
 
@@ -1152,38 +1219,60 @@ class Segment(Element):
         the search elsewhere than on the axis. `num_iterations` Newton steps, a fixed count, run inside one kernel launch: the
         call never synchronises, and `residual` = max |turn(orbit) - orbit| over the closed coordinates tells whether each search
         arrived. A seed that fails (beyond the dynamic aperture, a singular system) is NaN in its own rows.
+        `wrt`: as in `one_turn_map` — every field then carries gradients to those settings, the orbit moving with them.
         Out of scope: the synchrotron tune of a 6-D search — `matrix` is returned, take its eigenvalues."""
         from ..particles.optics import ClosedOrbit
 
-        out = self._closed_orbit("closed_orbit", energy, species, delta, guess, longitudinal, num_iterations, False)
+        out = self._closed_orbit("closed_orbit", energy, species, delta, guess, longitudinal, num_iterations, False, wrt)
         return ClosedOrbit(self._rows7(out["orbit"]), out["residual"], out["matrix"], out["dispersion"])
 
     def ring_optics(self, energy, species=None, delta=None, guess=None, longitudinal: bool = False, num_iterations: int = 10,
-                    along: bool = True):
+                    along: bool = True, wrt=None):
         """The linear optics of this lattice taken as a ring: the closed-orbit search of `closed_orbit` (same arguments), then the
         tunes, beta, alpha, phase advance, dispersion and slip factor from the one-turn matrix on that orbit — a `RingOptics`
         (particles/optics.py lists the fields); with `along` (default) the functions behind every item, index 0 the start.
         beta, alpha and the phase are the uncoupled (projected) functions: `coupling` tells when to distrust them. One kernel
-        launch and a few float64 torch operations, no synchronisation. Out of scope: Edwards-Teng or other coupled
-        parametrisations, vectorised settings, gradients of the optics with respect to settings."""
+        launch and a few float64 torch operations, no synchronisation.
+        `wrt`: as in `one_turn_map` — tunes, beta, alpha, phase advance, dispersion, slip and orbit then carry gradients to those
+        settings (total derivatives: the closed orbit moves with a setting), e.g. `opt.tunes.sum().backward()`.
+        Out of scope: Edwards-Teng or other coupled parametrisations, vectorised settings, second derivatives."""
         from ..particles.optics import ClosedOrbit, ring_optics_from
 
-        out = self._closed_orbit("ring_optics", energy, species, delta, guess, longitudinal, num_iterations, along)
+        out = self._closed_orbit("ring_optics", energy, species, delta, guess, longitudinal, num_iterations, along, wrt)
         closed = ClosedOrbit(self._rows7(out["orbit"]), out["residual"], out["matrix"], out["dispersion"])
         if not along:
             return ring_optics_from(closed)
         return ring_optics_from(closed, self._rows7(out["orbit_along"]), out["matrix_along"], out["s_along"])
 
-    def chromaticity(self, energy, species=None, h: float = 1e-4) -> torch.Tensor:
+    def chromaticity(self, energy, species=None, h: float = 1e-4, wrt=None) -> torch.Tensor:
         """(dQx / d delta, dQy / d delta), shape (2,): the central difference of the FULL tunes (the integer part from the phase
-        advance along the ring) of one `ring_optics` call at delta = (-h, 0, +h). No synchronisation."""
+        advance along the ring) of one `ring_optics` call at delta = (-h, 0, +h). No synchronisation. `wrt`: as in `ring_optics`
+        (the chromaticity then carries gradients to those settings, two sextupole families say)."""
         h = float(h)
         if not h > 0:
             raise ValueError("chromaticity: h must be positive")
         dev = energy.device if isinstance(energy, torch.Tensor) else "cuda"
-        opt = self.ring_optics(energy, species, delta=torch.tensor([-h, 0.0, h], dtype=torch.float64, device=dev))
+        opt = self.ring_optics(energy, species, delta=torch.tensor([-h, 0.0, h], dtype=torch.float64, device=dev), wrt=wrt)
         q = opt.phase_advance[:, -1, :] / (2.0 * math.pi)
         return (q[2] - q[0]) / (2.0 * h)
+
+    def ring_sensitivity(self, energy, wrt, species=None, delta=None, guess=None, longitudinal: bool = False, num_iterations: int = 10,
+                         along: bool = True):
+        """The derivatives of the closed orbit and the linear optics of this ring with respect to the settings `wrt` — a sequence
+        of settings of the ring's elements (found by identity) or "all", as in `one_turn_map` — in one call: a `RingSensitivity`
+        (particles/optics.py lists the fields) with the `ClosedOrbit` of `closed_orbit` (same arguments) and d_orbit, d_matrix,
+        d_dispersion, d_tunes, d_beta and, with `along`, d_orbit_along and d_matrix_along behind every item, (B, K, ...) for K
+        knobs: a 0-d setting is one knob, an (n,) setting n knobs, a tensor shared by many elements one knob. Total derivatives
+        (the orbit moves with the knob) from second-order dual numbers through the maps (`chx_dkd_ring_sensitivity`), no finite
+        differences and no step. With order-0 Multipole correctors as knobs `d_orbit_along[..., 0]` is the orbit response
+        matrix. The settings need not require grad. No synchronisation."""
+        from ..particles.optics import ClosedOrbit, ring_sensitivity_from
+
+        if wrt is None:
+            raise ValueError("ring_sensitivity: wrt must be a sequence of settings or 'all'")
+        out, sens = self._closed_orbit("ring_sensitivity", energy, species, delta, guess, longitudinal, num_iterations, along, wrt, True)
+        closed = ClosedOrbit(self._rows7(out["orbit"]), out["residual"], out["matrix"], out["dispersion"])
+        return ring_sensitivity_from(closed, sens, out.get("matrix_along"))
 
     @staticmethod
     def _stable_energy(ent: dict, energy: torch.Tensor, mass: float, e_out: torch.Tensor) -> torch.Tensor:

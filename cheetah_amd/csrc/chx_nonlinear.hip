@@ -10,12 +10,16 @@
 // Both are one streaming pass over particles[B][N][7] (56 B/particle fp32, 112 B fp64) through the same
 // LDS tile staging as chx_apply.hip; the per-particle arithmetic runs in fp64 whatever the storage
 // dtype is (transcendental-heavy but far below the HBM time of the pass on 256 CUs).
+#include <algorithm>
 #include <cstdlib>
 #include <initializer_list>
 #include <type_traits>
+#include <utility>
+#include <vector>
 
 #include "chx_common.h"
 #include "chx_dual.h"
+#include "chx_dual2.h"
 #include "chx_optics_dev.h"
 
 // parameters per drift-kick-drift kind (include/chx.h), -1 for anything else: what every entry point below counts with
@@ -145,7 +149,7 @@ template <typename S>
 __device__ __forceinline__ QuadCoef<S> quad_coefficients(S k1, S len, S rel_p) {
     S cx, sx;
     const S w = -k1;
-    if constexpr (std::is_same<S, Dual>::value) {
+    if constexpr (std::is_same<S, Dual>::value || std::is_same<S, Dual2>::value) {
         if (quad_cs_series(w, len, cx, sx)) return quad_from_cs<S>(k1, len, rel_p, cx, sx);
     }
     if (val(w) > 0.0) {
@@ -189,6 +193,12 @@ __device__ __forceinline__ void turn_sincos(Dual u, Dual& s, Dual& c) {
     turn_sincos(u.v, sv, cv);
     s = mk(sv, 2.0 * kPi * cv * u.d);
     c = mk(cv, -2.0 * kPi * sv * u.d);
+}
+__device__ __forceinline__ void turn_sincos(Dual2 u, Dual2& s, Dual2& c) {
+    double sv, cv;
+    turn_sincos(u.v, sv, cv);
+    s = chain2(u, sv, 2.0 * kPi * cv, -(2.0 * kPi) * (2.0 * kPi) * sv);
+    c = chain2(u, cv, -2.0 * kPi * sv, -(2.0 * kPi) * (2.0 * kPi) * cv);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -935,6 +945,163 @@ __global__ __launch_bounds__(chx_optics::kLanes) void dkd_ring_jacobian_kernel(c
         }
         __syncthreads();
         if (live && m < 4) o.dispersion[seed * 4 + m] = sStep[g][m];
+    }
+}
+
+// ---- the derivative of all that with respect to settings of the ring (chx_dkd_ring_sensitivity) ---------------------------------
+// A group of lanes per (seed, knob) pair, eight pairs a wave. The lane carries six Dual2 numbers: e1 = e_m in phase space (lane
+// m < 6 of the group), e2 = (w in phase space, the knob's direction in the settings). The items' constants are the values the
+// Jacobian kernel reads (wave-uniform scalar loads) with the tangent dkd_ring_sensitivity_prepare_kernel left for the group's
+// knob in the e2 part (kSensStride doubles per (knob, item), zeros for the items the knob does not touch); their e1 and mixed
+// parts are literal zeros. Pass 1 (w = 0): the e2 parts of the image are d f / d theta, the e1 parts M; lane 0 of the group
+// solves (I - M_n) w = (d f / d theta)_n (chx_optics_dev.h). Pass 2 (with w): the e2 parts are d orbit / d theta along the ring,
+// the mixed parts column m of d matrix / d theta — the total derivative, the orbit moving with the knob. Mode 0 is pass 1
+// alone. Two passes whatever the values, nothing of a pair leaves its wave, no atomics: two calls give the same bits.
+constexpr int kSensStride = C_N + 1;
+struct RingSensitivityOut {
+    double* d_orbit;          // [B][K][6]
+    double* d_image;          // [B][K][6]
+    double* d_matrix;         // [B][K][6][6]
+    double* d_dispersion;     // [B][K][4]
+    double* d_orbit_along;    // [B][K][E + 1][6] or null
+    double* d_matrix_along;   // [B][K][E + 1][6][6] or null
+};
+
+__global__ __launch_bounds__(chx_optics::kLanes) void dkd_ring_sensitivity_kernel(const double* __restrict__ cst, const double* __restrict__ dcst,
+                                                                                 int E, double mc2, const double* __restrict__ orbit, int64_t B,
+                                                                                 int64_t K, int mode, RingSensitivityOut o) {
+    using namespace chx_optics;
+    __shared__ double sM[kSeeds][36];
+    __shared__ double sA[kSeeds][36];
+    __shared__ double sF[kSeeds][6];
+    __shared__ double sW[kSeeds][6];
+    __shared__ double sD[kSeeds][36];
+    const int lane = threadIdx.x, g = group_of_lane(lane), m = tangent_of_lane(lane);
+    bool live;
+    int64_t seed, knob;
+    pair_of_group(blockIdx.x, g, B, K, live, seed, knob);
+    const int64_t pair = seed * K + knob;
+    const bool column = live && m < 6;                        // the lane stores column m of its pair's matrices
+    const int n = closed_count(mode);
+    const int passes = mode == 0 ? 1 : 2;
+    const double* __restrict__ dc_knob = dcst + knob * (int64_t)E * kSensStride;
+
+    double x[6], w[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        x[j] = orbit[seed * 6 + j];
+        w[j] = 0.0;
+    }
+
+#pragma unroll 1
+    for (int pass = 0; pass < passes; ++pass) {
+        const bool last = pass == passes - 1;
+        const bool along = last && o.d_matrix_along != nullptr;
+        Dual2 v[6];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) v[j] = mk2(x[j], j == m ? 1.0 : 0.0, w[j], 0.0);
+        if (along && column) {
+            double* Ma = o.d_matrix_along + pair * (int64_t)(E + 1) * 36;
+#pragma unroll
+            for (int i = 0; i < 6; ++i) Ma[i * 6 + m] = v[i].ab;
+            if (m == 0) {
+                double* xa = o.d_orbit_along + pair * (int64_t)(E + 1) * 6;
+#pragma unroll
+                for (int i = 0; i < 6; ++i) xa[i] = v[i].b;
+            }
+        }
+#pragma unroll 1
+        for (int e = 0; e < E; ++e) {
+            const double* __restrict__ c = cst + (int64_t)e * kRingCstStride;
+            const double* __restrict__ dc = dc_knob + (int64_t)e * kSensStride;
+            const int32_t* wd = reinterpret_cast<const int32_t*>(c + kRingMeta);
+            const int kind = wd[0], steps = wd[1];
+            Dual2 cd[C_N + 1], out[6];
+#pragma unroll
+            for (int k = 0; k <= C_N; ++k) cd[k] = mk2(c[k], 0.0, dc[k], 0.0);
+            if (kind == CHX_DKD_DRIFT) dkd_map<CHX_DKD_DRIFT, Dual2>(cd, v, mc2, steps, out);
+            else if (kind == CHX_DKD_QUADRUPOLE) dkd_map<CHX_DKD_QUADRUPOLE, Dual2>(cd, v, mc2, steps, out);
+            else if (kind == CHX_DKD_DIPOLE) dkd_map<CHX_DKD_DIPOLE, Dual2>(cd, v, mc2, steps, out);
+            else if (kind == CHX_DKD_SEXTUPOLE) dkd_map<CHX_DKD_SEXTUPOLE, Dual2>(cd, v, mc2, steps, out);
+            else if (kind == CHX_DKD_RFCAVITY) dkd_map<CHX_DKD_RFCAVITY, Dual2>(cd, v, mc2, steps, out);
+            else dkd_map<CHX_DKD_MULTIPOLE, Dual2>(cd, v, mc2, steps, out);
+#pragma unroll
+            for (int j = 0; j < 6; ++j) v[j] = out[j];
+            if (along && column) {
+                double* Ma = o.d_matrix_along + (pair * (int64_t)(E + 1) + e + 1) * 36;
+#pragma unroll
+                for (int i = 0; i < 6; ++i) Ma[i * 6 + m] = v[i].ab;
+                if (m == 0) {
+                    double* xa = o.d_orbit_along + (pair * (int64_t)(E + 1) + e + 1) * 6;
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) xa[i] = v[i].b;
+                }
+            }
+        }
+        if (!last) {
+            // the group's matrix and d f / d theta in LDS: lane m < 6 holds column m, every lane the same e2 parts
+            if (m < 6) {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) sM[g][i * 6 + m] = v[i].a;
+            }
+            if (m == 0) {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) sF[g][i] = v[i].b;
+            }
+            __syncthreads();
+            if (m == 0) orbit_sensitivity(n, sM[g], sF[g], sA[g], sW[g]);
+            __syncthreads();
+#pragma unroll
+            for (int j = 0; j < 6; ++j) w[j] = sW[g][j];
+            continue;
+        }
+        // a pair whose orbit or image is not finite is NaN in ALL its rows, as its seed is in chx_dkd_ring_jacobian's
+        bool lost = false;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) lost = lost || !(fabs(v[i].v) <= 1.79769313486231570815e308) || !(fabs(x[i]) <= 1.79769313486231570815e308);
+        if (column) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) o.d_matrix[pair * 36 + i * 6 + m] = lost ? NAN : v[i].ab;
+            double wm = w[0], fm = v[0].b;
+#pragma unroll
+            for (int j = 1; j < 6; ++j) {
+                wm = m == j ? w[j] : wm;
+                fm = m == j ? v[j].b : fm;
+            }
+            o.d_orbit[pair * 6 + m] = lost ? NAN : wm;
+            o.d_image[pair * 6 + m] = lost ? NAN : fm;
+            // (the rows along the ring were stored during the walk, before `lost` was known, each by the lane that stores it here
+            // or by lane 0 of the same wave: stores of one wave to one address retire in program order, so the NaN stays)
+            if (lost && along) {
+                for (int e = 0; e <= E; ++e) {
+                    double* Ma = o.d_matrix_along + (pair * (int64_t)(E + 1) + e) * 36;
+#pragma unroll
+                    for (int i = 0; i < 6; ++i) Ma[i * 6 + m] = NAN;
+                    o.d_orbit_along[(pair * (int64_t)(E + 1) + e) * 6 + m] = NAN;
+                }
+            }
+        }
+        // the dispersion's derivative: (I - M_4) eta = M[:4, 5] gives (I - M_4) d eta = d M[:4, 5] + d M_4 eta, by the same solver
+        if (m < 6) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) {
+                sM[g][i * 6 + m] = v[i].a;
+                sD[g][i * 6 + m] = v[i].ab;
+            }
+        }
+        __syncthreads();
+        if (live && m == 0) {
+            double eta[4], rhs[4];
+            dispersion(sM[g], sA[g], eta);
+            for (int i = 0; i < 4; ++i) {
+                rhs[i] = sD[g][i * 6 + 5];
+                for (int k = 0; k < 4; ++k) rhs[i] = rhs[i] + sD[g][i * 6 + k] * eta[k];
+            }
+            for (int i = 0; i < 4; ++i)
+                for (int k = 0; k < 4; ++k) sA[g][i * 6 + k] = (i == k ? 1.0 : 0.0) - sM[g][i * 6 + k];
+            solve(4, sA[g], 6, rhs);
+            for (int i = 0; i < 4; ++i) o.d_dispersion[pair * 4 + i] = lost ? NAN : rhs[i];
+        }
     }
 }
 
@@ -2627,6 +2794,155 @@ extern "C" int chx_dkd_ring_jacobian(const int32_t* kinds, const void* const* pa
     const int passes = mode == 0 ? 1 : (int)num_iterations + 1;
     hipLaunchKernelGGL(dkd_ring_jacobian_kernel, dim3((unsigned)groups), dim3(chx_optics::kLanes), 0, s, (const double*)cst, (int)E, mass_eV, start,
                        B, mode, passes, dtype == CHX_F32 ? 1 : 0, o);
+    CHX_CHECK_LAUNCH();
+    return CHX_OK;
+}
+
+// The derivative of chx_dkd_ring_jacobian's results with respect to K knobs (include/chx.h). Four launches: the constants of one
+// turn as above, a fill of the tangents' block with zeros, dkd_ring_sensitivity_prepare_kernel for the (knob, item) pairs a knob
+// touches (in pieces of kSensPairs pairs: they travel as kernel arguments), then dkd_ring_sensitivity_kernel.
+namespace {
+constexpr int kSensPairs = 128;
+struct SensPairs {
+    const void* params[kSensPairs];        // the item's parameters
+    int32_t knob[kSensPairs];
+    int32_t meta[kSensPairs];              // item | kind << 8 | fringe_at << 12 | (bit k: the knob moves parameter k) << 14
+};
+
+// (a workaround: with a hipMemsetAsync node in its place one replay of a captured graph read stale words where the zeros belong;
+// the cause was not found — the node may not have been ordered before its readers —, with a kernel launch it did not happen)
+__global__ void dkd_ring_sensitivity_zero_kernel(double* __restrict__ dcst, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dcst[i] = 0.0;
+}
+
+// the tangent of an item's constants along its knob: dkd_constants<Dual> (what dkd_bwd_kernel evaluates) seeded in the knob's
+// parameters, for the energy dkd_chain_prepare_kernel gives the item (a ring has no linear runs: every item in front of it makes
+// the round trip)
+template <typename T>
+__global__ __launch_bounds__(64) void dkd_ring_sensitivity_prepare_kernel(SensPairs p, int count, int E, const T* __restrict__ energy_in, double mc2, double nq,
+                                                    double* __restrict__ dcst) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const int item = p.meta[i] & 255, kind = (p.meta[i] >> 8) & 15, fringe = (p.meta[i] >> 12) & 3, mask = p.meta[i] >> 14;
+    const T m = (T)mc2;
+    T Ee = *energy_in;
+    for (int k = 0; k < item; ++k) {
+        const T En = dkd_energy_round_trip<T>(Ee, m);
+        if (En == Ee) break;
+        Ee = En;
+    }
+    const int P = kind == CHX_DKD_DRIFT ? 1 : (kind == CHX_DKD_DIPOLE ? 9 : (kind == CHX_DKD_RFCAVITY ? 4 : (kind == CHX_DKD_MULTIPOLE ? 6 : 5)));
+    const T* pe = (const T*)p.params[i];
+    Dual pd[CHX_MAX_PARAMS], cd[C_N + 1];
+#pragma unroll
+    for (int k = 0; k < CHX_MAX_PARAMS; ++k) pd[k] = mk(k < P ? (double)pe[k] : 0.0, ((mask >> k) & 1) ? 1.0 : 0.0);
+#pragma unroll
+    for (int k = 0; k <= C_N; ++k) cd[k] = mk(0.0, 0.0);
+    dkd_constants<Dual>(kind, pd, mk((double)Ee, 0.0), mc2, nq, fringe, cd);
+    double* out = dcst + ((int64_t)p.knob[i] * E + item) * kSensStride;
+#pragma unroll
+    for (int k = 0; k <= C_N; ++k) out[k] = cd[k].d;
+}
+}  // namespace
+
+extern "C" size_t chx_dkd_ring_sensitivity_workspace_bytes(int64_t E, int64_t K) {
+    if (E < 1 || E > kDkdChainMax || K < 0 || K > (1 << 20)) return 0;
+    return chx_dkd_ring_jacobian_workspace_bytes(E) + (size_t)K * (size_t)E * kSensStride * sizeof(double);
+}
+
+extern "C" int chx_dkd_ring_sensitivity(const int32_t* kinds, const void* const* params, const int32_t* num_steps, const int32_t* fringe_at,
+                                        int64_t E, const void* energy_in, double mass_eV, double n_charges, int dtype, const double* orbit,
+                                        int64_t B, int mode, const int32_t* knob_of, const int32_t* item_of, const int32_t* slot_of,
+                                        int64_t num_components, int64_t K, int record_along, double* d_orbit, double* d_image,
+                                        double* d_matrix, double* d_dispersion, double* d_orbit_along, double* d_matrix_along, void* workspace,
+                                        size_t workspace_bytes, void* stream) {
+    if (dtype != CHX_F32 && dtype != CHX_F64) return CHX_ERR_DTYPE;
+    if (!kinds || !params || !num_steps || !fringe_at || E < 1 || E > kDkdChainMax || !energy_in || !orbit || B < 1 || K < 0 || K > (1 << 20) ||
+        num_components < 0 || num_components > K * E * CHX_MAX_PARAMS || (num_components > 0 && (!knob_of || !item_of || !slot_of)))
+        return CHX_ERR_INVALID_ARG;
+    if (mode < 0 || mode > 2 || (record_along != 0 && record_along != 1)) return CHX_ERR_INVALID_ARG;
+    if (K > 0 && (!d_orbit || !d_image || !d_matrix || !d_dispersion || !workspace || (record_along && (!d_orbit_along || !d_matrix_along)))) return CHX_ERR_INVALID_ARG;
+    for (int64_t e = 0; e < E; ++e) {
+        if (!params[e] || (kinds[e] != CHX_DKD_DRIFT && kinds[e] != CHX_DKD_QUADRUPOLE && kinds[e] != CHX_DKD_DIPOLE && kinds[e] != CHX_DKD_SEXTUPOLE &&
+                           kinds[e] != CHX_DKD_RFCAVITY && kinds[e] != CHX_DKD_MULTIPOLE) ||
+            num_steps[e] < 1 || num_steps[e] >= (1 << 25) || fringe_at[e] < 0 || fringe_at[e] > 3)
+            return CHX_ERR_INVALID_ARG;
+    }
+    // the components by (knob, item): one pair each, with the set of parameters the knob moves (a component named twice is refused)
+    std::vector<std::pair<int64_t, int32_t>> comps((size_t)num_components);
+    for (int64_t c = 0; c < num_components; ++c) {
+        if (knob_of[c] < 0 || knob_of[c] >= K || item_of[c] < 0 || item_of[c] >= E || slot_of[c] < 0 ||
+            slot_of[c] >= dkd_num_params(kinds[item_of[c]]))
+            return CHX_ERR_INVALID_ARG;
+        comps[(size_t)c] = {(int64_t)knob_of[c] * E + item_of[c], slot_of[c]};
+    }
+    std::sort(comps.begin(), comps.end());
+    for (size_t c = 1; c < comps.size(); ++c)
+        if (comps[c] == comps[c - 1]) return CHX_ERR_INVALID_ARG;
+    if (K == 0) return CHX_OK;
+    const int64_t groups = chx_optics::pair_workgroups(B, K);
+    if (groups > 0x7fffffffLL) return CHX_ERR_INVALID_ARG;
+    if (workspace_bytes < chx_dkd_ring_sensitivity_workspace_bytes(E, K) || !chx_aligned16(workspace)) return CHX_ERR_INVALID_ARG;
+
+    DkdChainArgs items;
+    for (int e = 0; e < kDkdChainMax; ++e) {
+        items.params[e] = e < E ? params[e] : nullptr;
+        items.length[e] = nullptr;
+        items.meta[e] = e < E ? (kinds[e] | (fringe_at[e] << 4) | (num_steps[e] << 6)) : 0;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    double* cst = (double*)workspace;
+    void* energies = (char*)workspace + (size_t)E * kDkdCstStride * sizeof(double);
+    double* dcst = (double*)((char*)workspace + chx_dkd_ring_jacobian_workspace_bytes(E));
+    if (dtype == CHX_F32)
+        hipLaunchKernelGGL(dkd_chain_prepare_kernel<float>, dim3((unsigned)E), dim3(64), 0, s, items, (int)E, (const float*)energy_in, mass_eV,
+                           n_charges, cst, (float*)energies, (const float*)nullptr, (float*)nullptr);
+    else
+        hipLaunchKernelGGL(dkd_chain_prepare_kernel<double>, dim3((unsigned)E), dim3(64), 0, s, items, (int)E, (const double*)energy_in, mass_eV,
+                           n_charges, cst, (double*)energies, (const double*)nullptr, (double*)nullptr);
+    CHX_CHECK_LAUNCH();
+    const int64_t tangents = K * E * kSensStride;
+    hipLaunchKernelGGL(dkd_ring_sensitivity_zero_kernel, dim3((unsigned)((tangents + 255) / 256)), dim3(256), 0, s, dcst, tangents);
+    CHX_CHECK_LAUNCH();
+    SensPairs pairs;
+    int count = 0;
+    auto flush = [&]() -> int {
+        if (count == 0) return CHX_OK;
+        for (int i = count; i < kSensPairs; ++i) {
+            pairs.params[i] = nullptr;
+            pairs.knob[i] = pairs.meta[i] = 0;
+        }
+        if (dtype == CHX_F32)
+            hipLaunchKernelGGL(dkd_ring_sensitivity_prepare_kernel<float>, dim3((kSensPairs + 63) / 64), dim3(64), 0, s, pairs, count, (int)E,
+                               (const float*)energy_in, mass_eV, n_charges, dcst);
+        else
+            hipLaunchKernelGGL(dkd_ring_sensitivity_prepare_kernel<double>, dim3((kSensPairs + 63) / 64), dim3(64), 0, s, pairs, count, (int)E,
+                               (const double*)energy_in, mass_eV, n_charges, dcst);
+        CHX_CHECK_LAUNCH();
+        count = 0;
+        return CHX_OK;
+    };
+    for (size_t c = 0; c < comps.size(); ++c) {
+        const bool same = c > 0 && comps[c].first == comps[c - 1].first;
+        if (!same) {
+            if (count == kSensPairs) {
+                const int rc = flush();
+                if (rc != CHX_OK) return rc;
+            }
+            const int item = (int)(comps[c].first % E);
+            pairs.params[count] = params[item];
+            pairs.knob[count] = (int32_t)(comps[c].first / E);
+            pairs.meta[count] = item | (kinds[item] << 8) | (fringe_at[item] << 12);
+            ++count;
+        }
+        pairs.meta[count - 1] |= (1 << comps[c].second) << 14;
+    }
+    const int rc = flush();
+    if (rc != CHX_OK) return rc;
+    const RingSensitivityOut o{d_orbit, d_image, d_matrix, d_dispersion, record_along ? d_orbit_along : nullptr, record_along ? d_matrix_along : nullptr};
+    hipLaunchKernelGGL(dkd_ring_sensitivity_kernel, dim3((unsigned)groups), dim3(chx_optics::kLanes), 0, s, (const double*)cst, (const double*)dcst,
+                       (int)E, mass_eV, orbit, B, K, mode, o);
     CHX_CHECK_LAUNCH();
     return CHX_OK;
 }

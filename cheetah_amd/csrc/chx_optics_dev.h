@@ -1,6 +1,7 @@
-// chx_optics_dev.h — the host-callable parts of chx_dkd_ring_jacobian (Segment.ring_optics; the kernel stands in chx_nonlinear.hip
-// next to the templates it evaluates): which lane carries which seed and tangent, the linear systems of the closed-orbit Newton
-// step and of the dispersion, and the small dense solver both go through. tests/host/optics_check.hip runs all of it against
+// chx_optics_dev.h — the host-callable parts of chx_dkd_ring_jacobian and chx_dkd_ring_sensitivity (Segment.ring_optics,
+// ring_sensitivity; the kernels stand in chx_nonlinear.hip next to the templates they evaluate): which lane carries which seed,
+// knob and tangent, the linear systems of the closed-orbit Newton step, of the orbit's derivative and of the dispersion, and the
+// small dense solver they go through. tests/host/optics_check.hip runs all of it against
 // long-double eliminations without a GPU, built with the address and undefined-behaviour sanitizers; the kernel runs the same
 // functions, one seed per group of lanes.
 #pragma once
@@ -108,6 +109,31 @@ __host__ __device__ inline double closing_error(int n, const double* f, const do
         if (d > r || d != d) r = d;                // (a NaN takes over and stays: no later d is > NaN)
     }
     return r;
+}
+
+// ---- chx_dkd_ring_sensitivity: a group of kGroup lanes works on a (seed, knob) PAIR, pair = seed * K + knob, as a group of
+// chx_dkd_ring_jacobian works on a seed. Lane m < 6 of the group carries e1 = e_m in phase space, every lane e2 = the knob.
+// workgroups for B seeds and K knobs (B >= 1, K >= 1)
+__host__ __device__ inline int64_t pair_workgroups(int64_t B, int64_t K) { return (B * K + kSeeds - 1) / kSeeds; }
+// the (seed, knob) a group works on: the last pair again for the groups past the end of the last workgroup (they store nothing)
+__host__ __device__ inline void pair_of_group(int64_t workgroup, int group, int64_t B, int64_t K, bool& live, int64_t& seed, int64_t& knob) {
+    int64_t pair = workgroup * kSeeds + group;
+    live = pair < B * K;
+    if (!live) pair = B * K - 1;
+    seed = pair / K;
+    knob = pair % K;
+}
+
+// How the closed orbit moves with a knob: x = f(x, theta) on the first n coordinates gives (I - M_n) w = (d f / d theta)_n — the
+// matrix of the Newton step with the other sign — from M[i * 6 + m] = d f_i / d x_m and dfdt[6]. w[6] is left 0 on the held
+// coordinates and NaN on the closed ones when there is no solution; a[36] is scratch.
+__host__ __device__ inline bool orbit_sensitivity(int n, const double* M, const double* dfdt, double* a, double* w) {
+    for (int i = 0; i < 6; ++i) w[i] = 0.0;
+    for (int i = 0; i < n; ++i) {
+        for (int m = 0; m < n; ++m) a[i * 6 + m] = (i == m ? 1.0 : 0.0) - M[i * 6 + m];
+        w[i] = dfdt[i];
+    }
+    return solve(n, a, 6, w);
 }
 
 }  // namespace chx_optics

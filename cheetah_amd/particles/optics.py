@@ -13,8 +13,14 @@ coupling (tilted quadrupoles, skew multipoles, an orbit off the axis of a sextup
 modes; `RingOptics.coupling` — the largest absolute entry of the two off-diagonal 2 x 2 blocks of M_4 — says when to distrust
 them. The tunes are eigen-tunes of the full 4 x 4 block and stay right with coupling.
 
-Out of scope here: vectorised lattice settings, gradients of the optics with respect to settings, Edwards-Teng or other coupled
-parametrisations, the synchrotron tune of a 6-D search (`matrix` is returned: take its eigenvalues), second-order and linear rings."""
+Gradients with respect to settings: `Segment.ring_sensitivity` returns the raw tangents (`RingSensitivity`), and with `wrt=...` the
+results of `one_turn_map`, `closed_orbit`, `ring_optics` and `chromaticity` carry an autograd graph to the named settings — one
+node (`RingValues`) whose forward keeps the tangents of `chx_dkd_ring_sensitivity` and whose backward contracts them with the
+cotangents; the algebra below differentiates by itself from there.
+
+Out of scope here: vectorised lattice settings, second derivatives of the optics, gradients with respect to the energy, Edwards-Teng
+or other coupled parametrisations, the synchrotron tune of a 6-D search (`matrix` is returned: take its eigenvalues), second-order
+and linear rings."""
 from __future__ import annotations
 
 import math
@@ -23,7 +29,7 @@ from typing import Optional
 
 import torch
 
-__all__ = ["OneTurnMap", "ClosedOrbit", "RingOptics", "twiss_from_matrix", "propagate_twiss", "eigen_tunes"]
+__all__ = ["OneTurnMap", "ClosedOrbit", "RingOptics", "RingSensitivity", "twiss_from_matrix", "propagate_twiss", "eigen_tunes"]
 
 _TWO_PI = 2.0 * math.pi
 
@@ -183,3 +189,114 @@ def ring_optics_from(closed: ClosedOrbit, orbit_along=None, matrix_along=None, s
     eta = (matrix_along[:, :, :4, :4] @ eta0[:, None, :, None]).squeeze(-1) + matrix_along[:, :, :4, 5]
     return RingOptics(closed.orbit, closed.residual, M, eta0, tunes=tunes, stable=stable, coupling=coupling, beta=beta, alpha=alpha,
                       phase_advance=phase, slip=slip, dispersion_along=eta, orbit_along=orbit_along, s=s)
+
+
+@dataclass
+class RingSensitivity:
+    """`Segment.ring_sensitivity`: the derivatives of a closed orbit and its optics with respect to K knobs — the tensors of `wrt` in
+    their order, a 0-d setting one knob, an (n,) setting (a misalignment) n knobs in a row; a tensor shared by many elements is ONE
+    knob. Total derivatives: the closed orbit moves with the knob. float64.
+    closed                the `ClosedOrbit` the derivatives were taken on
+    d_orbit (B, K, 6)                 d orbit / d knob at the start of the ring (0 on the held coordinates tau, delta of a 4-D orbit)
+    d_matrix (B, K, 6, 6)             d one-turn matrix / d knob
+    d_dispersion (B, K, 4)            d dispersion / d knob
+    d_orbit_along (B, K, E + 1, 6)    d orbit / d knob behind every item, index 0 the start (None without `along`): with order-0
+                                      Multipole correctors as knobs, d_orbit_along[..., 0] is the orbit response matrix
+    d_matrix_along (B, K, E + 1, 6, 6)   d cumulative matrix / d knob (None without `along`)
+    d_tunes (B, K, 2)                 d eigen-tunes / d knob (`eigen_tunes`)
+    d_beta (B, K, E + 1, 2)           d beta / d knob behind every item (`twiss_from_matrix`, `propagate_twiss`); without `along`
+                                      (B, K, 2), the start values
+    A seed whose search failed is NaN in its own rows. (Through `wrt=`, the gradient of a loss is NaN only if a failed seed's results
+    enter it with a cotangent that is not zero.)"""
+    closed: ClosedOrbit
+    d_orbit: torch.Tensor
+    d_matrix: torch.Tensor
+    d_dispersion: torch.Tensor
+    d_orbit_along: Optional[torch.Tensor]
+    d_matrix_along: Optional[torch.Tensor]
+    d_tunes: torch.Tensor
+    d_beta: torch.Tensor
+
+
+def _start_beta(M: torch.Tensor):
+    """beta and alpha at the start from the diagonal blocks of M (..., 6, 6): two tensors (..., 2)."""
+    ba = [twiss_from_matrix(_block(M, plane))[:2] for plane in range(2)]
+    return torch.stack([b for b, _ in ba], -1), torch.stack([a for _, a in ba], -1)
+
+
+def ring_sensitivity_from(closed: ClosedOrbit, sens: dict, matrix_along=None) -> RingSensitivity:
+    """The `RingSensitivity` of the raw tangents of `chx_dkd_ring_sensitivity`: d_tunes and d_beta by forward-mode differentiation
+    (`torch.func.jvp`) of the algebra above, every (seed, knob) a row of one batch. torch only."""
+    M, dM = closed.matrix, sens["d_matrix"]
+    B, K = dM.shape[:2]
+    rows = M[:, None].expand(B, K, 6, 6).contiguous().view(B * K, 6, 6)     # (a copy: forward mode takes no overlapping primal)
+    d_rows = dM.reshape(B * K, 6, 6)
+
+    def tangent(f, primals, tangents):
+        """The tangent of f, NaN where its value is (a seed that failed is NaN in its own rows, like the value)."""
+        value, t = torch.func.jvp(f, primals, tangents)
+        return torch.where(torch.isnan(value), value, t)
+
+    if K == 0:
+        d_tunes = dM.new_zeros((B, 0, 2))
+        d_beta = dM.new_zeros((B, 0, 2) if matrix_along is None else (B, 0, matrix_along.shape[1], 2))
+    else:
+        d_tunes = tangent(lambda m: eigen_tunes(m[:, :4, :4])[0], (rows,), (d_rows,)).reshape(B, K, 2)
+        if matrix_along is None:
+            d_beta = tangent(lambda m: _start_beta(m)[0], (rows,), (d_rows,)).reshape(B, K, 2)
+        else:
+            E1 = matrix_along.shape[1]
+            along = matrix_along[:, None].expand(B, K, E1, 6, 6).contiguous().view(B * K, E1, 6, 6)
+            d_along = sens["d_matrix_along"].reshape(B * K, E1, 6, 6)
+            d_beta = tangent(lambda m, a: _along(a, *_start_beta(m))[0], (rows, along), (d_rows, d_along)).reshape(B, K, E1, 2)
+    return RingSensitivity(closed, sens["d_orbit"], dM, sens["d_dispersion"], sens.get("d_orbit_along"), sens.get("d_matrix_along"),
+                           d_tunes, d_beta)
+
+
+class RingValues(torch.autograd.Function):
+    """The results of `chx_dkd_ring_jacobian` as functions of the settings in `wrt`: forward hands out the kernel's tensors as they are
+    (the bits of a call without `wrt`) and keeps the tangents of `chx_dkd_ring_sensitivity`; backward contracts the cotangents with
+    them (einsum, no kernel of this library) and hands every setting the entries of its knobs."""
+
+    NAMES = (("orbit", "d_orbit", "bi,bki->k"), ("image", "d_image", "bi,bki->k"), ("matrix", "d_matrix", "bij,bkij->k"),
+             ("dispersion", "d_dispersion", "bi,bki->k"), ("orbit_along", "d_orbit_along", "bei,bkei->k"),
+             ("matrix_along", "d_matrix_along", "beij,bkeij->k"))
+
+    @staticmethod
+    def forward(ctx, out: dict, sens: dict, knobs, *wrt):
+        ctx.set_materialize_grads(False)
+        names = [n for n in RingValues.NAMES if n[0] in out and n[1] in sens]
+        ctx.tangents = [(sens[d], rule) for _, d, rule in names]
+        ctx.knobs = knobs                                     # per tensor of wrt: (first knob, count, 0-d?)
+        ctx.like = [(t.dtype, t.shape) for t in wrt]
+        return tuple(out[v] for v, _, _ in names)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        total = None
+        for g, (tangent, rule) in zip(grads, ctx.tangents):
+            if g is None:
+                continue
+            # a seed that failed has NaN tangents: it counts where its cotangent is not zero and nowhere else (a loss that never
+            # touches a lost seed keeps finite gradients)
+            lost = torch.isnan(tangent)
+            part = torch.einsum(rule, g, torch.where(lost, torch.zeros_like(tangent), tangent))
+            touched = torch.einsum(rule, (g != 0).to(tangent.dtype), lost.to(tangent.dtype)) > 0
+            part = torch.where(touched, torch.full_like(part, float("nan")), part)
+            total = part if total is None else total + part
+        if total is None:
+            return (None, None, None) + (None,) * len(ctx.like)
+        per = [total[first].to(dtype) if scalar else total[first:first + count].to(dtype).reshape(shape)
+               for (first, count, scalar), (dtype, shape) in zip(ctx.knobs, ctx.like)]
+        return (None, None, None) + tuple(per)
+
+
+def attach_gradients(out: dict, sens: dict, knobs, wrt, n_closed: int) -> dict:
+    """`out` (the dict of `chx_dkd_ring_jacobian`'s tensors) with an autograd graph to the settings `wrt`: the same bits, `residual`
+    recomputed from image and orbit so that it carries gradients too."""
+    names = [v for v, d, _ in RingValues.NAMES if v in out and d in sens]
+    res = dict(out)
+    res.update(zip(names, RingValues.apply(out, sens, knobs, *wrt)))
+    r = (res["image"] - res["orbit"])[:, :n_closed].abs().amax(-1)          # closing_error of the kernel, with a graph
+    res["residual"] = out["residual"] + (r - r.detach())
+    return res

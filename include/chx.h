@@ -1315,6 +1315,35 @@ int chx_dkd_ring_jacobian(const int32_t* kinds, const void* const* params, const
                           int64_t B, int mode, int64_t num_iterations, int record_along, double* orbit, double* image,
                           double* matrix, double* residual, double* dispersion, double* orbit_along, double* matrix_along,
                           void* s_along, void* workspace, size_t workspace_bytes, void* stream);
+/* The derivative of chx_dkd_ring_jacobian's results with respect to K knobs on the ring's settings (Segment.ring_sensitivity,
+ * the `wrt` argument of Segment.ring_optics). The ring's HOST arrays, energy_in, mass_eV, n_charges, dtype and mode as above.
+ *   orbit[B][6]: the CONVERGED orbits of a chx_dkd_ring_jacobian call of the same mode (mode 0: its seeds), not guesses.
+ *   A knob is a direction in the ring's flat space of parameters, given by components: HOST arrays knob_of, item_of, slot_of
+ *     [num_components], component c moves parameter slot_of[c] of item item_of[c] with weight 1 as part of knob knob_of[c]. One
+ *     setting shared by many items is one knob with many components. A knob without a component has zero derivatives.
+ *   d_orbit[B][K][6] = d orbit / d knob (zero in mode 0 and on the held coordinates of mode 1), d_image[B][K][6] = d image / d knob,
+ *     d_matrix[B][K][6][6] = d matrix / d knob: TOTAL derivatives, in modes 1 and 2 the orbit moves with the knob,
+ *     (I - M_c) d orbit_c = (d f / d knob)_c by the solver of the Newton step. d_dispersion[B][K][4] = d dispersion / d knob, the
+ *     solution of (I - M_4) d eta = d matrix[:4][5] + d matrix[:4][:4] eta.
+ *   record_along = 1: d_orbit_along[B][K][E + 1][6] and d_matrix_along[B][K][E + 1][6][6], the derivatives of orbit_along and
+ *     matrix_along (index 0: d orbit and zeros). With record_along = 0 the two pointers are not read.
+ *   workspace: chx_dkd_ring_sensitivity_workspace_bytes(E, K) bytes, 16-byte aligned (the constants of a turn and their tangents,
+ *     17 doubles per knob and item); 0 for E or K out of range (K <= 2^20).
+ * The maps are evaluated in second-order dual numbers (csrc/chx_dual2.h): eight lanes per (seed, knob), lane m carrying the phase-
+ * space direction e_m, every lane the knob; pass 1 gives d f / d knob and M, pass 2 (modes 1, 2) runs with the orbit's derivative.
+ * A fixed number of passes, no atomics: two calls give the same bits, a (seed, knob)'s rows do not depend on B or K. A seed whose
+ * orbit or image is not finite, or whose system is singular, is NaN in all its own rows and in no other's. K = 0 launches nothing.
+ * CHX_ERR_INVALID_ARG, before any launch: the ring's conditions above, B < 1, K < 0, mode outside 0..2, record_along outside 0..1,
+ * num_components < 0, a knob, item or slot out of range (slot < the item's parameter count), a component named twice, a
+ * required pointer that is NULL, a workspace too small or not 16-byte aligned; CHX_ERR_DTYPE: dtype other than CHX_F32 / CHX_F64.
+ * (An additive export: CHX_ABI_VERSION stays as it is.) */
+size_t chx_dkd_ring_sensitivity_workspace_bytes(int64_t E, int64_t K);
+int chx_dkd_ring_sensitivity(const int32_t* kinds, const void* const* params, const int32_t* num_steps, const int32_t* fringe_at,
+                             int64_t E, const void* energy_in, double mass_eV, double n_charges, int dtype, const double* orbit,
+                             int64_t B, int mode, const int32_t* knob_of, const int32_t* item_of, const int32_t* slot_of,
+                             int64_t num_components, int64_t K, int record_along, double* d_orbit, double* d_image,
+                             double* d_matrix, double* d_dispersion, double* d_orbit_along, double* d_matrix_along, void* workspace,
+                             size_t workspace_bytes, void* stream);
 /* Backward of chx_dkd_track (the reference gets it from torch autograd through utils/bmadx.py): forward-mode dual
  * numbers on device, one seeded evaluation per input. dx[B][N][7] (dtype, may be NULL) = dY . d x_out / d x_in;
  * partials (may be NULL) = chx_dkd_bwd_partials_count() doubles laid out [B][ceil(N/256)][P + 1]: per workgroup
