@@ -42,7 +42,7 @@ from .accelerator import (  # noqa: F401
     laser_modulation_amplitude,
 )
 from .particles import BeamSlices, ParameterBeam, ParticleBeam, Species, TurnByTurn  # noqa: F401
-from .particles import ClosedOrbit, OneTurnMap, RingOptics, RingSensitivity, eigen_tunes, propagate_twiss, twiss_from_matrix  # noqa: F401
+from .particles import ClosedOrbit, OneTurnMap, RadiationIntegrals, RingOptics, RingSensitivity, eigen_tunes, propagate_twiss, twiss_from_matrix  # noqa: F401
 from . import converters, graph, latticejson, track_methods, utils  # noqa: F401,E402
 from .particles.beam import Beam  # noqa: F401,E402
 from .warnings import (  # noqa: F401,E402

@@ -16,7 +16,7 @@ from . import _lib
 from ._lib import c_i64, c_int, c_void_p
 from ._ops import check, dtype_code, ptr, require_device, stream_ptr, workspace
 
-__all__ = ["RING_MAX_ITEMS", "RING_MODES", "dkd_ring_jacobian", "dkd_ring_sensitivity"]
+__all__ = ["RING_MAX_ITEMS", "RING_MODES", "dkd_ring_jacobian", "dkd_ring_sensitivity", "dkd_ring_radiation"]
 
 #: the most items one ring may have (kDkdChainMax of csrc/chx_nonlinear.hip, the limit of chx_dkd_turns)
 RING_MAX_ITEMS = 192
@@ -31,9 +31,13 @@ _lib.SIGNATURES["chx_dkd_ring_sensitivity_workspace_bytes"] = (ctypes.c_size_t, 
 _lib.SIGNATURES["chx_dkd_ring_sensitivity"] = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, ctypes.c_double, ctypes.c_double,
                                                        c_int, c_void_p, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_i64, c_i64, c_int, c_void_p,
                                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p])
+_lib.SIGNATURES["chx_dkd_ring_radiation_workspace_bytes"] = (ctypes.c_size_t, [c_i64])
+_lib.SIGNATURES["chx_dkd_ring_radiation"] = (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, ctypes.c_double, ctypes.c_double,
+                                                     c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p,
+                                                     ctypes.c_size_t, c_void_p])
 if _lib._lib is not None:                       # the library was loaded before this module: bind the symbols now
     for _name in ("chx_dkd_ring_jacobian_workspace_bytes", "chx_dkd_ring_jacobian", "chx_dkd_ring_sensitivity_workspace_bytes",
-                  "chx_dkd_ring_sensitivity"):
+                  "chx_dkd_ring_sensitivity", "chx_dkd_ring_radiation_workspace_bytes", "chx_dkd_ring_radiation"):
         _fn = getattr(_lib._lib, _name)
         _fn.restype, _fn.argtypes = _lib.SIGNATURES[_name]
 
@@ -92,4 +96,27 @@ def dkd_ring_sensitivity(arrays, E: int, energy: torch.Tensor, mass_eV: float, n
                                        ptr(orbit), B, int(mode), knob_of, item_of, slot_of, len(components), K, int(bool(along)),
                                        ptr(out["d_orbit"]), ptr(out["d_image"]), ptr(out["d_matrix"]), ptr(out["d_dispersion"]), ptr(out.get("d_orbit_along")),
                                        ptr(out.get("d_matrix_along")), ptr(ws), ws.numel(), stream_ptr()), "chx_dkd_ring_sensitivity")
+    return out
+
+
+def dkd_ring_radiation(arrays, E: int, energy: torch.Tensor, mass_eV: float, n_charges: float, orbit: torch.Tensor, beta0: torch.Tensor,
+                       alpha0: torch.Tensor, eta0: torch.Tensor, along: bool):
+    """chx_dkd_ring_radiation for the host arrays of `dkd_turn_arrays` (E items), the converged 4-D orbits (B, 6) float64 of a
+    `dkd_ring_jacobian` call and the start values beta0 (B, 2), alpha0 (B, 2), eta0 (B, 4) of its one-turn matrix: a dict of float64
+    tensors integrals (B, 7) = (I1, I2, I3, I4x, I4y, I5x, I5y) and, with `along`, integrals_along (B, E, 7). Launches only."""
+    B = int(orbit.shape[0]) if orbit.dim() == 2 else -1
+    for name, t, width in (("orbits", orbit, 6), ("beta0", beta0, 2), ("alpha0", alpha0, 2), ("eta0", eta0, 4)):
+        if t.dim() != 2 or t.shape[0] != B or t.shape[1] != width or t.dtype != torch.float64:
+            raise ValueError(f"the {name} must be a float64 tensor of the shape (B, {width}), got {t.dtype} {tuple(t.shape)}")
+    require_device(orbit, energy, beta0, alpha0, eta0)
+    orbit, beta0, alpha0, eta0 = orbit.contiguous(), beta0.contiguous(), alpha0.contiguous(), eta0.contiguous()
+    dev = orbit.device
+    out = {"integrals": torch.empty((B, 7), dtype=torch.float64, device=dev)}
+    if along:
+        out["integrals_along"] = torch.empty((B, E, 7), dtype=torch.float64, device=dev)
+    lib = _lib.lib()
+    ws = workspace(lib.chx_dkd_ring_radiation_workspace_bytes(E), dev)
+    check(lib.chx_dkd_ring_radiation(arrays[0], arrays[1], arrays[2], arrays[3], E, ptr(energy), mass_eV, n_charges, dtype_code(energy.dtype),
+                                     ptr(orbit), ptr(beta0), ptr(alpha0), ptr(eta0), B, ptr(out["integrals"]), ptr(out.get("integrals_along")),
+                                     ptr(ws), ws.numel(), stream_ptr()), "chx_dkd_ring_radiation")
     return out

@@ -1099,11 +1099,12 @@ class Segment(Element):
         return wrt, layout, components, K
 
     def _ring_jacobian(self, what: str, energy, species, start: torch.Tensor, mode: int, num_iterations: int, along: bool, wrt=None,
-                       raw: bool = False):
+                       raw: bool = False, ring_call=None):
         """`_ops.dkd_ring_jacobian` for this lattice taken as a ring: the conditions of `_turn_items_dkd` (whose reason a lattice
         that does not qualify is refused with), the energy as a 0-d tensor of the settings' dtype on the seeds' device.
         With `wrt` (`_ring_knobs`) also `_ops.dkd_ring_sensitivity` on the orbits found: the same dict with an autograd graph to
-        those settings (`particles.optics.attach_gradients`) or, with `raw`, the pair (values, tangents) as the kernels left them."""
+        those settings (`particles.optics.attach_gradients`) or, with `raw`, the pair (values, tangents) as the kernels left them.
+        `ring_call`: a dict that receives what a further kernel call on the same ring needs (`radiation_integrals`)."""
         if not isinstance(energy, torch.Tensor):
             lengths = [e.length for e in self._leaves() if isinstance(getattr(e, "length", None), torch.Tensor)]
             energy = torch.as_tensor(float(energy), dtype=lengths[0].dtype if lengths else torch.float64, device=start.device)
@@ -1137,6 +1138,8 @@ class Segment(Element):
             arrays = _ops.dkd_turn_arrays(ring.kinds, ring.params, ring.num_steps, ring.fringe_at)
             out = _ops.dkd_ring_jacobian(arrays, len(ring.kinds), energy, species.mass_eV_float, species.num_elementary_charges_float,
                                          start, mode, num_iterations, along)
+            if ring_call is not None:
+                ring_call.update(arrays=arrays, ring=ring, energy=energy, species=species)
             if wrt is None or (K == 0 and not raw):
                 return out
             sens = _ops.dkd_ring_sensitivity(arrays, len(ring.kinds), energy, species.mass_eV_float, species.num_elementary_charges_float,
@@ -1188,7 +1191,7 @@ class Segment(Element):
         return OneTurnMap(self._rows7(out["orbit"]), self._rows7(out["image"]), out["matrix"], self._rows7(out["orbit_along"]),
                           out["matrix_along"], out["s_along"])
 
-    def _closed_orbit(self, what, energy, species, delta, guess, longitudinal, num_iterations, along, wrt=None, raw=False):
+    def _closed_orbit(self, what, energy, species, delta, guess, longitudinal, num_iterations, along, wrt=None, raw=False, ring_call=None):
         num_iterations = int(num_iterations)
         if num_iterations < 1:
             raise ValueError(f"{what}: num_iterations must be at least 1")
@@ -1207,7 +1210,7 @@ class Segment(Element):
                     raise ValueError(f"{what}: {d.shape[0]} values of delta for {x.shape[0]} guesses")
                 x = x.expand(max(d.shape[0], x.shape[0]), 6).clone()
             x[:, 5] = d
-        return self._ring_jacobian(what, energy, species, x, 2 if longitudinal else 1, num_iterations, along, wrt, raw)
+        return self._ring_jacobian(what, energy, species, x, 2 if longitudinal else 1, num_iterations, along, wrt, raw, ring_call)
 
     def closed_orbit(self, energy, species=None, delta=None, guess=None, longitudinal: bool = False, num_iterations: int = 10, wrt=None):
         """The closed orbit of this lattice taken as a ring (the conditions of `one_turn_map`): a `ClosedOrbit` with `orbit` (B, 7),
@@ -1243,6 +1246,55 @@ class Segment(Element):
         if not along:
             return ring_optics_from(closed)
         return ring_optics_from(closed, self._rows7(out["orbit_along"]), out["matrix_along"], out["s_along"])
+
+    def radiation_integrals(self, energy, species=None, delta=None, guess=None, num_iterations: int = 10, along: bool = False):
+        """The synchrotron-radiation integrals I1 .. I5 of this lattice taken as a ring, on its 4-D closed orbit (`delta` held), and
+        what an electron ring is judged by: energy loss per turn, damping partition and times, equilibrium emittance and energy
+        spread — a `RadiationIntegrals` (particles/optics.py lists the fields), float64 whatever the settings' dtype. The lattice
+        conditions, `energy`, `species`, `delta`, `guess` and `num_iterations` are those of `ring_optics` (refused with the reason);
+        there is no `longitudinal`: the integrals are defined on the 4-D optics. The `chx_dkd_ring_jacobian` call of `ring_optics`
+        (without `along`), its float64 torch operations for beta0, alpha0, eta0, ONE more kernel call (`chx_dkd_ring_radiation`: one
+        pass through the ring) and a handful of torch operations for the derived quantities: no synchronisation, deterministic,
+        capturable. No autograd: an input or a setting that requires grad raises ValueError. With `along`, `integrals_along`
+        (B, E, 7) holds every item's contribution in the order (I1, I2, I3, I4x, I4y, I5x, I5y).
+
+        Only Dipoles contribute (one with L = 0 or angle = 0: zeros). Out of scope: feed-down in quadrupoles on an off-axis orbit,
+        order-0 Multipoles, the `k1` of a Dipole (the drift-kick-drift Dipole does not track it), the opening-angle limit of eps_y,
+        coupled normal-mode emittances, gradients with respect to settings. For a Dipole with h = angle / L and tilt t:
+          a point s = f L inside the body, 0 < f < 1: the map from the item's entrance to s rotates by the tilt, applies the entrance
+            fringe kick if the face's fringe is on, the exact Bmad-X body map of length f L and angle f angle at the same h, and rotates
+            back (no exit fringe); A(s) is the 6 x 6 Jacobian from the ring's start to s on the closed orbit
+          eta(s) = beta0 (A[:4, :4] eta0 + A[:4, 5]) with beta0 = p0c / E0: delta is dE / p0c here and the integrals are defined on
+            d x / d (dp / p); eta' is d px / d delta (the canonical convention)
+          beta_u(s), alpha_u(s) = `propagate_twiss` of the diagonal 2 x 2 block of A(s) with the start values: the projected functions
+            of `ring_optics`; a plane without a periodic solution is NaN in its I5 only
+          H_u = (eta_u^2 + (beta_u eta_u' + alpha_u eta_u)^2) / beta_u
+          I2 = L h^2, I3 = L |h|^3 directly; with sum_j the 8-point Gauss-Legendre rule on f in (0, 1), eta_b = eta_x cos t + eta_y sin t:
+          I1  = L h sum_j w_j eta_b(s_j)
+          I4x = L h^3 cos t sum_j w_j eta_x(s_j) - h cos t (h tan e1 eta_b(entrance) + h tan e2 eta_b(exit)); I4y with sin t and eta_y.
+            h tan e are the tracking's edge constants, zero where the face's fringe is off (a rectangular magnet's path length does
+            not grow with x)
+          I5u = L |h|^3 sum_j w_j H_u(s_j)
+        The quadrature error for a bend of angle theta is of order theta^16 / 16!: about 1e-10 at theta = pi / 2 per Dipole (split a
+        stronger bend). With gamma0 = E0 / mc^2, r_c and lambda_c = hbar c / mc^2 of the species as in `SynchrotronRadiationKick`:
+          U0 = (2/3) r_c mc^2 beta0^3 gamma0^4 I2;  J_x = 1 - I4x / I2, J_y = 1 - I4y / I2, J_E = 2 + (I4x + I4y) / I2;
+          eps_u = C_q gamma0^2 I5u / (J_u I2), sigma_delta^2 = C_q gamma0^2 I3 / (J_E I2), C_q = 55 / (32 sqrt 3) lambda_c;
+          damping_turns = 2 E0 / (J U0), damping_time = damping_turns C / (beta0 c).
+        On the axis I1 = closed.slip beta0^2 + C / gamma0^2 (`slip` is d tau / d delta per turn, -C / (beta0^2 gamma0^2) in a ring of
+        Drifts, where I1 = 0)."""
+        from ..particles.optics import ClosedOrbit, radiation_integrals_from, ring_optics_from
+
+        call = {}
+        out = self._closed_orbit("radiation_integrals", energy, species, delta, guess, False, num_iterations, False, ring_call=call)
+        closed = ring_optics_from(ClosedOrbit(self._rows7(out["orbit"]), out["residual"], out["matrix"], out["dispersion"]))
+        ring, species = call["ring"], call["species"]
+        with torch.no_grad():
+            rad = _ops.dkd_ring_radiation(call["arrays"], len(ring.kinds), call["energy"], species.mass_eV_float,
+                                          species.num_elementary_charges_float, out["orbit"], closed.beta, closed.alpha, out["dispersion"],
+                                          bool(along))
+            circumference = torch.cat([p[0, :1] for p in ring.params]).to(torch.float64).sum()
+        return radiation_integrals_from(closed, rad["integrals"], rad.get("integrals_along"), call["energy"], species.mass_eV_float,
+                                        species.num_elementary_charges_float, circumference)
 
     def chromaticity(self, energy, species=None, h: float = 1e-4, wrt=None) -> torch.Tensor:
         """(dQx / d delta, dQy / d delta), shape (2,): the central difference of the FULL tunes (the integer part from the phase

@@ -21,6 +21,7 @@
 #include "chx_dual.h"
 #include "chx_dual2.h"
 #include "chx_optics_dev.h"
+#include "chx_radiation_dev.h"
 
 // parameters per drift-kick-drift kind (include/chx.h), -1 for anything else: what every entry point below counts with
 static int dkd_num_params(int kind) {
@@ -945,6 +946,145 @@ __global__ __launch_bounds__(chx_optics::kLanes) void dkd_ring_jacobian_kernel(c
         }
         __syncthreads();
         if (live && m < 4) o.dispersion[seed * 4 + m] = sStep[g][m];
+    }
+}
+
+// ---- the synchrotron-radiation integrals of such a ring on its closed orbit (chx_dkd_ring_radiation) ----------------------------
+// The Jacobian kernel's layout and one pass of it: a group of kGroup lanes per seed, lane m < 6 carries the orbit and the tangent
+// e_m through all items, the constants come from the same 56-double blocks through wave-uniform loads. At a Dipole the group first
+// evaluates the map from the item's entrance to the kNodes Gauss-Legendre points inside the body — dkd_map<CHX_DKD_DIPOLE, Dual>
+// itself on a copy of the constants with C_A, C_B, C_D, C_E2, C_F, C_G rebuilt for the part f L, f theta and C_J = C_N = 0 (no exit
+// fringe) — and then, through the same call site with the constants as they are, the whole item: ONE inlined bend, no second
+// definition. After a partial map lane m holds column m of A(s); the kTerms sums of chx_radiation_dev.h are butterflies over the
+// group's lanes (nothing of a seed leaves its wave, every lane ends with the same bits), the algebra from there is that header's.
+// Every lane of a group accumulates the same float64 numbers in the same fixed order; lane k < 7 stores integral k. No atomics.
+struct RingRadiationIn {
+    const double* orbit;    // [B][6]
+    const double* beta0;    // [B][2]
+    const double* alpha0;   // [B][2]
+    const double* eta0;     // [B][4]
+};
+
+__device__ __forceinline__ double group_butterfly(double v) {
+    v = v + __shfl_xor(v, 1, chx_optics::kGroup);
+    v = v + __shfl_xor(v, 2, chx_optics::kGroup);
+    v = v + __shfl_xor(v, 4, chx_optics::kGroup);
+    return v;
+}
+
+// the kTerms sums of the group for the point whose tangents the lanes hold in p[0..3].d
+__device__ __forceinline__ void group_terms(int m, const Dual (&p)[6], const double* eta0, const double* beta0, const double* alpha0, double* s) {
+    const double col[4] = {p[0].d, p[1].d, p[2].d, p[3].d};
+    double t[chx_radiation::kTerms];
+    chx_radiation::lane_terms(m, col, eta0, beta0, alpha0, t);
+#pragma unroll
+    for (int k = 0; k < chx_radiation::kTerms; ++k) s[k] = group_butterfly(t[k]);
+}
+
+__global__ __launch_bounds__(chx_optics::kLanes) void dkd_ring_radiation_kernel(const double* __restrict__ cst, int E, double mc2, RingRadiationIn in,
+                                                                               int64_t B, double* __restrict__ integrals,
+                                                                               double* __restrict__ along) {
+    using namespace chx_optics;
+    using namespace chx_radiation;
+    const int lane = threadIdx.x, g = group_of_lane(lane), m = tangent_of_lane(lane);
+    bool live;
+    const int64_t seed = seed_of_group(blockIdx.x, g, B, live);
+    const bool stores = live && m < kIntegrals;               // the lane stores integral m of its seed
+
+    double eta0[4], beta0[2], alpha0[2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) eta0[j] = in.eta0[seed * 4 + j];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        beta0[j] = in.beta0[seed * 2 + j];
+        alpha0[j] = in.alpha0[seed * 2 + j];
+    }
+    Dual v[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) v[j] = mk(in.orbit[seed * 6 + j], j == m ? 1.0 : 0.0);
+    double total[kIntegrals];
+#pragma unroll
+    for (int k = 0; k < kIntegrals; ++k) total[k] = 0.0;
+
+#pragma unroll 1
+    for (int e = 0; e < E; ++e) {
+        const double* __restrict__ c = cst + (int64_t)e * kRingCstStride;
+        const int32_t* w = reinterpret_cast<const int32_t*>(c + kRingMeta);
+        const int kind = w[0], steps = w[1];
+        Dual cd[C_N + 1], out[6];
+#pragma unroll
+        for (int k = 0; k <= C_N; ++k) cd[k] = mk(c[k], 0.0);
+        double part[kIntegrals];
+#pragma unroll
+        for (int k = 0; k < kIntegrals; ++k) part[k] = 0.0;
+        if (kind == CHX_DKD_DIPOLE) {
+            const double L = c[C_A], theta = c[C_B], h = c[C_C], cos_t = c[C_COS], sin_t = c[C_SIN];
+            const double rel_beta = c[C_P0C] / c[C_E];
+            const bool bends = L != 0.0 && theta != 0.0;      // (wave-uniform) else zeros and the item alone
+            double s[kTerms], eta[4], eta_in = 0.0;
+            BendSums sums = bend_sums_zero();
+            if (bends) {
+                group_terms(m, v, eta0, beta0, alpha0, s);
+                eta_from_sums(s, rel_beta, eta);
+                eta_in = eta_bend(eta, cos_t, sin_t);
+            }
+#pragma unroll 1
+            for (int j = bends ? 0 : kNodes; j <= kNodes; ++j) {
+                const bool inside = j < kNodes;               // a point inside the body; j == kNodes: the whole item
+                Dual cj[C_N + 1];
+#pragma unroll
+                for (int k = 0; k <= C_N; ++k) cj[k] = cd[k];
+                if (inside) {
+                    const double f = gl8_node(j), Lf = f * L, tf = f * theta;
+                    cj[C_A] = mk(Lf, 0.0);
+                    cj[C_B] = mk(tf, 0.0);
+                    cj[C_D] = mk(sinc1<double>(tf), 0.0);
+                    cj[C_E2] = mk(cosc1<double>(tf), 0.0);
+                    cj[C_F] = mk(cos(tf), 0.0);
+                    cj[C_G] = mk(sin(tf), 0.0);
+                    cj[C_J] = mk(0.0, 0.0);
+                    cj[C_N] = mk(0.0, 0.0);
+                }
+                dkd_map<CHX_DKD_DIPOLE, Dual>(cj, v, mc2, steps, out);
+                if (inside) {
+                    Node node;
+                    group_terms(m, out, eta0, beta0, alpha0, s);
+                    node_from_sums(s, beta0, rel_beta, node);
+                    bend_sums_add(sums, gl8_weight(j), cos_t, sin_t, node);
+                }
+            }
+            if (bends) {
+                group_terms(m, out, eta0, beta0, alpha0, s);
+                eta_from_sums(s, rel_beta, eta);
+                bend_contribution(L, h, cos_t, sin_t, c[C_H], c[C_J], eta_in, eta_bend(eta, cos_t, sin_t), sums, part);
+            }
+        } else if (kind == CHX_DKD_DRIFT) dkd_map<CHX_DKD_DRIFT, Dual>(cd, v, mc2, steps, out);
+        else if (kind == CHX_DKD_QUADRUPOLE) dkd_map<CHX_DKD_QUADRUPOLE, Dual>(cd, v, mc2, steps, out);
+        else if (kind == CHX_DKD_SEXTUPOLE) dkd_map<CHX_DKD_SEXTUPOLE, Dual>(cd, v, mc2, steps, out);
+        else if (kind == CHX_DKD_RFCAVITY) dkd_map<CHX_DKD_RFCAVITY, Dual>(cd, v, mc2, steps, out);
+        else dkd_map<CHX_DKD_MULTIPOLE, Dual>(cd, v, mc2, steps, out);
+#pragma unroll
+        for (int j = 0; j < 6; ++j) v[j] = out[j];
+#pragma unroll
+        for (int k = 0; k < kIntegrals; ++k) total[k] = total[k] + part[k];
+        if (along && stores) {                                // (a store per entry under its lane's mask: no register is indexed by the lane)
+#pragma unroll
+            for (int k = 0; k < kIntegrals; ++k)
+                if (m == k) along[(seed * (int64_t)E + e) * kIntegrals + k] = part[k];
+        }
+    }
+    // a seed whose orbit is NaN or whose image is not finite is NaN in ALL its rows, as in chx_dkd_ring_jacobian (every lane of the
+    // group sees the same values; the lane that stored a number along the ring is the one that takes it back)
+    bool lost = false;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) lost = lost || !(fabs(v[i].v) <= 1.79769313486231570815e308);
+    if (stores) {
+#pragma unroll
+        for (int k = 0; k < kIntegrals; ++k)
+            if (m == k) integrals[seed * kIntegrals + k] = lost ? NAN : total[k];
+        if (along && lost) {
+            for (int e = 0; e < E; ++e) along[(seed * (int64_t)E + e) * kIntegrals + m] = NAN;
+        }
     }
 }
 
@@ -2794,6 +2934,71 @@ extern "C" int chx_dkd_ring_jacobian(const int32_t* kinds, const void* const* pa
     const int passes = mode == 0 ? 1 : (int)num_iterations + 1;
     hipLaunchKernelGGL(dkd_ring_jacobian_kernel, dim3((unsigned)groups), dim3(chx_optics::kLanes), 0, s, (const double*)cst, (int)E, mass_eV, start,
                        B, mode, passes, dtype == CHX_F32 ? 1 : 0, o);
+    CHX_CHECK_LAUNCH();
+    return CHX_OK;
+}
+
+// The synchrotron-radiation integrals on the closed orbits a chx_dkd_ring_jacobian call found (include/chx.h). Two launches: the
+// constants of one turn as above, then dkd_ring_radiation_kernel.
+namespace {
+// [p, p + n) and [q, q + k) share a byte (null pointers are absent arguments)
+bool bytes_overlap(const void* p, size_t n, const void* q, size_t k) {
+    if (!p || !q) return false;
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return a < b + k && b < a + n;
+}
+}  // namespace
+
+extern "C" size_t chx_dkd_ring_radiation_workspace_bytes(int64_t E) { return chx_dkd_ring_jacobian_workspace_bytes(E); }
+
+extern "C" int chx_dkd_ring_radiation(const int32_t* kinds, const void* const* params, const int32_t* num_steps, const int32_t* fringe_at,
+                                      int64_t E, const void* energy_in, double mass_eV, double n_charges, int dtype, const double* orbit,
+                                      const double* beta0, const double* alpha0, const double* eta0, int64_t B, double* integrals,
+                                      double* along, void* workspace, size_t workspace_bytes, void* stream) {
+    if (dtype != CHX_F32 && dtype != CHX_F64) return CHX_ERR_DTYPE;
+    if (!kinds || !params || !num_steps || !fringe_at || E < 1 || E > kDkdChainMax || !energy_in || !orbit || !beta0 || !alpha0 || !eta0 ||
+        B < 1 || !integrals || !workspace)
+        return CHX_ERR_INVALID_ARG;
+    for (int64_t e = 0; e < E; ++e) {
+        if (!params[e] || (kinds[e] != CHX_DKD_DRIFT && kinds[e] != CHX_DKD_QUADRUPOLE && kinds[e] != CHX_DKD_DIPOLE && kinds[e] != CHX_DKD_SEXTUPOLE &&
+                           kinds[e] != CHX_DKD_RFCAVITY && kinds[e] != CHX_DKD_MULTIPOLE) ||
+            num_steps[e] < 1 || num_steps[e] >= (1 << 25) || fringe_at[e] < 0 || fringe_at[e] > 3)
+            return CHX_ERR_INVALID_ARG;
+    }
+    const int64_t groups = chx_optics::workgroups(B);
+    if (groups > 0x7fffffffLL) return CHX_ERR_INVALID_ARG;
+    if (workspace_bytes < chx_dkd_ring_radiation_workspace_bytes(E) || !chx_aligned16(workspace)) return CHX_ERR_INVALID_ARG;
+    // aliasing: nothing that is written may share a byte with anything else
+    const size_t row = (size_t)B * sizeof(double);
+    const std::pair<const void*, size_t> written[] = {{integrals, row * chx_radiation::kIntegrals},
+                                                      {along, row * (size_t)E * chx_radiation::kIntegrals},
+                                                      {workspace, workspace_bytes}};
+    const std::pair<const void*, size_t> read[] = {{orbit, row * 6}, {beta0, row * 2}, {alpha0, row * 2}, {eta0, row * 4}};
+    for (size_t i = 0; i < 3; ++i) {
+        for (size_t j = i + 1; j < 3; ++j)
+            if (bytes_overlap(written[i].first, written[i].second, written[j].first, written[j].second)) return CHX_ERR_INVALID_ARG;
+        for (const auto& r : read)
+            if (bytes_overlap(written[i].first, written[i].second, r.first, r.second)) return CHX_ERR_INVALID_ARG;
+    }
+    DkdChainArgs items;
+    for (int e = 0; e < kDkdChainMax; ++e) {
+        items.params[e] = e < E ? params[e] : nullptr;
+        items.length[e] = nullptr;                            // every kind's first parameter is its length
+        items.meta[e] = e < E ? (kinds[e] | (fringe_at[e] << 4) | (num_steps[e] << 6)) : 0;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    double* cst = (double*)workspace;
+    void* energies = (char*)workspace + (size_t)E * kDkdCstStride * sizeof(double);
+    if (dtype == CHX_F32)
+        hipLaunchKernelGGL(dkd_chain_prepare_kernel<float>, dim3((unsigned)E), dim3(64), 0, s, items, (int)E, (const float*)energy_in, mass_eV,
+                           n_charges, cst, (float*)energies, (const float*)nullptr, (float*)nullptr);
+    else
+        hipLaunchKernelGGL(dkd_chain_prepare_kernel<double>, dim3((unsigned)E), dim3(64), 0, s, items, (int)E, (const double*)energy_in, mass_eV,
+                           n_charges, cst, (double*)energies, (const double*)nullptr, (double*)nullptr);
+    CHX_CHECK_LAUNCH();
+    const RingRadiationIn in{orbit, beta0, alpha0, eta0};
+    hipLaunchKernelGGL(dkd_ring_radiation_kernel, dim3((unsigned)groups), dim3(chx_optics::kLanes), 0, s, (const double*)cst, (int)E, mass_eV, in, B,
+                       integrals, along);
     CHX_CHECK_LAUNCH();
     return CHX_OK;
 }

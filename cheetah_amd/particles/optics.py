@@ -29,7 +29,8 @@ from typing import Optional
 
 import torch
 
-__all__ = ["OneTurnMap", "ClosedOrbit", "RingOptics", "RingSensitivity", "twiss_from_matrix", "propagate_twiss", "eigen_tunes"]
+__all__ = ["OneTurnMap", "ClosedOrbit", "RingOptics", "RingSensitivity", "RadiationIntegrals", "twiss_from_matrix", "propagate_twiss",
+           "eigen_tunes"]
 
 _TWO_PI = 2.0 * math.pi
 
@@ -189,6 +190,71 @@ def ring_optics_from(closed: ClosedOrbit, orbit_along=None, matrix_along=None, s
     eta = (matrix_along[:, :, :4, :4] @ eta0[:, None, :, None]).squeeze(-1) + matrix_along[:, :, :4, 5]
     return RingOptics(closed.orbit, closed.residual, M, eta0, tunes=tunes, stable=stable, coupling=coupling, beta=beta, alpha=alpha,
                       phase_advance=phase, slip=slip, dispersion_along=eta, orbit_along=orbit_along, s=s)
+
+
+_ELECTRON_RADIUS = 2.8179403205e-15       # r_e, m (CODATA 2022; csrc/chx_sr.hip)
+_ELECTRON_MASS_EV = 510998.95069          # m_e c^2, eV
+_HBAR_C = 1.973269804593025e-7            # hbar c, eV m
+_SPEED_OF_LIGHT = 299792458.0
+
+
+@dataclass
+class RadiationIntegrals:
+    """`Segment.radiation_integrals`: the synchrotron-radiation integrals of a ring on its 4-D closed orbit and what follows from
+    them, float64, B seeds, E items, planes u = x, y (the definitions: the method's docstring, include/chx.h).
+    I1, I2, I3 (B,)       I4, I5 (B, 2)
+    integrals_along (B, E, 7)   every item's contribution in the order (I1, I2, I3, I4x, I4y, I5x, I5y), exact zeros for items
+                          that are no Dipoles (None without `along`); the totals are the sums over the items in their order
+    closed                the `RingOptics` (without `along`) the integrals were evaluated on
+    energy_loss (B,)      U0 = (2/3) r_c mc^2 beta0^3 gamma0^4 I2, eV per turn
+    partition (B, 3)      (J_x, J_y, J_E) = (1 - I4x / I2, 1 - I4y / I2, 2 + (I4x + I4y) / I2)
+    damping_turns (B, 3)  2 E0 / (J U0)
+    damping_time (B, 3)   damping_turns C / (beta0 c), s
+    emittance (B, 2)      eps_u = C_q gamma0^2 I5u / (J_u I2), geometric, m rad; C_q = 55 / (32 sqrt 3) lambda_c. The vertical
+                          opening-angle limit is not included: eps_y = 0 in a flat ring
+    energy_spread (B,)    sigma_delta = sqrt(C_q gamma0^2 I3 / (J_E I2))
+    circumference         C, the sum of the items' lengths (0-d)
+    A seed whose search failed is NaN in its own rows; a plane without a periodic solution is NaN in its I5 and emittance."""
+    I1: torch.Tensor
+    I2: torch.Tensor
+    I3: torch.Tensor
+    I4: torch.Tensor
+    I5: torch.Tensor
+    integrals_along: Optional[torch.Tensor]
+    closed: "RingOptics"
+    energy_loss: torch.Tensor
+    partition: torch.Tensor
+    damping_turns: torch.Tensor
+    damping_time: torch.Tensor
+    emittance: torch.Tensor
+    energy_spread: torch.Tensor
+    circumference: torch.Tensor
+
+
+def radiation_constants(mass_eV: float, num_charges: float):
+    """(r_c, C_q) of a species: r_c = Z^2 r_e m_e / m in m and C_q = 55 / (32 sqrt 3) hbar c / mc^2 in m, as `SynchrotronRadiationKick`
+    takes them."""
+    r_c = num_charges * num_charges * _ELECTRON_RADIUS * _ELECTRON_MASS_EV / mass_eV
+    return r_c, 55.0 / (32.0 * math.sqrt(3.0)) * _HBAR_C / mass_eV
+
+
+def radiation_integrals_from(closed: "RingOptics", integrals: torch.Tensor, integrals_along, energy: torch.Tensor, mass_eV: float,
+                             num_charges: float, circumference: torch.Tensor) -> RadiationIntegrals:
+    """The `RadiationIntegrals` of the kernel's sums (B, 7): a handful of float64 torch operations, no synchronisation."""
+    I1, I2, I3, I4, I5 = integrals[:, 0], integrals[:, 1], integrals[:, 2], integrals[:, 3:5], integrals[:, 5:7]
+    E0 = energy.to(torch.float64)
+    r_c, c_q = radiation_constants(mass_eV, num_charges)
+    gamma2 = (E0 / mass_eV) ** 2
+    beta_rel = torch.sqrt(1.0 - 1.0 / gamma2)
+    loss = (2.0 / 3.0) * r_c * mass_eV * beta_rel ** 3 * gamma2 * gamma2 * I2
+    ratio = I4 / I2[:, None]
+    partition = torch.cat([1.0 - ratio, 2.0 + ratio.sum(-1, keepdim=True)], dim=-1)
+    turns = 2.0 * E0 / (partition * loss[:, None])
+    C = circumference.to(torch.float64)
+    emittance = c_q * gamma2 * I5 / (partition[:, :2] * I2[:, None])
+    spread = torch.sqrt(c_q * gamma2 * I3 / (partition[:, 2] * I2))
+    return RadiationIntegrals(I1, I2, I3, I4, I5, integrals_along, closed, loss, partition, turns, turns * (C / (beta_rel * _SPEED_OF_LIGHT)),
+                              emittance, spread, C)
 
 
 @dataclass

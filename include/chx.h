@@ -1344,6 +1344,41 @@ int chx_dkd_ring_sensitivity(const int32_t* kinds, const void* const* params, co
                              int64_t num_components, int64_t K, int record_along, double* d_orbit, double* d_image,
                              double* d_matrix, double* d_dispersion, double* d_orbit_along, double* d_matrix_along, void* workspace,
                              size_t workspace_bytes, void* stream);
+/* The synchrotron-radiation integrals I1 .. I5 of such a ring on closed orbits chx_dkd_ring_jacobian found
+ * (Segment.radiation_integrals). The ring's HOST arrays, energy_in, mass_eV, n_charges and dtype as in chx_dkd_ring_jacobian.
+ *   orbit[B][6]: the CONVERGED orbits (mode 1), beta0[B][2], alpha0[B][2]: the periodic projected functions of the diagonal 2 x 2
+ *     blocks of the one-turn matrix at the start of the ring, eta0[B][4]: its dispersion (chx_dkd_ring_jacobian's).
+ *   integrals[B][7] = (I1, I2, I3, I4x, I4y, I5x, I5y); along[B][E][7] (may be NULL): every item's contribution, exact zeros for
+ *     items that are no Dipoles. The totals are the sums over the items in their order, with and without `along`.
+ * Only Dipoles contribute (one with L = 0 or angle = 0: zeros). Out of scope: feed-down in quadrupoles on an off-axis orbit,
+ * order-0 Multipoles, a Dipole's k1 (the drift-kick-drift Dipole does not track it). For a Dipole with h = angle / L, tilt t:
+ *   a point s = f L inside the body, 0 < f < 1: the map from the item's entrance to s rotates by the tilt, applies the entrance
+ *     fringe kick if its fringe_at bit is set, the exact body map of length f L and angle f angle at the same h, and rotates back
+ *     (no exit fringe). A(s) is the 6 x 6 Jacobian from the ring's start to s on the closed orbit.
+ *   eta(s) = beta_rel (A[:4][:4] eta0 + A[:4][5]), beta_rel = p0c / E0: delta is dE / p0c here, the integrals are defined on
+ *     d x / d (dp / p); eta' is d px / d delta (canonical). beta_u(s), alpha_u(s): the diagonal 2 x 2 block of A(s) applied to beta0_u,
+ *     alpha0_u (the projected functions; a plane without a periodic solution is NaN in its I5 only).
+ *     H_u = (eta_u^2 + (beta_u eta_u' + alpha_u eta_u)^2) / beta_u.
+ *   I2 = L h^2 and I3 = L |h|^3 directly; with sum_j the 8-point Gauss-Legendre rule on f in (0, 1) and eta_b = eta_x cos t + eta_y sin t:
+ *     I1 = L h sum_j w_j eta_b(s_j)
+ *     I4x = L h^3 cos t sum_j w_j eta_x(s_j) - h cos t (h tan e1 eta_b(entrance) + h tan e2 eta_b(exit)), I4y with sin t and eta_y;
+ *       h tan e are the edge constants of the tracking (zero where the face's fringe is off): a rectangular magnet's path length
+ *       does not grow with x
+ *     I5u = L |h|^3 sum_j w_j H_u(s_j)
+ *   The quadrature error for a bend of angle theta is of order theta^16 / 16!: about 1e-10 at theta = pi / 2 per Dipole.
+ *   workspace: chx_dkd_ring_radiation_workspace_bytes(E) bytes, 16-byte aligned (chx_dkd_ring_jacobian's); 0 for E out of range.
+ * Eight lanes per seed as in chx_dkd_ring_jacobian, one pass; at a Dipole the group evaluates the eight partial maps from the
+ * entrance state (the one dual-number bend map on rebuilt constants), the sums over a seed's lanes stay in its wave, every
+ * accumulation is float64 in a fixed order, no atomics. Two launches, none synchronising; two calls give the same bits and a
+ * seed's rows do not depend on B. A seed whose orbit is NaN or whose image is not finite is NaN in all its rows.
+ * CHX_ERR_INVALID_ARG, before any launch: the ring's conditions of chx_dkd_ring_jacobian, B < 1, a required pointer that is
+ * NULL, integrals, along or the workspace sharing bytes with one another or with an input, a workspace too small or not 16-byte
+ * aligned; CHX_ERR_DTYPE: dtype other than CHX_F32 / CHX_F64. (An additive export: CHX_ABI_VERSION stays as it is.) */
+size_t chx_dkd_ring_radiation_workspace_bytes(int64_t E);
+int chx_dkd_ring_radiation(const int32_t* kinds, const void* const* params, const int32_t* num_steps, const int32_t* fringe_at,
+                           int64_t E, const void* energy_in, double mass_eV, double n_charges, int dtype, const double* orbit,
+                           const double* beta0, const double* alpha0, const double* eta0, int64_t B, double* integrals,
+                           double* along, void* workspace, size_t workspace_bytes, void* stream);
 /* Backward of chx_dkd_track (the reference gets it from torch autograd through utils/bmadx.py): forward-mode dual
  * numbers on device, one seeded evaluation per input. dx[B][N][7] (dtype, may be NULL) = dY . d x_out / d x_in;
  * partials (may be NULL) = chx_dkd_bwd_partials_count() doubles laid out [B][ceil(N/256)][P + 1]: per workgroup
