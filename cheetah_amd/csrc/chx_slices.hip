@@ -357,7 +357,9 @@ __global__ void slice_bwd_table_kernel(const double* __restrict__ out, const dou
     if (!any) return;
     const double W = o[0], W2 = o[1];
     t[0] = 1.0;
-    for (int c = 0; c < 6; ++c) t[1 + c] = o[2 + c];
+    // (a slice whose members carry no weight has no mean, but its W and W2 are sums with a gradient like any other: dW = g_W +
+    //  2 w g_W2. A centre of 0 keeps the A.d and d.H d terms, whose coefficients are 0 there, from turning into 0 * NaN)
+    for (int c = 0; c < 6; ++c) t[1 + c] = W > 0.0 ? o[2 + c] : 0.0;
     for (int c = 0; c < 6; ++c) t[7 + c] = g[2 + c] == 0.0 ? 0.0 : g[2 + c] / W;
     t[34] = g[0];
     t[35] = 2.0 * g[1];
