@@ -24,7 +24,7 @@
 #include "chx_radiation_dev.h"
 
 // parameters per drift-kick-drift kind (include/chx.h), -1 for anything else: what every entry point below counts with
-static int dkd_num_params(int kind) {
+static __host__ __device__ int dkd_num_params(int kind) {
     switch (kind) {
         case CHX_DKD_DRIFT: return 1;
         case CHX_DKD_QUADRUPOLE: return 5;
@@ -816,6 +816,55 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_bwd_kernel(const T* __restrict_
 // has converged keeps stepping (by rounding-size steps), a seed that cannot converge is NaN in its own rows, and two calls give
 // the same bits. The last pass starts from the final point and is the one whose image, matrix and per-item records are stored.
 constexpr int kRingCstStride = 56, kRingMeta = 54;          // kDkdCstStride, kDkdMeta below (asserted equal at the entry point)
+
+// What dkd_ring_radiation_kernel and dkd_ring_sensitivity_kernel do per item, each stated once; S = Dual or Dual2.
+// dkd_ring_jacobian_kernel has the same WRITTEN OUT, as it always had: on any of these helpers its registers are allocated otherwise,
+// and the NaNs a lost seed of a plain map (mode 0) leaves in the records along the ring — the one place where a ring kernel stores
+// NaNs as the maps made them — came out with the other sign bit (profiles/dkd_entry_points.md). A new kind: a line there, a line here.
+__device__ __forceinline__ Dual ring_constant(Dual, double c, const double*, int) { return mk(c, 0.0); }
+__device__ __forceinline__ Dual2 ring_constant(Dual2, double c, const double* dc, int k) { return mk2(c, 0.0, dc[k], 0.0); }
+__device__ __forceinline__ double ring_row(Dual v) { return v.v; }
+__device__ __forceinline__ double ring_row(Dual2 v) { return v.b; }
+__device__ __forceinline__ double ring_column(Dual v) { return v.d; }
+__device__ __forceinline__ double ring_column(Dual2 v) { return v.ab; }
+// an item's constants (block c of cst) as S, its kind and step count. Dual2: the knob's tangent dc[kSensStride] in the e2 part.
+template <typename S>
+__device__ __forceinline__ void ring_item_load(const double* __restrict__ c, const double* __restrict__ dc, S (&cd)[C_N + 1], int& kind, int& steps) {
+    const int32_t* w = reinterpret_cast<const int32_t*>(c + kRingMeta);
+    kind = w[0];
+    steps = w[1];
+#pragma unroll
+    for (int k = 0; k <= C_N; ++k) cd[k] = ring_constant(S{}, c[k], dc, k);
+}
+// the map of an item of any ring kind. BEND as in dkd_items: false compiles no Dipole in (the caller has dealt with that kind).
+template <bool BEND, typename S>
+__device__ __forceinline__ void dkd_map_kind(int kind, const S* cd, const S (&v)[6], double mc2, int steps, S (&out)[6]) {
+    if (kind == CHX_DKD_DRIFT) dkd_map<CHX_DKD_DRIFT, S>(cd, v, mc2, steps, out);
+    else if (kind == CHX_DKD_QUADRUPOLE) dkd_map<CHX_DKD_QUADRUPOLE, S>(cd, v, mc2, steps, out);
+    else if (BEND && kind == CHX_DKD_DIPOLE) dkd_map<CHX_DKD_DIPOLE, S>(cd, v, mc2, steps, out);
+    else if (kind == CHX_DKD_SEXTUPOLE) dkd_map<CHX_DKD_SEXTUPOLE, S>(cd, v, mc2, steps, out);
+    else if (kind == CHX_DKD_RFCAVITY) dkd_map<CHX_DKD_RFCAVITY, S>(cd, v, mc2, steps, out);
+    else dkd_map<CHX_DKD_MULTIPOLE, S>(cd, v, mc2, steps, out);
+}
+// record `row` of the records along the ring: the lane of tangent m < 6 stores column m of the matrix, lane 0 the orbit row as well
+template <typename S>
+__device__ __forceinline__ void ring_record_store(const S (&v)[6], int m, int64_t row, double* __restrict__ matrix_along, double* __restrict__ orbit_along) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) matrix_along[row * 36 + i * 6 + m] = ring_column(v[i]);
+    if (m == 0) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) orbit_along[row * 6 + i] = ring_row(v[i]);
+    }
+}
+// a point with a coordinate that is not finite (NaN, or beyond the largest double): its seed is lost
+template <typename S>
+__device__ __forceinline__ bool ring_lost(const S (&v)[6]) {
+    bool lost = false;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) lost = lost || !(fabs(val(v[i])) <= 1.79769313486231570815e308);
+    return lost;
+}
+
 struct RingJacobianOut {
     double* orbit;          // [B][6]
     double* image;          // [B][6]
@@ -1009,11 +1058,9 @@ __global__ __launch_bounds__(chx_optics::kLanes) void dkd_ring_radiation_kernel(
 #pragma unroll 1
     for (int e = 0; e < E; ++e) {
         const double* __restrict__ c = cst + (int64_t)e * kRingCstStride;
-        const int32_t* w = reinterpret_cast<const int32_t*>(c + kRingMeta);
-        const int kind = w[0], steps = w[1];
+        int kind, steps;
         Dual cd[C_N + 1], out[6];
-#pragma unroll
-        for (int k = 0; k <= C_N; ++k) cd[k] = mk(c[k], 0.0);
+        ring_item_load<Dual>(c, nullptr, cd, kind, steps);
         double part[kIntegrals];
 #pragma unroll
         for (int k = 0; k < kIntegrals; ++k) part[k] = 0.0;
@@ -1058,11 +1105,9 @@ __global__ __launch_bounds__(chx_optics::kLanes) void dkd_ring_radiation_kernel(
                 eta_from_sums(s, rel_beta, eta);
                 bend_contribution(L, h, cos_t, sin_t, c[C_H], c[C_J], eta_in, eta_bend(eta, cos_t, sin_t), sums, part);
             }
-        } else if (kind == CHX_DKD_DRIFT) dkd_map<CHX_DKD_DRIFT, Dual>(cd, v, mc2, steps, out);
-        else if (kind == CHX_DKD_QUADRUPOLE) dkd_map<CHX_DKD_QUADRUPOLE, Dual>(cd, v, mc2, steps, out);
-        else if (kind == CHX_DKD_SEXTUPOLE) dkd_map<CHX_DKD_SEXTUPOLE, Dual>(cd, v, mc2, steps, out);
-        else if (kind == CHX_DKD_RFCAVITY) dkd_map<CHX_DKD_RFCAVITY, Dual>(cd, v, mc2, steps, out);
-        else dkd_map<CHX_DKD_MULTIPOLE, Dual>(cd, v, mc2, steps, out);
+        } else {
+            dkd_map_kind<false, Dual>(kind, cd, v, mc2, steps, out);
+        }
 #pragma unroll
         for (int j = 0; j < 6; ++j) v[j] = out[j];
 #pragma unroll
@@ -1075,9 +1120,7 @@ __global__ __launch_bounds__(chx_optics::kLanes) void dkd_ring_radiation_kernel(
     }
     // a seed whose orbit is NaN or whose image is not finite is NaN in ALL its rows, as in chx_dkd_ring_jacobian (every lane of the
     // group sees the same values; the lane that stored a number along the ring is the one that takes it back)
-    bool lost = false;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) lost = lost || !(fabs(v[i].v) <= 1.79769313486231570815e308);
+    const bool lost = ring_lost(v);
     if (stores) {
 #pragma unroll
         for (int k = 0; k < kIntegrals; ++k)
@@ -1140,43 +1183,16 @@ __global__ __launch_bounds__(chx_optics::kLanes) void dkd_ring_sensitivity_kerne
         Dual2 v[6];
 #pragma unroll
         for (int j = 0; j < 6; ++j) v[j] = mk2(x[j], j == m ? 1.0 : 0.0, w[j], 0.0);
-        if (along && column) {
-            double* Ma = o.d_matrix_along + pair * (int64_t)(E + 1) * 36;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) Ma[i * 6 + m] = v[i].ab;
-            if (m == 0) {
-                double* xa = o.d_orbit_along + pair * (int64_t)(E + 1) * 6;
-#pragma unroll
-                for (int i = 0; i < 6; ++i) xa[i] = v[i].b;
-            }
-        }
+        if (along && column) ring_record_store(v, m, pair * (int64_t)(E + 1), o.d_matrix_along, o.d_orbit_along);
 #pragma unroll 1
         for (int e = 0; e < E; ++e) {
-            const double* __restrict__ c = cst + (int64_t)e * kRingCstStride;
-            const double* __restrict__ dc = dc_knob + (int64_t)e * kSensStride;
-            const int32_t* wd = reinterpret_cast<const int32_t*>(c + kRingMeta);
-            const int kind = wd[0], steps = wd[1];
+            int kind, steps;
             Dual2 cd[C_N + 1], out[6];
-#pragma unroll
-            for (int k = 0; k <= C_N; ++k) cd[k] = mk2(c[k], 0.0, dc[k], 0.0);
-            if (kind == CHX_DKD_DRIFT) dkd_map<CHX_DKD_DRIFT, Dual2>(cd, v, mc2, steps, out);
-            else if (kind == CHX_DKD_QUADRUPOLE) dkd_map<CHX_DKD_QUADRUPOLE, Dual2>(cd, v, mc2, steps, out);
-            else if (kind == CHX_DKD_DIPOLE) dkd_map<CHX_DKD_DIPOLE, Dual2>(cd, v, mc2, steps, out);
-            else if (kind == CHX_DKD_SEXTUPOLE) dkd_map<CHX_DKD_SEXTUPOLE, Dual2>(cd, v, mc2, steps, out);
-            else if (kind == CHX_DKD_RFCAVITY) dkd_map<CHX_DKD_RFCAVITY, Dual2>(cd, v, mc2, steps, out);
-            else dkd_map<CHX_DKD_MULTIPOLE, Dual2>(cd, v, mc2, steps, out);
+            ring_item_load<Dual2>(cst + (int64_t)e * kRingCstStride, dc_knob + (int64_t)e * kSensStride, cd, kind, steps);
+            dkd_map_kind<true, Dual2>(kind, cd, v, mc2, steps, out);
 #pragma unroll
             for (int j = 0; j < 6; ++j) v[j] = out[j];
-            if (along && column) {
-                double* Ma = o.d_matrix_along + (pair * (int64_t)(E + 1) + e + 1) * 36;
-#pragma unroll
-                for (int i = 0; i < 6; ++i) Ma[i * 6 + m] = v[i].ab;
-                if (m == 0) {
-                    double* xa = o.d_orbit_along + (pair * (int64_t)(E + 1) + e + 1) * 6;
-#pragma unroll
-                    for (int i = 0; i < 6; ++i) xa[i] = v[i].b;
-                }
-            }
+            if (along && column) ring_record_store(v, m, pair * (int64_t)(E + 1) + e + 1, o.d_matrix_along, o.d_orbit_along);
         }
         if (!last) {
             // the group's matrix and d f / d theta in LDS: lane m < 6 holds column m, every lane the same e2 parts
@@ -1196,9 +1212,7 @@ __global__ __launch_bounds__(chx_optics::kLanes) void dkd_ring_sensitivity_kerne
             continue;
         }
         // a pair whose orbit or image is not finite is NaN in ALL its rows, as its seed is in chx_dkd_ring_jacobian's
-        bool lost = false;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) lost = lost || !(fabs(v[i].v) <= 1.79769313486231570815e308) || !(fabs(x[i]) <= 1.79769313486231570815e308);
+        const bool lost = ring_lost(v) || ring_lost(x);
         if (column) {
 #pragma unroll
             for (int i = 0; i < 6; ++i) o.d_matrix[pair * 36 + i * 6 + m] = lost ? NAN : v[i].ab;
@@ -1420,7 +1434,7 @@ __device__ __forceinline__ void dkd_item_constants(int kind, int fringe, int ste
     int32_t* w = reinterpret_cast<int32_t*>(out + kDkdMeta);
     w[0] = kind;
     w[1] = steps;
-    const int P = kind == CHX_DKD_DRIFT ? 1 : (kind == CHX_DKD_DIPOLE ? 9 : (kind == CHX_DKD_RFCAVITY ? 4 : (kind == CHX_DKD_MULTIPOLE ? 6 : 5)));          // (Quadrupole, Sextupole: 5)
+    const int P = dkd_num_params(kind);
     double par[CHX_MAX_PARAMS];
     for (int k = 0; k < P; ++k) par[k] = (double)pe[k];
     double c[C_MIXED_N];
@@ -1612,6 +1626,94 @@ __global__ __launch_bounds__(CHX_BLOCK) void dkd_chain_kernel_f64(const double* 
                                                                   double* x_out, int64_t N, int in_vec_ok, int out_vec_ok) {
     dkd_chain_tile<0, BEND, SEXT, RF, MP, double>(x_in, cst, E, mc2, x_out, N, in_vec_ok, out_vec_ok);
 }
+
+// ---- the host rules of the entry points over a list of drift-kick-drift items (chx_dkd_chain_mixed, chx_dkd_turns, the three
+// chx_dkd_ring_*), each stated once, in front of the first of them (TurnsCall and turns_call_ok stand with the *_turns entry points)
+// an item the fused kernels take: one of the six ring kinds, its parameters, a step count that fits the meta word, fringe bits
+bool dkd_item_ok(int kind, const void* params, int num_steps, int fringe_at) {
+    const bool ring_kind = kind == CHX_DKD_DRIFT || kind == CHX_DKD_QUADRUPOLE || kind == CHX_DKD_DIPOLE || kind == CHX_DKD_SEXTUPOLE ||
+                           kind == CHX_DKD_RFCAVITY || kind == CHX_DKD_MULTIPOLE;
+    return ring_kind && params && num_steps >= 1 && num_steps < (1 << 25) && fringe_at >= 0 && fringe_at <= 3;
+}
+// which kinds a run contains: what chooses the compiled variant of its kernel (dkd_items)
+struct DkdKinds {
+    bool bend = false, sext = false, rf = false, mp = false;
+    void add(int kind) {
+        bend = bend || kind == CHX_DKD_DIPOLE;
+        sext = sext || kind == CHX_DKD_SEXTUPOLE;
+        rf = rf || kind == CHX_DKD_RFCAVITY;
+        mp = mp || kind == CHX_DKD_MULTIPOLE;
+    }
+};
+// all E items of a ring are good (false: the entry point refuses), and the kinds among them
+bool dkd_items_ok(const int32_t* kinds, const void* const* params, const int32_t* num_steps, const int32_t* fringe_at, int64_t E, DkdKinds* has = nullptr) {
+    for (int64_t e = 0; e < E; ++e) {
+        if (!dkd_item_ok(kinds[e], params[e], num_steps[e], fringe_at[e])) return false;
+        if (has) has->add(kinds[e]);
+    }
+    return true;
+}
+// the compiled variants <BEND, SEXT, RF, MP> of a kernel over dkd_items: launch(BEND, SEXT, RF, MP) is called once, the flags as
+// std::bool_constant values. A run with a Multipole has every kind compiled in, a run with a cavity every kind but that.
+template <typename Launch>
+void dkd_variant(const DkdKinds& k, Launch&& launch) {
+    constexpr std::true_type T{};
+    constexpr std::false_type F{};
+    if (k.mp) launch(T, T, T, T);
+    else if (k.rf) launch(T, T, T, F);
+    else if (k.bend && k.sext) launch(T, T, F, F);
+    else if (k.bend) launch(T, F, F, F);
+    else if (k.sext) launch(F, T, F, F);
+    else launch(F, F, F, F);
+}
+// likewise the arithmetic mode of a float32 beam (chx_dkd_track_p's storage_precision): launch(MODE)
+template <typename Launch>
+void dkd_mode_variant(int mode, Launch&& launch) {
+    if (mode == 2) launch(std::integral_constant<int, 2>{});
+    else if (mode == 1) launch(std::integral_constant<int, 1>{});
+    else launch(std::integral_constant<int, 0>{});
+}
+// items [done, done + n) of a list as the argument of the kernels that prepare the constants (a linear run: kDkdLinear alone in its
+// meta word); the slots behind n are zeroed. lengths may be null: every kind's first parameter is its length.
+DkdChainArgs dkd_chain_args(const int32_t* kinds, const void* const* params, const void* const* lengths, const int32_t* num_steps,
+                            const int32_t* fringe_at, int64_t done, int n) {
+    DkdChainArgs a;
+    for (int e = 0; e < kDkdChainMax; ++e) {
+        const bool lin = e < n && kinds[done + e] == kDkdLinear;
+        a.params[e] = e < n ? params[done + e] : nullptr;
+        a.length[e] = e < n && lengths ? lengths[done + e] : nullptr;
+        a.meta[e] = e >= n ? 0 : (lin ? kDkdLinear : (kinds[done + e] | (fringe_at[done + e] << 4) | (num_steps[done + e] << 6)));
+    }
+    return a;
+}
+// dkd_chain_prepare_kernel in the settings' dtype: `blocks` is n, or n + 1 with the path length (s_in and s_out given)
+int dkd_prepare_launch(int dtype, unsigned blocks, const DkdChainArgs& a, int n, const void* energy_in, double mass_eV, double n_charges,
+                       void* cst, void* energies, const void* s_in, void* s_out, hipStream_t s) {
+    if (dtype == CHX_F32)
+        hipLaunchKernelGGL(dkd_chain_prepare_kernel<float>, dim3(blocks), dim3(64), 0, s, a, n, (const float*)energy_in, mass_eV, n_charges,
+                           (double*)cst, (float*)energies, (const float*)s_in, (float*)s_out);
+    else
+        hipLaunchKernelGGL(dkd_chain_prepare_kernel<double>, dim3(blocks), dim3(64), 0, s, a, n, (const double*)energy_in, mass_eV, n_charges,
+                           (double*)cst, (double*)energies, (const double*)s_in, (double*)s_out);
+    CHX_CHECK_LAUNCH();
+    return CHX_OK;
+}
+// the workspace of the three chx_dkd_ring_* entry points, the constants of ONE turn: cst[E][kDkdCstStride] (double) | energies[E]
+// (the settings' dtype, room for doubles, rounded up to 16 bytes) as byte offsets, and the size ...
+size_t round_up16(size_t n) { return (n + 15) & ~(size_t)15; }
+struct DkdRingLayout { size_t cst, energies, total; };
+DkdRingLayout dkd_ring_layout(int64_t E) {
+    const size_t energies = (size_t)E * kDkdCstStride * sizeof(double);
+    return {0, energies, energies + round_up16((size_t)E * sizeof(double))};
+}
+// ... and its launch (the walk of the reference energy a first turn of chx_dkd_turns makes); cst: where the ring kernels read
+int dkd_ring_prepare(const int32_t* kinds, const void* const* params, const int32_t* num_steps, const int32_t* fringe_at, int64_t E,
+                     int dtype, const void* energy_in, double mass_eV, double n_charges, void* workspace, hipStream_t s, const double*& cst) {
+    const DkdRingLayout l = dkd_ring_layout(E);
+    cst = (const double*)((const char*)workspace + l.cst);
+    return dkd_prepare_launch(dtype, (unsigned)E, dkd_chain_args(kinds, params, nullptr, num_steps, fringe_at, 0, (int)E), (int)E, energy_in,
+                              mass_eV, n_charges, (char*)workspace + l.cst, (char*)workspace + l.energies, nullptr, nullptr, s);
+}
 }  // namespace
 
 // A run of drift-kick-drift elements on ONE beam with scalar settings. float32 Drifts and Quadrupoles of one arithmetic mode: two
@@ -1682,75 +1784,43 @@ extern "C" int chx_dkd_chain_mixed(const int32_t* kinds, const void* const* para
     // before it writes)
     const int64_t per_pass = std::min<int64_t>(kDkdChainMax, N * 7 * (int64_t)esz / (kDkdCstStride * (int64_t)sizeof(double)));
     bool fuse = !fused_off && E >= 2 && per_pass >= 2 && chx_aligned16(x_tmp) && first >= 0;
-    bool bend = false, sext = false, rf = false, mp = false;
+    DkdKinds has;
     for (int64_t e = 0; fuse && e < E; ++e) {      // (float64 beams ignore storage_precision, like chx_dkd_track_p)
         if (kinds[e] == kDkdLinear) continue;
-        fuse = (kinds[e] == CHX_DKD_DRIFT || kinds[e] == CHX_DKD_QUADRUPOLE || kinds[e] == CHX_DKD_DIPOLE || kinds[e] == CHX_DKD_SEXTUPOLE ||
-                kinds[e] == CHX_DKD_RFCAVITY || kinds[e] == CHX_DKD_MULTIPOLE) &&
-               (dtype == CHX_F64 || (storage_precision[e] == storage_precision[first] && storage_precision[e] >= 0 && storage_precision[e] <= 2)) &&
-               num_steps[e] >= 1 && num_steps[e] < (1 << 25) && fringe_at[e] >= 0 && fringe_at[e] <= 3;
-        bend = bend || kinds[e] == CHX_DKD_DIPOLE;
-        sext = sext || kinds[e] == CHX_DKD_SEXTUPOLE;
-        rf = rf || kinds[e] == CHX_DKD_RFCAVITY;
-        mp = mp || kinds[e] == CHX_DKD_MULTIPOLE;
+        fuse = dkd_item_ok(kinds[e], params[e], num_steps[e], fringe_at[e]) &&
+               (dtype == CHX_F64 || (storage_precision[e] == storage_precision[first] && storage_precision[e] >= 0 && storage_precision[e] <= 2));
+        has.add(kinds[e]);
     }
     if (fuse) {
         hipStream_t s = (hipStream_t)stream;
         const int64_t tiles = (N + CHX_BLOCK - 1) / CHX_BLOCK;
         if (tiles > 0x7fffffffLL) return CHX_ERR_INVALID_ARG;
         const int mode = storage_precision[first];
+        const dim3 grid((unsigned)tiles), wg(CHX_BLOCK);
         for (int64_t done = 0; done < E; done += per_pass) {
             const int n = (int)std::min<int64_t>(per_pass, E - done);
-            DkdChainArgs a;
-            for (int e = 0; e < kDkdChainMax; ++e) {
-                const bool lin = e < n && kinds[done + e] == kDkdLinear;
-                a.params[e] = e < n ? params[done + e] : nullptr;
-                a.length[e] = e < n && lengths ? lengths[done + e] : nullptr;
-                a.meta[e] = e >= n ? 0 : (lin ? kDkdLinear : (kinds[done + e] | (fringe_at[done + e] << 4) | (num_steps[done + e] << 6)));
-            }
+            const DkdChainArgs a = dkd_chain_args(kinds, params, lengths, num_steps, fringe_at, done, n);
             const void* e_from = done == 0 ? energy_in : (const void*)((const char*)energies + (size_t)(done - 1) * esz);
             void* e_to = (char*)energies + (size_t)done * esz;
             const void* s_from = done == 0 ? s_in : s_out;
             const unsigned blocks = (unsigned)(n + (s_out ? 1 : 0));
             const void* src = done == 0 ? x_in : x_out;
             const int in_ok = (int)chx_aligned16(src), out_ok = (int)chx_aligned16(x_out);
+            const int st = dkd_prepare_launch(dtype, blocks, a, n, e_from, mass_eV, n_charges, x_tmp, e_to, s_from, s_out, s);
+            if (st != CHX_OK) return st;
             if (dtype == CHX_F64) {
-                hipLaunchKernelGGL(dkd_chain_prepare_kernel<double>, dim3(blocks), dim3(64), 0, s, a, n, (const double*)e_from, mass_eV,
-                                   n_charges, (double*)x_tmp, (double*)e_to, (const double*)s_from, (double*)s_out);
-                CHX_CHECK_LAUNCH();
-#define CHX_DKD_CHAIN_LAUNCH_F64(B, S, R, M)                                                                                          \
-    hipLaunchKernelGGL((dkd_chain_kernel_f64<B, S, R, M>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const double*)src,              \
-                       (const double*)x_tmp, n, mass_eV, (double*)x_out, N, in_ok, out_ok)
-                if (mp) CHX_DKD_CHAIN_LAUNCH_F64(true, true, true, true);    // (a run with a Multipole: every kind compiled in)
-                else if (rf) CHX_DKD_CHAIN_LAUNCH_F64(true, true, true, false);          // (a run with a cavity: every kind but that)
-                else if (bend && sext) CHX_DKD_CHAIN_LAUNCH_F64(true, true, false, false);
-                else if (bend) CHX_DKD_CHAIN_LAUNCH_F64(true, false, false, false);
-                else if (sext) CHX_DKD_CHAIN_LAUNCH_F64(false, true, false, false);
-                else CHX_DKD_CHAIN_LAUNCH_F64(false, false, false, false);
-#undef CHX_DKD_CHAIN_LAUNCH_F64
-                CHX_CHECK_LAUNCH();
-                continue;
+                dkd_variant(has, [&](auto B, auto S, auto R, auto M) {
+                    hipLaunchKernelGGL((dkd_chain_kernel_f64<B.value, S.value, R.value, M.value>), grid, wg, 0, s, (const double*)src,
+                                       (const double*)x_tmp, n, mass_eV, (double*)x_out, N, in_ok, out_ok);
+                });
+            } else {
+                dkd_mode_variant(mode, [&](auto MODE) {
+                    dkd_variant(has, [&](auto B, auto S, auto R, auto M) {
+                        hipLaunchKernelGGL((dkd_chain_kernel<MODE.value, B.value, S.value, R.value, M.value>), grid, wg, 0, s, (const float*)src,
+                                           (const double*)x_tmp, n, mass_eV, (float*)x_out, N, in_ok, out_ok);
+                    });
+                });
             }
-            hipLaunchKernelGGL(dkd_chain_prepare_kernel<float>, dim3(blocks), dim3(64), 0, s, a, n, (const float*)e_from, mass_eV,
-                               n_charges, (double*)x_tmp, (float*)e_to, (const float*)s_from, (float*)s_out);
-            CHX_CHECK_LAUNCH();
-#define CHX_DKD_CHAIN_LAUNCH(M, B, S, R, MP)                                                                                         \
-    hipLaunchKernelGGL((dkd_chain_kernel<M, B, S, R, MP>), dim3((unsigned)tiles), dim3(CHX_BLOCK), 0, s, (const float*)src, (const double*)x_tmp, \
-                       n, mass_eV, (float*)x_out, N, in_ok, out_ok)
-#define CHX_DKD_CHAIN_MODE(M)                                                                                                     \
-    do {                                                                                                                          \
-        if (mp) CHX_DKD_CHAIN_LAUNCH(M, true, true, true, true);                                                                  \
-        else if (rf) CHX_DKD_CHAIN_LAUNCH(M, true, true, true, false);                                                            \
-        else if (bend && sext) CHX_DKD_CHAIN_LAUNCH(M, true, true, false, false);                                                 \
-        else if (bend) CHX_DKD_CHAIN_LAUNCH(M, true, false, false, false);                                                        \
-        else if (sext) CHX_DKD_CHAIN_LAUNCH(M, false, true, false, false);                                                        \
-        else CHX_DKD_CHAIN_LAUNCH(M, false, false, false, false);                                                                 \
-    } while (0)
-            if (mode == 2) CHX_DKD_CHAIN_MODE(2);
-            else if (mode == 1) CHX_DKD_CHAIN_MODE(1);
-            else CHX_DKD_CHAIN_MODE(0);
-#undef CHX_DKD_CHAIN_MODE
-#undef CHX_DKD_CHAIN_LAUNCH
             CHX_CHECK_LAUNCH();
         }
     } else {
@@ -2781,7 +2851,6 @@ namespace {
 struct DkdTurnsLayout {
     size_t blocks, cst, partials, total;                      // byte offsets of the parts behind start[], and the size
 };
-size_t round_up16(size_t n) { return (n + 15) & ~(size_t)15; }
 DkdTurnsLayout dkd_turns_layout(int64_t E, int64_t N, int64_t turns, int64_t records, int dtype) {
     DkdTurnsLayout l;
     l.blocks = round_up16((size_t)turns * (dtype == CHX_F32 ? 4 : 8));
@@ -2791,7 +2860,7 @@ DkdTurnsLayout dkd_turns_layout(int64_t E, int64_t N, int64_t turns, int64_t rec
     return l;
 }
 template <typename T>
-int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, bool sext, bool rf, bool mp, int mode, const TurnsCall& c, const void* energy_in,
+int dkd_turns_launch(const DkdChainArgs& items, int E, const DkdKinds& has, int mode, const TurnsCall& c, const void* energy_in,
                      void* energy_out, double mass_eV, double n_charges, const void* s_in, void* s_out, void* workspace,
                      const DkdTurnsLayout& l, int64_t tiles, hipStream_t s) {
     const int num_turns = (int)c.num_turns;
@@ -2806,25 +2875,19 @@ int dkd_turns_launch(const DkdChainArgs& items, int E, bool bend, bool sext, boo
     CHX_CHECK_LAUNCH();
     const SoTurnsArgs<T> a = turns_args<T>(c, E, (char*)workspace + l.partials);
     const dim3 grid((unsigned)tiles), wg(CHX_BLOCK);
-    const double* k = cst;
-    const int32_t* b = block_of_turn;
-#define CHX_DKD_TURNS_KINDS(K, ...)                                                                                               \
-    do {                                                                                                                          \
-        if (mp) hipLaunchKernelGGL((K<__VA_ARGS__ true, true, true, true>), grid, wg, 0, s, k, b, mass_eV, a);                       \
-        else if (rf) hipLaunchKernelGGL((K<__VA_ARGS__ true, true, true, false>), grid, wg, 0, s, k, b, mass_eV, a);                 \
-        else if (bend && sext) hipLaunchKernelGGL((K<__VA_ARGS__ true, true, false, false>), grid, wg, 0, s, k, b, mass_eV, a);      \
-        else if (bend) hipLaunchKernelGGL((K<__VA_ARGS__ true, false, false, false>), grid, wg, 0, s, k, b, mass_eV, a);             \
-        else if (sext) hipLaunchKernelGGL((K<__VA_ARGS__ false, true, false, false>), grid, wg, 0, s, k, b, mass_eV, a);             \
-        else hipLaunchKernelGGL((K<__VA_ARGS__ false, false, false, false>), grid, wg, 0, s, k, b, mass_eV, a);                      \
-    } while (0)
     if constexpr (sizeof(T) == 8) {
-        CHX_DKD_TURNS_KINDS(dkd_turns_kernel_f64, );
+        dkd_variant(has, [&](auto B, auto S, auto R, auto M) {
+            hipLaunchKernelGGL((dkd_turns_kernel_f64<B.value, S.value, R.value, M.value>), grid, wg, 0, s, (const double*)cst,
+                               (const int32_t*)block_of_turn, mass_eV, a);
+        });
     } else {
-        if (mode == 2) CHX_DKD_TURNS_KINDS(dkd_turns_kernel, 2, );
-        else if (mode == 1) CHX_DKD_TURNS_KINDS(dkd_turns_kernel, 1, );
-        else CHX_DKD_TURNS_KINDS(dkd_turns_kernel, 0, );
+        dkd_mode_variant(mode, [&](auto MODE) {
+            dkd_variant(has, [&](auto B, auto S, auto R, auto M) {
+                hipLaunchKernelGGL((dkd_turns_kernel<MODE.value, B.value, S.value, R.value, M.value>), grid, wg, 0, s, (const double*)cst,
+                                   (const int32_t*)block_of_turn, mass_eV, a);
+            });
+        });
     }
-#undef CHX_DKD_TURNS_KINDS
     CHX_CHECK_LAUNCH();
     return turns_reduce(c, a.partials, tiles, s);
 }
@@ -2851,17 +2914,8 @@ extern "C" int chx_dkd_turns(const int32_t* kinds, const void* const* params, co
     TurnsCall c{x_in, charges, survival, aperture, x_out, lost_turn, sums, probe, N, K, first_turn, num_turns, record_every, 0, 0};
     if (!turns_call_ok(c)) return CHX_ERR_INVALID_ARG;
     if ((s_in == nullptr) != (s_out == nullptr)) return CHX_ERR_INVALID_ARG;
-    bool bend = false, sext = false, rf = false, mp = false;
-    for (int64_t e = 0; e < E; ++e) {
-        if (!params[e] || (kinds[e] != CHX_DKD_DRIFT && kinds[e] != CHX_DKD_QUADRUPOLE && kinds[e] != CHX_DKD_DIPOLE && kinds[e] != CHX_DKD_SEXTUPOLE &&
-                           kinds[e] != CHX_DKD_RFCAVITY && kinds[e] != CHX_DKD_MULTIPOLE) ||
-            num_steps[e] < 1 || num_steps[e] >= (1 << 25) || fringe_at[e] < 0 || fringe_at[e] > 3)
-            return CHX_ERR_INVALID_ARG;
-        bend = bend || kinds[e] == CHX_DKD_DIPOLE;
-        sext = sext || kinds[e] == CHX_DKD_SEXTUPOLE;
-        rf = rf || kinds[e] == CHX_DKD_RFCAVITY;
-        mp = mp || kinds[e] == CHX_DKD_MULTIPOLE;
-    }
+    DkdKinds has;
+    if (!dkd_items_ok(kinds, params, num_steps, fringe_at, E, &has)) return CHX_ERR_INVALID_ARG;
     const int64_t tiles = (N + CHX_BLOCK - 1) / CHX_BLOCK;
     if (tiles > 0x7fffffffLL || num_turns * E >= 0x7fffffffLL) return CHX_ERR_INVALID_ARG;             // (grid sizes)
     const DkdTurnsLayout l = dkd_turns_layout(E, N, num_turns, c.records, dtype);
@@ -2871,24 +2925,19 @@ extern "C" int chx_dkd_turns(const int32_t* kinds, const void* const* params, co
     if (first_turn == 1 && x_in == x_out) return CHX_ERR_INVALID_ARG;
     if (!turns_no_alias({x_out, energy_out, lost_turn, sums, probe, workspace, s_out}, {x_in, energy_in, charges, survival, aperture, s_in}, 2))
         return CHX_ERR_INVALID_ARG;
-    DkdChainArgs items;
-    for (int e = 0; e < kDkdChainMax; ++e) {
-        items.params[e] = e < E ? params[e] : nullptr;
-        items.length[e] = nullptr;                            // every kind's first parameter is its length
-        items.meta[e] = e < E ? (kinds[e] | (fringe_at[e] << 4) | (num_steps[e] << 6)) : 0;
-    }
+    const DkdChainArgs items = dkd_chain_args(kinds, params, nullptr, num_steps, fringe_at, 0, (int)E);
     if (dtype == CHX_F32)
-        return dkd_turns_launch<float>(items, (int)E, bend, sext, rf, mp, storage_precision, c, energy_in, energy_out, mass_eV, n_charges, s_in,
-                                       s_out, workspace, l, tiles, (hipStream_t)stream);
-    return dkd_turns_launch<double>(items, (int)E, bend, sext, rf, mp, 0, c, energy_in, energy_out, mass_eV, n_charges, s_in, s_out, workspace, l,
-                                    tiles, (hipStream_t)stream);
+        return dkd_turns_launch<float>(items, (int)E, has, storage_precision, c, energy_in, energy_out, mass_eV, n_charges, s_in, s_out, workspace,
+                                       l, tiles, (hipStream_t)stream);
+    return dkd_turns_launch<double>(items, (int)E, has, 0, c, energy_in, energy_out, mass_eV, n_charges, s_in, s_out, workspace, l, tiles,
+                                    (hipStream_t)stream);
 }
 
 // The one-turn map of such a ring with its Jacobian, and the closed orbit (include/chx.h). Two launches: the constants of ONE turn
 // (dkd_chain_prepare_kernel: the walk of the reference energy a first turn of chx_dkd_turns makes), then dkd_ring_jacobian_kernel.
 extern "C" size_t chx_dkd_ring_jacobian_workspace_bytes(int64_t E) {
     if (E < 1 || E > kDkdChainMax) return 0;
-    return (size_t)E * kDkdCstStride * sizeof(double) + (((size_t)E * sizeof(double) + 15) / 16) * 16;
+    return dkd_ring_layout(E).total;
 }
 
 extern "C" int chx_dkd_ring_jacobian(const int32_t* kinds, const void* const* params, const int32_t* num_steps, const int32_t* fringe_at,
@@ -2904,31 +2953,14 @@ extern "C" int chx_dkd_ring_jacobian(const int32_t* kinds, const void* const* pa
     if (mode < 0 || mode > 2 || (mode != 0 && (num_iterations < 1 || num_iterations >= 0x7fffffffLL))) return CHX_ERR_INVALID_ARG;
     if (record_along != 0 && record_along != 1) return CHX_ERR_INVALID_ARG;
     if (record_along && (!orbit_along || !matrix_along || !s_along)) return CHX_ERR_INVALID_ARG;
-    for (int64_t e = 0; e < E; ++e) {
-        if (!params[e] || (kinds[e] != CHX_DKD_DRIFT && kinds[e] != CHX_DKD_QUADRUPOLE && kinds[e] != CHX_DKD_DIPOLE && kinds[e] != CHX_DKD_SEXTUPOLE &&
-                           kinds[e] != CHX_DKD_RFCAVITY && kinds[e] != CHX_DKD_MULTIPOLE) ||
-            num_steps[e] < 1 || num_steps[e] >= (1 << 25) || fringe_at[e] < 0 || fringe_at[e] > 3)
-            return CHX_ERR_INVALID_ARG;
-    }
+    if (!dkd_items_ok(kinds, params, num_steps, fringe_at, E)) return CHX_ERR_INVALID_ARG;
     const int64_t groups = chx_optics::workgroups(B);
     if (groups > 0x7fffffffLL) return CHX_ERR_INVALID_ARG;
-    if (workspace_bytes < chx_dkd_ring_jacobian_workspace_bytes(E) || !chx_aligned16(workspace)) return CHX_ERR_INVALID_ARG;
-    DkdChainArgs items;
-    for (int e = 0; e < kDkdChainMax; ++e) {
-        items.params[e] = e < E ? params[e] : nullptr;
-        items.length[e] = nullptr;                            // every kind's first parameter is its length
-        items.meta[e] = e < E ? (kinds[e] | (fringe_at[e] << 4) | (num_steps[e] << 6)) : 0;
-    }
+    if (workspace_bytes < dkd_ring_layout(E).total || !chx_aligned16(workspace)) return CHX_ERR_INVALID_ARG;
     hipStream_t s = (hipStream_t)stream;
-    double* cst = (double*)workspace;
-    void* energies = (char*)workspace + (size_t)E * kDkdCstStride * sizeof(double);
-    if (dtype == CHX_F32)
-        hipLaunchKernelGGL(dkd_chain_prepare_kernel<float>, dim3((unsigned)E), dim3(64), 0, s, items, (int)E, (const float*)energy_in, mass_eV,
-                           n_charges, cst, (float*)energies, (const float*)nullptr, (float*)nullptr);
-    else
-        hipLaunchKernelGGL(dkd_chain_prepare_kernel<double>, dim3((unsigned)E), dim3(64), 0, s, items, (int)E, (const double*)energy_in, mass_eV,
-                           n_charges, cst, (double*)energies, (const double*)nullptr, (double*)nullptr);
-    CHX_CHECK_LAUNCH();
+    const double* cst;
+    const int st = dkd_ring_prepare(kinds, params, num_steps, fringe_at, E, dtype, energy_in, mass_eV, n_charges, workspace, s, cst);
+    if (st != CHX_OK) return st;
     const RingJacobianOut o{orbit, image, matrix, residual, dispersion, record_along ? orbit_along : nullptr,
                             record_along ? matrix_along : nullptr, record_along ? s_along : nullptr};
     const int passes = mode == 0 ? 1 : (int)num_iterations + 1;
@@ -2959,15 +2991,10 @@ extern "C" int chx_dkd_ring_radiation(const int32_t* kinds, const void* const* p
     if (!kinds || !params || !num_steps || !fringe_at || E < 1 || E > kDkdChainMax || !energy_in || !orbit || !beta0 || !alpha0 || !eta0 ||
         B < 1 || !integrals || !workspace)
         return CHX_ERR_INVALID_ARG;
-    for (int64_t e = 0; e < E; ++e) {
-        if (!params[e] || (kinds[e] != CHX_DKD_DRIFT && kinds[e] != CHX_DKD_QUADRUPOLE && kinds[e] != CHX_DKD_DIPOLE && kinds[e] != CHX_DKD_SEXTUPOLE &&
-                           kinds[e] != CHX_DKD_RFCAVITY && kinds[e] != CHX_DKD_MULTIPOLE) ||
-            num_steps[e] < 1 || num_steps[e] >= (1 << 25) || fringe_at[e] < 0 || fringe_at[e] > 3)
-            return CHX_ERR_INVALID_ARG;
-    }
+    if (!dkd_items_ok(kinds, params, num_steps, fringe_at, E)) return CHX_ERR_INVALID_ARG;
     const int64_t groups = chx_optics::workgroups(B);
     if (groups > 0x7fffffffLL) return CHX_ERR_INVALID_ARG;
-    if (workspace_bytes < chx_dkd_ring_radiation_workspace_bytes(E) || !chx_aligned16(workspace)) return CHX_ERR_INVALID_ARG;
+    if (workspace_bytes < dkd_ring_layout(E).total || !chx_aligned16(workspace)) return CHX_ERR_INVALID_ARG;
     // aliasing: nothing that is written may share a byte with anything else
     const size_t row = (size_t)B * sizeof(double);
     const std::pair<const void*, size_t> written[] = {{integrals, row * chx_radiation::kIntegrals},
@@ -2980,22 +3007,10 @@ extern "C" int chx_dkd_ring_radiation(const int32_t* kinds, const void* const* p
         for (const auto& r : read)
             if (bytes_overlap(written[i].first, written[i].second, r.first, r.second)) return CHX_ERR_INVALID_ARG;
     }
-    DkdChainArgs items;
-    for (int e = 0; e < kDkdChainMax; ++e) {
-        items.params[e] = e < E ? params[e] : nullptr;
-        items.length[e] = nullptr;                            // every kind's first parameter is its length
-        items.meta[e] = e < E ? (kinds[e] | (fringe_at[e] << 4) | (num_steps[e] << 6)) : 0;
-    }
     hipStream_t s = (hipStream_t)stream;
-    double* cst = (double*)workspace;
-    void* energies = (char*)workspace + (size_t)E * kDkdCstStride * sizeof(double);
-    if (dtype == CHX_F32)
-        hipLaunchKernelGGL(dkd_chain_prepare_kernel<float>, dim3((unsigned)E), dim3(64), 0, s, items, (int)E, (const float*)energy_in, mass_eV,
-                           n_charges, cst, (float*)energies, (const float*)nullptr, (float*)nullptr);
-    else
-        hipLaunchKernelGGL(dkd_chain_prepare_kernel<double>, dim3((unsigned)E), dim3(64), 0, s, items, (int)E, (const double*)energy_in, mass_eV,
-                           n_charges, cst, (double*)energies, (const double*)nullptr, (double*)nullptr);
-    CHX_CHECK_LAUNCH();
+    const double* cst;
+    const int st = dkd_ring_prepare(kinds, params, num_steps, fringe_at, E, dtype, energy_in, mass_eV, n_charges, workspace, s, cst);
+    if (st != CHX_OK) return st;
     const RingRadiationIn in{orbit, beta0, alpha0, eta0};
     hipLaunchKernelGGL(dkd_ring_radiation_kernel, dim3((unsigned)groups), dim3(chx_optics::kLanes), 0, s, (const double*)cst, (int)E, mass_eV, in, B,
                        integrals, along);
@@ -3037,7 +3052,7 @@ __global__ __launch_bounds__(64) void dkd_ring_sensitivity_prepare_kernel(SensPa
         if (En == Ee) break;
         Ee = En;
     }
-    const int P = kind == CHX_DKD_DRIFT ? 1 : (kind == CHX_DKD_DIPOLE ? 9 : (kind == CHX_DKD_RFCAVITY ? 4 : (kind == CHX_DKD_MULTIPOLE ? 6 : 5)));
+    const int P = dkd_num_params(kind);
     const T* pe = (const T*)p.params[i];
     Dual pd[CHX_MAX_PARAMS], cd[C_N + 1];
 #pragma unroll
@@ -3053,7 +3068,7 @@ __global__ __launch_bounds__(64) void dkd_ring_sensitivity_prepare_kernel(SensPa
 
 extern "C" size_t chx_dkd_ring_sensitivity_workspace_bytes(int64_t E, int64_t K) {
     if (E < 1 || E > kDkdChainMax || K < 0 || K > (1 << 20)) return 0;
-    return chx_dkd_ring_jacobian_workspace_bytes(E) + (size_t)K * (size_t)E * kSensStride * sizeof(double);
+    return dkd_ring_layout(E).total + (size_t)K * (size_t)E * kSensStride * sizeof(double);
 }
 
 extern "C" int chx_dkd_ring_sensitivity(const int32_t* kinds, const void* const* params, const int32_t* num_steps, const int32_t* fringe_at,
@@ -3068,12 +3083,7 @@ extern "C" int chx_dkd_ring_sensitivity(const int32_t* kinds, const void* const*
         return CHX_ERR_INVALID_ARG;
     if (mode < 0 || mode > 2 || (record_along != 0 && record_along != 1)) return CHX_ERR_INVALID_ARG;
     if (K > 0 && (!d_orbit || !d_image || !d_matrix || !d_dispersion || !workspace || (record_along && (!d_orbit_along || !d_matrix_along)))) return CHX_ERR_INVALID_ARG;
-    for (int64_t e = 0; e < E; ++e) {
-        if (!params[e] || (kinds[e] != CHX_DKD_DRIFT && kinds[e] != CHX_DKD_QUADRUPOLE && kinds[e] != CHX_DKD_DIPOLE && kinds[e] != CHX_DKD_SEXTUPOLE &&
-                           kinds[e] != CHX_DKD_RFCAVITY && kinds[e] != CHX_DKD_MULTIPOLE) ||
-            num_steps[e] < 1 || num_steps[e] >= (1 << 25) || fringe_at[e] < 0 || fringe_at[e] > 3)
-            return CHX_ERR_INVALID_ARG;
-    }
+    if (!dkd_items_ok(kinds, params, num_steps, fringe_at, E)) return CHX_ERR_INVALID_ARG;
     // the components by (knob, item): one pair each, with the set of parameters the knob moves (a component named twice is refused)
     std::vector<std::pair<int64_t, int32_t>> comps((size_t)num_components);
     for (int64_t c = 0; c < num_components; ++c) {
@@ -3089,24 +3099,11 @@ extern "C" int chx_dkd_ring_sensitivity(const int32_t* kinds, const void* const*
     const int64_t groups = chx_optics::pair_workgroups(B, K);
     if (groups > 0x7fffffffLL) return CHX_ERR_INVALID_ARG;
     if (workspace_bytes < chx_dkd_ring_sensitivity_workspace_bytes(E, K) || !chx_aligned16(workspace)) return CHX_ERR_INVALID_ARG;
-
-    DkdChainArgs items;
-    for (int e = 0; e < kDkdChainMax; ++e) {
-        items.params[e] = e < E ? params[e] : nullptr;
-        items.length[e] = nullptr;
-        items.meta[e] = e < E ? (kinds[e] | (fringe_at[e] << 4) | (num_steps[e] << 6)) : 0;
-    }
     hipStream_t s = (hipStream_t)stream;
-    double* cst = (double*)workspace;
-    void* energies = (char*)workspace + (size_t)E * kDkdCstStride * sizeof(double);
-    double* dcst = (double*)((char*)workspace + chx_dkd_ring_jacobian_workspace_bytes(E));
-    if (dtype == CHX_F32)
-        hipLaunchKernelGGL(dkd_chain_prepare_kernel<float>, dim3((unsigned)E), dim3(64), 0, s, items, (int)E, (const float*)energy_in, mass_eV,
-                           n_charges, cst, (float*)energies, (const float*)nullptr, (float*)nullptr);
-    else
-        hipLaunchKernelGGL(dkd_chain_prepare_kernel<double>, dim3((unsigned)E), dim3(64), 0, s, items, (int)E, (const double*)energy_in, mass_eV,
-                           n_charges, cst, (double*)energies, (const double*)nullptr, (double*)nullptr);
-    CHX_CHECK_LAUNCH();
+    const double* cst;
+    const int st = dkd_ring_prepare(kinds, params, num_steps, fringe_at, E, dtype, energy_in, mass_eV, n_charges, workspace, s, cst);
+    if (st != CHX_OK) return st;
+    double* dcst = (double*)((char*)workspace + dkd_ring_layout(E).total);          // the tangents' block stands behind the turn's
     const int64_t tangents = K * E * kSensStride;
     hipLaunchKernelGGL(dkd_ring_sensitivity_zero_kernel, dim3((unsigned)((tangents + 255) / 256)), dim3(256), 0, s, dcst, tangents);
     CHX_CHECK_LAUNCH();

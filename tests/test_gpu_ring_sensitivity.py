@@ -467,6 +467,30 @@ def test_a_pair_alone_equals_the_pair_inside_the_batch(name):
             assert same_bits(getattr(alone, f)[0, col], getattr(full, f)[b, k]), (b, k, f)
 
 
+def test_more_pairs_than_one_prepare_launch_takes():
+    """129 (knob, item) pairs — the tangents of the constants are prepared 128 pairs a launch, so the last pair goes in a second one:
+    3 knobs (the length, the strength and the tilt all 43 Quadrupoles of a ring share; each item has a misalignment of its own, so
+    the closed orbit is off the axis and moves with every knob), B = 1, the 4-D closed orbit. Every row equals, bit for bit, the
+    row of the call with that knob alone (43 pairs, one launch)."""
+    import cheetah_amd as ca
+
+    length, k1, tilt = T(0.1), T(0.5), T(0.1)
+    seg = ca.Segment([ca.Quadrupole(length, k1=k1, tilt=tilt, misalignment=T([1e-4 * (i % 3 - 1), 5e-5 * (i % 5 - 2)]), num_steps=1 + i % 2,
+                                    name=f"q{i}", **DKD, **KW) for i in range(43)])
+    fields = ("d_orbit", "d_image", "d_matrix", "d_dispersion")
+
+    def raw(wrt):
+        return seg._closed_orbit("ring_sensitivity", T(ENERGY), None, T([1e-3]), None, False, 10, False, wrt, True)[1]
+
+    full = raw([length, k1, tilt])
+    for f in fields:
+        assert full[f].shape[:2] == (1, 3) and torch.isfinite(full[f]).all() and bool((full[f][0] != 0).flatten(1).any(dim=1).all()), f
+    for k, t in enumerate((length, k1, tilt)):
+        alone = raw([t])
+        for f in fields:
+            assert same_bits(alone[f][0, 0], full[f][0, k]), (k, f)
+
+
 def test_a_captured_graph_replays_after_an_edit():
     import cheetah_amd as ca
 
