@@ -6,7 +6,8 @@ element list is partitioned into maximal skippable runs (each composed and appli
 non-skippable elements (active Cavity / Screen / SpaceChargeKick / BPM / Aperture) are tracked one by
 one. Here: the container, the planner cache, the per-run map products and the fused launchers. The plan classes live in `_plans.py`,
 the ParticleBeam dispatch table in `_planner.py`, the stretch call ([run | Cavity | BPM | Aperture | Screen]+ as one call of the
-host step) in `_stretch.py`: `Segment._lattice_stretch*` only forward there.
+host step) in `_stretch.py`, the runs of non-linear elements in registers in `_nonlinear.py`, the lattice taken as a ring (`track_turns`,
+the ring optics) in `_ring.py`: `Segment._lattice_stretch*`, `_second_order_run`, `_dkd_run` and the ring methods only forward there.
 
 Host-side cost matters here (the merged pass is a ~10 us kernel), so unlike the reference
  * no nn.Module sub-segments are built per call (segment.py:558-569);
@@ -41,7 +42,8 @@ from .. import _lib, _ops
 from ..particles.parameter_beam import ParameterBeam
 from ..particles.particle_beam import ParticleBeam
 from ..particles.species import Species
-from . import _planner, _stretch
+from . import _nonlinear, _planner, _ring, _stretch
+from ._nonlinear import _DKD_IN_REGISTERS  # noqa: F401  (the kinds a run keeps in registers; tests read them here)
 from ._plans import _IDENTITY, _FastRun, _LatticePlan, _Run  # noqa: F401  (the plan classes; tests reach them through this module)
 from .element import Element, tracking_call
 from .space_charge_kick import SpaceChargeKick
@@ -107,14 +109,6 @@ class _ElementList(nn.ModuleList):
 
 
 _CHECK_PLANS = os.environ.get("CHX_CHECK_PLANS", "0") == "1"
-#: drift-kick-drift kinds chx_dkd_chain carries through a run in registers
-_DKD_IN_REGISTERS = (_ops.DKD_KIND["drift"], _ops.DKD_KIND["quadrupole"], _ops.DKD_KIND["dipole"], _ops.DKD_KIND["sextupole"],
-                     _ops.DKD_KIND["rfcavity"], _ops.DKD_KIND["multipole"])
-#: what `Segment._turn_items` hands `_track_turns_fused` for a ring of drift-kick-drift elements (chx_dkd_turns): per element the
-#: kind, the (1, P) parameter tensor, num_steps and fringe_at; `storage` = the ring's one arithmetic mode
-_DkdRing = collections.namedtuple("_DkdRing", "kinds params num_steps fringe_at storage")
-#: the electrons `one_turn_map`, `closed_orbit` and `ring_optics` take for `species=None`, by (dtype, device)
-_DEFAULT_SPECIES = {}
 #: CHX_SC_CHAIN = auto (default) | on | off — how `Segment.track` takes [SpaceChargeKick, linear run, SpaceChargeKick, ...]:
 #: "auto" starts on the tile-ordered chain and lets the asynchronous guard (`_chain_allowed`) send a plan whose beam reshuffles
 #: between kicks back to kick-by-kick tracking. The two paths sum the charge in different orders, so WHEN the guard's header
@@ -735,185 +729,33 @@ class Segment(Element):
 
     def _lattice_stretch_parameter(self, plan, i: int, incoming: ParameterBeam):
         return _stretch.track_parameter(self, plan, i, incoming)
-
+    # the runs of non-linear elements (accelerator/_nonlinear.py) and the lattice as a ring (accelerator/_ring.py) behind the methods
+    # the planner, the plans and the tests go through: a stand-in for any of them is honoured
     @staticmethod
     def _identity_run(run) -> bool:
-        """A run of pass-through elements only (Markers, inactive BPMs / Screens between two non-linear elements): nothing to
-        apply, zero length."""
-        return all(e._chx_kind == _IDENTITY and e._static_skippable and not e._parameters for e in run.elements)
+        return _nonlinear.identity_run(run)
 
     def _second_order_run(self, plan, i: int, incoming: ParticleBeam):
-        """plan[i] and what follows it as one `chx_second_order_chain_mixed` call — second-order elements and the merged runs of
-        linear elements between them (a lattice whose drifts are linear and whose magnets second order): (outgoing beam, index
-        behind the stretch), or None when fewer than two items or no second-order element qualify (one plain beam without a
-        graph, (7, 7, 7) maps and scalar lengths of the beam's dtype without gradients, the stock `track`; runs with scalar
-        settings). Same numbers as the walk item by item."""
-        x, energy, s = incoming.particles, incoming.energy, incoming.s
-        if x.dim() != 2 or not x.is_cuda or energy.dim() != 0 or s.dim() != 0 or s.dtype != x.dtype or s.device != x.device or (
-                torch.is_grad_enabled() and (x.requires_grad or energy.requires_grad or s.requires_grad)):
-            return None
-        grad = torch.is_grad_enabled()
-        species = incoming.species
-        # the stretch as it was found last time stands while no attribute of any element was assigned (`Element._epoch`), the
-        # energy is the same tensor at the same version and no setting was edited in place: O(1) + one version sweep instead
-        # of ~2.5 us of cache look-ups per element
-        cache = self.__dict__.get("_so_run_cache")
-        if cache is None or cache[0] is not plan:
-            cache = self.__dict__["_so_run_cache"] = (plan, {})
-        ent = cache[1].get(i)
-        if ent is not None and ent["epoch"] == Element._epoch and ent["energy"] is energy and ent["energy_version"] == energy._version \
-                and ent["dtype"] == x.dtype and ent["device"] == x.device and ent["mass"] == species.mass_eV_float \
-                and ent["nq"] == species.num_elementary_charges_float \
-                and [t._version for t in ent["tensors"]] == ent["versions"] and not _ops.CAPTURING[0] \
-                and not (grad and any(t.requires_grad for t in ent["tensors"])):
-            out, s_out, _ = _ops.second_order_chain(ent["maps"], ent["lengths"], x, s, ent["ptrs"])
-            return ParticleBeam(out, energy, particle_charges=incoming.particle_charges,
-                                survival_probabilities=incoming.survival_probabilities, s=s_out, species=species), ent["end"]
-        maps, lengths, linear, tensors, j, last_so = self._second_order_items(plan, i, x, energy, species, grad)
-        if last_so is None or len(maps) < 2:
-            return None
-        out, s_out, ptrs = _ops.second_order_chain(maps, lengths, x, s, linear=linear)
-        if not _ops.CAPTURING[0] and not any(t.requires_grad for t in tensors) and not energy.requires_grad:
-            # (maps of tensors that carry gradients are rebuilt on every track, Element._cached_map: nothing to keep)
-            cache[1][i] = {"epoch": Element._epoch, "energy": energy, "energy_version": energy._version, "dtype": x.dtype,
-                           "device": x.device, "mass": species.mass_eV_float, "nq": species.num_elementary_charges_float,
-                           "tensors": tensors, "versions": [t._version for t in tensors], "maps": maps, "lengths": lengths,
-                           "ptrs": ptrs, "end": j}
-        return ParticleBeam(out, energy, particle_charges=incoming.particle_charges,
-                            survival_probabilities=incoming.survival_probabilities, s=s_out, species=species), j
+        return _nonlinear.second_order_run(self, plan, i, incoming)
 
-    def _second_order_items(self, plan, i: int, x: torch.Tensor, energy: torch.Tensor, species: Species, grad: bool):
-        """The items of the stretch that begins at plan[i], as `chx_second_order_chain_mixed` and `chx_second_order_turns` take
-        them: (maps, lengths, linear flags, setting tensors, index behind the stretch, index of the last second-order element or
-        None). Second-order elements give their (7, 7, 7) map, a merged run of linear elements its composed (7, 7) map (a copy)
-        and its summed length; the stretch ends in front of the first item that does not qualify."""
-        maps, lengths, linear, tensors = [], [], [], []
-        j, last_so = i, None
-        while j < len(plan):
-            kind, e = plan[j]
-            if kind == "run":
-                # a merged run of linear elements: its composed map (chx_run_map, one launch now, none while the stretch stands)
-                # in a tensor of its own — the plan's state is shared with every other way this run can be tracked
-                if j + 1 < len(plan) and plan[j + 1][0] == "element" and plan[j + 1][1]._is_cavity:
-                    break                                      # that run belongs to the cavity's stretch (chx_lattice_track)
-                if self._identity_run(e):
-                    j += 1                                     # Markers between two magnets: nothing to apply, s + 0
-                    continue
-                zero = self.__dict__.get("_zero_s")
-                if zero is None or zero.dtype != x.dtype or zero.device != x.device:
-                    zero = self.__dict__["_zero_s"] = torch.zeros((), dtype=x.dtype, device=x.device)
-                got = self._run_map_fast(e, x, energy, species, zero)
-                if got is None or got[1].dim() != 0 or got[1].dtype != x.dtype or got[1].device != x.device:
-                    break
-                maps.append(got[0].clone())
-                lengths.append(got[1])                         # 0 + (l_0 + l_1 + ...): the run's length as the walk adds it
-                linear.append(1)
-                tensors += e.fast.tensors
-            elif kind == "element":
-                cls = type(e)
-                if e._tracking_method != "second_order" or e._t_kind is None or cls.track is not Element.track \
-                        or cls._track_second_order is not Element._track_second_order \
-                        or cls._track_internal is not Element._track_internal:
-                    break
-                length = e.length
-                if length.dim() != 0 or length.dtype != x.dtype or length.device != x.device or (grad and length.requires_grad):
-                    break
-                T = e.second_order_transfer_map(energy, species)
-                if T.dim() != 3 or T.dtype != x.dtype or T.device != x.device or (grad and T.requires_grad):
-                    break
-                maps.append(T if T.is_contiguous() else T.contiguous())
-                lengths.append(length)
-                linear.append(0)
-                tensors += e._feature_key()[1]
-                last_so = j
-            else:
-                break
-            j += 1
-        return maps, lengths, linear, tensors, j, last_so
-
-    # ---- multi-turn tracking ---------------------------------------------------------------------------------
-    def _turn_items(self, incoming: ParticleBeam):
-        """(maps, lengths, linear) when the WHOLE lattice is one stretch the fused turn kernel takes — second-order elements and
-        merged linear runs as in `_second_order_run`, or a single merged linear run —, a `_DkdRing` when it is a ring of
-        drift-kick-drift elements instead (`_turn_items_dkd`), else the reason (a str) why neither."""
-        x, energy, s = incoming.particles, incoming.energy, incoming.s
-        if x.dim() != 2 or not x.is_cuda:
-            return "the beam is not one plain (N, 7) beam on the device"
-        if energy.dim() != 0 or s.dim() != 0 or s.dtype != x.dtype or s.device != x.device or energy.dtype != x.dtype:
-            return "the beam's energy and path length are not scalars of the particles' dtype on their device"
-        if energy.device != x.device:
-            return "the beam's energy is not on the particles' device"
-        # the kernel reads the weights as N values of the particles' dtype through their addresses: nothing else may reach it (a
-        # beam with vectorised charges, (B, N) under particles (N, 7), is a vectorised beam: the general path)
-        for name, wt in (("particle_charges", incoming.particle_charges), ("survival_probabilities", incoming.survival_probabilities)):
-            if wt.shape != x.shape[:1] or wt.dtype != x.dtype or wt.device != x.device:
-                return f"the beam's {name} are not one (N,) tensor of the particles' dtype on their device"
-        if type(self).track is not Segment.track or type(self)._track_internal is not Segment._track_internal:
-            return "the segment overrides `track`"
-        plan = self._plan()
-        if not plan:
-            return "the lattice holds nothing to track"
-        # (the caller runs under no_grad, so the `grad` flag is False here and `_second_order_items` skips its own requires_grad
-        # tests: trainable settings are turned away by the sweep over `tensors` below)
-        maps, lengths, linear, tensors, j, _ = self._second_order_items(plan, 0, x, energy, incoming.species, torch.is_grad_enabled())
-        if j < len(plan):
-            kind, item = plan[j]
-            what = "a run of linear elements that does not qualify (vectorised or trainable settings, or the run in front of a cavity)" \
-                if kind == "run" else \
-                f"{type(item).__name__} '{item.name}' (tracking method '{item._tracking_method}')"
-            reason = f"the lattice is not one stretch of second-order and linear items: {what} ends it"
-        elif not 1 <= len(maps) <= 224:
-            reason = f"the lattice has {len(maps)} items, the fused kernel takes 1 to 224"
-        elif any(t.requires_grad for t in tensors):
-            reason = "a setting of the lattice requires grad"
-        else:
-            return maps, lengths, linear
-        ring = self._turn_items_dkd(plan, x)
-        if isinstance(ring, str):
-            return f"{reason}; nor is it a ring of drift-kick-drift elements: {ring}"
-        return ring
+    def _dkd_run(self, plan, i: int, incoming: ParticleBeam):
+        return _nonlinear.dkd_run(self, plan, i, incoming)
 
     def _turn_items_dkd(self, plan, x: torch.Tensor, trainable=()):
-        """A `_DkdRing` when the WHOLE plan is a ring `chx_dkd_turns` takes — drift-kick-drift Drifts, Quadrupoles, Dipoles, Sextupoles, RFCavities and Multipoles as
-        `_dkd_run` keeps them in registers, all of one arithmetic class, 1 to 192 of them, Markers in between skipped — else the
-        reason (a str) why not. Nothing is kept between calls: settings and `dkd_precision` are read here every time.
-        `trainable`: the ids of the settings that may require grad (the `wrt` of the ring optics; `track_turns` has none), or
-        "all"."""
-        kinds, params, steps, fringes, classes, tensors = [], [], [], [], [], []
-        single = x.dtype == torch.float64                      # (float64 beams are evaluated in fp64 whatever `dkd_precision` says)
-        for kind, e in plan:
-            if kind == "run":
-                if self._identity_run(e):
-                    continue                                   # Markers between two magnets: nothing to apply, s + 0
-                return "a run of linear elements stands in the ring (its map depends on the reference energy in front of it, and an " \
-                       "energy that drifts from turn to turn would need a map per turn: left to the general path on purpose)"
-            cls = type(e)
-            name = f"{cls.__name__} '{e.name}'"
-            if e._tracking_method != "drift_kick_drift" or e._dkd_kind not in _DKD_IN_REGISTERS:
-                return f"{name} (tracking method '{e._tracking_method}') is not a drift-kick-drift Drift, Quadrupole, Dipole, Sextupole, RFCavity or Multipole"
-            if cls.track is not Element.track or cls._track_drift_kick_drift is not Element._track_drift_kick_drift \
-                    or cls._track_internal is not Element._track_internal:
-                return f"{name} overrides `track`"
-            if e.dkd_precision not in _ops.DKD_PRECISION:
-                return f"{name} has the unknown dkd_precision {e.dkd_precision!r}"
-            p = e._dkd_params_stacked(x.dtype, x.device)
-            if p is None:
-                return f"the settings of {name} are not all scalars of the beam's dtype on its device (vectorised settings take the general path)"
-            n, f = e._dkd_options()
-            kinds.append(e._dkd_kind)
-            params.append(p)
-            steps.append(n)
-            fringes.append(f)
-            classes.append(0 if single else _ops.DKD_PRECISION[e.dkd_precision])
-            tensors += [t for t, _ in e._dkd_scalar_refs()]
-        if not 1 <= len(kinds) <= 192:
-            return f"the ring has {len(kinds)} drift-kick-drift elements, the fused kernel takes 1 to 192"
-        if len(set(classes)) > 1:
-            return "the elements' `dkd_precision` settings put them into more than one arithmetic class (one launch evaluates one)"
-        if trainable != "all" and any(t.requires_grad and id(t) not in trainable for t in tensors):
-            return "a setting of the lattice requires grad"
-        return _DkdRing(kinds, params, steps, fringes, classes[0])
+        return _ring.turn_items_dkd(self, plan, x, trainable)
 
+    @staticmethod
+    def _ring_knobs(what: str, plan, wrt):
+        return _ring.ring_knobs(what, plan, wrt)
+
+    def _ring_jacobian(self, what: str, energy, species, start: torch.Tensor, mode: int, num_iterations: int, along: bool, wrt=None,
+                       raw: bool = False, ring_call=None):
+        return _ring.ring_jacobian(self, what, energy, species, start, mode, num_iterations, along, wrt, raw, ring_call)
+
+    def _closed_orbit(self, what, energy, species, delta, guess, longitudinal, num_iterations, along, wrt=None, raw=False, ring_call=None):
+        return _ring.find_closed_orbit(self, what, energy, species, delta, guess, longitudinal, num_iterations, along, wrt, raw, ring_call)
+
+    # ---- multi-turn tracking ---------------------------------------------------------------------------------
     def track_turns(self, incoming: ParticleBeam, num_turns: int, *, record_every: int = 1, aperture=None, record_first: int = 0,
                     fused=None):
         """`num_turns` passes of the beam through this lattice taken as a ring, with turn-by-turn records: a `TurnByTurn`
@@ -958,211 +800,9 @@ class Segment(Element):
         Second-order maps are TRUNCATED Taylor maps and not symplectic: over many turns amplitudes drift where the true motion
         is bounded (or the reverse), so dynamic-aperture and long-term stability figures from that tracking carry that caveat.
         The drift-kick-drift maps are symplectic: a ring of them is the one to use for such figures."""
-        from ..particles import turns as _turns
-
-        if not isinstance(incoming, ParticleBeam):
-            raise TypeError(f"track_turns takes a ParticleBeam, got {type(incoming)}")
-        num_turns, record_every, record_first = int(num_turns), int(record_every), int(record_first)
-        if num_turns < 1 or record_every < 1:
-            raise ValueError("num_turns and record_every must be at least 1")
-        x = incoming.particles
-        if record_first < 0 or record_first > x.shape[-2]:
-            raise ValueError(f"record_first = {record_first} is not within 0 .. {x.shape[-2]} (the number of particles)")
-        sp = incoming.species
-        if any(t.requires_grad for t in (x, incoming.energy, incoming.s, incoming.particle_charges, incoming.survival_probabilities,
-                                         sp.mass_eV, sp.num_elementary_charges)) or (aperture is not None and aperture.requires_grad):
-            raise ValueError("track_turns has no autograd: an input requires grad")
-        if aperture is not None and (aperture.shape != (2,) or aperture.dtype != x.dtype or aperture.device != x.device):
-            raise ValueError("aperture must be a tensor (a_x, a_y) of the beam's dtype on its device")
-        with torch.no_grad():
-            items = "fused=False" if fused is False else self._turn_items(incoming)
-            if isinstance(items, str):
-                if fused:
-                    raise ValueError(f"track_turns(fused=True): {items}")
-                return self._track_turns_general(incoming, num_turns, record_every, aperture, record_first, _turns)
-            return self._track_turns_fused(incoming, items, num_turns, record_every, aperture, record_first, _turns)
-
-    def _track_turns_fused(self, incoming, items, num_turns, record_every, aperture, record_first, _turns):
-        dkd = isinstance(items, _DkdRing)
-        x = _ops.aligned(incoming.particles)
-        N, E, dev = x.shape[0], len(items[0]), x.device
-        _ops.check_current_device(dev)
-        charges, survival = _ops.aligned(incoming.particle_charges), _ops.aligned(incoming.survival_probabilities)
-        if aperture is not None and not aperture.is_contiguous():
-            raise ValueError("aperture must be contiguous (it is read through its address)")
-        R = num_turns // record_every
-        if dkd:
-            ws_bytes = lambda records, turns=1: _ops.dkd_turns_workspace_bytes(E, N, turns, records, x.dtype)  # noqa: E731
-        else:
-            ws_bytes = lambda records, turns=1: _ops.second_order_turns_workspace_bytes(E, N, records, x.dtype)  # noqa: E731
-        per_record = ws_bytes(1) - ws_bytes(0)
-        chunks = _turns.plan_chunks(num_turns, E, record_every, per_record, _turns._MAX_ITEM_STEPS, _turns._MAX_PARTIAL_BYTES)
-        # the coefficient block (a drift-kick-drift ring: a block of constants per turn of a launch, the worst case of a drifting
-        # reference energy) and the partials: an allocation of its own, sized for the longest launch and the one that records most
-        ws = _ops.workspace(ws_bytes(max(_turns.chunk_records(f, n, record_every) for f, n in chunks), max(n for _, n in chunks)), dev)
-        out = torch.empty_like(x)
-        lost = torch.zeros(N, dtype=torch.int32, device=dev)
-        sums = torch.empty((R, _turns.NUM_SUMS), dtype=torch.float64, device=dev)
-        probe = torch.empty((R, record_first, 7), dtype=x.dtype, device=dev) if record_first else None
-        s_one = torch.empty_like(incoming.s)
-        energy = incoming.energy
-        if dkd:
-            # the reference energy travels from launch to launch through one device scalar: behind the call the energy behind
-            # the last turn
-            sp = incoming.species
-            arrays = _ops.dkd_turn_arrays(items.kinds, items.params, items.num_steps, items.fringe_at)
-            energy = torch.empty_like(incoming.energy)
-            for first, n in chunks:
-                _ops.dkd_turns(arrays, items.storage, E, x if first == 1 else out, out, incoming.energy if first == 1 else energy, energy,
-                               sp.mass_eV_float, sp.num_elementary_charges_float, charges, survival, first, n, record_every, aperture,
-                               lost, sums, probe, ws, incoming.s if first == 1 else None, s_one if first == 1 else None)
-        else:
-            maps, lengths, linear = items
-            ptrs = _ops.second_order_turn_ptrs(maps, lengths, linear)
-            for first, n in chunks:
-                _ops.second_order_turns(ptrs, E, x if first == 1 else out, out, charges, survival, first, n, record_every, aperture, lost,
-                                        sums, probe, ws, incoming.s if first == 1 else None, s_one if first == 1 else None)
-        s_out = incoming.s + num_turns * (s_one - incoming.s)
-        beam = ParticleBeam(out, energy, particle_charges=incoming.particle_charges,
-                            survival_probabilities=incoming.survival_probabilities * (lost == 0), s=s_out, species=incoming.species)
-        return _turns.TurnByTurn(beam, lost, _turns.recorded_turns(num_turns, record_every, dev), sums, probe, record_every=record_every)
-
-    def _track_turns_general(self, incoming, num_turns, record_every, aperture, record_first, _turns):
-        x = incoming.particles
-        dev = x.device
-        w = incoming.particle_charges.to(torch.float64) * incoming.survival_probabilities.to(torch.float64)
-        lost = torch.zeros(x.shape[:-1], dtype=torch.int32, device=dev)     # (batch dimensions of a vectorised beam in front)
-        beam, sums, probe, s_one = incoming, [], [], None
-        for t in range(1, num_turns + 1):
-            before = beam.particles
-            beam = self.track(beam)
-            if t == 1:
-                s_one = beam.s
-            alive_before = lost == 0
-            xt = torch.where(alive_before.unsqueeze(-1), beam.particles, before)     # a lost particle stands where it was lost
-            lost = torch.where(alive_before & _turns.is_lost(xt, aperture), torch.full_like(lost, t), lost)
-            # (survival 0 from the turn of the loss on: a collective kick of the lattice no longer counts the particle's charge)
-            beam = ParticleBeam(xt, beam.energy, particle_charges=beam.particle_charges,
-                                survival_probabilities=beam.survival_probabilities * (lost == 0), s=beam.s, species=beam.species)
-            if t % record_every == 0:
-                sums.append(_turns.record_sums(xt, lost == 0, w))
-                if record_first:
-                    probe.append(xt[..., :record_first, :].clone())
-        beam = ParticleBeam(beam.particles, beam.energy, particle_charges=beam.particle_charges,
-                            survival_probabilities=beam.survival_probabilities, s=incoming.s + num_turns * (s_one - incoming.s),
-                            species=beam.species)
-        lead = tuple(beam.particles.shape[:-2])
-        sums = torch.stack(sums) if sums else torch.empty((0, *lead, _turns.NUM_SUMS), dtype=torch.float64, device=dev)
-        if record_first:
-            probe = torch.stack(probe) if probe else torch.empty((0, *lead, record_first, 7), dtype=x.dtype, device=dev)
-        return _turns.TurnByTurn(beam, lost, _turns.recorded_turns(num_turns, record_every, dev), sums, probe if record_first else None,
-                                 record_every=record_every)
+        return _ring.track_turns(self, incoming, num_turns, record_every, aperture, record_first, fused)
 
     # ---- linear optics of a ring --------------------------------------------------------------------------------
-    @staticmethod
-    def _ring_knobs(what: str, plan, wrt):
-        """The knobs of `wrt` — a sequence of tensors, each by identity a setting `_dkd_scalar_refs()` lists for an element of the
-        ring, or "all": every such setting that requires grad — as (tensors, per tensor (first knob, count, 0-d?), components
-        [(knob, item, slot)], K). A 0-d setting is one knob, an (n,) setting n knobs; a tensor many elements share is one knob
-        with a component per element."""
-        refs = []                                              # (item, slot, tensor, index) in the ring's order
-        item = 0
-        for kind, e in plan:
-            if kind == "run":
-                continue                                       # (Markers: `_turn_items_dkd` has refused every other run)
-            for slot, (t, index) in enumerate(e._dkd_scalar_refs()):
-                refs.append((item, slot, t, index))
-            item += 1
-        if isinstance(wrt, str):
-            if wrt != "all":
-                raise ValueError(f"{what}: wrt must be a sequence of tensors or 'all', got {wrt!r}")
-            seen, wrt = set(), []
-            for _, _, t, _ in refs:
-                if t.requires_grad and id(t) not in seen:
-                    seen.add(id(t))
-                    wrt.append(t)
-        wrt = list(wrt)
-        first, layout, components = {}, [], []
-        K = 0
-        for pos, t in enumerate(wrt):
-            if not isinstance(t, torch.Tensor) or not any(r[2] is t for r in refs):
-                raise ValueError(f"{what}: wrt[{pos}] is not a setting of a drift-kick-drift element of this ring (settings are found by "
-                                 "identity: pass the tensor the element holds)")
-            if id(t) in first:
-                raise ValueError(f"{what}: wrt[{pos}] is the tensor of wrt[{[id(u) for u in wrt].index(id(t))}] again")
-            first[id(t)] = K
-            layout.append((K, max(t.numel(), 1), t.dim() == 0))
-            K += max(t.numel(), 1)
-        for item, slot, t, index in refs:
-            if id(t) in first:
-                components.append((first[id(t)] + (0 if index is None else int(index)), item, slot))
-        return wrt, layout, components, K
-
-    def _ring_jacobian(self, what: str, energy, species, start: torch.Tensor, mode: int, num_iterations: int, along: bool, wrt=None,
-                       raw: bool = False, ring_call=None):
-        """`_ops.dkd_ring_jacobian` for this lattice taken as a ring: the conditions of `_turn_items_dkd` (whose reason a lattice
-        that does not qualify is refused with), the energy as a 0-d tensor of the settings' dtype on the seeds' device.
-        With `wrt` (`_ring_knobs`) also `_ops.dkd_ring_sensitivity` on the orbits found: the same dict with an autograd graph to
-        those settings (`particles.optics.attach_gradients`) or, with `raw`, the pair (values, tangents) as the kernels left them.
-        `ring_call`: a dict that receives what a further kernel call on the same ring needs (`radiation_integrals`)."""
-        if not isinstance(energy, torch.Tensor):
-            lengths = [e.length for e in self._leaves() if isinstance(getattr(e, "length", None), torch.Tensor)]
-            energy = torch.as_tensor(float(energy), dtype=lengths[0].dtype if lengths else torch.float64, device=start.device)
-        if energy.dim() != 0 or not energy.is_floating_point():
-            raise ValueError(f"{what}: the energy must be one scalar")
-        if species is None:
-            # one electron per dtype and device, kept: its tensors are made (and read back once) outside any graph capture
-            key = (energy.dtype, energy.device)
-            species = _DEFAULT_SPECIES.get(key)
-            if species is None:
-                species = _DEFAULT_SPECIES[key] = Species("electron", dtype=energy.dtype, device=energy.device)
-                species.mass_eV_float
-        if any(t.requires_grad for t in (start, energy, species.mass_eV, species.num_elementary_charges)):
-            raise ValueError(f"{what} has no autograd: an input requires grad")
-        if type(self).track is not Segment.track or type(self)._track_internal is not Segment._track_internal:
-            raise ValueError(f"{what}: the segment overrides `track`")
-        if wrt is not None and not isinstance(wrt, str):
-            try:
-                wrt = list(wrt)                               # once: a generator is read here and nowhere else
-            except TypeError:
-                raise ValueError(f"{what}: wrt must be a sequence of tensors or 'all', got {type(wrt).__name__}") from None
-        with torch.no_grad():
-            plan = self._plan()
-            trainable = () if wrt is None else ("all" if isinstance(wrt, str) else {id(t) for t in wrt})
-            ring = self._turn_items_dkd(plan, torch.empty((0, 7), dtype=energy.dtype, device=energy.device), trainable) if plan else \
-                "the lattice holds nothing to track"
-            if isinstance(ring, str):
-                raise ValueError(f"{what}: {ring}")
-            if wrt is not None:
-                wrt, layout, components, K = self._ring_knobs(what, plan, wrt)
-            arrays = _ops.dkd_turn_arrays(ring.kinds, ring.params, ring.num_steps, ring.fringe_at)
-            out = _ops.dkd_ring_jacobian(arrays, len(ring.kinds), energy, species.mass_eV_float, species.num_elementary_charges_float,
-                                         start, mode, num_iterations, along)
-            if ring_call is not None:
-                ring_call.update(arrays=arrays, ring=ring, energy=energy, species=species)
-            if wrt is None or (K == 0 and not raw):
-                return out
-            sens = _ops.dkd_ring_sensitivity(arrays, len(ring.kinds), energy, species.mass_eV_float, species.num_elementary_charges_float,
-                                             out["orbit"], mode, components, K, along)
-        if raw:
-            return out, sens
-        from ..particles.optics import attach_gradients
-
-        return attach_gradients(out, sens, layout, wrt, 6 if mode == 2 else 4)
-
-    @staticmethod
-    def _seeds(start: torch.Tensor) -> torch.Tensor:
-        """(B, 6) float64 from (B, 6), (B, 7) or one such row."""
-        if start.dim() == 1:
-            start = start.unsqueeze(0)
-        if start.dim() != 2 or start.shape[1] not in (6, 7):
-            raise ValueError(f"the seeds must have the shape (B, 6) or (B, 7) or be one such row, got {tuple(start.shape)}")
-        return start[:, :6].to(torch.float64).contiguous()
-
-    @staticmethod
-    def _rows7(x6: torch.Tensor) -> torch.Tensor:
-        return torch.cat([x6, torch.ones_like(x6[..., :1])], dim=-1)
-
     def one_turn_map(self, start: torch.Tensor, energy, species=None, along: bool = False, wrt=None):
         """One turn of this lattice, taken as a ring of drift-kick-drift elements, for the seeds `start` — (B, 6), (B, 7) or one
         such row, on the device — together with the 6 x 6 Jacobian of the turn at every seed: an `OneTurnMap` (particles/optics.py)
@@ -1182,35 +822,7 @@ class Segment(Element):
         derivatives come from `chx_dkd_ring_sensitivity` (`ring_sensitivity` returns them raw). A setting that requires grad and
         is not in `wrt` is still refused; `start`, `energy` and the species stay without gradient.
         Out of scope: vectorised settings, second-order and linear rings."""
-        from ..particles.optics import OneTurnMap
-
-        x = self._seeds(start)
-        out = self._ring_jacobian("one_turn_map", energy, species, x, 0, 1, along, wrt)
-        if not along:
-            return OneTurnMap(self._rows7(out["orbit"]), self._rows7(out["image"]), out["matrix"])
-        return OneTurnMap(self._rows7(out["orbit"]), self._rows7(out["image"]), out["matrix"], self._rows7(out["orbit_along"]),
-                          out["matrix_along"], out["s_along"])
-
-    def _closed_orbit(self, what, energy, species, delta, guess, longitudinal, num_iterations, along, wrt=None, raw=False, ring_call=None):
-        num_iterations = int(num_iterations)
-        if num_iterations < 1:
-            raise ValueError(f"{what}: num_iterations must be at least 1")
-        if guess is not None:
-            x = self._seeds(guess).clone()
-        else:
-            dev = delta.device if isinstance(delta, torch.Tensor) else (energy.device if isinstance(energy, torch.Tensor) else "cuda")
-            n = delta.numel() if isinstance(delta, torch.Tensor) else 1
-            x = torch.zeros((n, 6), dtype=torch.float64, device=dev)
-        if delta is not None:
-            d = delta.to(torch.float64).reshape(-1) if isinstance(delta, torch.Tensor) else torch.full((1,), float(delta), dtype=torch.float64, device=x.device)
-            if d.requires_grad:
-                raise ValueError(f"{what} has no autograd: an input requires grad")
-            if d.shape[0] != x.shape[0]:
-                if x.shape[0] != 1 and d.shape[0] != 1:
-                    raise ValueError(f"{what}: {d.shape[0]} values of delta for {x.shape[0]} guesses")
-                x = x.expand(max(d.shape[0], x.shape[0]), 6).clone()
-            x[:, 5] = d
-        return self._ring_jacobian(what, energy, species, x, 2 if longitudinal else 1, num_iterations, along, wrt, raw, ring_call)
+        return _ring.one_turn_map(self, start, energy, species, along, wrt)
 
     def closed_orbit(self, energy, species=None, delta=None, guess=None, longitudinal: bool = False, num_iterations: int = 10, wrt=None):
         """The closed orbit of this lattice taken as a ring (the conditions of `one_turn_map`): a `ClosedOrbit` with `orbit` (B, 7),
@@ -1224,10 +836,7 @@ class Segment(Element):
         arrived. A seed that fails (beyond the dynamic aperture, a singular system) is NaN in its own rows.
         `wrt`: as in `one_turn_map` — every field then carries gradients to those settings, the orbit moving with them.
         Out of scope: the synchrotron tune of a 6-D search — `matrix` is returned, take its eigenvalues."""
-        from ..particles.optics import ClosedOrbit
-
-        out = self._closed_orbit("closed_orbit", energy, species, delta, guess, longitudinal, num_iterations, False, wrt)
-        return ClosedOrbit(self._rows7(out["orbit"]), out["residual"], out["matrix"], out["dispersion"])
+        return _ring.closed_orbit(self, energy, species, delta, guess, longitudinal, num_iterations, wrt)
 
     def ring_optics(self, energy, species=None, delta=None, guess=None, longitudinal: bool = False, num_iterations: int = 10,
                     along: bool = True, wrt=None):
@@ -1239,13 +848,7 @@ class Segment(Element):
         `wrt`: as in `one_turn_map` — tunes, beta, alpha, phase advance, dispersion, slip and orbit then carry gradients to those
         settings (total derivatives: the closed orbit moves with a setting), e.g. `opt.tunes.sum().backward()`.
         Out of scope: Edwards-Teng or other coupled parametrisations, vectorised settings, second derivatives."""
-        from ..particles.optics import ClosedOrbit, ring_optics_from
-
-        out = self._closed_orbit("ring_optics", energy, species, delta, guess, longitudinal, num_iterations, along, wrt)
-        closed = ClosedOrbit(self._rows7(out["orbit"]), out["residual"], out["matrix"], out["dispersion"])
-        if not along:
-            return ring_optics_from(closed)
-        return ring_optics_from(closed, self._rows7(out["orbit_along"]), out["matrix_along"], out["s_along"])
+        return _ring.ring_optics(self, energy, species, delta, guess, longitudinal, num_iterations, along, wrt)
 
     def radiation_integrals(self, energy, species=None, delta=None, guess=None, num_iterations: int = 10, along: bool = False):
         """The synchrotron-radiation integrals I1 .. I5 of this lattice taken as a ring, on its 4-D closed orbit (`delta` held), and
@@ -1282,31 +885,13 @@ class Segment(Element):
           damping_turns = 2 E0 / (J U0), damping_time = damping_turns C / (beta0 c).
         On the axis I1 = closed.slip beta0^2 + C / gamma0^2 (`slip` is d tau / d delta per turn, -C / (beta0^2 gamma0^2) in a ring of
         Drifts, where I1 = 0)."""
-        from ..particles.optics import ClosedOrbit, radiation_integrals_from, ring_optics_from
-
-        call = {}
-        out = self._closed_orbit("radiation_integrals", energy, species, delta, guess, False, num_iterations, False, ring_call=call)
-        closed = ring_optics_from(ClosedOrbit(self._rows7(out["orbit"]), out["residual"], out["matrix"], out["dispersion"]))
-        ring, species = call["ring"], call["species"]
-        with torch.no_grad():
-            rad = _ops.dkd_ring_radiation(call["arrays"], len(ring.kinds), call["energy"], species.mass_eV_float,
-                                          species.num_elementary_charges_float, out["orbit"], closed.beta, closed.alpha, out["dispersion"],
-                                          bool(along))
-            circumference = torch.cat([p[0, :1] for p in ring.params]).to(torch.float64).sum()
-        return radiation_integrals_from(closed, rad["integrals"], rad.get("integrals_along"), call["energy"], species.mass_eV_float,
-                                        species.num_elementary_charges_float, circumference)
+        return _ring.radiation_integrals(self, energy, species, delta, guess, num_iterations, along)
 
     def chromaticity(self, energy, species=None, h: float = 1e-4, wrt=None) -> torch.Tensor:
         """(dQx / d delta, dQy / d delta), shape (2,): the central difference of the FULL tunes (the integer part from the phase
         advance along the ring) of one `ring_optics` call at delta = (-h, 0, +h). No synchronisation. `wrt`: as in `ring_optics`
         (the chromaticity then carries gradients to those settings, two sextupole families say)."""
-        h = float(h)
-        if not h > 0:
-            raise ValueError("chromaticity: h must be positive")
-        dev = energy.device if isinstance(energy, torch.Tensor) else "cuda"
-        opt = self.ring_optics(energy, species, delta=torch.tensor([-h, 0.0, h], dtype=torch.float64, device=dev), wrt=wrt)
-        q = opt.phase_advance[:, -1, :] / (2.0 * math.pi)
-        return (q[2] - q[0]) / (2.0 * h)
+        return _ring.chromaticity(self, energy, species, h, wrt)
 
     def ring_sensitivity(self, energy, wrt, species=None, delta=None, guess=None, longitudinal: bool = False, num_iterations: int = 10,
                          along: bool = True):
@@ -1318,172 +903,7 @@ class Segment(Element):
         (the orbit moves with the knob) from second-order dual numbers through the maps (`chx_dkd_ring_sensitivity`), no finite
         differences and no step. With order-0 Multipole correctors as knobs `d_orbit_along[..., 0]` is the orbit response
         matrix. The settings need not require grad. No synchronisation."""
-        from ..particles.optics import ClosedOrbit, ring_sensitivity_from
-
-        if wrt is None:
-            raise ValueError("ring_sensitivity: wrt must be a sequence of settings or 'all'")
-        out, sens = self._closed_orbit("ring_sensitivity", energy, species, delta, guess, longitudinal, num_iterations, along, wrt, True)
-        closed = ClosedOrbit(self._rows7(out["orbit"]), out["residual"], out["matrix"], out["dispersion"])
-        return ring_sensitivity_from(closed, sens, out.get("matrix_along"))
-
-    @staticmethod
-    def _stable_energy(ent: dict, energy: torch.Tensor, mass: float, e_out: torch.Tensor) -> torch.Tensor:
-        """The reference energy behind a cached drift-kick-drift stretch as the SAME tensor object from track to track while the
-        incoming energy is the same tensor at the same version (then the value is the same): what stands downstream and depends
-        on the energy — run maps of a later stretch, second-order maps — recognises it by identity and keeps its own products.
-        A tensor somebody edited in place since is not handed out again."""
-        last = ent.get("e_out")
-        if last is not None and ent["e_in"] is energy and ent["e_in_version"] == energy._version and ent["e_mass"] == mass \
-                and last._version == ent["e_out_version"]:
-            return last
-        ent["e_in"], ent["e_in_version"], ent["e_mass"], ent["e_out"], ent["e_out_version"] = energy, energy._version, mass, e_out, \
-            e_out._version
-        return e_out
-
-    def _dkd_run(self, plan, i: int, incoming: ParticleBeam):
-        """plan[i] and the drift-kick-drift elements behind it as one `chx_dkd_chain_mixed` call: (outgoing beam, index behind
-        the run), or None when fewer than two items qualify (one plain beam without a graph; scalar settings of the beam's
-        dtype that carry no gradient; the stock `track`) — then `Element.track` takes each of them as before. Drifts,
-        Quadrupoles, Dipoles, Sextupoles and RFCavities of one arithmetic mode keep the particles in registers, and the merged runs of linear elements
-        between them (a lattice whose drifts are linear and whose magnets drift-kick-drift) ride in the same pass."""
-        x, energy, s = incoming.particles, incoming.energy, incoming.s
-        if x.dim() != 2 or not x.is_cuda or energy.dim() != 0 or energy.dtype != x.dtype or energy.device != x.device \
-                or s.dim() != 0 or s.dtype != x.dtype or s.device != x.device or (
-                    torch.is_grad_enabled() and (x.requires_grad or energy.requires_grad or s.requires_grad)):
-            return None
-        grad = torch.is_grad_enabled()
-        species = incoming.species
-        # the run as it was found last time stands while no attribute of any element was assigned (`Element._epoch`) and no
-        # setting was edited in place (one sweep over the version counters instead of ~3 us of look-ups per element); with
-        # linear runs inside also: the same energy tensor at the same version, the same species (their maps depend on both)
-        cache = self.__dict__.get("_dkd_run_cache")
-        if cache is None or cache[0] is not plan:
-            cache = self.__dict__["_dkd_run_cache"] = (plan, {})
-        ent = cache[1].get(i)
-        if ent is not None and ent["epoch"] == Element._epoch and ent["dtype"] == x.dtype and ent["device"] == x.device \
-                and [t._version for t in ent["tensors"]] == ent["versions"] and not _ops.CAPTURING[0] \
-                and [e.dkd_precision for e in ent["dkd"]] == ent["precisions"] \
-                and not (grad and any(t.requires_grad for t in ent["tensors"])) \
-                and (ent["energy"] is None or (ent["energy"] is energy and ent["energy_version"] == energy._version
-                                               and ent["mass"] == species.mass_eV_float
-                                               and ent["nq"] == species.num_elementary_charges_float)):
-            out, e_out, s_out, _ = _ops.dkd_chain(ent["kinds"], ent["params"], None, None, None, x, energy, s, species.mass_eV_float,
-                                                  species.num_elementary_charges_float, ent["arrays"])
-            e_out = self._stable_energy(ent, energy, species.mass_eV_float, e_out)
-            return ParticleBeam(out, e_out, particle_charges=incoming.particle_charges,
-                                survival_probabilities=incoming.survival_probabilities, s=s_out, species=species), ent["end"]
-        # what stands at plan[i:]: drift-kick-drift elements that qualify (with their argument set) and runs of linear elements
-        seq, after = [], []                                    # after[k]: the plan index behind item k (and the Markers behind it)
-        j = i
-        while j < len(plan):
-            kind, e = plan[j]
-            if kind == "run":
-                if j + 1 < len(plan) and plan[j + 1][0] == "element" and plan[j + 1][1]._is_cavity:
-                    break                                      # that run belongs to the cavity's stretch (chx_lattice_track)
-                if self._identity_run(e):
-                    j += 1                                     # Markers between two magnets: nothing to apply, s + 0
-                    if after:
-                        after[-1] = j
-                    continue
-                seq.append((e, None))
-            elif kind == "element":
-                cls = type(e)
-                if e._tracking_method != "drift_kick_drift" or e._dkd_kind is None or cls.track is not Element.track \
-                        or cls._track_drift_kick_drift is not Element._track_drift_kick_drift \
-                        or cls._track_internal is not Element._track_internal or e.dkd_precision not in _ops.DKD_PRECISION:
-                    break
-                p = e._dkd_params_stacked(x.dtype, x.device)
-                if p is None:
-                    break
-                n, f = e._dkd_options()
-                seq.append((e, (e._dkd_kind, p, n, f, _ops.DKD_PRECISION[e.dkd_precision], [t for t, _ in e._dkd_scalar_refs()])))
-            else:
-                break
-            j += 1
-            after.append(j)
-        # the arithmetic class of every item: a linear run goes with any (None); Drifts, Quadrupoles, Dipoles, Sextupoles, RFCavities and Multipoles with their
-        # `dkd_precision` (float64 beams are evaluated in fp64 whatever it says: one class); anything else has none (-1)
-        single = x.dtype == torch.float64
-        classes = [None if a is None else ((0 if single else a[4]) if a[0] in _DKD_IN_REGISTERS and x.dtype in (torch.float32, torch.float64)
-                                           else -1) for _, a in seq]
-        first = next((k for k, c in enumerate(classes) if c is not None), None)
-        if first is None:
-            return None
-        k = 0
-        if classes[first] >= 0:
-            while k < len(seq) and classes[k] in (None, classes[first]):
-                k += 1
-        while k >= 2:
-            # a stretch whose particles stay in registers: seq[:k]
-            kinds = [_ops.DKD_LINEAR if a is None else a[0] for _, a in seq[:k]]
-            has_runs = _ops.DKD_LINEAR in kinds
-            params, lengths, steps, fringes, storage, tensors = [], [], [], [], [], []
-            energies = _ops.dkd_energy_chain(kinds, energy, species.mass_eV_float) if has_runs else None
-            failed = None
-            for r, (obj, a) in enumerate(seq[:k]):
-                if a is None:
-                    # the run's composed map for the energy in front of it (chx_run_map: one launch now, none while the stretch
-                    # stands) in a tensor of its own — the plan's state is shared with every other way this run can be tracked
-                    zero = self.__dict__.get("_zero_s")
-                    if zero is None or zero.dtype != x.dtype or zero.device != x.device:
-                        zero = self.__dict__["_zero_s"] = torch.zeros((), dtype=x.dtype, device=x.device)
-                    got = self._run_map_fast(obj, x, energy if r == 0 else energies[r - 1], species, zero)
-                    if got is None or got[1].dim() != 0 or got[1].dtype != x.dtype or got[1].device != x.device:
-                        failed = r
-                        break
-                    params.append(got[0].clone())
-                    lengths.append(got[1])                     # 0 + (l_0 + l_1 + ...): the run's length as the walk adds it
-                    steps.append(1)
-                    fringes.append(0)
-                    storage.append(0)
-                    tensors += obj.fast.tensors
-                else:
-                    params.append(a[1])
-                    lengths.append(None)
-                    steps.append(a[2])
-                    fringes.append(a[3])
-                    storage.append(a[4])
-                    tensors += a[5]
-            if failed is not None:
-                k = failed                                     # the stretch ends in front of the run that does not qualify
-                continue
-            if not any(a is not None for _, a in seq[:k]):
-                return None
-            out, e_out, s_out, arrays = _ops.dkd_chain(kinds, params, steps, fringes, storage, x, energy, s, species.mass_eV_float,
-                                                       species.num_elementary_charges_float, lengths=lengths if has_runs else None)
-            if not _ops.CAPTURING[0]:
-                cache[1][i] = {"epoch": Element._epoch, "dtype": x.dtype, "device": x.device, "tensors": tensors,
-                               "versions": [t._version for t in tensors], "kinds": kinds, "params": params, "lengths": lengths,
-                               "arrays": arrays, "end": after[k - 1], "energy": energy if has_runs else None,
-                               "energy_version": energy._version, "mass": species.mass_eV_float,
-                               "nq": species.num_elementary_charges_float,
-                               # (`dkd_precision` may be set on the CLASS, which moves no epoch: compared on every hit)
-                               "dkd": [obj for obj, a in seq[:k] if a is not None],
-                               "precisions": [obj.dkd_precision for obj, a in seq[:k] if a is not None]}
-            return ParticleBeam(out, e_out, particle_charges=incoming.particle_charges,
-                                survival_probabilities=incoming.survival_probabilities, s=s_out, species=species), after[k - 1]
-        # no such stretch starts here: consecutive drift-kick-drift elements (no runs) in one call, element passes, up to where
-        # a stretch could start
-        if seq[0][1] is None:
-            return None
-        k = 1
-        while k < len(seq) and seq[k][1] is not None and not (
-                classes[k] >= 0 and k + 1 < len(seq) and classes[k + 1] in (None, classes[k])):
-            k += 1
-        if k < 2:
-            return None
-        kinds, params = [a[0] for _, a in seq[:k]], [a[1] for _, a in seq[:k]]
-        tensors = [t for _, a in seq[:k] for t in a[5]]
-        out, e_out, s_out, arrays = _ops.dkd_chain(kinds, params, [a[2] for _, a in seq[:k]], [a[3] for _, a in seq[:k]],
-                                                   [a[4] for _, a in seq[:k]], x, energy, s, species.mass_eV_float,
-                                                   species.num_elementary_charges_float)
-        if not _ops.CAPTURING[0]:
-            cache[1][i] = {"epoch": Element._epoch, "dtype": x.dtype, "device": x.device, "tensors": tensors,
-                           "versions": [t._version for t in tensors], "kinds": kinds, "params": params, "arrays": arrays,
-                           "end": after[k - 1], "energy": None, "dkd": [obj for obj, _ in seq[:k]],
-                           "precisions": [obj.dkd_precision for obj, _ in seq[:k]]}
-        return ParticleBeam(out, e_out, particle_charges=incoming.particle_charges,
-                            survival_probabilities=incoming.survival_probabilities, s=s_out, species=species), after[k - 1]
+        return _ring.ring_sensitivity(self, energy, wrt, species, delta, guess, longitudinal, num_iterations, along)
 
     @staticmethod
     def _next_chain_kick(plan, i: int, kick, dtype):

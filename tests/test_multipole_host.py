@@ -132,12 +132,16 @@ def test_lattice_json_round_trip(tmp_path):
 
 def test_the_ring_refusal_names_the_kind():
     """The text `track_turns(fused=True)` raises for a ring it does not take lists the Multipole (the check itself runs on the GPU)."""
-    import inspect
-
+    import cheetah_amd as ca
     from cheetah_amd.accelerator import segment
 
-    text = inspect.getsource(segment.Segment._turn_items_dkd)
-    assert "is not a drift-kick-drift Drift, Quadrupole, Dipole, Sextupole, RFCavity or Multipole" in text
+    ring = ca.Segment([make(), ca.Drift(t(1.0), tracking_method="drift_kick_drift", **F64),
+                       ca.Quadrupole(t(0.2), k1=t(1.0), tracking_method="second_order", name="q", **F64)])
+    reason = ring._turn_items_dkd(ring._plan(), torch.empty((0, 7), **F64))
+    assert reason == "Quadrupole 'q' (tracking method 'second_order') is not a drift-kick-drift Drift, Quadrupole, Dipole, Sextupole, " \
+                     "RFCavity or Multipole"
+    ring.elements[2] = ca.Drift(t(0.5), tracking_method="drift_kick_drift", **F64)
+    assert ring._turn_items_dkd(ring._plan(), torch.empty((0, 7), **F64)).kinds == [8, 0, 0]       # the Multipole itself is taken
     assert segment._DKD_IN_REGISTERS == (0, 1, 2, 5, 6, 8)
 
 
